@@ -21,6 +21,12 @@ pairs / max-over-ranks time.  --scaling weak keeps an independent strip per rank
 `python -m torch.distributed.run --nproc-per-node N` on 127.0.0.1, so the plain command form measures N ranks too.
 The line carries `transport` and `rccl_ranks` (ncclCommCount of the C ABI's communicator); with the default transport a
 rank that cannot create that communicator fails the run instead of falling back.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the configuration).  --full adds everything else the line has carried: kernel events in the timed region, the
+untimed phase step, the exclusive passes and rooflines, quality against the ground truth, the CPU baseline with its parity
+sample and the host-frame sample.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs); the inputs are synthetic and seeded, the same on every run with the same arguments.
 """
 import argparse
 import ctypes
@@ -132,6 +138,12 @@ def parse():
     ap.add_argument("--align-input", default="auto", choices=["auto", "records", "moments"], help="auto = records on one GPU, and with N > 1 (strong) the moments on every rank + the records to rank 0's host only (mi355_allgather_results root = 0, the rank that would run the unchanged driver). What the host alignment starts from: the accepted pair records (9664 B each) or their second moments formed on the device (mi355_allgather_moments / mi355_pair_moments_dev, 184 B each; same transforms bit for bit)")
     ap.add_argument("--as-rank", default=None, help="ONE-GPU PROXY of a rank's share of an --of G rank run (no launcher, no other rank): comma list of ranks, e.g. 0,7")
     ap.add_argument("--of", type=int, default=8, help="rank count the --as-rank proxy pretends to be part of")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: kernel events in the timed region, the untimed phase step, the exclusive passes and "
+                         "rooflines, quality against the ground truth, the CPU baseline with its parity sample and the host-frame sample. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
     return ap.parse_args()
 
 
@@ -492,9 +504,65 @@ def rank_share_proxy(args):
     ctx.close()
 
 
+DUMP_SEED = 20240607       # fixed samples of --dump-outputs: the same positions on every run with the same arguments
+DUMP_PAIRS = 1 << 17       # pair records written whole up to this many scheduled pairs, a fixed sample of as many beyond
+DUMP_INLIER_PAIRS = 1024   # pairs whose inlier lists are written (all of them up to this many, a fixed sample beyond)
+DUMP_PIXELS = 1 << 20      # canvas pixels sampled for canvas_sample.npy
+DUMP_CAP = 64 << 20        # bytes of all dumped arrays together
+
+
+def dump_outputs(d, results, n_pairs, h9, canvas, cw, ch, cws, rows):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files in d.
+      pairs.npy           (P, 6) i, j, ok, accepted, n_selected, n_in of every scheduled pair (or of a fixed sample of DUMP_PAIRS)
+      pairs_H.npy         (P, 9) the homography of the same pairs where accepted, 0 elsewhere
+      pairs_inliers.npy   (Q, 2, 400, 3) x, y, keypoint id of the inlier lists a / b of up to DUMP_INLIER_PAIRS of those pairs, 0 past n_in
+      transforms.npy      (F, 9) what the warp used (m8 = 0: image left out)
+      canvas_size.npy     cw, ch, first row, rows rendered by this rank
+      canvas_row_sums.npy / canvas_col_sums.npy   byte sums of every rendered canvas row / of every byte column over those rows
+      canvas_sample.npy   (N, 3) B, G, R of a fixed sample of DUMP_PIXELS rendered canvas pixels"""
+    import imagemosaicing_amd as im
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = results.device
+    pick = np.arange(n_pairs) if n_pairs <= DUMP_PAIRS else np.sort(rng.choice(n_pairs, DUMP_PAIRS, replace=False))
+    res = results[torch.from_numpy(pick).to(dev)].cpu().numpy().reshape(-1).view(im.PAIR_RESULT)
+    acc = res["accepted"] != 0
+    out = {"pairs": np.stack([res[f].astype(np.float32) for f in ("i", "j", "ok", "accepted", "n_selected", "n_in")], 1),
+           "pairs_H": np.where(acc[:, None], res["H"], np.float32(0)).astype(np.float32)}
+    q = np.arange(len(res)) if len(res) <= DUMP_INLIER_PAIRS else np.sort(rng.choice(len(res), DUMP_INLIER_PAIRS, replace=False))
+    inl = np.zeros((len(q), 2, 400, 3), np.float32)
+    for s, side in enumerate(("a", "b")):
+        pts = res[side][q]
+        inl[:, s] = np.stack([pts["x"], pts["y"], pts["id"].astype(np.float32)], 2)
+    live = acc[q, None] & (np.arange(400)[None, :] < res["n_in"][q, None])
+    out["pairs_inliers"] = np.where(live[:, None, :, None], inl, np.float32(0))
+    out["transforms"] = np.ascontiguousarray(h9, np.float32)
+    row0, nrows = rows
+    out["canvas_size"] = np.array([cw, ch, row0, nrows], np.float64)
+    region = canvas[row0 * cws:(row0 + nrows) * cws].view(nrows, cws)[:, :3 * cw]
+    row_sums, col_sums = [], torch.zeros(3 * cw, dtype=torch.float64, device=dev)
+    for r in range(0, nrows, 256):
+        chunk = region[r:r + 256].to(torch.float64)
+        row_sums.append(chunk.sum(1))
+        col_sums += chunk.sum(0)
+    out["canvas_row_sums"] = torch.cat(row_sums).cpu().numpy() if row_sums else np.zeros(0)
+    out["canvas_col_sums"] = col_sums.cpu().numpy()
+    npix = nrows * cw
+    px = np.arange(npix) if npix <= DUMP_PIXELS else np.sort(rng.integers(0, npix, DUMP_PIXELS))
+    offs = torch.from_numpy((px // cw) * cws + 3 * (px % cw)).to(dev)
+    flat = canvas[row0 * cws:(row0 + nrows) * cws]
+    out["canvas_sample"] = torch.stack([flat[offs + c] for c in range(3)], 1).to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_CAP, "outputs of %d bytes exceed the dump's cap" % total
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.as_rank is not None:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the main path, not of the --as-rank proxy")
         return rank_share_proxy(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args)
@@ -692,7 +760,7 @@ def main():
                                  "host_global_alignment": (t3 - t2) * 1e3, "warp": (t4 - t3) * 1e3}
             if os.environ.get("MI355_BENCH_PHASES"):
                 print("[phases ms] sift %.1f  match+D2H %.1f  host align %.1f  warp %.1f" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3), file=sys.stderr)
-        state.update(r=r, cw=cw, ch=ch, n_valid=int(label.sum()), h9=h9)
+        state.update(r=r, cw=cw, ch=ch, n_valid=int(label.sum()), h9=h9, cws=cws, rows=mine if (strong and world > 1) else (0, ch))
 
     def barrier():
         torch.cuda.synchronize()
@@ -700,9 +768,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
     for i in range(args.warmup):
         step(1 + i)
-    ctx.profile_enable(not os.environ.get("MI355_BENCH_NOPROF"))
+    # kernel events in the timed region feed the rooflines of --full only
+    ctx.profile_enable((args.full or args.profile_all) and not os.environ.get("MI355_BENCH_NOPROF"))
     ctx.profile_only(None if args.profile_all else DOM + ",match,ransac")
     # the dominant class is launched 16 times per batch of frames (one launch per pyramid level of the wide octaves): bracket every 5th
     # launch (5 and 16 are coprime: every level is sampled equally often) -- two event records around each of ~500 launches per step
@@ -722,11 +793,13 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev) if args.backend == "nccl" else torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, n_pairs, state["h9"], canvas, state["cw"], state["ch"], state["cws"], state["rows"])
     g_ms, g_n, g_bytes = ctx.profile_get(DOM)
     m_ms, m_n, _ = ctx.profile_get("match")
     rs_ms, rs_n, _ = ctx.profile_get("ransac")
     ctx.set_option("profile_every:" + DOM, 1)
-    if world == 1:                       # one extra UNTIMED step with a synchronisation after every phase: where a step's time goes
+    if world == 1 and args.full:         # one extra UNTIMED step with a synchronisation after every phase: where a step's time goes
         ctx.profile_enable(False)
         phases = True
         step(999)
@@ -747,7 +820,7 @@ def main():
     # of the timed region as in_situ.
     excl, iso = None, None
     HEAVY = ("gauss_stream", "gauss", "downsample", "extrema")     # every class of the pyramid + extrema phase
-    if not os.environ.get("MI355_BENCH_NO_STANDALONE"):
+    if args.full and not os.environ.get("MI355_BENCH_NO_STANDALONE"):
         ctx.synchronize()
         ctx.set_option("serial_heavy", 1)
         ctx.profile_enable(True); ctx.profile_only(",".join(HEAVY)); ctx.profile_reset()
@@ -782,27 +855,28 @@ def main():
                    "note": "one batch work area in flight: no other kernel on the chip while a bracketed launch runs (what rocprofv3 --kernel-trace of scratch/sift_time.py ... serial reports: profiles/r06_rocprofv3_kernel_stats_serial_pass.txt), untimed extra pass"}
 
     # quality of the last step against ground truth (accepted pairs): corner transfer error in pixels
-    ctx.synchronize()
-    r = state["r"]
-    if r is None:                                                   # --align-input moments without the root gather: the records of the last step, fetched once, untimed
-        if exchange and strong:
-            r = ex.allgather_results(results, n_pairs, accepted_only=True)
-        else:
-            r = local_accepted()
-    if exchange and strong and rank == 0:
-        r = r[np.lexsort((r["j"], r["i"]))]                         # (rank 0 holds the records in both forms of the exchange)
-    state["r"] = r
-    errs = []
-    corners = np.array([[0, 0, 1], [w - 1, 0, 1], [w - 1, h - 1, 1], [0, h - 1, 1]], np.float64).T
-    for rec in r:
-        if not rec["accepted"]:
-            continue
-        i, j = int(rec["i"]), int(rec["j"])
-        Hg = np.linalg.inv(affine3(A[i])) @ affine3(A[j])
-        He = rec["H"].astype(np.float64).copy(); He[8] = 1.0; He = He.reshape(3, 3)
-        a, b = He @ corners, Hg @ corners
-        errs.append(float(np.abs(a[:2] / a[2] - b[:2] / b[2]).max()))
-    accepted = int(r["accepted"].sum()) if n_pairs else 0
+    if args.full:
+        ctx.synchronize()
+        r = state["r"]
+        if r is None:                                                   # --align-input moments without the root gather: the records of the last step, fetched once, untimed
+            if exchange and strong:
+                r = ex.allgather_results(results, n_pairs, accepted_only=True)
+            else:
+                r = local_accepted()
+        if exchange and strong and rank == 0:
+            r = r[np.lexsort((r["j"], r["i"]))]                         # (rank 0 holds the records in both forms of the exchange)
+        state["r"] = r
+        errs = []
+        corners = np.array([[0, 0, 1], [w - 1, 0, 1], [w - 1, h - 1, 1], [0, h - 1, 1]], np.float64).T
+        for rec in r:
+            if not rec["accepted"]:
+                continue
+            i, j = int(rec["i"]), int(rec["j"])
+            Hg = np.linalg.inv(affine3(A[i])) @ affine3(A[j])
+            He = rec["H"].astype(np.float64).copy(); He[8] = 1.0; He = He.reshape(3, 3)
+            a, b = He @ corners, Hg @ corners
+            errs.append(float(np.abs(a[:2] / a[2] - b[:2] / b[2]).max()))
+        accepted = int(r["accepted"].sum()) if n_pairs else 0
 
     blend = None
     if args.blend and (world == 1 or strong):
@@ -848,15 +922,39 @@ def main():
     # HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes of this same command
     # (profiles/pmc_traffic.py; counters cannot be read from inside the process): reported only when the workload matches
     traffic, traffic_src = None, None
-    try:
-        pj = json.load(open(os.path.join(ROOT, "profiles", PMC_JSON)))
-        if pj.get("frames") == str(F) and pj.get("frame") == "%dx%d" % (w, h) and pj.get("batch") == str(BATCH):
-            traffic, traffic_src = float(pj["bytes_per_launch"]), "profiles/%s (FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes)" % PMC_JSON
-    except Exception:
-        pass
+    if args.full:
+        try:
+            pj = json.load(open(os.path.join(ROOT, "profiles", PMC_JSON)))
+            if pj.get("frames") == str(F) and pj.get("frame") == "%dx%d" % (w, h) and pj.get("batch") == str(BATCH):
+                traffic, traffic_src = float(pj["bytes_per_launch"]), "profiles/%s (FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes)" % PMC_JSON
+        except Exception:
+            pass
     if rank == 0:
         total_pairs = survey_pairs * args.steps
         value = total_pairs / dt
+        out = {
+            "metric": "image-pairs/sec (detect+match+H+warp), 4000x3000 UAV frames",
+            "value": value, "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / max(args.steps, 1) * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "vs_baseline": None, "dtype": "i16 fixed-point pyramid filtered in f32 (as the reference's OpenCV), f32 (RANSAC / warp coordinates), int8 MFMA with int32 accumulation (descriptor distances, exact), u8 (pixels)",
+            "data": "synthetic",
+            "transport": transport if exchange else None, "rccl_ranks": rccl_ranks,
+            "config": {"workload": "%s: %s, pair window %d (%d pairs), SIFT(2000,3,0.01,20) + exact BF match + 3x3 grid select + Ransac2D + MosaicImagesRefined warp"
+                                   % (("C3" if args.window == 2 else (("C5" if F >= 2000 else "C4") if args.window == 182 else "window-%d" % args.window)) + (" (block layout)" if args.layout == "block" else ""),
+                                      ("ONE %d-frame %dx%d UAV survey" % (F, w, h)) if strong else ("%d-frame %dx%d UAV strip per GPU" % (F, w, h)),
+                                      args.window, survey_pairs),
+                       "frames": F if strong else F * world, "pairs": survey_pairs, "frames_per_gpu": len(own), "pairs_per_gpu": n_pairs,
+                       "frame": [w, h], "canvas": [state["cw"], state["ch"]],
+                       "sharding": ("single GPU" if world == 1 else
+                                    ("frames %s, pairs i mod G, canvas stripes; %s exchanges: feature records, pair records / moments, frames" % ("in blocks of ceil(F/G)" if args.frame_owner == "blocks" else "k mod G", transport)) if strong else
+                                    ("independent strip per rank; %s all-gather of accepted pair records" % transport))},
+            "blend": blend,
+        }
+        if state.get("frame_exchange"):
+            out["frame_exchange_rank0"] = state["frame_exchange"]
+        out["frames_resident"] = (("owned (%s) + mi355_exchange_frames per step" % ("blocks of ceil(F/N)" if args.frame_owner == "blocks" else "k mod N")) if owned_only else "all frames on every rank") if world > 1 and strong else "single GPU"
+        out["align_input"] = align_input + (" + records to rank 0's host (mi355_allgather_results root = 0, not waited for inside the step's host path)" if records_to_root else "")
+    if rank == 0 and args.full:
         n_frames_total = F if strong else F * world
         in_situ = (g_bytes / 1e9) / (g_ms / 1e3) if g_ms > 0 else 0.0
         head = iso or excl                       # the kernel alone on the chip; the shared-chip pass if that one was skipped
@@ -882,22 +980,7 @@ def main():
                                    "(it runs alone on the chip); the committed rocprofv3 --kernel-trace summary of this command reports the same average"}
         blur_step_ms = head["dominant_kernel_ms"] if head else 0.0
         pair_dominates = ransac_roof is not None and ransac_roof["ms_per_step"] > blur_step_ms
-        out = {
-            "metric": "image-pairs/sec (detect+match+H+warp), 4000x3000 UAV frames",
-            "value": value, "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / max(args.steps, 1) * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "vs_baseline": None, "dtype": "i16 fixed-point pyramid filtered in f32 (as the reference's OpenCV), f32 (RANSAC / warp coordinates), int8 MFMA with int32 accumulation (descriptor distances, exact), u8 (pixels)",
-            "data": "synthetic",
-            "transport": transport if exchange else None, "rccl_ranks": rccl_ranks,
-            "config": {"workload": "%s: %s, pair window %d (%d pairs), SIFT(2000,3,0.01,20) + exact BF match + 3x3 grid select + Ransac2D + MosaicImagesRefined warp"
-                                   % (("C3" if args.window == 2 else (("C5" if F >= 2000 else "C4") if args.window == 182 else "window-%d" % args.window)) + (" (block layout)" if args.layout == "block" else ""),
-                                      ("ONE %d-frame %dx%d UAV survey" % (F, w, h)) if strong else ("%d-frame %dx%d UAV strip per GPU" % (F, w, h)),
-                                      args.window, survey_pairs),
-                       "frames": F if strong else F * world, "pairs": survey_pairs, "frames_per_gpu": len(own), "pairs_per_gpu": n_pairs,
-                       "frame": [w, h], "canvas": [state["cw"], state["ch"]],
-                       "sharding": ("single GPU" if world == 1 else
-                                    ("frames %s, pairs i mod G, canvas stripes; %s exchanges: feature records, pair records / moments, frames" % ("in blocks of ceil(F/G)" if args.frame_owner == "blocks" else "k mod G", transport)) if strong else
-                                    ("independent strip per rank; %s all-gather of accepted pair records" % transport))},
+        out.update({
             "roofline": {"bound": "valu", "bound_note": "a streaming stencil priced against HBM as SURVEY 8d asks (achieved / peak / frac are GB/s of algorithmic bytes), but what limits it is f32 vector instruction issue: see `valu` (PMC traffic = 1.06 x the algorithmic bytes: nothing is re-read)",
                          "kernel": "blur16_stream<R,D,BGR> (streaming separable Gaussian 16S -> 32F -> 16S, one pyramid level of all frames of a batch per launch: every level at least 512 columns wide, the base level straight from the BGR frames)",
                          "achieved": head["achieved"] if head else in_situ, "peak": HBM_PEAK_GBS,
@@ -945,12 +1028,11 @@ def main():
                                   "note": "nominal dense int8 rate (2 x the 2.5 PFLOP/s bf16 figure); round 2 ran this product in bf16 at 0.33 of 2500"})(
                          n_pairs * args.steps * 2.0 * 2000 * 2000 * 128 / 1e12),
             "phase_ms": state.get("phase_ms"), "host_parts_ms": state.get("host_parts_ms"),
-            "blend": blend,
             "roofline_shared_chip_frac": (excl["achieved"] / HBM_PEAK_GBS) if excl else None,      # dominant kernel with the other batches' keypoint kernels beside it (the pipeline's figure; roofline.frac is the kernel's own)
             "quality": {"pairs_accepted": accepted, "pairs": survey_pairs if strong else n_pairs, "images_aligned": state["n_valid"],
                         "h_corner_err_px_median": float(np.median(errs)) if errs else None,
                         "h_corner_err_px_max": float(np.max(errs)) if errs else None},
-        }
+        })
         if prof_all:
             out["kernel_ms_per_step"] = prof_all
         # the line's `roofline` is the kernel that dominates THIS configuration's step: the blur for adjacent pairs (C3),
@@ -959,12 +1041,8 @@ def main():
         if pair_dominates:
             out["roofline_by_kernel"]["blur16_stream"] = out["roofline"]
             out["roofline"] = dict(ransac_roof, dominant_because="ransac_kernel %.1f ms per step against %.1f ms of blur16_stream (exclusive pass)" % (ransac_roof["ms_per_step"], blur_step_ms))
-        if state.get("frame_exchange"):
-            out["frame_exchange_rank0"] = state["frame_exchange"]
-        out["frames_resident"] = (("owned (%s) + mi355_exchange_frames per step" % ("blocks of ceil(F/N)" if args.frame_owner == "blocks" else "k mod N")) if owned_only else "all frames on every rank") if world > 1 and strong else "single GPU"
-        out["align_input"] = align_input + (" + records to rank 0's host (mi355_allgather_results root = 0, not waited for inside the step's host path)" if records_to_root else "")
     # ---- CPU baseline: rank 0 at N=1 only, bounded sample; its pairs double as a parity sample for the GPU records ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         ns = min(20, F)
         fh = frames[:ns].cpu().numpy()
         try:
@@ -1018,12 +1096,12 @@ def main():
                     min(24, len(acc_i)), min(24, len(rej_i)), args.window)
         except Exception as e:       # the baseline must never take the GPU number down with it
             out["cpu_baseline"] = {"value": None, "unit": "image-pairs/s", "cores": None, "kind": "port", "sample": "failed: %r" % (e,)}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None
     # ---- what INTEGRATION.md's caller gets: frames in PAGEABLE host memory, as the reference's IplImages are, through
     # mi355_sift_extract (deferred form: staged into HBM, batched) -> mi355_match_pairs (records to the host) -> host alignment ->
     # mi355_mosaic_refined (host frames in, host canvas out).  Untimed extra on a bounded sample; `value` stays the resident figure.
-    if rank == 0 and world == 1 and not args.no_host_frames:
+    if rank == 0 and world == 1 and args.full and not args.no_host_frames:
         try:
             nH = min(F, 96)
             host = [frames[slot_of[k]].cpu().numpy() for k in range(nH)]

@@ -12,9 +12,9 @@ for C in FETCH_SIZE WRITE_SIZE; do
 done
 python profiles/pmc_traffic.py <(zcat $O/r05_pmc_FETCH_SIZE_blur16_stream.csv.gz) <(zcat $O/r05_pmc_WRITE_SIZE_blur16_stream.csv.gz) blur16_stream $O/r05_pmc_blur16_stream.json frames=500 frame=4000x3000 batch=32 "command=rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE (two passes) --kernel-include-regex blur16_stream --output-format csv -- python bench.py --no-cpu-baseline --steps 1 --warmup 0, with MI355_BENCH_NO_STANDALONE=1 MI355_BENCH_NOPROF=1"
 cp $O/r05_pmc_blur16_stream.json profiles/r05_pmc_blur16_stream.json
-python bench.py --steps 5 --warmup 2 > $O/r05_bench_n1.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 5 > $O/r05_bench_n1_driver_style.json 2>> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/r05_bench_n1_under_rocprofv3.json 2>> $O/bench.err
+python bench.py --full --steps 5 --warmup 2 > $O/r05_bench_n1.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/r05_bench_n1_driver_style.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/r05_bench_n1_under_rocprofv3.json 2>> $O/bench.err
 DB=$(find $O/trace -name "*.db" | head -1)
 python profiles/rocpd_summary.py $DB $O/r05_rocprofv3_kernel_stats_bench_n1.txt
 python profiles/rocpd_by_grid.py $DB > $O/r05_rocprofv3_kernel_stats_by_grid_bench_n1.txt 2>/dev/null
@@ -27,11 +27,11 @@ python profiles/rocpd_summary.py $DB $O/r05_rocprofv3_kernel_stats_serial_pass.t
 python profiles/rocpd_by_grid.py $DB > $O/r05_rocprofv3_kernel_stats_by_grid_serial_pass.txt 2>/dev/null
 rm -rf $O/trace2
 # C4 on one GPU (74 029 window pairs) and the 2-rank dry run of the strong-scaling path on one device (gloo, torch transport)
-MI355_BENCH_NO_STANDALONE=1 python bench.py --window 182 --steps 2 --warmup 1 > $O/r05_bench_c4_n1.json 2>> $O/bench.err
+MI355_BENCH_NO_STANDALONE=1 python bench.py --full --window 182 --steps 2 --warmup 1 > $O/r05_bench_c4_n1.json 2>> $O/bench.err
 # C5: 2000 frames piled onto a 20000^2-class canvas, window 182, warp + LaplacianPyramidBlending with everything co-resident
-MI355_BENCH_NO_STANDALONE=1 python bench.py --frames 2000 --layout block --blend --window 182 --steps 1 --warmup 1 > $O/r05_bench_c5_blend_n1.json 2>> $O/bench.err
+MI355_BENCH_NO_STANDALONE=1 python bench.py --full --frames 2000 --layout block --blend --window 182 --steps 1 --warmup 1 > $O/r05_bench_c5_blend_n1.json 2>> $O/bench.err
 # C4 under the tracer: bf_match_kernel / ransac_kernel / select_kernel durations recomputable from a committed file
-MI355_BENCH_NO_STANDALONE=1 rocprofv3 --kernel-trace --stats -d $O/trace3 -o t -- python bench.py --window 182 --steps 1 --warmup 1 --no-cpu-baseline > $O/r05_bench_c4_n1_under_rocprofv3.json 2>> $O/bench.err
+MI355_BENCH_NO_STANDALONE=1 rocprofv3 --kernel-trace --stats -d $O/trace3 -o t -- python bench.py --full --window 182 --steps 1 --warmup 1 --no-cpu-baseline > $O/r05_bench_c4_n1_under_rocprofv3.json 2>> $O/bench.err
 DB=$(find $O/trace3 -name "*.db" | head -1)
 python profiles/rocpd_summary.py $DB $O/r05_rocprofv3_kernel_stats_bench_c4.txt
 rm -rf $O/trace3
@@ -44,7 +44,7 @@ python bench.py --as-rank 0,7 --of 8 --window 182 --steps 5 --warmup 1 > $O/r05_
 MI355_BENCH_NO_STANDALONE=1 python bench.py --as-rank 0,3,7 --of 8 --frames 2000 --layout block --window 182 --blend --steps 1 --warmup 1 > $O/r05_rank_share_proxy_c5_blend.json 2>> $O/bench.err
 python scratch/small_batch_time.py 2>&1 | grep "^ransac_split" > $O/r05_small_batch_time.txt
 python scratch/sift_time.py 96 4000 3000 32 > $O/r05_sift_time.txt 2>> $O/bench.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 2 --backend gloo --all-ranks-on-device0 --steps 2 --warmup 1 --frames 96 --no-cpu-baseline > $O/r05_bench_dryrun_2ranks_1device.json 2>> $O/bench.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 2 --full --backend gloo --all-ranks-on-device0 --steps 2 --warmup 1 --frames 96 --no-cpu-baseline > $O/r05_bench_dryrun_2ranks_1device.json 2>> $O/bench.err
 # the blend's kernel breakdown (200 resident 12 MP chips) and the counters behind DESIGN's RANSAC paragraph
 bash scratch/prof_blend.sh 200 > /dev/null 2>&1; cp gpurun_out/prof_blend/blend_kernel_stats.txt $O/r05_blend_kernel_stats.txt; grep "^blend" gpurun_out/prof_blend/log.txt >> $O/r05_blend_kernel_stats.txt
 bash scratch/pmc_ransac.sh 2>/dev/null | grep "^p[123] " > $O/r05_pmc_ransac.txt

@@ -1,6 +1,6 @@
 """pytest configuration: registers the `gpu` marker and shared fixtures.
 
-`-m "not gpu"` : oracle vs golden vectors / vs the compiled reference (when oracle/_ref exists),
+`-m "not gpu"` : oracle vs golden vectors / vs the compiled reference (oracle/_ref, or its recorded outputs),
                  host logic, C-ABI symbol checks.  No GPU needed.
 `-m gpu`       : parity tests proper: the HIP path (through the C ABI) vs the oracle.
 """
@@ -25,10 +25,11 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref():
+    """the reference's own code (oracle/_ref); where it cannot be built, its recorded outputs for the same calls"""
     from tests import oracle_lib
     lib = oracle_lib.load_ref()
     if lib is None:
-        pytest.skip("oracle/_ref/libref_oracle.so not built (needs /root/reference)")
+        return oracle_lib.RefReplay()
     return lib
 
 

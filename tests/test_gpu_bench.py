@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_contract_small():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full",
                         "--frames", "6", "--width", "1000", "--height", "750"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -41,6 +41,39 @@ def test_bench_contract_small():
     assert d["value"] > 0
 
 
+def _bench_line(args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_what_the_full_run_computes(tmp_path):
+    """a plain run prints the headline line only (no rooflines, baselines or checks: those are --full's); --dump-outputs writes the
+    last timed step's outputs, and a --full run with the same arguments computes the same ones"""
+    import numpy as np
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "6", "--width", "1000", "--height", "750"]
+    d = _bench_line(small + ["--dump-outputs", str(tmp_path / "plain")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["value"] > 0 and abs(d["value"] - 5 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-6
+    for k in ("roofline", "roofline_by_kernel", "cpu_baseline", "host_frames", "quality", "phase_ms", "parity_sample"):
+        assert k not in d, k
+    f = _bench_line(small + ["--full", "--no-cpu-baseline", "--no-host-frames", "--dump-outputs", str(tmp_path / "full")])
+    assert f["quality"]["pairs_accepted"] == 5
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "canvas_sample.npy" in names and "pairs_H.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    p = np.load(tmp_path / "plain" / "pairs.npy")
+    assert p.shape == (5, 6) and (p[:, 3] == 1).all()
+    assert np.load(tmp_path / "plain" / "canvas_row_sums.npy").sum() > 0
+
+
 def _two_ranks(extra, launcher=True):
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -48,7 +81,7 @@ def _two_ranks(extra, launcher=True):
     if launcher:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
     cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-            "--width", "1000", "--height", "750", "--backend", "gloo", "--all-ranks-on-device0"] + extra
+            "--width", "1000", "--height", "750", "--backend", "gloo", "--all-ranks-on-device0", "--full"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -104,7 +137,7 @@ def test_bench_two_ranks_replicas_and_records_forms_still_run():
 def test_bench_window_line_quotes_the_kernel_that_dominates():
     """with the reference's pair window the pair stage outweighs detect+describe: the line's roofline is ransac_kernel's, against the
     f32 vector peak, from the counted lane-operation formula (VERDICT r05 #7)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-host-frames",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-frames",
                         "--frames", "150", "--width", "640", "--height", "480", "--window", "182"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,6 +1,6 @@
-"""CPU, build container only: the oracle restatement against the reference's own code
-(oracle/_ref/libref_oracle.so) on fresh random inputs -- wider than the committed vectors.
-Skipped where oracle/_ref is absent and /root/reference cannot rebuild it."""
+"""CPU: the oracle restatement against the reference's own code
+(oracle/_ref/libref_oracle.so) on seeded random inputs -- wider than the committed vectors.  Where oracle/_ref cannot be
+built, the `ref` fixture replays that library's recorded outputs for the same inputs (tests/golden/ref_replay.npz)."""
 import numpy as np
 from tests.golden_util import bits
 from tests.synth import synth_pairs, texture

@@ -1,7 +1,7 @@
 """CPU: pieces of the blend path that are now pinned by the reference's own code (oracle/_ref, VERDICT r01 "next" #7 / #8):
 
   * mi355_resample_by_overlap (product, host C++) against the reference's ResampleByOverlap (MosaicImage.cpp:2069-2201),
-    on random layouts where oracle/_ref exists and on the committed vectors everywhere;
+    on seeded random layouts (oracle/_ref, or its recorded outputs: tests/golden/ref_replay.npz) and on the committed vectors;
   * the oracle's chips + distance-map masks (oracle_warp.c) against the reference's LaplacianPyramidBlending warp stage
     (:2216-2460) + FindMasksByDistMap (:1761-1881), same two ways."""
 import numpy as np

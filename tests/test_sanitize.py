@@ -3,6 +3,8 @@ csrc/host_io.cpp + csrc/overlap.cpp are compiled directly with g++ -fsanitize=ad
 together with tests/cxx/host_sanitize.cpp, and run on the reference's committed artefacts.  (mi355_pair_schedule lives in api.hip
 and needs HIP headers: a two-line stand-alone copy would not test the product, so the driver only calls it when linked in.)"""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -11,7 +13,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "imagemosaicing_amd", "csrc")
 
 
+def _runner(tmp_path, flags, tag):
+    """how a program built with these flags is started here.  GCC 11's ThreadSanitizer runtime cannot place its shadow memory under the
+    address-space randomisation of newer kernels (vm.mmap_rnd_bits above 28) and dies before main with no message; with randomisation
+    off for that one process (setarch -R) it starts.  A probe program tells whether the runtime can start here at all."""
+    prefix = [shutil.which("setarch"), platform.machine(), "-R"] if tag == "tsan" and shutil.which("setarch") else []
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("#include <thread>\nint x;\nint main() { std::thread t([] { x = 1; }); t.join(); return x - 1; }\n")
+    r = subprocess.run(["g++", "-std=c++17", "-pthread"] + flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+    if r.returncode != 0 and ("cannot find" in r.stderr or "unrecognized" in r.stderr):
+        pytest.skip("sanitizer runtime not installed: " + r.stderr[-300:])
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run(prefix + [str(tmp_path / "probe")], capture_output=True, text=True, timeout=120)
+    if r.returncode < 0:
+        pytest.skip("the %s runtime cannot start on this machine: a two-line program dies with signal %d before main" % (tag, -r.returncode))
+    return prefix
+
+
 def _build_and_run(tmp_path, flags, tag):
+    prefix = _runner(tmp_path, flags, tag)
     exe = str(tmp_path / ("host_sanitize_" + tag))
     # mi355_pair_schedule is defined in api.hip (HIP TU): give the driver the one symbol through a weak stub that reports "not linked"
     stub = tmp_path / "stub.cpp"
@@ -25,7 +45,7 @@ def _build_and_run(tmp_path, flags, tag):
         pytest.skip("sanitizer runtime not installed: " + r.stderr[-300:])
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
-    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden"), str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run(prefix + [exe, os.path.join(ROOT, "tests", "golden"), str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "SANITIZE_OK" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 

@@ -6,7 +6,7 @@ angle or a descriptor of its run, so neither mode can be compared with the binar
   (i)  how many angles and descriptor bytes move between the two modes on the reference's own photographs, and
   (ii) whether the reference's committed inlier correspondences (found under the BINARY's descriptors) are nearest neighbours more often
        under one mode's descriptors than under the other's.
-Measured on the 20 frames of the reference's run (build container; the two committed frames elsewhere) -- the numbers are asserted below and
+Measured on the 20 frames of the reference's run (committed under tests/golden) -- the numbers are asserted below and
 quoted in DESIGN.md section 2a."""
 import ctypes as C
 import os
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from tests.golden_util import load_match_pairs
-from tests.test_sift_reference_run import frame, available_frames, REF_DATA
+from tests.test_sift_reference_run import frame, available_frames
 
 DLL = "/root/reference/code/MosaicingCode/Release/opencv_core240.dll"
 

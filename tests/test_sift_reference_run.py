@@ -1,8 +1,7 @@
 """SIFT against the reference's ONE committed run -- the only output of OpenCV 2.4.0's cv::SIFT that exists in the reference tree:
 Release/feature_temp/matchPairs.match holds, for the 58 accepted pairs of Release/test_data/DSC00004..23.JPG, the inlier keypoints
-(float32 x, y and the keypoint's INDEX in OpenCV's vector).  Two of those frames are committed as fixtures (data files of the
-reference: tests/golden/DSC00004.JPG, DSC00005.JPG = images 0 and 1 of the run); where /root/reference exists (the build
-container) all 20 frames are used.
+(float32 x, y and the keypoint's INDEX in OpenCV's vector).  The 20 frames are committed as fixtures (data files of the
+reference: tests/golden/DSC00004.JPG .. DSC00023.JPG = images 0 .. 19 of the run); the GPU tests take images 0 and 1.
 
 What the test pins (oracle/oracle_sift.c restates the reference's OpenCV binary; this is its check against that binary's output):
   * EVERY keypoint record of the file is reproduced bit for bit: oracle.sift(frame, nfeatures = 0) -- OpenCV's "keep all", its
@@ -24,18 +23,16 @@ import pytest
 from tests.golden_util import GOLD, load_match_pairs
 
 PIL = pytest.importorskip("PIL.Image")
-REF_DATA = "/root/reference/code/MosaicingCode/Release/test_data"
+GPU_FRAMES = [0, 1]        # the frames the GPU tests below take
 
 
 def frame(k):
     p = os.path.join(GOLD, "DSC%05d.JPG" % (4 + k))
-    if not os.path.exists(p):
-        p = os.path.join(REF_DATA, "DSC%05d.JPG" % (4 + k))
     return np.ascontiguousarray(np.array(PIL.open(p).convert("RGB"))[:, :, ::-1])
 
 
 def available_frames():
-    return list(range(20)) if os.path.isdir(REF_DATA) else [0, 1]
+    return list(range(20))
 
 
 def test_every_keypoint_record_of_the_reference_run_is_reproduced_bit_for_bit():
@@ -119,7 +116,7 @@ def test_gpu_keep_all_meets_the_reference_records_directly():
     prm = im.default_params()
     prm.nfeatures = 0
     ctx = im.Context(0, prm)
-    ks = available_frames()
+    ks = GPU_FRAMES
     tot = ok = 0
     for k in ks:
         img = frame(k)
@@ -169,7 +166,6 @@ def test_gpu_keep_all_meets_the_reference_records_directly():
     ctx.close()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="needs the reference's 20 test frames (build container only)")
 def test_the_reference_run_end_to_end_from_the_oracles_own_features():
     """the whole pair stage on the reference's 20 frames -- oracle SIFT (nfeatures = 0 as that run), exact 1-NN, grid
     selection, Ransac2D (seed 1), acceptance above 30 inliers over all 190 pairs -- against the 58 pairs of the committed

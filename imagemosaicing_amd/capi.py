@@ -496,6 +496,72 @@ class Context:
         self.synchronize()
         return out, cw, ch, cws
 
+    # ---- frames kept in HBM after extraction, renders into caller memory -------------------------------------------------
+    def DropFrames(self, img_id=-1):
+        """releases the kept frame of img_id (set_option("keep_frames", 1)); img_id < 0: all of them"""
+        self._chk(self.L.mi355_drop_frames(self._h, int(img_id)))
+
+    def FrameDev(self, img_id):
+        """(device address, w, h, ws) of the kept frame of img_id"""
+        d = C.c_void_p()
+        w, h, ws = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_get_frame_dev(self._h, int(img_id), C.byref(d), C.byref(w), C.byref(h), C.byref(ws)))
+        return d.value or 0, w.value, h.value, ws.value
+
+    def _into_args(self, imgs, img_ids, geom):
+        """host pointers (None where a kept frame is the source), ids (-1: the host image) and w, h, ws; geom[k] = (w, h, ws) of an image
+        given only by its id (default: the kept frame's)"""
+        n = len(imgs) if imgs is not None else len(img_ids)
+        ids = np.full(n, -1, np.int32) if img_ids is None else np.ascontiguousarray(img_ids, np.int32)
+        keepalive, ptrs = [], (C.c_void_p * n)()
+        w, h, ws = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        for k in range(n):
+            im = None if imgs is None else imgs[k]
+            if im is not None:
+                a = np.ascontiguousarray(im, np.uint8)
+                keepalive.append(a)
+                ptrs[k] = a.ctypes.data
+                w[k], h[k], ws[k] = a.shape[1], a.shape[0], a.strides[0]
+            elif geom is not None and geom[k] is not None:
+                w[k], h[k], ws[k] = geom[k]
+            elif ids[k] >= 0:
+                _, w[k], h[k], ws[k] = self.FrameDev(int(ids[k]))
+        return ptrs, ids, w, h, ws, keepalive
+
+    @staticmethod
+    def _out_array(out, pitch, cw, ch):
+        if out is None:
+            pitch = pitch or (3 * cw + 3) & ~3
+            out = np.zeros((ch, pitch), np.uint8)
+        if out.dtype != np.uint8 or not out.flags["C_CONTIGUOUS"] or out.ndim < 2:
+            raise ValueError("out must be a C-contiguous uint8 array of rows")
+        pitch = int(pitch or out.strides[0])
+        if ch > 0 and pitch >= 3 * cw and out.nbytes < pitch * (ch - 1) + 3 * cw:
+            raise ValueError("out holds %d bytes, the canvas needs %d rows of pitch %d" % (out.nbytes, ch, pitch))
+        return out, pitch
+
+    def MosaicImagesRefinedInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None):
+        """mi355_mosaic_refined_into: image k from the kept frame of img_ids[k] (>= 0) or the host image imgs[k]; the canvas is written into
+        out (rows of `pitch` bytes, default out's row stride; out=None: a fresh (ch, cws) array).  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_refined_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s),
+                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
+    def MosaicBlendedInto(self, imgs, img_ids, h9s, keep=None, band=5, out=None, pitch=None, geom=None):
+        """mi355_mosaic_blended_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        cw, ch, _ = blend_layout(w, h, h9s, keep_a)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_blended_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), _p(keep_a), int(band),
+                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
 
 # ---- host-only helpers (no ctx) ---------------------------------------------------------------------------
 def comm_unique_id():

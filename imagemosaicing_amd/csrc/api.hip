@@ -80,6 +80,7 @@ extern "C" void mi355_destroy(mi355_ctx* ctx) {
     mi_sift_release(ctx);
     mi_comm_release(ctx);
     mi_surf_release(ctx);
+    mi_frames_release(ctx);
     for (auto& kv : ctx->feats) kv.second.release();
     for (auto& kv : ctx->ws) kv.second.release();
     for (auto& kv : ctx->hws) kv.second.release();
@@ -138,7 +139,18 @@ extern "C" int mi355_sift_extract(mi355_ctx* ctx, int img_id, const uint8_t* bgr
         LOCKED_PROLOGUE
         if (!bgr || w < 16 || h < 16 || width_step < 3 * w) { ctx->set_error("sift_extract: bad image geometry"); return MI355_ERR_ARG; }
         const size_t bytes = (size_t)width_step * h;
-        if (deferred) {
+        if (ctx->keep_frames) {
+            // option "keep_frames": the frame is uploaded straight into its kept buffer, which the batch reads in place of a ring slot (one
+            // copy over the link and none in HBM; the kept frame's event orders its replacement the way host_frame_ev orders a slot's reuse)
+            uint8_t* dkeep = nullptr;
+            int rc = mi_kept_frame_slot(ctx, img_id, w, h, width_step, "sift_extract", &dkeep);
+            if (rc != MI355_OK) return rc;
+            MI_HIP(hipMemcpyAsync(dkeep, bgr, bytes, hipMemcpyHostToDevice, ctx->stream));
+            ctx->pend_event = ctx->kept_frames[img_id].ev;
+            rc = mi_sift_extract_dev(ctx, img_id, dkeep, w, h, width_step, deferred ? nullptr : &n);
+            ctx->pend_event = nullptr;
+            if (rc != MI355_OK || deferred) return rc;
+        } else if (deferred) {
             // staging ring in HBM: a slot is reused only after the batch that read it has finished (event of its work area)
             const size_t ring = (size_t)(ctx->sift_nslots + 1) * (size_t)(ctx->sift_batch < 1 ? 1 : ctx->sift_batch);
             if (ctx->host_frames.size() != ring) {
@@ -168,12 +180,13 @@ extern "C" int mi355_sift_extract(mi355_ctx* ctx, int img_id, const uint8_t* bgr
             const int rc = mi_sift_extract_dev(ctx, img_id, dimg.as<uint8_t>(), w, h, width_step, nullptr);
             ctx->pend_event = nullptr;
             return rc;
+        } else {
+            DevBuf& dimg = ctx->buf("sift_host_img");
+            MI_HIP(dimg.reserve(bytes + 16));
+            MI_HIP(hipMemcpyAsync(dimg.p, bgr, bytes, hipMemcpyHostToDevice, ctx->stream));
+            int rc = mi_sift_extract_dev(ctx, img_id, dimg.as<uint8_t>(), w, h, width_step, &n);
+            if (rc != MI355_OK) return rc;
         }
-        DevBuf& dimg = ctx->buf("sift_host_img");
-        MI_HIP(dimg.reserve(bytes + 16));
-        MI_HIP(hipMemcpyAsync(dimg.p, bgr, bytes, hipMemcpyHostToDevice, ctx->stream));
-        int rc = mi_sift_extract_dev(ctx, img_id, dimg.as<uint8_t>(), w, h, width_step, &n);
-        if (rc != MI355_OK) return rc;
     }
     if (n_kp) *n_kp = n;
     if (kp || desc128) return mi355_get_features(ctx, img_id, kp, desc128, max_kp, nullptr);
@@ -402,6 +415,14 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
         struct { const char* n; int* p; } knobs[] = {{"ransac_split", &ctx->ransac_split}, {"strict_frames", &ctx->strict_frames}};
         for (auto& k : knobs) if (std::string(name) == k.n) { *k.p = value; return MI355_OK; }
     }
+    if (std::string(name) == "keep_frames") { ctx->keep_frames = value ? 1 : 0; return MI355_OK; }      // frames kept so far stay until mi355_drop_frames
+    if (std::string(name) == "download_chunk_mb") {
+        if (value < 1) { ctx->set_error("set_option: download_chunk_mb must be >= 1"); return MI355_ERR_ARG; }
+        ctx->download_chunk = (size_t)value << 20;
+        return MI355_OK;
+    }
+    if (std::string(name) == "download_threads") { ctx->download_threads = value < 1 ? 1 : (value > 16 ? 16 : value); return MI355_OK; }
+    if (std::string(name) == "download_mode") { ctx->download_mode = value < 0 || value > 2 ? 0 : value; return MI355_OK; }
     if (std::string(name) == "sift_flush") return mi_sift_flush(ctx);      // close the batch that is collecting frames now (no wait): the caller shapes the batches of a short survey
     if (std::string(name) == "blur_stream") { ctx->blur_stream = value ? 1 : 0; return MI355_OK; }
     if (std::string(name) == "sift_cascade") { ctx->cascade = value < 0 ? 0 : (value > 3 ? 3 : value); return MI355_OK; }

@@ -86,6 +86,14 @@ struct Features {
     void release() { kp.release(); xy.release(); d8.release(); s8.release(); n8.release(); }
 };
 
+// a host frame kept in HBM after its extraction (option "keep_frames"): the source of the render calls' img_ids
+struct KeptFrame {
+    void*  p = nullptr;
+    size_t cap = 0;
+    int w = 0, h = 0, ws = 0;
+    hipEvent_t ev = nullptr;         // recorded after the SIFT batch that read the frame (the staging ring's host_frame_ev, per kept frame)
+};
+
 struct ProfClass {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     size_t used = 0;
@@ -129,6 +137,13 @@ struct mi355_ctx {
     std::vector<char> host_frame_used;
     size_t host_frame_next = 0;
     hipEvent_t pend_event = nullptr;                   // handed to the frame being parked by mi_sift_extract_dev
+    int keep_frames = 0;                               // option "keep_frames": host-frame extractions keep their HBM copy under img_id (kept_frames)
+    std::unordered_map<int, KeptFrame> kept_frames;
+    size_t download_chunk = (size_t)64 << 20;          // option "download_chunk_mb": bytes per chunk of the _into calls' canvas download
+    int download_threads = 4;                          // option "download_threads" (1..16): host threads copying a pinned chunk into the caller's rows
+    int download_mode = 0;                             // option "download_mode" (measurement): 0 pinned double buffer, 1 hipMemcpy2DAsync into dst, 2 hipHostRegister(dst) + 2D copy
+    hipStream_t dl_stream = nullptr;                   // copy stream of those downloads
+    hipEvent_t dl_ev[3] = {nullptr, nullptr, nullptr}; // [0], [1]: the pinned halves filled; [2]: the render finished on ctx->stream
     int cascade = 3;                                   // octaves >= 2000 px wide: 3 (default) = the first three levels ({gray | L0} -> L0/L1 L2) in one pass (pyr_chain), the rest per level; 2 = also L3..L5 in one pass; 1 = all six in one pass (pyr_cascade); 0 = every level on its own. Same bits; option "sift_cascade"
     int blur_stream = 1;                               // big pyramid levels through blur_stream (0: tile kernel only); option "blur_stream"
     int sift_nslots = 3;                               // batch work areas in flight, each on its own stream (option "sift_slots", env MI355_SIFT_SLOTS)
@@ -208,6 +223,8 @@ int mi_sift_extract_dev(mi355_ctx*, int img_id, const uint8_t* d_bgr, int w, int
 void mi_sift_release(mi355_ctx*);
 void mi_comm_release(mi355_ctx*);
 void mi_surf_release(mi355_ctx*);
+int  mi_kept_frame_slot(mi355_ctx*, int img_id, int w, int h, int ws, const char* who, uint8_t** d_frame);   // frames.hip: the kept buffer of img_id, ready for a new frame
+void mi_frames_release(mi355_ctx*);
 
 // host helpers
 int  mi_inverse_matrix_host(const float* src, int order, float* dst, float eps);   // matrix.h:147-296 (host side of the warps)

@@ -1,0 +1,252 @@
+// csrc/frames.hip -- host frames kept in HBM after their extraction (option "keep_frames") and the render calls that write straight
+// into caller memory (mi355_mosaic_refined_into / mi355_mosaic_blended_into).  Host code only: the canvases come from the kernels of
+// warp.hip / blend.hip; what is new is where their inputs come from and how the canvas reaches the caller's rows.
+#include "common.h"
+#include <thread>
+
+// ---- kept frames ------------------------------------------------------------------------------------------------------
+// The kept buffer of img_id made ready to take a new frame of this geometry.  A SIFT batch may still read the old frame (it was parked
+// with the kept frame's event, which the batch records when it finishes): a batch still collecting frames is launched first, then the ctx
+// stream waits for the event before the caller uploads into the same buffer -- or, when the buffer must grow, the host waits before the
+// old one is freed.  Renders and _dev calls that read the frame run on the ctx stream, so the upload is ordered after them too.
+int mi_kept_frame_slot(mi355_ctx* ctx, int img_id, int w, int h, int ws, const char* who, uint8_t** d_frame) {
+    KeptFrame& f = ctx->kept_frames[img_id];
+    const size_t bytes = (size_t)ws * h + 16;
+    if (!f.ev) {
+        MI_HIP(hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+    } else {
+        int rc = mi_sift_flush_if_parked(ctx, f.ev);
+        if (rc != MI355_OK) return rc;
+        if (bytes > f.cap && f.p) {
+            MI_HIP(hipEventSynchronize(f.ev));
+            MI_HIP(hipStreamSynchronize(ctx->stream));
+        } else {
+            MI_HIP(hipStreamWaitEvent(ctx->stream, f.ev, 0));
+        }
+    }
+    if (bytes > f.cap) {
+        if (f.p) { MI_HIP(hipFree(f.p)); f.p = nullptr; f.cap = 0; }
+        const hipError_t e = hipMalloc(&f.p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipEventDestroy(f.ev);
+            ctx->kept_frames.erase(img_id);
+            ctx->set_error(std::string(who) + ": no device memory to keep the frame of image " + std::to_string(img_id) + " (" +
+                           std::to_string(bytes) + " bytes, option keep_frames): " + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? MI355_ERR_NOMEM : MI355_ERR_DEVICE;
+        }
+        f.cap = bytes;
+    }
+    f.w = w; f.h = h; f.ws = ws;
+    *d_frame = (uint8_t*)f.p;
+    return MI355_OK;
+}
+
+// every reader of the frame done: a batch still collecting it is launched and waited for, and the ctx stream is drained
+static int kept_frame_idle(mi355_ctx* ctx, KeptFrame& f) {
+    if (!f.ev) return MI355_OK;
+    int rc = mi_sift_flush_if_parked(ctx, f.ev);
+    if (rc != MI355_OK) return rc;
+    MI_HIP(hipEventSynchronize(f.ev));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    return MI355_OK;
+}
+
+static void kept_frame_free(KeptFrame& f) {
+    if (f.p) (void)hipFree(f.p);
+    if (f.ev) (void)hipEventDestroy(f.ev);
+    f = KeptFrame();
+}
+
+// mi355_destroy (the streams are idle by then)
+void mi_frames_release(mi355_ctx* ctx) {
+    for (auto& kv : ctx->kept_frames) { if (kv.second.ev) (void)hipEventSynchronize(kv.second.ev); kept_frame_free(kv.second); }
+    ctx->kept_frames.clear();
+    for (int i = 0; i < 2; i++) ctx->hbuf(i ? "download_1" : "download_0").release();
+    for (hipEvent_t& e : ctx->dl_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (ctx->dl_stream) { (void)hipStreamDestroy(ctx->dl_stream); ctx->dl_stream = nullptr; }
+}
+
+extern "C" int mi355_drop_frames(mi355_ctx* ctx, int img_id) {
+    LOCKED_PROLOGUE
+    if (img_id >= 0) {
+        auto it = ctx->kept_frames.find(img_id);
+        if (it == ctx->kept_frames.end()) return MI355_OK;
+        const int rc = kept_frame_idle(ctx, it->second);
+        if (rc != MI355_OK) return rc;
+        kept_frame_free(it->second);
+        ctx->kept_frames.erase(it);
+        return MI355_OK;
+    }
+    for (auto& kv : ctx->kept_frames) { const int rc = kept_frame_idle(ctx, kv.second); if (rc != MI355_OK) return rc; }
+    for (auto& kv : ctx->kept_frames) kept_frame_free(kv.second);
+    ctx->kept_frames.clear();
+    return MI355_OK;
+}
+
+extern "C" int mi355_get_frame_dev(mi355_ctx* ctx, int img_id, const uint8_t** d_frame, int* w, int* h, int* ws) {
+    LOCKED_PROLOGUE
+    if (!d_frame) { ctx->set_error("get_frame_dev: d_frame is NULL"); return MI355_ERR_ARG; }
+    *d_frame = nullptr;
+    auto it = ctx->kept_frames.find(img_id);
+    if (img_id < 0 || it == ctx->kept_frames.end()) {
+        ctx->set_error("get_frame_dev: image " + std::to_string(img_id) + " holds no kept frame" + (ctx->keep_frames ? "" : " (option keep_frames is 0)"));
+        return MI355_ERR_ARG;
+    }
+    MI_HIP(hipStreamSynchronize(ctx->stream));     // the upload is complete: the pointer may be read on any stream
+    *d_frame = (const uint8_t*)it->second.p;
+    if (w) *w = it->second.w;
+    if (h) *h = it->second.h;
+    if (ws) *ws = it->second.ws;
+    return MI355_OK;
+}
+
+// ---- the render calls' sources --------------------------------------------------------------------------------------------
+// Device pointers of the images a render reads: kept frames where img_ids names one, the host images staged in "into_srcs" otherwise.
+// Images the render skips (skip[k]) are neither read nor checked.
+static int render_sources(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                          const int* ws, int n, const std::vector<char>& skip, std::vector<const uint8_t*>& dptr) {
+    dptr.assign((size_t)n, nullptr);
+    std::vector<size_t> off((size_t)n, 0);
+    size_t total = 0;
+    for (int k = 0; k < n; k++) {
+        if (skip[k]) continue;
+        if (img_ids && img_ids[k] >= 0) {
+            auto it = ctx->kept_frames.find(img_ids[k]);
+            if (it == ctx->kept_frames.end()) {
+                ctx->set_error(std::string(who) + ": image " + std::to_string(k) + ": id " + std::to_string(img_ids[k]) + " holds no kept frame");
+                return MI355_ERR_ARG;
+            }
+            const KeptFrame& f = it->second;
+            if (f.w != w[k] || f.h != h[k] || f.ws != ws[k]) {
+                ctx->set_error(std::string(who) + ": image " + std::to_string(k) + ": the kept frame of id " + std::to_string(img_ids[k]) + " is " +
+                               std::to_string(f.w) + "x" + std::to_string(f.h) + " (width_step " + std::to_string(f.ws) + "), the call says " +
+                               std::to_string(w[k]) + "x" + std::to_string(h[k]) + " (width_step " + std::to_string(ws[k]) + ")");
+                return MI355_ERR_ARG;
+            }
+            dptr[k] = (const uint8_t*)f.p;
+            continue;
+        }
+        if (!imgs || !imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) {
+            ctx->set_error(std::string(who) + ": image " + std::to_string(k) + ": no host image or bad geometry");
+            return MI355_ERR_ARG;
+        }
+        off[k] = total;
+        total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255;
+    }
+    if (total == 0) return MI355_OK;
+    DevBuf& dall = ctx->buf("into_srcs");
+    MI_HIP(dall.reserve(total + 16));
+    for (int k = 0; k < n; k++) {
+        if (skip[k] || dptr[k]) continue;
+        dptr[k] = dall.as<uint8_t>() + off[k];
+        MI_HIP(hipMemcpyAsync((void*)dptr[k], imgs[k], (size_t)ws[k] * h[k], hipMemcpyHostToDevice, ctx->stream));
+    }
+    return MI355_OK;
+}
+
+// ---- canvas download ------------------------------------------------------------------------------------------------------
+// rows of row_bytes from the device canvas (pitch src_pitch) into the caller's host rows (pitch dst_pitch); the bytes past row_bytes of
+// every destination row are left as they are.  Default: chunks of whole rows go device -> pinned on the copy stream into two halves in
+// turn, and the host copies chunk k out of one half while chunk k + 1 lands in the other.
+static void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t src_pitch, size_t row_bytes, int rows, int threads) {
+    auto part = [&](int r0, int r1) { for (int r = r0; r < r1; r++) memcpy(dst + (size_t)r * dst_pitch, src + (size_t)r * src_pitch, row_bytes); };
+    if (threads <= 1 || (size_t)rows * row_bytes < ((size_t)4 << 20)) { part(0, rows); return; }
+    if (threads > rows) threads = rows;
+    std::vector<std::thread> th;
+    for (int t = 1; t < threads; t++) th.emplace_back(part, (int)((long)rows * t / threads), (int)((long)rows * (t + 1) / threads));
+    part(0, (int)((long)rows / threads));
+    for (auto& x : th) x.join();
+}
+
+static int download_rows(mi355_ctx* ctx, const uint8_t* d_src, size_t src_pitch, uint8_t* dst, size_t dst_pitch, size_t row_bytes, int rows) {
+    if (!ctx->dl_stream) MI_HIP(hipStreamCreateWithFlags(&ctx->dl_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : ctx->dl_ev) if (!e) MI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    MI_HIP(hipEventRecord(ctx->dl_ev[2], ctx->stream));
+    MI_HIP(hipStreamWaitEvent(ctx->dl_stream, ctx->dl_ev[2], 0));
+    if (ctx->download_mode == 1 || ctx->download_mode == 2) {
+        const bool reg = ctx->download_mode == 2;
+        if (reg) MI_HIP(hipHostRegister(dst, dst_pitch * (size_t)(rows - 1) + row_bytes, hipHostRegisterDefault));
+        hipError_t e = hipMemcpy2DAsync(dst, dst_pitch, d_src, src_pitch, row_bytes, (size_t)rows, hipMemcpyDeviceToHost, ctx->dl_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->dl_stream);
+        if (reg) (void)hipHostUnregister(dst);
+        if (e != hipSuccess) { ctx->set_error(std::string("download: ") + hipGetErrorString(e)); return MI355_ERR_DEVICE; }
+        return MI355_OK;
+    }
+    int chunk_rows = (int)(ctx->download_chunk / src_pitch);
+    if (chunk_rows < 1) chunk_rows = 1;
+    if (chunk_rows > rows) chunk_rows = rows;
+    HostBuf* pb[2] = {&ctx->hbuf("download_0"), &ctx->hbuf("download_1")};
+    const int nchunks = (rows + chunk_rows - 1) / chunk_rows;
+    for (int i = 0; i < (nchunks > 1 ? 2 : 1); i++) MI_HIP(pb[i]->reserve((size_t)chunk_rows * src_pitch));
+    auto issue = [&](int c) -> hipError_t {
+        const int r0 = c * chunk_rows, nr = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        hipError_t e = hipMemcpyAsync(pb[c & 1]->p, d_src + (size_t)r0 * src_pitch, (size_t)nr * src_pitch, hipMemcpyDeviceToHost, ctx->dl_stream);
+        return e == hipSuccess ? hipEventRecord(ctx->dl_ev[c & 1], ctx->dl_stream) : e;
+    };
+    MI_HIP(issue(0));
+    if (nchunks > 1) MI_HIP(issue(1));
+    for (int c = 0; c < nchunks; c++) {
+        MI_HIP(hipEventSynchronize(ctx->dl_ev[c & 1]));
+        const int r0 = c * chunk_rows, nr = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        copy_rows(dst + (size_t)r0 * dst_pitch, dst_pitch, pb[c & 1]->as<uint8_t>(), src_pitch, row_bytes, nr, ctx->download_threads);
+        if (c + 2 < nchunks) MI_HIP(issue(c + 2));
+    }
+    return MI355_OK;
+}
+
+static int check_dst(mi355_ctx* ctx, const char* who, const uint8_t* dst, int dst_pitch, int cw, int ch, int lw, int lh) {
+    if (cw != lw || ch != lh) {
+        ctx->set_error(std::string(who) + ": cw x ch = " + std::to_string(cw) + "x" + std::to_string(ch) + ", the layout is " + std::to_string(lw) + "x" + std::to_string(lh));
+        return MI355_ERR_ARG;
+    }
+    if (!dst) { ctx->set_error(std::string(who) + ": dst is NULL"); return MI355_ERR_ARG; }
+    if ((long)dst_pitch < 3L * cw) { ctx->set_error(std::string(who) + ": dst_pitch " + std::to_string(dst_pitch) + " < 3 * cw = " + std::to_string(3L * cw)); return MI355_ERR_ARG; }
+    return MI355_OK;
+}
+
+// ---- render into caller memory --------------------------------------------------------------------------------------------
+extern "C" int mi355_mosaic_refined_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                         const int* ws, int n, const float* h9s, uint8_t* dst, int dst_pitch, int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_refined_into: bad arguments"); return MI355_ERR_ARG; }
+    if (n <= 1) { ctx->set_error("mosaic_refined_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
+    int lw, lh, lws;
+    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
+    if (rc != MI355_OK) { ctx->set_error("mosaic_refined_into: empty canvas"); return rc; }
+    rc = check_dst(ctx, "mosaic_refined_into", dst, dst_pitch, cw, ch, lw, lh);
+    if (rc != MI355_OK) return rc;
+    std::vector<char> skip((size_t)n);
+    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
+    std::vector<const uint8_t*> dptr;
+    rc = render_sources(ctx, "mosaic_refined_into", imgs, img_ids, w, h, ws, n, skip, dptr);
+    if (rc != MI355_OK) return rc;
+    DevBuf& dcan = ctx->buf("into_canvas");
+    MI_HIP(dcan.reserve((size_t)lws * lh));
+    rc = mi_mosaic_refined_dev(ctx, dptr.data(), w, h, ws, n, h9s, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
+    if (rc != MI355_OK) return rc;
+    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+}
+
+extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                         const int* ws, int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch,
+                                         int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || n <= 0 || (!imgs && !img_ids)) { ctx->set_error("mosaic_blended_into: bad arguments"); return MI355_ERR_ARG; }
+    int lw = 0, lh = 0;
+    int rc = mi_blend_layout(w, h, n, h9s, keep, &lw, &lh);
+    if (rc != MI355_OK) return rc;
+    const int lws = (lw * 3 + 3) & ~3;
+    rc = check_dst(ctx, "mosaic_blended_into", dst, dst_pitch, cw, ch, lw, lh);
+    if (rc != MI355_OK) return rc;
+    std::vector<char> skip((size_t)n);
+    for (int k = 0; k < n; k++) skip[k] = (keep && !keep[k]) || h9s[9 * k + 8] == 0.0f;
+    std::vector<const uint8_t*> dptr;
+    rc = render_sources(ctx, "mosaic_blended_into", imgs, img_ids, w, h, ws, n, skip, dptr);
+    if (rc != MI355_OK) return rc;
+    DevBuf& dcan = ctx->buf("into_canvas");
+    MI_HIP(dcan.reserve((size_t)lws * lh));
+    rc = mi_mosaic_blended_dev(ctx, dptr.data(), w, h, ws, n, h9s, keep, band, dcan.as<uint8_t>(), lw, lh, lws);
+    if (rc != MI355_OK) return rc;
+    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+}

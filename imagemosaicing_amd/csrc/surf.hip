@@ -802,10 +802,17 @@ extern "C" int mi355_surf_extract(mi355_ctx* ctx, int img_id, const uint8_t* bgr
     LOCKED_PROLOGUE
     int n = 0;
     if (!bgr || w < 16 || h < 16 || width_step < 3 * w) { ctx->set_error("surf_extract: bad image geometry"); return MI355_ERR_ARG; }
-    DevBuf& dimg = ctx->buf("surf_host_img");
-    MI_HIP(dimg.reserve((size_t)width_step * h + 16));
-    MI_HIP(hipMemcpyAsync(dimg.p, bgr, (size_t)width_step * h, hipMemcpyHostToDevice, ctx->stream));
-    int rc = surf_extract_dev(ctx, img_id, dimg.as<uint8_t>(), w, h, width_step, hessian_threshold, max_kp, &n);
+    uint8_t* dsrc = nullptr;
+    if (ctx->keep_frames) {                  // option "keep_frames": the frame's upload is kept under img_id for the render calls
+        const int rc = mi_kept_frame_slot(ctx, img_id, w, h, width_step, "surf_extract", &dsrc);
+        if (rc != MI355_OK) return rc;
+    } else {
+        DevBuf& dimg = ctx->buf("surf_host_img");
+        MI_HIP(dimg.reserve((size_t)width_step * h + 16));
+        dsrc = dimg.as<uint8_t>();
+    }
+    MI_HIP(hipMemcpyAsync(dsrc, bgr, (size_t)width_step * h, hipMemcpyHostToDevice, ctx->stream));
+    int rc = surf_extract_dev(ctx, img_id, dsrc, w, h, width_step, hessian_threshold, max_kp, &n);
     if (rc != MI355_OK) return rc;
     if (n_kp) *n_kp = n;
     if (kp || desc128) return surf_get_features_locked(ctx, img_id, kp, desc128, max_kp, nullptr);

@@ -58,6 +58,38 @@ static_assert(sizeof(MI355_NS SfPoint) == sizeof(mi355_sfpoint), "SfPoint layout
 static_assert(sizeof(MI355_NS MatchPointPairs) == sizeof(mi355_match_point_pairs), "MatchPointPairs layout");
 static_assert(sizeof(MI355_NS ImageTransform) == sizeof(mi355_image_transform), "ImageTransform layout");
 
+// MI355_ADAPTOR_KEEP_FRAMES (opt-in): the SIFT and SURF front-ends set "keep_frames" on the context, so that every frame
+// they extract stays in HBM under its image index, and record per index the imageData pointer and geometry they extracted.  The render
+// functions then take image k from its kept frame wherever pImgs[k] still has that pointer and geometry, and upload it otherwise.  This
+// assumes what the reference's driver does (MosaicWithoutPos.cpp:4430-4679): the frames are rendered with the indices they were extracted
+// under and no pixel changes in between.  Without the macro no frame is kept.
+namespace detail {
+struct FrameRecord { const void* data; int w, h, ws; };
+inline std::mutex& frames_mu() { static std::mutex m; return m; }
+inline std::vector<FrameRecord>& frame_records() { static std::vector<FrameRecord> v; return v; }
+inline void record_frame(int i, const void* data, int w, int h, int ws) {
+    std::lock_guard<std::mutex> lk(frames_mu());
+    std::vector<FrameRecord>& v = frame_records();
+    if ((int)v.size() <= i) { FrameRecord none = {NULL, 0, 0, 0}; v.resize((size_t)i + 1, none); }
+    FrameRecord r = {data, w, h, ws};
+    v[(size_t)i] = r;
+}
+// the id to render image k from: k where its kept frame is this very image, -1 (upload) otherwise
+inline int32_t kept_id(int k, const void* data, int w, int h, int ws) {
+    std::lock_guard<std::mutex> lk(frames_mu());
+    const std::vector<FrameRecord>& v = frame_records();
+    if (!data || k >= (int)v.size()) return -1;
+    const FrameRecord& r = v[(size_t)k];
+    return (r.data == data && r.w == w && r.h == h && r.ws == ws) ? k : -1;
+}
+// image k is released (ownership passed to the adaptor): its kept frame goes too, before its address can be reused
+inline void forget_frame(mi355_ctx* c, int k) {
+    std::lock_guard<std::mutex> lk(frames_mu());
+    std::vector<FrameRecord>& v = frame_records();
+    if (k < (int)v.size() && v[(size_t)k].data) { v[(size_t)k].data = NULL; mi355_drop_frames(c, k); }
+}
+}  // namespace detail
+
 // One process-wide context per device (the reference is a single-process program).  Creation is guarded: the reference calls the
 // per-pair code from up to 8 worker threads at once (MosaicWithoutPos.cpp:5246-5292); the ctx itself is thread-safe per the C ABI.
 inline mi355_ctx* context(int device = 0) {
@@ -189,6 +221,9 @@ inline int GetMatchedPairsOneToAllSIFT_MultiThread(const PoseT* pImgPoses, const
     mi355_ctx* c = context();
     if (!c || !pImgPoses || nImages < 0) return -1;
     std::vector<int32_t> fixed(nImages > 0 ? nImages : 1, 0);
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+    mi355_set_option(c, "keep_frames", 1);
+#endif
     for (int i = 0; i < nImages; i++) {
         const MI355_NS IplImage* im = pImgPoses[i].pImg;
         if (!im) return -1;
@@ -196,6 +231,9 @@ inline int GetMatchedPairsOneToAllSIFT_MultiThread(const PoseT* pImgPoses, const
         // deferred form (no output pointers): the frame is staged in HBM and joins a batch; the match call below waits for the features
         const int rc = mi355_sift_extract(c, i, (const uint8_t*)im->imageData, im->width, im->height, im->widthStep, NULL, NULL, 0, NULL);
         if (rc != MI355_OK) return rc;
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+        detail::record_frame(i, im->imageData, im->width, im->height, im->widthStep);
+#endif
     }
     int n_pairs = 0;
     mi355_pair_schedule(nImages, window, 0, 1, NULL, 0, &n_pairs);
@@ -232,6 +270,9 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
     mi355_ctx* c = context();
     if (!c || !pImgPoses) return -1;
     std::vector<int32_t> fixed(nImages > 0 ? nImages : 1, 0);
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+    mi355_set_option(c, "keep_frames", 1);
+#endif
     for (int i = 0; i < nImages; i++) {
         const MI355_NS IplImage* im = pImgPoses[i].pImg;
         if (!im) return -1;
@@ -239,6 +280,9 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
         int n = 0;
         const int rc = mi355_surf_extract(c, i, (const uint8_t*)im->imageData, im->width, im->height, im->widthStep, (float)minHessian, 1 << 21 /* every keypoint, like the reference */, NULL, NULL, &n);
         if (rc != MI355_OK) return rc;
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+        detail::record_frame(i, im->imageData, im->width, im->height, im->widthStep);
+#endif
     }
     int np = 0;
     mi355_surf_pair_schedule(nImages, NULL, 0, &np);
@@ -272,20 +316,25 @@ inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const 
     if (NULL == pImgPoses || NULL == pRectified || nImages <= 0) return -1;
     mi355_ctx* c = context();
     if (!c) return -2;
-    std::vector<const uint8_t*> imgs(nImages); std::vector<int> w(nImages), h(nImages), ws(nImages); std::vector<float> h9((size_t)9 * nImages);
+    std::vector<const uint8_t*> imgs(nImages); std::vector<int32_t> ids(nImages, -1);
+    std::vector<int> w(nImages), h(nImages), ws(nImages); std::vector<float> h9((size_t)9 * nImages);
     for (int n = 0; n < nImages; n++) {
         const MI355_NS IplImage* im = pImgPoses[n].pImg;
         std::memcpy(&h9[(size_t)9 * n], pRectified[n].h.m, 9 * sizeof(float));
         if (!im) { imgs[n] = NULL; w[n] = h[n] = ws[n] = 0; h9[(size_t)9 * n + 8] = 0.0f; continue; }     // no image: skipped like h.m[8] == 0 (:2256)
         imgs[n] = (const uint8_t*)im->imageData; w[n] = im->width; h[n] = im->height; ws[n] = im->widthStep;
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+        ids[n] = detail::kept_id(n, im->imageData, w[n], h[n], ws[n]);
+#endif
     }
-    uint8_t* canvas = NULL; int cw = 0, ch = 0, cws = 0;
-    const int rc = mi355_mosaic_refined(c, &imgs[0], &w[0], &h[0], &ws[0], nImages, &h9[0], &canvas, &cw, &ch, &cws);
+    if (nImages <= 1) return -2;                                         // mi355_mosaic_refined's convention (MergeImagesRefined, :2164-2167)
+    int cw = 0, ch = 0, cws = 0;
+    int rc = mi355_mosaic_layout(&w[0], &h[0], nImages, &h9[0], &cw, &ch, &cws, NULL);
     if (rc != MI355_OK) return rc == MI355_ERR_ARG ? -1 : -2;
-    MI355_NS IplImage* out = MI355_CREATE_IMAGE_8U(cw, ch, 3);          // :2246-2248
-    if (!out) { mi355_free(canvas); return -2; }
-    for (int y = 0; y < ch; y++) std::memcpy(out->imageData + (size_t)y * out->widthStep, canvas + (size_t)y * cws, (size_t)3 * cw);
-    mi355_free(canvas);
+    MI355_NS IplImage* out = MI355_CREATE_IMAGE_8U(cw, ch, 3);          // :2246-2248; the library renders straight into its rows
+    if (!out) return -2;
+    rc = mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
+    if (rc != MI355_OK) { cvReleaseImage(&out); return rc == MI355_ERR_ARG ? -1 : -2; }
     if (pMosaicResult) cvReleaseImage(&pMosaicResult);
     pMosaicResult = out;
     return 0;
@@ -301,22 +350,28 @@ inline MI355_NS IplImage* LaplacianPyramidBlending(MI355_NS IplImage** pImages, 
     mi355_ctx* c = context();
     if (!c) return NULL;
     for (int i = 0; i < imagesNum; i++) for (int j = 0; j < 6; j++) pImgT[i].m[j] *= resScale;
-    std::vector<const uint8_t*> imgs(imagesNum); std::vector<int> w(imagesNum), h(imagesNum), ws(imagesNum); std::vector<float> h9((size_t)9 * imagesNum);
+    std::vector<const uint8_t*> imgs(imagesNum); std::vector<int32_t> ids(imagesNum, -1);
+    std::vector<int> w(imagesNum), h(imagesNum), ws(imagesNum); std::vector<float> h9((size_t)9 * imagesNum);
     for (int n = 0; n < imagesNum; n++) {
         std::memcpy(&h9[(size_t)9 * n], pImgT[n].m, 9 * sizeof(float));
         if (!pImages[n]) { imgs[n] = NULL; w[n] = h[n] = 2; ws[n] = 8; h9[(size_t)9 * n + 8] = 0.0f; continue; }
         imgs[n] = (const uint8_t*)pImages[n]->imageData; w[n] = pImages[n]->width; h[n] = pImages[n]->height; ws[n] = pImages[n]->widthStep;
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+        ids[n] = detail::kept_id(n, pImages[n]->imageData, w[n], h[n], ws[n]);
+#endif
     }
     std::vector<uint8_t> keep(imagesNum, 1);
     MI355_NS IplImage* result = NULL;
-    if (mi355_resample_by_overlap(&w[0], &h[0], imagesNum, &h9[0], 0.7f, &keep[0]) == MI355_OK) {
-        uint8_t* out = NULL; int ow = 0, oh = 0, ows = 0;
-        if (mi355_mosaic_blended(c, &imgs[0], &w[0], &h[0], &ws[0], imagesNum, &h9[0], &keep[0], band, &out, &ow, &oh, &ows) == MI355_OK) {
-            result = MI355_CREATE_IMAGE_8U(ow, oh, 3);
-            if (result) for (int y = 0; y < oh; y++) std::memcpy(result->imageData + (size_t)y * result->widthStep, out + (size_t)y * ows, (size_t)3 * ow);
-            mi355_free(out);
-        }
+    int ow = 0, oh = 0;
+    if (mi355_resample_by_overlap(&w[0], &h[0], imagesNum, &h9[0], 0.7f, &keep[0]) == MI355_OK &&
+        mi355_blend_layout(&w[0], &h[0], imagesNum, &h9[0], &keep[0], &ow, &oh, NULL) == MI355_OK) {
+        result = MI355_CREATE_IMAGE_8U(ow, oh, 3);                        // the library renders straight into its rows
+        if (result && mi355_mosaic_blended_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], imagesNum, &h9[0], &keep[0], band,
+                                                (uint8_t*)result->imageData, result->widthStep, ow, oh) != MI355_OK) cvReleaseImage(&result);
     }
+#ifdef MI355_ADAPTOR_KEEP_FRAMES
+    for (int n = 0; n < imagesNum; n++) if (pImages[n]) detail::forget_frame(c, n);
+#endif
     for (int n = 0; n < imagesNum; n++) cvReleaseImage(&pImages[n]);     // :2464-2467: the sources are gone whatever happened
     return result;
 }

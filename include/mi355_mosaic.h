@@ -108,7 +108,11 @@ int  mi355_synchronize(mi355_ctx* ctx);
  * first three levels in one pass, handed from wave to wave through LDS and written to HBM once, the other levels on their own
  * (+4 % end to end); 2: the other three in a second such pass; 1: all six in one pass.  The same bits in every mode (2 and 1 are
  * VALU-issue-bound and no faster end to end on MI355X); "profile_every:<class>" = n (measurement only, default 1): with
- * mi355_profile_enable only every n-th launch of that kernel class is bracketed by events (the average duration is then a sample). */
+ * mi355_profile_enable only every n-th launch of that kernel class is bracketed by events (the average duration is then a sample);
+ * "keep_frames" = 1 (default 0): host-frame extractions keep their HBM copy (see mi355_get_frame_dev); "download_chunk_mb" (default 64):
+ * bytes per chunk, in MB, of the _into calls' canvas download; "download_threads" (1..16, default 4): host threads that copy a downloaded
+ * chunk into the caller's rows; "download_mode" (measurement only, default 0): 1 copies with hipMemcpy2DAsync straight into dst,
+ * 2 page-locks dst with hipHostRegister for that copy (the same bytes in every mode). */
 int  mi355_set_option(mi355_ctx* ctx, const char* name, int value);
 void mi355_free(void* p);                               /* frees host buffers returned by this library */
 
@@ -224,6 +228,33 @@ int  mi355_mosaic_blended_rows_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs,
                                    const uint8_t* keep, int band, uint8_t* d_rows, int cw, int ch, int cws, int row0, int rows);
 /* canvas size of LaplacianPyramidBlending for these transforms (MosaicImage.cpp:2233-2292; host geometry, no ctx) */
 int  mi355_blend_layout(const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, int* cw, int* ch, int* cws);
+
+/* ---- frames kept in HBM after extraction, renders into caller memory ----------------------------------------------------
+ * The reference's driver extracts features from pImgPoses[i].pImg and later renders the same images with the same indices
+ * (MosaicWithoutPos.cpp:4430-4679) without changing a pixel in between.  With mi355_set_option(ctx, "keep_frames", 1) every host-frame
+ * extraction -- mi355_sift_extract in both forms, mi355_surf_extract -- keeps its HBM copy of the frame under img_id with its w, h and
+ * width_step, so that the render needs no second upload.  A later extraction under the same id replaces the frame (after any batch that
+ * still reads the old one).  The copy is taken when the extraction is called: changing the caller's pixels afterwards does NOT change
+ * what a render through img_ids sees.  No HBM for the copy: the extraction fails with MI355_ERR_NOMEM.  Features are the same bits with
+ * the option on or off.  Kept frames live until mi355_drop_frames or mi355_destroy (mi355_drop_features leaves them alone). */
+/* releases the kept frame of img_id (img_id < 0: all of them), after any work that still reads it */
+int  mi355_drop_frames(mi355_ctx* ctx, int img_id);
+/* the device pointer and geometry of a kept frame (MI355_ERR_ARG when img_id holds none), complete on return and valid until the frame
+ * is replaced or dropped: device frames for mi355_mosaic_refined_dev, mi355_mosaic_blended_rows_dev, mi355_exchange_frames */
+int  mi355_get_frame_dev(mi355_ctx* ctx, int img_id, const uint8_t** d_frame, int* w, int* h, int* ws);
+/* mi355_mosaic_refined / mi355_mosaic_blended, written into the caller's host memory.  Image k comes from the kept frame of img_ids[k]
+ * when img_ids != NULL and img_ids[k] >= 0 (imgs[k] may then be NULL; MI355_ERR_ARG naming k and the id when the id holds no kept frame
+ * or its geometry differs from w, h, ws[k]), from the host image imgs[k] otherwise.  Images the render skips (h9s[9k+8] == 0; for the
+ * blended form also keep[k] == 0) are neither read nor checked.  dst: ch rows of dst_pitch >= 3 * cw bytes (pageable memory is fine);
+ * cw, ch must be what mi355_mosaic_layout / mi355_blend_layout return for the same arguments (else MI355_ERR_ARG).  Bytes [0, 3 * cw)
+ * of every row are written, the rest of each row is left untouched; the bytes are those of mi355_mosaic_refined / mi355_mosaic_blended
+ * whatever mix of sources is used.  The canvas is rendered in HBM and comes back in row chunks through pinned buffers of the ctx
+ * ("download_chunk_mb"); no host buffer of the canvas's size is allocated.  Returns when dst is complete.  n <= 1 in the refined form:
+ * MI355_ERR_FAILED, as mi355_mosaic_refined. */
+int  mi355_mosaic_refined_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                               int n, const float* h9s, uint8_t* dst, int dst_pitch, int cw, int ch);
+int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                               int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 
 /* ---- callers / formats either side of the path ("next" rows f1, f2 of SURVEY 8f) ---------------------- */
 /* matchPairs.match: int32 n + n x 40-byte records (WriteMatchPairs / LoadMatchPairs, MosaicWithoutPos.cpp:4736-4797) */

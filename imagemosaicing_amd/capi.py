@@ -22,6 +22,11 @@ IMAGE_TRANSFORM = np.dtype([("m", "<f4", (9,)), ("fixed", "<i4")])
 PAIR_MOMENTS = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("_pad", "<i4"), ("aa", "<f8", (6,)), ("ab", "<f8", (9,)), ("bb", "<f8", (6,))])
 FEATURE_HEADER = np.dtype([("img_id", "<i4"), ("n_kp", "<i4"), ("w", "<i4"), ("h", "<i4")])
 FEATURE_RECORD_BYTES = 319488
+# one chunk record of a frame's rows [row0, row0 + rows) (mi355_feature_chunk_header): a frame of n_kp keypoints takes max(1, ceil(n_kp / 2048))
+FEATURE_CHUNK_HEADER = np.dtype([("img_id", "<i4"), ("n_kp", "<i4"), ("w", "<i4"), ("h", "<i4"), ("chunk", "<i4"), ("n_chunks", "<i4"),
+                                 ("row0", "<i4"), ("rows", "<i4")])
+FEATURE_CHUNK_ROWS = 2048
+assert FEATURE_CHUNK_HEADER.itemsize == 32
 assert SFPOINT.itemsize == 12 and KEYPOINT.itemsize == 28 and MATCHPAIR.itemsize == 40 and PAIR_RESULT.itemsize == 9664 and PAIR_MOMENTS.itemsize == 184
 
 
@@ -315,6 +320,27 @@ class Context:
         hdr = np.ascontiguousarray(hdr, FEATURE_HEADER)
         self._chk(self.L.mi355_install_features_dev(self._h, _p(hdr), C.c_void_p(int(d_payload)), len(hdr)))
 
+    def FeatureChunkCount(self, img_ids):
+        """the chunk records the resident features of img_ids take (sum of max(1, ceil(n_kp / 2048)))"""
+        ids = np.ascontiguousarray(img_ids, np.int32)
+        n = C.c_int(0)
+        self._chk(self.L.mi355_feature_chunk_count(self._h, _p(ids), len(ids), C.byref(n)))
+        return n.value
+
+    def PackFeatureChunksDev(self, img_ids, d_payload, max_records):
+        """resident features of img_ids (any keypoint count) -> chunk records at d_payload (device, max_records x FEATURE_RECORD_BYTES);
+        returns the FEATURE_CHUNK_HEADER array of the records written"""
+        ids = np.ascontiguousarray(img_ids, np.int32)
+        hdr = np.zeros(max(int(max_records), 1), FEATURE_CHUNK_HEADER)
+        n = C.c_int(0)
+        self._chk(self.L.mi355_pack_feature_chunks_dev(self._h, _p(ids), len(ids), _p(hdr), C.c_void_p(int(d_payload) or None), int(max_records), C.byref(n)))
+        return hdr[:n.value].copy()
+
+    def InstallFeatureChunksDev(self, hdr, d_payload):
+        """chunk records -> resident features (the whole table is checked first: a bad one raises and changes nothing)"""
+        hdr = np.ascontiguousarray(hdr, FEATURE_CHUNK_HEADER)
+        self._chk(self.L.mi355_install_feature_chunks_dev(self._h, _p(hdr), C.c_void_p(int(d_payload) or None), len(hdr)))
+
     def CompactAcceptedDev(self, d_in, n, d_out):
         k = C.c_int(0)
         self._chk(self.L.mi355_compact_accepted_dev(self._h, C.c_void_p(int(d_in)), int(n), C.c_void_p(int(d_out)), C.byref(k)))
@@ -342,6 +368,12 @@ class Context:
     def AllGatherFeatures(self, img_ids, n_max_per_rank):
         ids = np.ascontiguousarray(img_ids, np.int32)
         self._chk(self.L.mi355_allgather_features(self._h, _p(ids), len(ids), int(n_max_per_rank)))
+
+    def AllGatherFeatureChunks(self, img_ids, install_own=False):
+        """mi355_allgather_feature_chunks: the features of every rank's frames, any keypoint count, resident on every rank afterwards.
+        install_own: this rank's own frames are re-installed from the received records too."""
+        ids = np.ascontiguousarray(img_ids, np.int32)
+        self._chk(self.L.mi355_allgather_feature_chunks(self._h, _p(ids), len(ids), 1 if install_own else 0))
 
     def AllGatherResults(self, d_local, n_local, accepted_only=True, root=-1, copy=True, wait=True):
         """mi355_allgather_results.  root < 0: every rank receives all ranks' records; root >= 0: only that rank (the others send and

@@ -21,6 +21,7 @@
 // The pack / install halves are separate entry points so that a caller with its own transport (the gloo CPU tests, MPI)
 // moves the same records.
 #include "common.h"
+#include <algorithm>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -301,6 +302,217 @@ extern "C" int mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_he
     return install_features(ctx, hdr, d_payload, n, nullptr, 0);
 }
 
+// ---- chunk records (frames of any keypoint count: keep-all, <= 32768 rows) ---------------------------------------------------------------
+// A frame travels as max(1, ceil(n / 2048)) records of the fixed layout, chunk c holding rows [row0, row0 + rows): a frame of <= 2048 keypoints
+// is ONE chunk, byte for byte the record above, so a transport that moves fixed records keeps one record size.
+static_assert(sizeof(mi355_feature_chunk_header) == 32, "feature chunk header");
+static_assert(MI355_FEATURE_CHUNK_ROWS * sizeof(mi355_keypoint) == REC_KP_BYTES && MI355_FEATURE_CHUNK_ROWS * 128 == REC_D8_BYTES, "chunk rows");
+static_assert((MI355_FEATURE_CHUNK_ROWS * sizeof(mi355_keypoint)) % 16 == 0, "a chunk's keypoints start 16-byte aligned");
+
+struct ChunkSrc { const uint8_t* kp; const uint8_t* d8; int row0, rows; };
+
+// pack_features_kernel with a row window: one workgroup column per chunk record (blockIdx.y), a lane per 16 bytes, zero fill beyond `rows`.
+// The grid's x extent covers a record in one pass (78 workgroups of 256 lanes), so every lane moves one 16-byte piece.
+__global__ __launch_bounds__(256) void pack_feature_chunks_kernel(const ChunkSrc* src, uint8_t* payload) {
+    const ChunkSrc s = src[blockIdx.y];
+    uint4* dst = reinterpret_cast<uint4*>(payload + (size_t)blockIdx.y * MI355_FEATURE_RECORD_BYTES);
+    const uint8_t* kp = s.kp + (size_t)s.row0 * sizeof(mi355_keypoint);     // row0 is a multiple of 2048: 16-byte aligned
+    const uint8_t* d8 = s.d8 + (size_t)s.row0 * 128;
+    const size_t kp_bytes = (size_t)s.rows * sizeof(mi355_keypoint), d8_bytes = (size_t)s.rows * 128;
+    const size_t total16 = MI355_FEATURE_RECORD_BYTES / 16;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < total16; q += (size_t)gridDim.x * 256) {
+        const size_t b = q * 16;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (b < REC_KP_BYTES) {
+            if (b + 16 <= kp_bytes) v = *reinterpret_cast<const uint4*>(kp + b);
+            else if (b < kp_bytes) { uint8_t t[16] = {0}; for (size_t i = 0; b + i < kp_bytes; i++) t[i] = kp[b + i]; v = *reinterpret_cast<uint4*>(t); }
+        } else {
+            const size_t o = b - REC_D8_OFF;
+            if (o + 16 <= d8_bytes) v = *reinterpret_cast<const uint4*>(d8 + o);      // d8_bytes is a multiple of 128
+        }
+        dst[q] = v;
+    }
+}
+
+// install_features_kernel by chunk: one launch for every received chunk (blockIdx.y).  Record row r lands at image row row0 + r; the record
+// that holds an image's last chunk also writes the padding rows [n, npad) of s8 / n8 (lim = npad - row0 there, rows elsewhere).
+struct ChunkDst { const uint8_t* rec; mi355_keypoint* kp; uint8_t* d8; float2* xy; int8_t* s8; int* n8; int row0, rows, lim, _pad; };
+
+__global__ __launch_bounds__(256) void install_feature_chunks_kernel(const ChunkDst* tab) {
+    const ChunkDst t = tab[blockIdx.y];
+    const int r = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;      // 8 lanes per descriptor row, 16 bytes each
+    if (r >= t.lim) return;
+    const size_t row = (size_t)t.row0 + r;
+    uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);          // padding rows: zeros after the shift
+    if (r < t.rows) {
+        v = *reinterpret_cast<const uint4*>(t.rec + REC_D8_OFF + (size_t)r * 128 + part * 16);
+        *reinterpret_cast<uint4*>(t.d8 + row * 128 + part * 16) = v;
+    }
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    int s = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) { const int u = (int)((w[q] >> (8 * b)) & 0xffu) - 128; s += u * u; }
+    *reinterpret_cast<uint4*>(t.s8 + row * 128 + part * 16) = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
+    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
+    if (part == 0) t.n8[row] = s;
+    if (r < t.rows && part < 7) {
+        const unsigned kw = reinterpret_cast<const unsigned*>(t.rec + (size_t)r * sizeof(mi355_keypoint))[part];
+        reinterpret_cast<unsigned*>(t.kp + row)[part] = kw;
+        if (part < 2) reinterpret_cast<unsigned*>(t.xy + row)[part] = kw;                 // x, y are the first two fields
+    }
+}
+
+static int chunks_of(int n_kp) { return n_kp > 0 ? (n_kp + MI355_FEATURE_CHUNK_ROWS - 1) / MI355_FEATURE_CHUNK_ROWS : 1; }
+
+// caller holds the ctx lock and has resolved pending extractions
+static int count_chunks(mi355_ctx* ctx, const char* who, const int32_t* img_ids, int n, int* n_records) {
+    long long total = 0;
+    for (int k = 0; k < n; k++) {
+        auto it = ctx->feats.find(img_ids[k]);
+        if (it == ctx->feats.end()) { ctx->set_error(std::string(who) + ": no resident features for image " + std::to_string(img_ids[k])); return MI355_ERR_ARG; }
+        const int nk = it->second.n;
+        if (nk < 0 || nk > MI355_SIFT_KEEPALL_MAX) { ctx->set_error(std::string(who) + ": image " + std::to_string(img_ids[k]) + " has more than 32768 keypoints"); return MI355_ERR_ARG; }
+        total += chunks_of(nk);
+    }
+    if (total > 0x7fffffffLL) { ctx->set_error(std::string(who) + ": too many records"); return MI355_ERR_ARG; }
+    *n_records = (int)total;
+    return MI355_OK;
+}
+
+// headers to the host array, the pack enqueued on the ctx stream; `src_buf`: the device table (reserved here, before anything is enqueued)
+static int pack_chunks(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_chunk_header* hdr, uint8_t* d_payload, int n_records) {
+    if (n_records == 0) return MI355_OK;
+    std::vector<ChunkSrc> src;
+    src.reserve(n_records);
+    for (int k = 0; k < n; k++) {
+        const Features& f = ctx->feats.find(img_ids[k])->second;          // count_chunks found every id
+        const int nc = chunks_of(f.n);
+        for (int c = 0; c < nc; c++) {
+            mi355_feature_chunk_header& h = hdr[src.size()];
+            const int row0 = c * MI355_FEATURE_CHUNK_ROWS, rows = f.n - row0 < MI355_FEATURE_CHUNK_ROWS ? f.n - row0 : MI355_FEATURE_CHUNK_ROWS;
+            h.img_id = img_ids[k]; h.n_kp = f.n; h.w = f.w; h.h = f.h; h.chunk = c; h.n_chunks = nc; h.row0 = row0; h.rows = rows > 0 ? rows : 0;
+            src.push_back(ChunkSrc{f.kp.as<uint8_t>(), f.d8.as<uint8_t>(), row0, h.rows});
+        }
+    }
+    DevBuf& dsrc = ctx->buf("pack_chunk_src");
+    MI_HIP(dsrc.reserve(sizeof(ChunkSrc) * src.size()));
+    MI_HIP(hipMemcpyAsync(dsrc.p, src.data(), sizeof(ChunkSrc) * src.size(), hipMemcpyHostToDevice, ctx->stream));
+    constexpr unsigned GX = (MI355_FEATURE_RECORD_BYTES / 16 + 255) / 256;
+    {
+        ProfScope ps(ctx, "feature_pack", 2.0 * (double)MI355_FEATURE_RECORD_BYTES * (double)src.size());
+        hipLaunchKernelGGL(pack_feature_chunks_kernel, dim3(GX, (unsigned)src.size()), dim3(256), 0, ctx->stream, dsrc.as<ChunkSrc>(), d_payload);
+    }
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // `src` goes out of scope
+    return MI355_OK;
+}
+
+extern "C" int mi355_feature_chunk_count(mi355_ctx* ctx, const int32_t* img_ids, int n, int* n_records) {
+    LOCKED_PROLOGUE
+    if (n < 0 || !n_records || (n > 0 && !img_ids)) return MI355_ERR_ARG;
+    *n_records = 0;
+    { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
+    return count_chunks(ctx, "feature_chunk_count", img_ids, n, n_records);
+}
+
+extern "C" int mi355_pack_feature_chunks_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_chunk_header* hdr, void* d_payload,
+                                             int max_records, int* n_records) {
+    LOCKED_PROLOGUE
+    if (n < 0 || max_records < 0 || !n_records || (n > 0 && !img_ids)) return MI355_ERR_ARG;
+    *n_records = 0;
+    { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
+    int nr = 0;
+    { int rc = count_chunks(ctx, "pack_feature_chunks", img_ids, n, &nr); if (rc != MI355_OK) return rc; }
+    if (nr > max_records) { ctx->set_error("pack_feature_chunks: " + std::to_string(nr) + " records do not fit in max_records = " + std::to_string(max_records)); return MI355_ERR_ARG; }
+    if (nr > 0 && (!hdr || !d_payload)) return MI355_ERR_ARG;
+    { int rc = pack_chunks(ctx, img_ids, n, hdr, reinterpret_cast<uint8_t*>(d_payload), nr); if (rc != MI355_OK) return rc; }
+    *n_records = nr;
+    return MI355_OK;
+}
+
+// Checks the whole table, then installs it (one launch).  Records with img_id < 0 and the images in skip_ids are left out.  Nothing of the
+// ctx's features changes before every image of the table has passed (missing / duplicate chunks, disagreeing headers, rows that do not tile).
+static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n, const int32_t* skip_ids, int n_skip) {
+    std::map<int, std::vector<int>> by_img;              // image -> its records, in chunk order after the sort
+    for (int k = 0; k < n; k++) {
+        const mi355_feature_chunk_header& h = hdr[k];
+        if (h.img_id < 0) continue;
+        bool skip = false;
+        for (int q = 0; q < n_skip; q++) if (skip_ids[q] == h.img_id) { skip = true; break; }
+        if (!skip) by_img[h.img_id].push_back(k);
+    }
+    auto bad = [&](int img, const std::string& why) { ctx->set_error("install_feature_chunks: image " + std::to_string(img) + ": " + why); return MI355_ERR_ARG; };
+    for (auto& kv : by_img) {
+        std::vector<int>& ks = kv.second;
+        const mi355_feature_chunk_header& h0 = hdr[ks[0]];
+        if (h0.n_kp < 0 || h0.n_kp > MI355_SIFT_KEEPALL_MAX) return bad(kv.first, "n_kp outside [0, 32768]");
+        if (h0.w <= 0 || h0.h <= 0) return bad(kv.first, "bad image size");
+        if (h0.n_chunks < 1 || h0.n_chunks != (int)ks.size()) return bad(kv.first, "n_chunks = " + std::to_string(h0.n_chunks) + " but " + std::to_string(ks.size()) + " records");
+        for (int k : ks) {
+            const mi355_feature_chunk_header& h = hdr[k];
+            if (h.n_kp != h0.n_kp || h.w != h0.w || h.h != h0.h || h.n_chunks != h0.n_chunks) return bad(kv.first, "chunks disagree on n_kp / w / h / n_chunks");
+            if (h.chunk < 0 || h.chunk >= h0.n_chunks) return bad(kv.first, "chunk index out of range");
+        }
+        std::sort(ks.begin(), ks.end(), [&](int a, int b) { return hdr[a].chunk < hdr[b].chunk; });
+        int next = 0;
+        for (size_t c = 0; c < ks.size(); c++) {
+            const mi355_feature_chunk_header& h = hdr[ks[c]];
+            if (h.chunk != (int)c) return bad(kv.first, "chunk " + std::to_string(c) + " missing or duplicated");
+            const bool empty_frame = h0.n_kp == 0;
+            if (h.row0 != next || h.rows > MI355_FEATURE_CHUNK_ROWS || (empty_frame ? h.rows != 0 : h.rows < 1)) return bad(kv.first, "rows do not tile [0, n_kp)");
+            next += h.rows;
+        }
+        if (next != h0.n_kp) return bad(kv.first, "rows do not tile [0, n_kp)");
+    }
+    if (by_img.empty()) return MI355_OK;
+    // the table is good: resident buffers (grow only: sized for 2048 rows at least, like install_features), then one launch
+    std::vector<ChunkDst> tab;
+    tab.reserve(n);
+    int max_lim = 0;
+    for (auto& kv : by_img) {
+        const mi355_feature_chunk_header& h0 = hdr[kv.second[0]];
+        Features& f = ctx->feats[kv.first];
+        const int npad = h0.n_kp > 0 ? ((h0.n_kp + 255) / 256) * 256 : 256;
+        const size_t cap = (size_t)(npad > 2048 ? npad : 2048);
+        MI_HIP(f.kp.reserve(sizeof(mi355_keypoint) * cap));
+        MI_HIP(f.d8.reserve((size_t)128 * cap));
+        MI_HIP(f.xy.reserve(sizeof(float2) * cap));
+        MI_HIP(f.s8.reserve((size_t)128 * cap));
+        MI_HIP(f.n8.reserve(sizeof(int) * cap));
+        f.n = h0.n_kp; f.w = h0.w; f.h = h0.h; f.pending = false; f.h_cnt = nullptr; f.npad = npad;
+        for (size_t c = 0; c < kv.second.size(); c++) {
+            const int k = kv.second[c];
+            const mi355_feature_chunk_header& h = hdr[k];
+            ChunkDst t;
+            t.rec = reinterpret_cast<const uint8_t*>(d_payload) + (size_t)k * MI355_FEATURE_RECORD_BYTES;
+            t.kp = f.kp.as<mi355_keypoint>(); t.d8 = f.d8.as<uint8_t>(); t.xy = f.xy.as<float2>(); t.s8 = f.s8.as<int8_t>(); t.n8 = f.n8.as<int>();
+            t.row0 = h.row0; t.rows = h.rows; t._pad = 0;
+            t.lim = c + 1 == kv.second.size() ? npad - h.row0 : h.rows;        // the last chunk also writes the padding rows [n, npad)
+            if (t.lim > max_lim) max_lim = t.lim;
+            tab.push_back(t);
+        }
+    }
+    DevBuf& dtab = ctx->buf("install_chunk_tab");
+    MI_HIP(dtab.reserve(sizeof(ChunkDst) * tab.size()));
+    MI_HIP(hipMemcpyAsync(dtab.p, tab.data(), sizeof(ChunkDst) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, "feature_install", 2.0 * (double)MI355_FEATURE_RECORD_BYTES * (double)tab.size());
+        hipLaunchKernelGGL(install_feature_chunks_kernel, dim3((unsigned)((max_lim + 31) / 32), (unsigned)tab.size()), dim3(256), 0, ctx->stream, dtab.as<ChunkDst>());
+    }
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // `tab` goes out of scope; the caller may reuse d_payload
+    return MI355_OK;
+}
+
+extern "C" int mi355_install_feature_chunks_dev(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n_records) {
+    LOCKED_PROLOGUE
+    if (n_records < 0 || (n_records > 0 && (!hdr || !d_payload))) return MI355_ERR_ARG;
+    { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }     // an extraction in flight must not land on installed rows
+    return install_chunks(ctx, hdr, d_payload, n_records, nullptr, 0);
+}
+
 // ---- communicator ------------------------------------------------------------------------------------------------------------
 extern "C" int mi355_comm_unique_id(uint8_t id128[128]) {
     if (!id128) return MI355_ERR_ARG;
@@ -414,6 +626,69 @@ extern "C" int mi355_allgather_features(mi355_ctx* ctx, const int32_t* img_ids, 
     for (int r = 0; r < world; r++)
         if (hdr[nm * r].img_id == -2) { ctx->set_error("allgather_features: rank " + std::to_string(r) + " failed before the exchange"); return MI355_ERR_FAILED; }
     return install_features(ctx, hdr.data(), dpay.p, (int)(nm * world), img_ids, n_local);      // own frames are resident already
+}
+
+// The chunk-record form: no n_max, the counts travel first.  Two small all-gathers of {records, status} carry every rank-local outcome -- the
+// count (unknown ids), then the reservation of world x R records and this rank's pack -- so that a failure anywhere makes every rank return
+// together before any payload moves; after the second one nothing allocates and nothing can fail on one rank alone until the payload is here.
+extern "C" int mi355_allgather_feature_chunks(mi355_ctx* ctx, const int32_t* img_ids, int n_local, int flags) {
+    LOCKED_PROLOGUE
+    if (!ctx->comm) { ctx->set_error("allgather_feature_chunks: no communicator (mi355_comm_init)"); return MI355_ERR_ARG; }
+    RcclApi* api = rccl_api();
+    const int world = ctx->comm->world, rank = ctx->comm->rank;
+    DevBuf& dctl = ctx->buf("agc_ctl");                  // [world] x {records, status}
+    MI_HIP(dctl.reserve(sizeof(int) * 2 * (size_t)world));
+    int* d_ctl = dctl.as<int>();
+    std::vector<int> ctl(2 * (size_t)world);
+    std::string err_local;
+    int rc_local = MI355_OK;
+    // exchange {n, status} of every rank; returns MI355_OK when every rank reported success, else the error to return on this rank
+    auto gather_status = [&](int n, int rc, const char* step) -> int {
+        const int mine[2] = {n, rc};
+        MI_HIP(hipMemcpyAsync(d_ctl + 2 * rank, mine, sizeof(mine), hipMemcpyHostToDevice, ctx->stream));
+        MI_NCCL(api->AllGather(d_ctl + 2 * rank, d_ctl, sizeof(int) * 2, ncclChar, ctx->comm->comm, ctx->stream));
+        MI_HIP(hipMemcpyAsync(ctl.data(), d_ctl, sizeof(int) * 2 * (size_t)world, hipMemcpyDeviceToHost, ctx->stream));
+        MI_HIP(hipStreamSynchronize(ctx->stream));       // (`mine` is consumed)
+        if (rc != MI355_OK) { ctx->set_error(err_local); return rc; }
+        for (int r = 0; r < world; r++)
+            if (ctl[2 * r + 1] != MI355_OK) { ctx->set_error(std::string("allgather_feature_chunks: rank ") + std::to_string(r) + " failed " + step); return MI355_ERR_FAILED; }
+        return MI355_OK;
+    };
+    // 1. local: the ids, the count
+    int n_rec = 0;
+    if (n_local < 0 || (n_local > 0 && !img_ids)) { ctx->set_error("allgather_feature_chunks: bad arguments"); rc_local = MI355_ERR_ARG; }
+    if (rc_local == MI355_OK) rc_local = mi_resolve_features(ctx);
+    if (rc_local == MI355_OK) rc_local = count_chunks(ctx, "allgather_feature_chunks", img_ids, n_local, &n_rec);
+    if (rc_local != MI355_OK) { err_local = ctx->err; n_rec = 0; }
+    // 2. {records, status} of every rank
+    { const int rc = gather_status(n_rec, rc_local, "before the exchange"); if (rc != MI355_OK) return rc; }
+    size_t R = 1;
+    for (int r = 0; r < world; r++) if ((size_t)ctl[2 * r] > R) R = (size_t)ctl[2 * r];
+    // 3. world x R records and headers; this rank's block packed (padding records: img_id = -1)
+    DevBuf& dhdr = ctx->buf("agc_hdr");
+    DevBuf& dpay = ctx->buf("agc_payload");
+    std::vector<mi355_feature_chunk_header> hdr(R * world);
+    mi355_feature_chunk_header* my_hdr = hdr.data() + R * rank;
+    auto reserve_and_pack = [&]() -> int {
+        MI_HIP(dhdr.reserve(sizeof(mi355_feature_chunk_header) * R * world));
+        MI_HIP(dpay.reserve((size_t)MI355_FEATURE_RECORD_BYTES * R * world));
+        for (size_t k = 0; k < R; k++) { my_hdr[k] = mi355_feature_chunk_header{-1, 0, 0, 0, 0, 0, 0, 0}; }
+        { const int rc = pack_chunks(ctx, img_ids, n_local, my_hdr, dpay.as<uint8_t>() + (size_t)MI355_FEATURE_RECORD_BYTES * R * rank, n_rec); if (rc != MI355_OK) return rc; }
+        MI_HIP(hipMemcpyAsync(dhdr.as<mi355_feature_chunk_header>() + R * rank, my_hdr, sizeof(mi355_feature_chunk_header) * R, hipMemcpyHostToDevice, ctx->stream));
+        return MI355_OK;
+    };
+    rc_local = reserve_and_pack();
+    if (rc_local != MI355_OK) err_local = ctx->err;
+    // 4. every rank ready?
+    { const int rc = gather_status(0, rc_local, "to reserve or pack its records"); if (rc != MI355_OK) return rc; }
+    // 5. in-place all-gathers: this rank's block of the receive buffers is its send buffer
+    MI_NCCL(api->AllGather(dhdr.as<mi355_feature_chunk_header>() + R * rank, dhdr.p, sizeof(mi355_feature_chunk_header) * R, ncclChar, ctx->comm->comm, ctx->stream));
+    MI_NCCL(api->AllGather(dpay.as<uint8_t>() + (size_t)MI355_FEATURE_RECORD_BYTES * R * rank, dpay.p, (size_t)MI355_FEATURE_RECORD_BYTES * R, ncclChar, ctx->comm->comm, ctx->stream));
+    MI_HIP(hipMemcpyAsync(hdr.data(), dhdr.p, sizeof(mi355_feature_chunk_header) * R * world, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    // 6. install: padding records skipped, own frames too unless asked for (every rank checks the same table: a bad one fails everywhere)
+    const bool own = (flags & MI355_FEATURES_INSTALL_OWN) != 0;
+    return install_chunks(ctx, hdr.data(), dpay.p, (int)(R * world), own ? nullptr : img_ids, own ? 0 : n_local);
 }
 
 extern "C" int mi355_allgather_results(mi355_ctx* ctx, const mi355_pair_result* d_local, int n_local, int flags, int root,

@@ -30,7 +30,7 @@
 
 // grow-only device buffer (workspaces live as long as the ctx: no hipMalloc in steady state)
 constexpr int MI355_SIFT_BATCH_MAX = 32;      // frames per SIFT batch (per-frame pointers travel in kernel arguments)
-constexpr int MI355_SIFT_KEEPALL_MAX = 32768;  // keypoints per frame the feature record holds with nfeatures <= 0 (keep all); the matcher takes such frames in chunks of 2048 (match.hip, large-pair path)
+constexpr int MI355_SIFT_KEEPALL_MAX = 32768;  // keypoints per frame the feature record holds with nfeatures <= 0 (keep all); the matcher takes such frames in chunks of 2048 (match.hip, large-pair path), the feature exchange as chunk records of 2048 rows (comm.hip, mi355_allgather_feature_chunks)
 
 struct DevBuf {
     void*  p = nullptr;

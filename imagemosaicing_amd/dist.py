@@ -7,7 +7,8 @@ data path crosses ranks:
 
   features   after detect+describe: all-gather of the fixed-size feature records (keypoints + u8 descriptors, 312 KB per
              frame) -- the reference hands features from the extraction threads to the matcher threads through
-             d:/feature_temp files (:4874-4880 -> :5100-5103)
+             d:/feature_temp files (:4874-4880 -> :5100-5103); keep-all frames (more than 2048 keypoints) as chunk records of
+             2048 rows each in the same layout (allgather_features(..., chunked=True))
   results    after match + select + RANSAC: all-gather of the accepted pair records (H + inlier lists, 9664 B each) that
              feed Select_Connected_Matched_Images / global alignment -- PushMatchPairs under a mutex in the reference
              (:5236, :10137-10145) -- or, for surveys whose records weigh a gigabyte (C5), the records to ONE root rank (the one
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .capi import PAIR_RESULT, FEATURE_HEADER, FEATURE_RECORD_BYTES, comm_unique_id, comm_available
+from .capi import PAIR_RESULT, FEATURE_HEADER, FEATURE_CHUNK_HEADER, FEATURE_RECORD_BYTES, comm_unique_id, comm_available
 
 REC = PAIR_RESULT.itemsize
 
@@ -166,6 +167,23 @@ def allgather_feature_records(hdr, payload, n_max=None):
     return hdrs, gp, counts
 
 
+def allgather_feature_chunk_records(hdr, payload):
+    """torch transport of the chunk-record feature exchange (frames of any keypoint count).  hdr: FEATURE_CHUNK_HEADER array [n_local];
+    payload: uint8 tensor [n_local, FEATURE_RECORD_BYTES].  The record counts are ragged across ranks (a keep-all frame takes up to 16);
+    they are gathered first and the payload is padded to the largest.  Returns (headers [world][count_r], payload uint8 [world, R, REC],
+    counts)."""
+    hdr = np.ascontiguousarray(hdr, FEATURE_CHUNK_HEADER)
+    h = torch.from_numpy(hdr.view(np.uint8).reshape(len(hdr), FEATURE_CHUNK_HEADER.itemsize).copy())
+    if dist.get_backend() == "nccl":
+        h = h.to(payload.device)                       # RCCL moves device tensors only
+    gh, counts = _allgather_rows(h, None)
+    gp, counts2 = _allgather_rows(payload, None)
+    assert counts == counts2
+    gh = gh.cpu()
+    hdrs = [gh[r, :c].contiguous().numpy().reshape(-1).view(FEATURE_CHUNK_HEADER) for r, c in enumerate(counts)]
+    return hdrs, gp, counts
+
+
 def exchange_frames_torch(frames, h, ws, need, owner, rank, world):
     """torch.distributed transport of mi355_exchange_frames (gloo CPU tests, 2-rank dry runs on one device): the same table, walked in
     the same order by every rank -- owner sends, reader receives, frame after frame (a total order: no two ranks ever wait for each other
@@ -228,6 +246,7 @@ class Exchange:
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rccl_ranks = None                         # what the communicator itself reports (ncclCommCount)
         self._payload = None
+        self._chunk_payload = None
         self._recv_frames = {}                         # torch transport of exchange_frames: the received frames, alive until the next call
         if transport == "rccl":
             ok = 1 if comm_available() else 0
@@ -250,8 +269,14 @@ class Exchange:
                     raise RuntimeError("mi355 dist: communicator reports rank %d of %d, expected %d of %d" % (r, n, self.rank, self.world))
                 self.rccl_ranks = n
 
-    def allgather_features(self, own_ids, n_max, device):
-        """afterwards every frame of every rank is resident in this rank's ctx"""
+    def allgather_features(self, own_ids, n_max, device, chunked=False):
+        """afterwards every frame of every rank is resident in this rank's ctx.  chunked=True: frames of any keypoint count (keep-all,
+        nfeatures <= 0) travel as chunk records of 2048 rows (mi355_allgather_feature_chunks / allgather_feature_chunk_records) and n_max is
+        ignored; chunked=False: one fixed record per frame of <= 2048 keypoints.  The choice is collective, like the transport: every rank
+        passes the same value."""
+        if chunked:
+            self._allgather_feature_chunks(own_ids, device)
+            return
         if self.transport == "rccl":
             self.ctx.AllGatherFeatures(own_ids, n_max)
             return
@@ -269,6 +294,38 @@ class Exchange:
                 continue
             block = gp[r].contiguous()
             self.ctx.InstallFeaturesDev(hdrs[r], block.data_ptr())
+
+    def _allgather_feature_chunks(self, own_ids, device):
+        if self.transport == "rccl":
+            self.ctx.AllGatherFeatureChunks(own_ids)
+            return
+        if self.world == 1:
+            return
+        # every rank counts its records first and the outcomes are MIN-reduced: a rank with an unknown id must not leave the others in
+        # the all-gathers
+        err, n_rec = None, 0
+        try:
+            n_rec = self.ctx.FeatureChunkCount(own_ids)
+        except Exception as e:                         # noqa: BLE001 -- re-raised below, on this rank
+            err = e
+        flag = torch.tensor([0 if err is not None else 1], dtype=torch.int32,
+                            device=torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        if err is not None:
+            raise err
+        if not int(flag.item()):
+            raise RuntimeError("mi355 dist: another rank failed before the feature chunk exchange")
+        if self._chunk_payload is None or self._chunk_payload.shape[0] < max(n_rec, 1):
+            self._chunk_payload = torch.empty((max(n_rec, 1), FEATURE_RECORD_BYTES), dtype=torch.uint8, device=device)
+        hdr = self.ctx.PackFeatureChunksDev(own_ids, self._chunk_payload.data_ptr(), n_rec) if n_rec else np.zeros(0, FEATURE_CHUNK_HEADER)
+        hdrs, gp, counts = allgather_feature_chunk_records(hdr, self._chunk_payload[:n_rec])
+        if gp.is_cuda:
+            torch.cuda.current_stream(gp.device).synchronize()     # the ctx stream may be another one: the records must have landed
+        for r in range(self.world):
+            if r == self.rank or counts[r] == 0:
+                continue
+            block = gp[r].contiguous()
+            self.ctx.InstallFeatureChunksDev(hdrs[r], block.data_ptr())
 
     def allgather_results(self, results, n_local, accepted_only=True, root=-1, copy=True, wait=True):
         """results: uint8 device tensor [>= n_local, 9664] written by MatchPairsDev.  root < 0: returns all ranks' records (numpy, rank-major)

@@ -69,7 +69,8 @@ typedef struct {
 typedef struct {
     int32_t nfeatures;         /* 2000   SIFT(2000,3,0.01,20)            MosaicWithoutPos.cpp:4852; 1 .. 2048, or <= 0 = cv::SIFT's keep-all
                                   (CVI/nonfree/features2d.hpp:61: every keypoint, OpenCV's generation order, <= 32768 per frame; what the
-                                  reference's committed run used; such frames can be read back but the matcher takes <= 2048 keypoints) */
+                                  reference's committed run used; the matcher takes such frames through its large-pair path, and the
+                                  multi-GPU feature exchange carries them as chunk records, mi355_allgather_feature_chunks) */
     int32_t n_octave_layers;   /* 3 */
     float   contrast_threshold;/* 0.01 */
     float   edge_threshold;    /* 20 */
@@ -339,6 +340,31 @@ typedef struct { int32_t img_id /* < 0: padding record */, n_kp, w, h; } mi355_f
  * transport (MPI, the gloo CPU tests); mi355_allgather_features does both around one RCCL all-gather. */
 int  mi355_pack_features_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_header* hdr, void* d_payload);
 int  mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n);
+
+/* Chunk records: the feature exchange of frames of any keypoint count (keep-all frames, nfeatures <= 0, hold up to 32768).  A frame of n_kp
+ * keypoints travels as max(1, ceil(n_kp / 2048)) records of the layout above; chunk c holds rows [row0, row0 + rows) of the frame (the
+ * packer writes row0 = 2048 c): keypoints at [0, rows * 28), descriptors at 57344 + [0, rows * 128), zeros elsewhere.  A frame of <= 2048
+ * keypoints is one chunk, byte for byte the record mi355_pack_features_dev writes. */
+typedef struct { int32_t img_id /* < 0: padding record */, n_kp /* whole frame */, w, h, chunk, n_chunks, row0, rows; } mi355_feature_chunk_header;  /* 32 B */
+#define MI355_FEATURE_CHUNK_ROWS 2048
+/* the records the frames take (sum of max(1, ceil(n_kp / 2048))); resolves pending extractions */
+int  mi355_feature_chunk_count(mi355_ctx* ctx, const int32_t* img_ids, int n, int* n_records);
+/* resident features -> chunk records at d_payload (device, max_records x MI355_FEATURE_RECORD_BYTES), one header per record to the HOST
+ * array hdr (max_records entries); *n_records = the records written.  More records than max_records: MI355_ERR_ARG, nothing written. */
+int  mi355_pack_feature_chunks_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_chunk_header* hdr, void* d_payload,
+                                   int max_records, int* n_records);
+/* chunk records -> resident features, as if extracted here (records with img_id < 0 are skipped).  Every table is checked before any
+ * state changes: each image's chunks 0 .. n_chunks - 1 appear exactly once, agree on n_kp / w / h, their rows tile [0, n_kp) in chunk order
+ * with 1 .. 2048 rows each (one chunk of 0 rows for n_kp = 0), n_kp <= 32768.  A bad table returns MI355_ERR_ARG and leaves the ctx's
+ * features as they were. */
+int  mi355_install_feature_chunks_dev(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n_records);
+/* The collective over the chunk records (ncclAllGather of the headers and the payload, in place): no n_max argument, the per-rank record
+ * counts travel first.  Every rank gathers {records, status} of every rank, reserves world x R records (R = the largest count), packs its
+ * own, and gathers a second status word: a failure on any rank up to there (an unknown id, no memory) makes EVERY rank return the error
+ * after one of the two small all-gathers, before any payload moves.  Own frames are not re-installed unless flags has
+ * MI355_FEATURES_INSTALL_OWN (a communicator of one rank then exercises the whole path). */
+#define MI355_FEATURES_INSTALL_OWN 1
+int  mi355_allgather_feature_chunks(mi355_ctx* ctx, const int32_t* img_ids, int n_local, int flags);
 /* Accepted pair records to the front of d_out (order kept): what the reference pushes to the driver (:5201-5227). */
 int  mi355_compact_accepted_dev(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, mi355_pair_result* d_out, int* n_out);
 

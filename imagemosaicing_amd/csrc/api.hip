@@ -411,6 +411,23 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
         ctx->sift_batch = value < 1 ? 1 : (value > 32 ? 32 : value);
         return MI355_OK;
     }
+    if (std::string(name) == "keepall_max") {
+        if (value < MI355_SIFT_KEEPALL_MAX || value > MI355_SIFT_KEEPALL_LIMIT || value % 2048 != 0) {
+            ctx->set_error("set_option: keepall_max must be a multiple of 2048 in [" + std::to_string(MI355_SIFT_KEEPALL_MAX) + ", " + std::to_string(MI355_SIFT_KEEPALL_LIMIT) + "]");
+            return MI355_ERR_ARG;
+        }
+        int rc = mi_resolve_features(ctx);
+        if (rc != MI355_OK) return rc;
+        for (const auto& kv : ctx->feats)
+            if (kv.second.n > value) {
+                ctx->set_error("set_option: keepall_max=" + std::to_string(value) + " is below the " + std::to_string(kv.second.n) + " keypoints of image " + std::to_string(kv.first));
+                return MI355_ERR_ARG;
+            }
+        ctx->keepall_max = value;
+        return MI355_OK;
+    }
+    if (std::string(name) == "keepall_order") { ctx->keepall_order = value == 1 ? 1 : 0; return MI355_OK; }
+    if (std::string(name) == "big_subpairs_max") { ctx->big_sub_max = value < 1 ? 1 : value; return MI355_OK; }
     {
         struct { const char* n; int* p; } knobs[] = {{"ransac_split", &ctx->ransac_split}, {"strict_frames", &ctx->strict_frames}};
         for (auto& k : knobs) if (std::string(name) == k.n) { *k.p = value; return MI355_OK; }

@@ -302,7 +302,7 @@ extern "C" int mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_he
     return install_features(ctx, hdr, d_payload, n, nullptr, 0);
 }
 
-// ---- chunk records (frames of any keypoint count: keep-all, <= 32768 rows) ---------------------------------------------------------------
+// ---- chunk records (frames of any keypoint count: keep-all, <= ctx->keepall_max rows) ---------------------------------------------------------------
 // A frame travels as max(1, ceil(n / 2048)) records of the fixed layout, chunk c holding rows [row0, row0 + rows): a frame of <= 2048 keypoints
 // is ONE chunk, byte for byte the record above, so a transport that moves fixed records keeps one record size.
 static_assert(sizeof(mi355_feature_chunk_header) == 32, "feature chunk header");
@@ -373,7 +373,7 @@ static int count_chunks(mi355_ctx* ctx, const char* who, const int32_t* img_ids,
         auto it = ctx->feats.find(img_ids[k]);
         if (it == ctx->feats.end()) { ctx->set_error(std::string(who) + ": no resident features for image " + std::to_string(img_ids[k])); return MI355_ERR_ARG; }
         const int nk = it->second.n;
-        if (nk < 0 || nk > MI355_SIFT_KEEPALL_MAX) { ctx->set_error(std::string(who) + ": image " + std::to_string(img_ids[k]) + " has more than 32768 keypoints"); return MI355_ERR_ARG; }
+        if (nk < 0 || nk > ctx->keepall_max) { ctx->set_error(std::string(who) + ": image " + std::to_string(img_ids[k]) + " has more than keepall_max=" + std::to_string(ctx->keepall_max) + " keypoints"); return MI355_ERR_ARG; }
         total += chunks_of(nk);
     }
     if (total > 0x7fffffffLL) { ctx->set_error(std::string(who) + ": too many records"); return MI355_ERR_ARG; }
@@ -447,7 +447,7 @@ static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr,
     for (auto& kv : by_img) {
         std::vector<int>& ks = kv.second;
         const mi355_feature_chunk_header& h0 = hdr[ks[0]];
-        if (h0.n_kp < 0 || h0.n_kp > MI355_SIFT_KEEPALL_MAX) return bad(kv.first, "n_kp outside [0, 32768]");
+        if (h0.n_kp < 0 || h0.n_kp > ctx->keepall_max) return bad(kv.first, "n_kp outside [0, " + std::to_string(ctx->keepall_max) + "] (keepall_max)");
         if (h0.w <= 0 || h0.h <= 0) return bad(kv.first, "bad image size");
         if (h0.n_chunks < 1 || h0.n_chunks != (int)ks.size()) return bad(kv.first, "n_chunks = " + std::to_string(h0.n_chunks) + " but " + std::to_string(ks.size()) + " records");
         for (int k : ks) {

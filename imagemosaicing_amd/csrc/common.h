@@ -30,7 +30,9 @@
 
 // grow-only device buffer (workspaces live as long as the ctx: no hipMalloc in steady state)
 constexpr int MI355_SIFT_BATCH_MAX = 32;      // frames per SIFT batch (per-frame pointers travel in kernel arguments)
-constexpr int MI355_SIFT_KEEPALL_MAX = 32768;  // keypoints per frame the feature record holds with nfeatures <= 0 (keep all); the matcher takes such frames in chunks of 2048 (match.hip, large-pair path), the feature exchange as chunk records of 2048 rows (comm.hip, mi355_allgather_feature_chunks)
+constexpr int MI355_SIFT_KEEPALL_MAX = 32768;  // default ceiling (option "keepall_max", ctx->keepall_max) of the keypoints per frame the feature record holds with nfeatures <= 0 (keep all); the matcher takes such frames in chunks of 2048 (match.hip, large-pair path), the feature exchange as chunk records of 2048 rows (comm.hip, mi355_allgather_feature_chunks)
+
+constexpr int MI355_SIFT_KEEPALL_LIMIT = 262144; // the largest "keepall_max" (a keep-all ordering key carries the keypoint index in 18 bits, sift.hip)
 
 struct DevBuf {
     void*  p = nullptr;
@@ -83,6 +85,7 @@ struct Features {
     volatile int* h_cnt = nullptr;   // 8 ints: extrema, refined, keypoints, kept, overflow, ...
     hipEvent_t ready = nullptr;      // recorded after the frame's batch (owned by ctx->batch_events): lets a match wait for ITS frames only
     unsigned caps[3] = {0, 0, 0};
+    int kp_limit = 0;                // keep-all: the ceiling (keepall_max) in force when the frame was extracted; 0: none
     void release() { kp.release(); xy.release(); d8.release(); s8.release(); n8.release(); }
 };
 
@@ -157,6 +160,9 @@ struct mi355_ctx {
     int num_cu = 256;
     mi355_comm* comm = nullptr;                        // RCCL communicator (mi355_comm_init), comm.hip
     SurfState* surf = nullptr;                         // SURF variant of the path (surf.hip)
+    int keepall_max = MI355_SIFT_KEEPALL_MAX;          // option "keepall_max": keypoints per keep-all frame (multiple of 2048 in [32768, 262144]); every check of a frame's or pair's keypoint count uses it
+    int keepall_order = 0;                             // option "keepall_order" (measurement): 0 tile sort + binary search (sift.hip), 1 the brute-force rank count
+    int big_sub_max = 65536;                           // option "big_subpairs_max" (debug): sub-pairs of <= 2048 x 2048 per large-pair run of the matcher (bounds the nn workspaces: 12 B x 2048 each)
     int last_counts[8] = {0};                          // SIFT counters of the last frame: candidates, refined, keypoints, selected, overflow
 
     void set_error(const std::string& s) { err = s; }

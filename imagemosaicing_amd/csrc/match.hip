@@ -33,7 +33,6 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define GLOBAL_PTR(T, p) ((const __attribute__((address_space(1))) T*)(p))
 
 constexpr int KSTRIDE = 2048;        // per-pair stride of the nn arrays (>= nfeatures rounded up); also the chunk size of the large-pair path
-constexpr int BIG_KP_MAX = MI355_SIFT_KEEPALL_MAX;   // keypoints per image the large-pair path takes (keep-all frames)
 constexpr int QTILE = 512;           // queries per workgroup (8 waves x 64): every staged train tile serves 512 queries
 constexpr int BF_NT = 512;           // threads per workgroup
 constexpr int ROWPAD = 256;          // descriptor matrices are padded to a multiple of this many rows (zeros)
@@ -436,7 +435,7 @@ int build_pair_table(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, std::vec
         auto fi = ctx->feats.find(i), fj = ctx->feats.find(j);
         if (fi == ctx->feats.end() || fj == ctx->feats.end()) { ctx->set_error("match_pairs: no resident features for image " + std::to_string(fi == ctx->feats.end() ? i : j)); return MI355_ERR_ARG; }
         const Features &a = fi->second, &b = fj->second;
-        if (a.n > BIG_KP_MAX || b.n > BIG_KP_MAX) { ctx->set_error("match_pairs: more than 32768 keypoints per image"); return MI355_ERR_ARG; }
+        if (a.n > ctx->keepall_max || b.n > ctx->keepall_max) { ctx->set_error("match_pairs: more than keepall_max=" + std::to_string(ctx->keepall_max) + " keypoints per image"); return MI355_ERR_ARG; }
         if ((a.n > KSTRIDE && a.npad < a.n) || (b.n > KSTRIDE && b.npad < b.n)) { ctx->set_error("match_pairs: the matcher's operands of a large image are incomplete"); return MI355_ERR_ARG; }
         PairDesc& d = pd[p];
         d.s8_i = a.s8.as<int8_t>(); d.n8_i = a.n8.as<int>(); d.xy_i = a.xy.as<float2>(); d.n_i = a.n; d.npad_i = a.npad;
@@ -467,7 +466,7 @@ int mi_finish_features(mi355_ctx* ctx, Features& f, const int* d_n, hipStream_t 
 int mi_finish_features_batch(mi355_ctx* ctx, Features* const* fs, int nf, const int* d_n, int n_stride, hipStream_t st, int max_rows) {
     if (nf <= 0) return MI355_OK;
     if (nf > MI355_SIFT_BATCH_MAX) return MI355_ERR_ARG;
-    if (max_rows < KSTRIDE) max_rows = KSTRIDE;          // keep-all frames (nfeatures <= 0) carry up to MI355_SIFT_KEEPALL_MAX rows: the large-pair path reads them all
+    if (max_rows < KSTRIDE) max_rows = KSTRIDE;          // keep-all frames (nfeatures <= 0) carry up to ctx->keepall_max rows: the large-pair path reads them all
     FinishBatch fb;
     memset(&fb, 0, sizeof(fb));
     const int npad = ((max_rows + ROWPAD - 1) / ROWPAD) * ROWPAD;
@@ -487,7 +486,7 @@ int mi_finish_features_batch(mi355_ctx* ctx, Features* const* fs, int nf, const 
 }
 
 int mi_set_features(mi355_ctx* ctx, int img_id, const mi355_keypoint* kp, const float* desc, int n, int w, int h) {
-    if (n < 0 || n > BIG_KP_MAX || (n > 0 && (!kp || !desc)) || w <= 0 || h <= 0) { ctx->set_error("set_features: bad arguments (n must be <= 32768)"); return MI355_ERR_ARG; }
+    if (n < 0 || n > ctx->keepall_max || (n > 0 && (!kp || !desc)) || w <= 0 || h <= 0) { ctx->set_error("set_features: bad arguments (n must be <= keepall_max=" + std::to_string(ctx->keepall_max) + ")"); return MI355_ERR_ARG; }
     (void)mi_resolve_features(ctx);
     Features& f = ctx->feats[img_id];
     f.n = n; f.w = w; f.h = h; f.pending = false;
@@ -642,6 +641,9 @@ static int run_match_select_big(mi355_ctx* ctx, const std::vector<PairDesc>& pd,
 }
 
 static bool pair_is_big(const PairDesc& d) { return d.n_i > KSTRIDE || d.n_j > KSTRIDE; }
+static long long sub_pairs_of(const PairDesc& d) {      // run_match_select_big's (query chunk, train chunk) sub-pairs of a pair
+    return (long long)(d.n_i > 0 ? (d.n_i + KSTRIDE - 1) / KSTRIDE : 1) * (long long)(d.n_j > 0 ? (d.n_j + KSTRIDE - 1) / KSTRIDE : 1);
+}
 
 int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float dist, uint32_t seed, mi355_pair_result* d_out) {
     if (n_pairs <= 0) return MI355_OK;
@@ -655,11 +657,13 @@ int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float 
         int rc = build_pair_table(ctx, pairs + 2 * b0, nb, pd);
         if (rc != MI355_OK) return rc;
         // maximal runs of pairs of one kind: the live path (every image <= 2048 keypoints) is ONE run per batch, exactly as before; a pair with
-        // a larger image (keep-all frames) goes through the large-pair form, at most 256 of them at a time (each may hold 256 sub-pairs)
+        // a larger image (keep-all frames) goes through the large-pair form, at most 256 of them and ctx->big_sub_max sub-pairs of <= 2048 x 2048
+        // at a time (the nn workspaces take 12 B x 2048 per sub-pair: 1.6 GB at 65 536; one 131 072 x 131 072 pair alone is 4 096), always one pair at least
         for (int r0 = 0; r0 < nb;) {
             const bool big = pair_is_big(pd[r0]);
             int r1 = r0 + 1;
-            while (r1 < nb && pair_is_big(pd[r1]) == big && (!big || r1 - r0 < 256)) r1++;
+            long long subs = big ? sub_pairs_of(pd[r0]) : 0;
+            while (r1 < nb && pair_is_big(pd[r1]) == big && (!big || (r1 - r0 < 256 && subs + sub_pairs_of(pd[r1]) <= ctx->big_sub_max))) { if (big) subs += sub_pairs_of(pd[r1]); r1++; }
             const int nr = r1 - r0;
             if (r0 == 0 && nr == nb && !big) rc = run_match_select(ctx, pd, nb, false);
             else {
@@ -711,7 +715,7 @@ int mi_bf_match(mi355_ctx* ctx, int img_i, int img_j, int sorted, mi355_dmatch* 
 // stand-alone SelectMatchPairs: host arrays in, the same select kernel on one synthetic "pair"
 int mi_select_grid(mi355_ctx* ctx, const mi355_dmatch* sorted, int n, const float* kp1, int nk1, const float* kp2, int nk2,
                    int nMatch, int width, int height, int gx, int gy, mi355_sfpoint* v1, mi355_sfpoint* v2, int* n_out) {
-    if (n < 0 || n > BIG_KP_MAX || !kp1 || !kp2 || !v1 || !v2 || !n_out || gx < 1 || gy < 1 || gx * gy > 64 || width < gx || height < gy) { ctx->set_error("select_grid: bad arguments (at most 32768 matches)"); return MI355_ERR_ARG; }
+    if (n < 0 || n > ctx->keepall_max || !kp1 || !kp2 || !v1 || !v2 || !n_out || gx < 1 || gy < 1 || gx * gy > 64 || width < gx || height < gy) { ctx->set_error("select_grid: bad arguments (at most keepall_max=" + std::to_string(ctx->keepall_max) + " matches)"); return MI355_ERR_ARG; }
     // The kernel sorts by (d2, queryIdx); feed it ranks so that the given order is kept: d2 := position.
     // Queries are remapped to 0..n-1 in the given order (x/y/id carried through).
     const bool big = n > KSTRIDE;                           // more matches than select_kernel's LDS list holds: the large-pair form (keys sorted in HBM)

@@ -280,7 +280,6 @@ constexpr int NREG = 64, REG_STRIDE = 32;   // candidate list split into 64 regi
 // batched launches: frame f = blockIdx.y (z for refine) works on its own copy of every buffer, a fixed stride apart
 struct BatchStride { size_t pyr, claimed, cand, refined, kps, cube, sel, mins; };   // elements of the respective type (sel: selected keypoints per frame; mins: keep-all's start-key table)
 constexpr size_t CNT_STRIDE = 64, CCNT_STRIDE = (size_t)64 * 32, SEL_STRIDE = 2048;
-constexpr int KEEPALL_MAX = MI355_SIFT_KEEPALL_MAX;      // keypoints per frame with nfeatures <= 0 (cv::SIFT's "keep all")
 struct FrameOuts { mi355_keypoint* kp[SIFT_BATCH_MAX]; uint8_t* d8[SIFT_BATCH_MAX]; };
 
 // ---------- K3b: sub-pixel refinement ---------------------------------------------------------------------------
@@ -1281,45 +1280,137 @@ __global__ __launch_bounds__(1024) void topk_kernel(const KpRec* kps, const unsi
 }
 
 // keep-all: a keypoint's place in the output = the number of keypoints with a smaller (octave, start key, orientation bin); the keys are
-// distinct (one refined record per start point, one keypoint per bin).  Every workgroup walks all keys of its frame in tiles through LDS.
-__global__ __launch_bounds__(256) void keepall_output_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, BatchStride bs) {
-    const size_t fr = blockIdx.y;
-    kps += fr * bs.kps; kp_count += fr * CNT_STRIDE; out_sel += fr * bs.sel; out_n += fr * CNT_STRIDE; overflow += fr * CNT_STRIDE;
-    mi355_keypoint* out_kp = outs.kp[0];
-#pragma unroll
-    for (int q = 1; q < SIFT_BATCH_MAX; q++) if ((int)fr == q) out_kp = outs.kp[q];
-    unsigned N = *kp_count;
-    if (N > kp_cap || N > (unsigned)KEEPALL_MAX) {                     // more keypoints than the record holds: the frame fails (OpenCV would keep them all)
-        if (blockIdx.x == 0 && threadIdx.x == 0) { *overflow = 1; *out_n = 0; }
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *out_n = (int)N;
-    auto key_of = [](const KpRec& k) { return ((unsigned long long)k.o << 40) | ((unsigned long long)k.start << 6) | (unsigned long long)k.bin; };
-    __shared__ unsigned long long s_key[1024];
-    const unsigned i = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x * 256 >= N) return;
-    KpRec mine;
-    unsigned long long mk = ~0ull;
-    if (i < N) { mine = kps[i]; mk = key_of(mine); }
-    unsigned rank = 0;
-    for (unsigned t0 = 0; t0 < N; t0 += 1024) {
-        __syncthreads();
-        for (unsigned q = threadIdx.x; q < 1024; q += 256) s_key[q] = t0 + q < N ? key_of(kps[t0 + q]) : ~0ull;
-        __syncthreads();
-        const unsigned cntq = N - t0 < 1024 ? N - t0 : 1024;
-        for (unsigned q = 0; q < cntq; q++) rank += s_key[q] < mk ? 1u : 0u;
-    }
-    if (i >= N) return;
-    const KpRec& k = mine;
+// distinct (one refined record per start point, one keypoint per bin).  The octave takes 4 bits (MAX_OCT = 16), the start key 30, the bin 6:
+// a key is below 2^44, and key << 18 | index (index < MI355_SIFT_KEEPALL_LIMIT = 2^18) still orders by the key alone.
+__device__ __forceinline__ unsigned long long keepall_key(const KpRec& k) {
+    return ((unsigned long long)k.o << 40) | ((unsigned long long)k.start << 6) | (unsigned long long)k.bin;
+}
+
+__device__ __forceinline__ void keepall_emit(const KpRec& k, mi355_keypoint* out_kp, SelRec* out_sel, unsigned pos) {
     const float s2 = (float)(1 << k.o);
     mi355_keypoint kp;
     kp.x = k.ptx * s2; kp.y = k.pty * s2; kp.size = (k.scl * s2) * 2.0f; kp.angle = k.angle;
     kp.response = __uint_as_float(k.resp_bits);
     kp.octave = (k.o & 255) | (k.layer << 8) | (((int)rintf((k.xi + 0.5f) * 255.0f)) << 16);
     kp.class_id = -1;
-    out_kp[rank] = kp;
+    out_kp[pos] = kp;
     SelRec sr; sr.ptx = k.ptx; sr.pty = k.pty; sr.scl = k.scl; sr.angle = k.angle; sr.o = k.o; sr.layer = k.layer;
-    out_sel[rank] = sr;
+    out_sel[pos] = sr;
+}
+
+// The frame's counters: more keypoints than the work area holds is an overflow (cnt[4]); more than the ctx's ceiling (option "keepall_max")
+// fails the frame without one -- the host reads that from the keypoint count, cnt[2].  Either way nothing is written and n_sel = 0.
+__device__ __forceinline__ bool keepall_fits(unsigned N, unsigned kp_cap, unsigned kmax, int* out_n, int* overflow, bool writer) {
+    if (N <= kp_cap && N <= kmax) return true;
+    if (writer) { if (N > kp_cap) *overflow = 1; *out_n = 0; }
+    return false;
+}
+
+// (measurement, option "keepall_order" = 1) the rank by brute force: every workgroup walks all keys of its frame in tiles through LDS, O(N^2)
+__global__ __launch_bounds__(256) void keepall_output_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, unsigned kmax, FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, BatchStride bs) {
+    const size_t fr = blockIdx.y;
+    kps += fr * bs.kps; kp_count += fr * CNT_STRIDE; out_sel += fr * bs.sel; out_n += fr * CNT_STRIDE; overflow += fr * CNT_STRIDE;
+    mi355_keypoint* out_kp = outs.kp[0];
+#pragma unroll
+    for (int q = 1; q < SIFT_BATCH_MAX; q++) if ((int)fr == q) out_kp = outs.kp[q];
+    unsigned N = *kp_count;
+    if (!keepall_fits(N, kp_cap, kmax, out_n, overflow, blockIdx.x == 0 && threadIdx.x == 0)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out_n = (int)N;
+    __shared__ unsigned long long s_key[1024];
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= N) return;
+    KpRec mine;
+    unsigned long long mk = ~0ull;
+    if (i < N) { mine = kps[i]; mk = keepall_key(mine); }
+    unsigned rank = 0;
+    for (unsigned t0 = 0; t0 < N; t0 += 1024) {
+        __syncthreads();
+        for (unsigned q = threadIdx.x; q < 1024; q += 256) s_key[q] = t0 + q < N ? keepall_key(kps[t0 + q]) : ~0ull;
+        __syncthreads();
+        const unsigned cntq = N - t0 < 1024 ? N - t0 : 1024;
+        for (unsigned q = 0; q < cntq; q++) rank += s_key[q] < mk ? 1u : 0u;
+    }
+    if (i >= N) return;
+    keepall_emit(mine, out_kp, out_sel, rank);
+}
+
+// The rank in O(N log N), two launches.  Phase A (keepall_sort_tiles_kernel): every workgroup sorts a tile of KA_TILE keys (key << 18 | index)
+// in LDS, bitonic, and writes it to the frame's scratch area padded with all-ones.  A frame of one tile is done there: the sorted position is
+// the output position.  Phase B (keepall_place_kernel, frames of more than one tile): a keypoint's position = the sum over the tiles of the
+// number of keys there below its own (lower_bound, 13 probes of a KA_TILE-sized tile; in its own tile that is its place in the tile).
+constexpr int KA_TILE = 4096;
+
+__global__ __launch_bounds__(1024) void keepall_sort_tiles_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, unsigned kmax, unsigned long long* sorted,
+                                                                  size_t sorted_stride, FrameOuts outs, SelRec* out_sel, BatchStride bs) {
+    const size_t fr = blockIdx.y;
+    kps += fr * bs.kps; kp_count += fr * CNT_STRIDE; sorted += fr * sorted_stride; out_sel += fr * bs.sel;
+    const unsigned N = *kp_count;
+    if (N > kp_cap || N > kmax) return;                                 // keepall_place_kernel reports it
+    const unsigned t0 = blockIdx.x * KA_TILE;
+    if (t0 >= N) return;
+    __shared__ unsigned long long s[KA_TILE];
+    const int tid = threadIdx.x;
+    for (int q = tid; q < KA_TILE; q += 1024) s[q] = t0 + q < N ? (keepall_key(kps[t0 + q]) << 18) | (unsigned long long)(t0 + q) : ~0ull;
+    __syncthreads();
+    // wave w owns the pairs [128 w, 128 w + 128): while j <= 128 they stay inside its block of 256 keys and the wave only syncs with itself;
+    // a workgroup barrier stands after every step with j >= 256 and before the first one (63 of the 78 steps take none)
+    const int lane = tid & 63, p0 = (tid >> 6) * 128 + lane;
+    for (int k = 2; k <= KA_TILE; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {                                  // compare-exchange pair p: (i, i + j), i with bit j clear
+                const int p = p0 + 64 * h, i = 2 * p - (p & (j - 1)), ixj = i + j;
+                const unsigned long long a = s[i], b = s[ixj];
+                if ((a > b) == ((i & k) == 0)) { s[i] = b; s[ixj] = a; }
+            }
+            if (j >= 256 || (j == 1 && k >= 256)) __syncthreads();
+            else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+        }
+    }
+    if (N <= (unsigned)KA_TILE) {
+        mi355_keypoint* out_kp = outs.kp[0];
+#pragma unroll
+        for (int q = 1; q < SIFT_BATCH_MAX; q++) if ((int)fr == q) out_kp = outs.kp[q];
+        for (unsigned q = tid; q < N; q += 1024) keepall_emit(kps[(unsigned)(s[q] & 0x3ffffu)], out_kp, out_sel, q);
+        return;
+    }
+    for (int q = tid; q < KA_TILE; q += 1024) sorted[t0 + q] = s[q];
+}
+
+__global__ __launch_bounds__(256) void keepall_place_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, unsigned kmax, const unsigned long long* sorted,
+                                                            size_t sorted_stride, FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, BatchStride bs) {
+    const size_t fr = blockIdx.y;
+    kps += fr * bs.kps; kp_count += fr * CNT_STRIDE; sorted += fr * sorted_stride; out_sel += fr * bs.sel; out_n += fr * CNT_STRIDE; overflow += fr * CNT_STRIDE;
+    const unsigned N = *kp_count;
+    if (!keepall_fits(N, kp_cap, kmax, out_n, overflow, blockIdx.x == 0 && threadIdx.x == 0)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out_n = (int)N;
+    if (N <= (unsigned)KA_TILE) return;                                 // one tile: keepall_sort_tiles_kernel wrote it
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    mi355_keypoint* out_kp = outs.kp[0];
+#pragma unroll
+    for (int q = 1; q < SIFT_BATCH_MAX; q++) if ((int)fr == q) out_kp = outs.kp[q];
+    const KpRec k = kps[i];
+    const unsigned long long key = keepall_key(k) << 18;                // below every composite of this key: lower_bound counts smaller keys only
+    const unsigned nt = (N + KA_TILE - 1) / KA_TILE;
+    unsigned rank = 0, t = 0;
+    for (; t + 4 <= nt; t += 4) {                                       // four independent searches in flight
+        unsigned pos[4] = {0u, 0u, 0u, 0u};
+        const unsigned long long* a = sorted + (size_t)t * KA_TILE;
+        for (unsigned step = KA_TILE / 2; step > 0; step >>= 1) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (a[(size_t)u * KA_TILE + pos[u] + step - 1] < key) pos[u] += step;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) rank += pos[u] + (a[(size_t)u * KA_TILE + pos[u]] < key ? 1u : 0u);
+    }
+    for (; t < nt; t++) {
+        const unsigned long long* a = sorted + (size_t)t * KA_TILE;
+        unsigned pos = 0;
+        for (unsigned step = KA_TILE / 2; step > 0; step >>= 1) if (a[pos + step - 1] < key) pos += step;
+        rank += pos + (a[pos] < key ? 1u : 0u);
+    }
+    keepall_emit(k, out_kp, out_sel, rank);
 }
 
 // ---------- K5: descriptors -----------------------------------------------------------------------------------------
@@ -1555,6 +1646,8 @@ struct SiftWork {
     DevBuf cand, refined, kps, kresp, sel, counters, rhist, ccnt;
     DevBuf olist;                            // per frame: indices of the refined points at or above the response threshold
     DevBuf mins; bool keepall = false;       // keep-all (nfeatures <= 0): smallest start key per refined location, all ones between batches
+    int kmax = 0;                            // keep-all: the ctx's ceiling (option "keepall_max") the batch was sized for; bs.sel = kmax
+    DevBuf ksort; size_t ksort_stride = 0;   // keep-all: per frame, its keys sorted tile by tile (keepall_sort_tiles_kernel)
     DevBuf cube; unsigned cube_cap = 0;       // 3x3x3 DoG neighbourhoods of the first cube_cap candidates of every region (128 B each)
     PyrDev P;                                // pointers of frame 0
     BatchStride bs;
@@ -1574,7 +1667,7 @@ void mi_sift_release(mi355_ctx* ctx) {
         if (!s) continue;
         if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
         if (s->done) (void)hipEventDestroy(s->done);
-        s->pyr.release(); s->claimed.release(); s->cand.release(); s->refined.release(); s->kps.release(); s->kresp.release(); s->sel.release(); s->counters.release(); s->rhist.release(); s->ccnt.release(); s->cube.release(); s->olist.release(); s->mins.release();
+        s->pyr.release(); s->claimed.release(); s->cand.release(); s->refined.release(); s->kps.release(); s->kresp.release(); s->sel.release(); s->counters.release(); s->rhist.release(); s->ccnt.release(); s->cube.release(); s->olist.release(); s->mins.release(); s->ksort.release();
         delete s;
     }
     ctx->sift_slots.clear();
@@ -1601,6 +1694,12 @@ static int adopt_counts(mi355_ctx* ctx, int img_id, Features& f) {
     for (int i = 0; i < 8; i++) ctx->last_counts[i] = c[i];
     if ((unsigned)c[0] > f.caps[0] || (unsigned)c[1] > f.caps[1] || (unsigned)c[2] > f.caps[2] || c[4]) {
         ctx->set_error("sift: candidate buffer overflow (image " + std::to_string(img_id) + " has more extrema than the buffers assume)");
+        f.n = 0;
+        return MI355_ERR_FAILED;
+    }
+    if (f.kp_limit > 0 && c[2] > f.kp_limit) {                 // keep-all: more keypoints than the ceiling the frame was extracted under
+        ctx->set_error("sift: keep-all frame (image " + std::to_string(img_id) + ") has " + std::to_string(c[2]) + " keypoints, more than keepall_max=" +
+                       std::to_string(f.kp_limit));
         f.n = 0;
         return MI355_ERR_FAILED;
     }
@@ -1661,8 +1760,8 @@ static int* pinned_slot(mi355_ctx* ctx) {
 
 static inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
-static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool keepall) {
-    if (s->w == w && s->h == h && s->nb == nb && s->keepall == keepall) return MI355_OK;
+static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool keepall, int kmax) {
+    if (s->w == w && s->h == h && s->nb == nb && s->keepall == keepall && s->kmax == kmax) return MI355_OK;
     MI_HIP(hipStreamSynchronize(s->stream));
     if (s->radius0 == 0) {
         // Gaussian kernels (double math on the host, like the oracle): sigma_i = sqrt((s k^i)^2 - (s k^(i-1))^2)
@@ -1699,7 +1798,8 @@ static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool 
     if (s->cube_cap > s->cand_cap) s->cube_cap = s->cand_cap;
     s->bs.cube = (size_t)s->cube_cap * NREG * 32;
     s->bs.pyr = fl; s->bs.claimed = cl; s->bs.cand = (size_t)s->cand_cap * NREG; s->bs.refined = s->ref_cap; s->bs.kps = s->kp_cap;
-    s->bs.sel = keepall ? (size_t)KEEPALL_MAX : SEL_STRIDE;
+    s->bs.sel = keepall ? (size_t)kmax : SEL_STRIDE;
+    s->ksort_stride = keepall ? (size_t)((kmax + KA_TILE - 1) / KA_TILE) * KA_TILE : 0;
     size_t ml = 0;                                              // keep-all: one word per claim bit (4 per pixel of every octave)
     if (keepall) for (int o = 0; o < no; o++) ml += (size_t)(w >> o) * (h >> o) * 4;
     s->bs.mins = ml;
@@ -1714,6 +1814,8 @@ static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool 
     MI_HIP(s->sel.reserve(B * s->bs.sel * sizeof(SelRec)));
     if (keepall) { MI_HIP(s->mins.reserve(B * ml * sizeof(unsigned))); MI_HIP(hipMemsetAsync(s->mins.p, 0xff, B * ml * sizeof(unsigned), s->stream)); }      // kept all ones between batches by keepall_reset_kernel
     else s->mins.release();
+    if (keepall) MI_HIP(s->ksort.reserve(B * s->ksort_stride * sizeof(unsigned long long)));
+    else s->ksort.release();
     MI_HIP(s->counters.reserve(B * CNT_STRIDE * sizeof(unsigned)));
     MI_HIP(s->rhist.reserve(B * s->bs.refined * sizeof(unsigned)));
     MI_HIP(s->olist.reserve(B * s->bs.refined * sizeof(unsigned)));      // |response| bits of the refined points (SoA next to `refined`)
@@ -1731,7 +1833,7 @@ static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool 
         mo += (size_t)ow * oh * 4;
     }
     s->P.n_oct = no; s->n_oct = no;
-    s->w = w; s->h = h; s->nb = nb; s->keepall = keepall;
+    s->w = w; s->h = h; s->nb = nb; s->keepall = keepall; s->kmax = kmax;
     return MI355_OK;
 }
 
@@ -1741,8 +1843,9 @@ static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool 
 // unchanged until then.  Returns without waiting; the keypoint count is adopted later by mi_resolve_features().
 int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w, int h, int ws, int* n_kp) {
     if (ctx->p.n_octave_layers != N_LAYERS || ctx->p.sigma != 1.6f) { ctx->set_error("sift: this build implements nOctaveLayers=3, sigma=1.6 (the reference's SIFT(2000,3,0.01,20))"); return MI355_ERR_ARG; }
-    if (ctx->p.nfeatures > 2048) { ctx->set_error("sift: nfeatures must be in [1,2048], or <= 0 for cv::SIFT's keep-all (up to 32768 keypoints per frame)"); return MI355_ERR_ARG; }
+    if (ctx->p.nfeatures > 2048) { ctx->set_error("sift: nfeatures must be in [1,2048], or <= 0 for cv::SIFT's keep-all (up to keepall_max=" + std::to_string(ctx->keepall_max) + " keypoints per frame)"); return MI355_ERR_ARG; }
     const bool keepall = ctx->p.nfeatures <= 0;
+    const int kmax = keepall ? ctx->keepall_max : 0;
     if (keepall && (w > 16384 || h > 16384)) { ctx->set_error("sift: keep-all frames are at most 16384 x 16384"); return MI355_ERR_ARG; }
     if ((size_t)w >= (1u << 20) || (size_t)h >= (1u << 20)) { ctx->set_error("sift: image too large"); return MI355_ERR_ARG; }
     if (w < 16 || h < 16) { ctx->set_error("sift: image too small"); return MI355_ERR_ARG; }
@@ -1771,15 +1874,15 @@ int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w,
         }
         if (keepall && nb > 8) nb = 8;
     }
-    if (!s->pend.empty() && (s->w != w || s->h != h || s->nb != nb || s->keepall != keepall)) { rc = sift_run_batch(ctx, s); if (rc != MI355_OK) return rc; }   // size change: close the batch
-    rc = sift_prepare(ctx, s, w, h, nb, keepall);
+    if (!s->pend.empty() && (s->w != w || s->h != h || s->nb != nb || s->keepall != keepall || s->kmax != kmax)) { rc = sift_run_batch(ctx, s); if (rc != MI355_OK) return rc; }   // size or ceiling change: close the batch
+    rc = sift_prepare(ctx, s, w, h, nb, keepall, kmax);
     if (rc != MI355_OK) return rc;
     auto fit = ctx->feats.find(img_id);
     if (fit != ctx->feats.end() && fit->second.pending) { rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }   // same id re-extracted while in flight
     Features& f = ctx->feats[img_id];
     f.w = w; f.h = h;
-    MI_HIP(f.kp.reserve(sizeof(mi355_keypoint) * (size_t)(keepall ? KEEPALL_MAX : 2048)));
-    MI_HIP(f.d8.reserve((size_t)128 * (size_t)(keepall ? KEEPALL_MAX : 2048)));
+    MI_HIP(f.kp.reserve(sizeof(mi355_keypoint) * (size_t)(keepall ? kmax : 2048)));
+    MI_HIP(f.d8.reserve((size_t)128 * (size_t)(keepall ? kmax : 2048)));
     f.pending = true; f.h_cnt = nullptr; f.ready = nullptr; f.n = 0;
     s->pend.push_back({img_id, d_bgr, ws, ctx->pend_event});
     if ((int)s->pend.size() >= nb) {
@@ -1919,8 +2022,16 @@ static int sift_run_batch(mi355_ctx* ctx, SiftWork* s) {
         }
         {
             ProfScope ps(ctx, "topk", 0.0, tt);
-            hipLaunchKernelGGL(keepall_output_kernel, dim3((KEEPALL_MAX + 255) / 256, n), dim3(256), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, outs, s->sel.as<SelRec>(),
-                               reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
+            const unsigned kmax = (unsigned)s->kmax;
+            if (ctx->keepall_order == 1) {
+                hipLaunchKernelGGL(keepall_output_kernel, dim3((kmax + 255) / 256, n), dim3(256), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax, outs, s->sel.as<SelRec>(),
+                                   reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
+            } else {
+                hipLaunchKernelGGL(keepall_sort_tiles_kernel, dim3((kmax + KA_TILE - 1) / KA_TILE, n), dim3(1024), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax,
+                                   s->ksort.as<unsigned long long>(), s->ksort_stride, outs, s->sel.as<SelRec>(), bs);
+                hipLaunchKernelGGL(keepall_place_kernel, dim3((kmax + 255) / 256, n), dim3(256), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax,
+                                   s->ksort.as<const unsigned long long>(), s->ksort_stride, outs, s->sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
+            }
         }
     } else {
     {
@@ -1948,7 +2059,7 @@ static int sift_run_batch(mi355_ctx* ctx, SiftWork* s) {
     MI_HIP(hipGetLastError());
     // the matcher's operands of all n frames in one launch, their counters in one strided copy (n launches + n copies of ~5 us each kept
     // the batch's stream, and a pipeline slot, busy for 0.3 ms per batch of 32)
-    { int rc = mi_finish_features_batch(ctx, fs.data(), n, reinterpret_cast<const int*>(cnt + 3), (int)CNT_STRIDE, tt, s->keepall ? KEEPALL_MAX : 2048); if (rc != MI355_OK) return rc; }
+    { int rc = mi_finish_features_batch(ctx, fs.data(), n, reinterpret_cast<const int*>(cnt + 3), (int)CNT_STRIDE, tt, s->keepall ? s->kmax : 2048); if (rc != MI355_OK) return rc; }
     {
         if (ctx->pinned_used % PINNED_CHUNK + (size_t)n > PINNED_CHUNK) ctx->pinned_used += PINNED_CHUNK - ctx->pinned_used % PINNED_CHUNK;   // n slots in one chunk
         int* h0 = nullptr;
@@ -1959,6 +2070,7 @@ static int sift_run_batch(mi355_ctx* ctx, SiftWork* s) {
             Features& f = *fs[k];
             f.h_cnt = hc; f.pending = true; f.n = 0;
             f.caps[0] = 0xffffffffu; f.caps[1] = s->ref_cap; f.caps[2] = s->kp_cap;      // candidate overflow is flagged by the kernel (cnt[4])
+            f.kp_limit = s->keepall ? s->kmax : 0;
         }
         MI_HIP(hipMemcpy2DAsync(h0, 8 * sizeof(int), cnt, CNT_STRIDE * sizeof(unsigned), 8 * sizeof(unsigned), (size_t)n, hipMemcpyDeviceToHost, tt));
     }

@@ -169,7 +169,8 @@ def allgather_feature_records(hdr, payload, n_max=None):
 
 def allgather_feature_chunk_records(hdr, payload):
     """torch transport of the chunk-record feature exchange (frames of any keypoint count).  hdr: FEATURE_CHUNK_HEADER array [n_local];
-    payload: uint8 tensor [n_local, FEATURE_RECORD_BYTES].  The record counts are ragged across ranks (a keep-all frame takes up to 16);
+    payload: uint8 tensor [n_local, FEATURE_RECORD_BYTES].  The record counts are ragged across ranks (a keep-all frame takes up to 16 at the default
+    keepall_max of 32 768, up to 128 at 262 144);
     they are gathered first and the payload is padded to the largest.  Returns (headers [world][count_r], payload uint8 [world, R, REC],
     counts)."""
     hdr = np.ascontiguousarray(hdr, FEATURE_CHUNK_HEADER)

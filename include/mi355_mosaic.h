@@ -68,7 +68,8 @@ typedef struct {
 /* Literals of the live path; mi355_default_params() fills the reference's values. */
 typedef struct {
     int32_t nfeatures;         /* 2000   SIFT(2000,3,0.01,20)            MosaicWithoutPos.cpp:4852; 1 .. 2048, or <= 0 = cv::SIFT's keep-all
-                                  (CVI/nonfree/features2d.hpp:61: every keypoint, OpenCV's generation order, <= 32768 per frame; what the
+                                  (CVI/nonfree/features2d.hpp:61: every keypoint, OpenCV's generation order, <= the ctx's keepall_max per
+                                  frame: 32768 unless mi355_set_option(ctx, "keepall_max", n) raised it, up to 262144; what the
                                   reference's committed run used; the matcher takes such frames through its large-pair path, and the
                                   multi-GPU feature exchange carries them as chunk records, mi355_allgather_feature_chunks) */
     int32_t n_octave_layers;   /* 3 */
@@ -113,7 +114,15 @@ int  mi355_synchronize(mi355_ctx* ctx);
  * "keep_frames" = 1 (default 0): host-frame extractions keep their HBM copy (see mi355_get_frame_dev); "download_chunk_mb" (default 64):
  * bytes per chunk, in MB, of the _into calls' canvas download; "download_threads" (1..16, default 4): host threads that copy a downloaded
  * chunk into the caller's rows; "download_mode" (measurement only, default 0): 1 copies with hipMemcpy2DAsync straight into dst,
- * 2 page-locks dst with hipHostRegister for that copy (the same bytes in every mode). */
+ * 2 page-locks dst with hipHostRegister for that copy (the same bytes in every mode); "keepall_max" (a multiple of 2048 in
+ * [32768, 262144], default 32768): the most keypoints a keep-all frame (nfeatures <= 0) may hold -- a frame with more fails its
+ * extraction ("... more than keepall_max=N"), mi355_set_features / mi355_select_grid / the pair stage / the chunk install and pack refuse
+ * more rows; resolves pending extractions first; any other value, or one below the keypoint count of a resident image (named in the
+ * error), returns MI355_ERR_ARG and leaves the ceiling as it was.  Every rank of a multi-GPU run sets the same value: a rank whose ceiling
+ * is below a frame it receives fails its install (MI355_ERR_ARG, its features unchanged) while the other ranks return normally;
+ * "keepall_order" (measurement only, default 0): 1 orders keep-all keypoints by the brute-force rank count instead of the tile sort (the
+ * same bytes); "big_subpairs_max" (debug, default 65536): sub-pairs of <= 2048 x 2048 per run of the matcher's large-pair path (the same
+ * results at any value >= 1). */
 int  mi355_set_option(mi355_ctx* ctx, const char* name, int value);
 void mi355_free(void* p);                               /* frees host buffers returned by this library */
 
@@ -341,7 +350,7 @@ typedef struct { int32_t img_id /* < 0: padding record */, n_kp, w, h; } mi355_f
 int  mi355_pack_features_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_header* hdr, void* d_payload);
 int  mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n);
 
-/* Chunk records: the feature exchange of frames of any keypoint count (keep-all frames, nfeatures <= 0, hold up to 32768).  A frame of n_kp
+/* Chunk records: the feature exchange of frames of any keypoint count (keep-all frames, nfeatures <= 0, hold up to keepall_max).  A frame of n_kp
  * keypoints travels as max(1, ceil(n_kp / 2048)) records of the layout above; chunk c holds rows [row0, row0 + rows) of the frame (the
  * packer writes row0 = 2048 c): keypoints at [0, rows * 28), descriptors at 57344 + [0, rows * 128), zeros elsewhere.  A frame of <= 2048
  * keypoints is one chunk, byte for byte the record mi355_pack_features_dev writes. */
@@ -355,7 +364,7 @@ int  mi355_pack_feature_chunks_dev(mi355_ctx* ctx, const int32_t* img_ids, int n
                                    int max_records, int* n_records);
 /* chunk records -> resident features, as if extracted here (records with img_id < 0 are skipped).  Every table is checked before any
  * state changes: each image's chunks 0 .. n_chunks - 1 appear exactly once, agree on n_kp / w / h, their rows tile [0, n_kp) in chunk order
- * with 1 .. 2048 rows each (one chunk of 0 rows for n_kp = 0), n_kp <= 32768.  A bad table returns MI355_ERR_ARG and leaves the ctx's
+ * with 1 .. 2048 rows each (one chunk of 0 rows for n_kp = 0), n_kp <= the ctx's keepall_max (32768 by default).  A bad table returns MI355_ERR_ARG and leaves the ctx's
  * features as they were. */
 int  mi355_install_feature_chunks_dev(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n_records);
 /* The collective over the chunk records (ncclAllGather of the headers and the payload, in place): no n_max argument, the per-rank record

@@ -4,7 +4,9 @@ brackets, GB/s over the carried bytes: one record read or written plus one writt
 mi355_allgather_feature_chunks with the own frames re-installed (wall clock, median of the repetitions).  The same for 63 frames of 2 900
 keypoints (the reference's frames) set through mi355_set_features.
 
-    python scratch/feature_chunks_time.py [--frames 63] [--reps 10] [--out profiles/feature_chunks_time.json]
+    python scratch/feature_chunks_time.py [--frames 63] [--reps 10] [--keepall-max 131072] [--out profiles/feature_chunks_time.json]
+
+--keepall-max sets the ctx's ceiling of keypoints per keep-all frame (option "keepall_max"); the survey frames keep about 83 000 each.
 """
 import argparse
 import json
@@ -18,9 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def time_share(ctx, ids, reps, torch, im):
+def time_share(ctx, ids, reps, torch, im, kmax=32768):
     n_rec = ctx.FeatureChunkCount(ids)
-    n_kp = [len(ctx.GetFeatures(k, max_kp=32768)[0]) for k in ids]
+    n_kp = [len(ctx.GetFeatures(k, max_kp=kmax)[0]) for k in ids]
     pay = torch.empty((n_rec, im.FEATURE_RECORD_BYTES), dtype=torch.uint8, device="cuda")
     carried = n_rec * im.FEATURE_RECORD_BYTES
     useful = sum(n * (28 + 128) for n in n_kp)
@@ -53,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=63)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--keepall-max", type=int, default=32768)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -63,11 +66,15 @@ def main():
     prm = im.default_params()
     prm.nfeatures = 0
     ctx = im.Context(0, prm)
+    if a.keepall_max != 32768:
+        ctx.set_option("keepall_max", a.keepall_max)
+    out["keepall_max"] = a.keepall_max
     md.init_comm(ctx)                                  # a communicator of one rank
     # 1. keep-all extractions of the survey's 4000x3000 frames
     w, h = 4000, 3000
     fr, _, _, ws = render_frames(ctx, torch, a.frames, w, h)
     survey = {"ok": [], "failed": {}}
+    t0 = time.perf_counter()
     for k in range(a.frames):
         try:
             ctx.SiftExtractDev(k, fr[k].data_ptr(), w, h, ws, want_count=True)
@@ -77,9 +84,10 @@ def main():
             ctx.DropFeatures(k)
     del fr
     torch.cuda.empty_cache()
+    out["survey_4000x3000_extract_ms_per_frame_one_at_a_time"] = (time.perf_counter() - t0) * 1e3 / a.frames
     out["survey_4000x3000_failed_frames"] = survey["failed"]
     if survey["ok"]:
-        out["survey_4000x3000_keepall"] = time_share(ctx, survey["ok"], a.reps, torch, im)
+        out["survey_4000x3000_keepall"] = time_share(ctx, survey["ok"], a.reps, torch, im, a.keepall_max)
     ctx.DropFeatures(-1)
     # 2. frames of 2 900 keypoints (the reference's 1000x750 frames kept about that many)
     rng = np.random.default_rng(1)
@@ -88,7 +96,7 @@ def main():
         kp = np.zeros(n, im.KEYPOINT)
         kp["x"] = rng.uniform(0, 1000, n); kp["y"] = rng.uniform(0, 750, n)
         ctx.SetFeatures(k, kp, rng.integers(0, 256, (n, 128)).astype(np.float32), 1000, 750)
-    out["reference_like_2900"] = time_share(ctx, list(range(a.frames)), a.reps, torch, im)
+    out["reference_like_2900"] = time_share(ctx, list(range(a.frames)), a.reps, torch, im, a.keepall_max)
     ctx.CommDestroy()
     ctx.close()
     s = json.dumps(out, indent=1)

@@ -37,6 +37,10 @@ class Params(C.Structure):
                 ("ransac_dist", C.c_float), ("sample_times", C.c_int32), ("pair_window", C.c_int32), ("ratio", C.c_float)]
 
 
+class ScreenParams(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("partners", C.c_int32), ("min_score", C.c_int32), ("ratio_pct", C.c_int32), ("window", C.c_int32)]
+
+
 class Mi355Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355 error %d: %s" % (code, msg))
@@ -211,6 +215,32 @@ class Context:
     def MatchPairsDev(self, pairs, d_out, ransac_dist=2.5, seed=1):
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         self._chk(self.L.mi355_match_pairs_dev(self._h, _p(pairs), len(pairs), C.c_float(ransac_dist), C.c_uint32(seed), C.c_void_p(int(d_out))))
+
+    # ---- descriptor-screened pair schedule (mi355_screen_pairs, csrc/screen.hip) ----------------------------------
+    def ScreenPairs(self, img_ids, window=0, top_k=256, partners=None, min_score=None, ratio_pct=80, rank=0, world=1, return_scores=False):
+        """the screened schedule over img_ids: [n_pairs, 2] image ids (positions a < b, sorted by (a, b), a mod world == rank); with
+        return_scores also the pairs' scores.  partners / min_score default to the library's (screen_params())."""
+        ids = np.ascontiguousarray(img_ids, np.int32).reshape(-1)
+        p = screen_params(window=window, top_k=top_k, partners=partners, min_score=min_score, ratio_pct=ratio_pct)
+        cap = len(ids) * p.partners if p.partners > 0 else 0
+        n = C.c_int(0)
+        while True:
+            out = np.zeros((max(cap, 1), 2), np.int32)
+            sc = np.zeros(max(cap, 1), np.int32)
+            rc = self.L.mi355_screen_pairs(self._h, _p(ids), len(ids), C.byref(p), int(rank), int(world), _p(out), _p(sc), cap, C.byref(n))
+            if rc == -1 and n.value > cap:
+                cap = n.value
+                continue
+            self._chk(rc)
+            break
+        pairs = out[:n.value].copy()
+        return (pairs, sc[:n.value].copy()) if return_scores else pairs
+
+    def ScreenScoresDev(self, img_ids, d_scores, **params):
+        """the n x n int32 score matrix of img_ids into device memory d_scores (-1 on the diagonal and outside the window)"""
+        ids = np.ascontiguousarray(img_ids, np.int32).reshape(-1)
+        p = screen_params(**params)
+        self._chk(self.L.mi355_screen_scores_dev(self._h, _p(ids), len(ids), C.byref(p), C.c_void_p(int(d_scores))))
 
     def BFMatch(self, img_i, img_j, sorted_=True, max_matches=2048):
         m = np.zeros(max_matches, DMATCH)
@@ -657,6 +687,18 @@ def surf_pair_schedule(n_images):
     out = np.zeros((max(n.value, 1), 2), np.int32)
     L.mi355_surf_pair_schedule(int(n_images), _p(out), n.value, C.byref(n))
     return out[:n.value]
+
+
+def screen_params(window=0, top_k=256, partners=None, min_score=None, ratio_pct=80):
+    """mi355_screen_params: the library's defaults (mi355_default_screen_params) with the given fields replaced"""
+    p = ScreenParams()
+    load_library().mi355_default_screen_params(C.byref(p))
+    p.window, p.top_k, p.ratio_pct = int(window), int(top_k), int(ratio_pct)
+    if partners is not None:
+        p.partners = int(partners)
+    if min_score is not None:
+        p.min_score = int(min_score)
+    return p
 
 
 def pair_schedule(n_images, window, rank=0, world=1):

@@ -207,7 +207,46 @@ inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned s
     return rc;
 }
 
-// int CMosaicByPose::GetMatchedPairsOneToAllSIFT_MultiThread()                                 MosaicWithoutPos.cpp:5244-5295
+// The same with the descriptor-screened schedule (mi355_screen_pairs) in place of the window: the pairs of images 0 .. nImages - 1 that the
+// screen keeps are matched, and vecMatchPairs is filled exactly as the window form fills it.  screen NULL: mi355_default_screen_params
+// (all pairs in scope); screen->window >= 2 screens the window's pairs only.
+inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned seed, const int* fixedFlags,
+                                       std::vector<MI355_NS MatchPointPairs>& vecMatchPairs, const mi355_screen_params* screen) {
+    mi355_ctx* c = context();
+    if (!c || nImages < 0) return -1;
+    mi355_screen_params sp;
+    if (screen) sp = *screen; else mi355_default_screen_params(&sp);
+    if (nImages < 2) return 0;
+    std::vector<int32_t> ids((size_t)nImages);
+    for (int i = 0; i < nImages; i++) ids[i] = i;
+    int cap = sp.partners > 0 ? nImages * sp.partners : 0, n_pairs = 0;
+    std::vector<int32_t> pairs((size_t)(cap > 0 ? cap : 1) * 2);
+    int rc = mi355_screen_pairs(c, &ids[0], nImages, &sp, 0, 1, &pairs[0], NULL, cap, &n_pairs);
+    if (rc == MI355_ERR_ARG && n_pairs > cap) {                  // partners == 0: the count is known now
+        cap = n_pairs;
+        pairs.resize((size_t)cap * 2);
+        rc = mi355_screen_pairs(c, &ids[0], nImages, &sp, 0, 1, &pairs[0], NULL, cap, &n_pairs);
+    }
+    if (rc != MI355_OK) return rc;
+    if (n_pairs == 0) return 0;
+    mi355_pair_result* res = (mi355_pair_result*)std::malloc(sizeof(mi355_pair_result) * (size_t)n_pairs);
+    if (!res) return -1;
+    rc = mi355_match_pairs(c, &pairs[0], n_pairs, ransacDist, seed, res);
+    if (rc == MI355_OK) {
+        mi355_match_point_pairs* v = NULL; int n = 0;
+        rc = mi355_results_to_match_pairs(res, n_pairs, fixedFlags, &v, &n);
+        if (rc == MI355_OK) {
+            const size_t old = vecMatchPairs.size();
+            vecMatchPairs.resize(old + n);
+            if (n) std::memcpy(&vecMatchPairs[old], v, sizeof(mi355_match_point_pairs) * n);
+            mi355_free(v);
+        }
+    }
+    std::free(res);
+    return rc;
+}
+
+// int CMosaicByPose::GetMatchedPairsOneToAllSIFT_MultiThread()                                MosaicWithoutPos.cpp:5244-5295
 // The reference's member reads m_pImgPoses / m_nImages / m_ransacDist and fills m_vecMatchPairs / m_nSuccess through its threads
 // (extraction :4832-4887, matching :5031-5241, results pushed under a mutex :10137-10145; the caller sets
 // m_pImgPoses / m_nImages at :4484-4486).  This is that whole call in one: SIFT(2000,3,0.01,20) of every image (parked as batches,

@@ -339,6 +339,47 @@ int  mi355_surf_match_pairs(mi355_ctx* ctx, const int32_t* pairs_ij, int n_pairs
  * of the window, so every rank needs every frame's features before matching: mi355_allgather_features. */
 int  mi355_pair_schedule(int n_images, int window, int rank, int world, int32_t* pairs_ij, int max_pairs, int* n_pairs);
 
+/* ---- descriptor-screened pair schedule (opt-in; csrc/screen.hip) ------------------------------------------------------------------
+ * An exact all-pairs score on the strongest top_k keypoints of every frame proposes the pairs worth matching; mi355_match_pairs(_dev) then
+ * matches only those.  For surveys whose capture order is not their spatial order (shuffled sets, several flights, lawnmower strips) and
+ * for large surveys whose window pairs are mostly rejected.  SIFT features only (resident through mi355_sift_extract*, mi355_set_features
+ * or the feature exchange); SURF features (float descriptors) are out of scope.
+ *
+ * Score of frames A, B (positions a, b of img_ids):
+ *   top-K list of a frame: its min(n, top_k) keypoints in the order (response descending, keypoint index ascending); its position in the
+ *     list breaks ties below.  D(q, t) = |q - t|^2 on the u8 descriptors, exact.
+ *   nn(q): the argmin of D over the other frame's list (ties: lower position); d1 its minimum; d2 the second smallest over the multiset
+ *     (d2 may equal d1; +infinity when the other list has one row).
+ *   score = #q in A's list with nn(nn(q)) == q and both q and nn(q) passing 10000 d1 < ratio_pct^2 d2 (int64; ratio_pct == 100: no test).
+ *   Symmetric; a frame without keypoints scores 0 with every other.
+ * Selection: position a ranks its in-scope candidates by (score descending, position ascending) and nominates the first `partners` of them
+ * whose score is >= min_score (partners == 0: every candidate with score >= min_score).  A pair is kept when either side nominates it.
+ * Scope: all pairs (window == 0) or the positions with |a - b| < window (mi355_pair_schedule's window).
+ * Limits: n <= 16384 (the n x n score matrix is 1 GB there).  MI355_ERR_ARG, with a message naming the value, for an unknown or duplicate
+ * id, top_k outside {32, 64, ..., 512}, partners < 0, ratio_pct outside [1, 100], window == 1 or < 0, and a bad rank / world.
+ * Results are identical across contexts and devices for the same features: every rank of a multi-GPU run computes the whole screen after
+ * the feature exchange and keeps its own rows (no collective). */
+typedef struct {
+    int32_t top_k;      /* keypoints per frame used by the screen: multiple of 32 in [32, 512]; default 256 */
+    int32_t partners;   /* per frame: nominate its best `partners` candidates; 0 = every candidate with score >= min_score */
+    int32_t min_score;  /* a nomination needs at least this score */
+    int32_t ratio_pct;  /* Lowe ratio in percent, 1..100 (100 = test off); default 80 */
+    int32_t window;     /* 0 = all pairs of the id list; >= 2 = only positions b - a < window (mi355_pair_schedule's window) */
+} mi355_screen_params;
+/* defaults measured on the C4 survey ("Screened pair schedule") */
+#define MI355_SCREEN_DEFAULT_PARTNERS  12
+#define MI355_SCREEN_DEFAULT_MIN_SCORE 6
+void mi355_default_screen_params(mi355_screen_params* p);
+
+/* n x n int32 scores, row-major, device memory (ctx's stream, complete on return); diagonal and out-of-window entries = -1.  p NULL: defaults. */
+int  mi355_screen_scores_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, const mi355_screen_params* p, int32_t* d_scores);
+
+/* the screened schedule: pairs {img_ids[a], img_ids[b]}, a < b, sorted by (a, b), only a mod world == rank; scores (the pairs' scores) may
+ * be NULL; same count / max_pairs convention as mi355_pair_schedule: *n_pairs = the count; pairs_ij == scores == NULL counts only; more
+ * pairs than max_pairs writes the first max_pairs and returns MI355_ERR_ARG.  With partners > 0, n * partners is always enough. */
+int  mi355_screen_pairs(mi355_ctx* ctx, const int32_t* img_ids, int n, const mi355_screen_params* p, int rank, int world,
+                        int32_t* pairs_ij, int32_t* scores, int max_pairs, int* n_pairs);
+
 /* Fixed-size feature record of one frame (what the reference keeps in keypoint_%d.key + discriptor_%d.xml,
  * MosaicWithoutPos.cpp:4682-4734): bytes [0, 57344) 2048 x cv::KeyPoint, [57344, 319488) 2048 x 128 u8 descriptors,
  * zero beyond the frame's n_kp.  The header travels separately (host-readable). */

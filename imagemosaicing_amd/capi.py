@@ -41,6 +41,15 @@ class ScreenParams(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("partners", C.c_int32), ("min_score", C.c_int32), ("ratio_pct", C.c_int32), ("window", C.c_int32)]
 
 
+class GainParams(C.Structure):
+    _fields_ = [("sigma_n", C.c_float), ("sigma_g", C.c_float), ("channels", C.c_int32), ("step", C.c_int32)]
+
+
+# mi355_gain_pair_stats: the overlap statistics of one listed pair (positions a, b in the frame list)
+GAIN_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)), ("sum_b", "<i8", (3,))])
+assert GAIN_PAIR_STATS.itemsize == 64
+
+
 class Mi355Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355 error %d: %s" % (code, msg))
@@ -558,6 +567,47 @@ class Context:
         self.synchronize()
         return out, cw, ch, cws
 
+    # ---- exposure gain compensation (mi355_gain_*, csrc/gain.hip) ----------------------------------------------------------
+    @staticmethod
+    def _frame_args(d_imgs, w, h, ws):
+        n = len(d_imgs)
+        ptrs = (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
+        return n, ptrs, np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32), np.ascontiguousarray(ws, np.int32)
+
+    @staticmethod
+    def _pairs_ab(pairs):
+        ab = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        return ab, len(ab)
+
+    def GainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8):
+        """overlap statistics of the listed pairs (positions in the frame list) on the lattice of `step`: (GAIN_PAIR_STATS [n_pairs],
+        frame cover N_k int64 [n])"""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        st = np.zeros(npairs, GAIN_PAIR_STATS)
+        cover = np.zeros(n, np.int64)
+        self._chk(self.L.mi355_gain_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), _p(st), _p(cover)))
+        return st, cover
+
+    def ApplyGainsDev(self, d_src, d_dst, w, h, ws, gains):
+        """d_dst[k] = LUT_k(d_src[k]) (d_dst[k] may be d_src[k]); gains [n, 3] float32.  Complete on return."""
+        n, sp, w, h, ws = self._frame_args(d_src, w, h, ws)
+        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        g = np.ascontiguousarray(gains, np.float32).reshape(n, 3)
+        self._chk(self.L.mi355_apply_gains_dev(self._h, sp, dp, _p(w), _p(h), _p(ws), n, _p(g)))
+
+    def GainCompensateDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
+        """statistics, solve and in-place apply on the device frames; returns the gains [n, 3] float32.  params: GainParams (gain_params())
+        or keyword fields of it."""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else gain_params(**kw)
+        g = np.zeros((n, 3), np.float32)
+        self._chk(self.L.mi355_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
+        return g
+
     # ---- frames kept in HBM after extraction, renders into caller memory -------------------------------------------------
     def DropFrames(self, img_id=-1):
         """releases the kept frame of img_id (set_option("keep_frames", 1)); img_id < 0: all of them"""
@@ -699,6 +749,35 @@ def screen_params(window=0, top_k=256, partners=None, min_score=None, ratio_pct=
     if min_score is not None:
         p.min_score = int(min_score)
     return p
+
+
+def gain_params(sigma_n=None, sigma_g=None, channels=None, step=None):
+    """mi355_gain_params: the library's defaults (mi355_default_gain_params: 10, 0.1, 3, 8) with the given fields replaced"""
+    p = GainParams()
+    load_library().mi355_default_gain_params(C.byref(p))
+    if sigma_n is not None:
+        p.sigma_n = float(sigma_n)
+    if sigma_g is not None:
+        p.sigma_g = float(sigma_g)
+    if channels is not None:
+        p.channels = int(channels)
+    if step is not None:
+        p.step = int(step)
+    return p
+
+
+def solve_gains(pair_stats, frame_cover, params=None, **kw):
+    """mi355_solve_gains (host only): gains [n, 3] float32 from GAIN_PAIR_STATS records and the frames' cover counts"""
+    L = load_library()
+    st = np.ascontiguousarray(pair_stats, GAIN_PAIR_STATS)
+    cover = np.ascontiguousarray(frame_cover, np.int64)
+    n = len(cover)
+    p = params if params is not None else gain_params(**kw)
+    g = np.zeros((max(n, 0), 3), np.float32)
+    rc = L.mi355_solve_gains(_p(st), len(st), _p(cover), n, C.byref(p), _p(g))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return g
 
 
 def pair_schedule(n_images, window, rank=0, world=1):

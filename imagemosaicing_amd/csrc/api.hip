@@ -4,7 +4,9 @@
 #include "common.h"
 #include <new>
 
-static thread_local std::string g_create_error;   // mi355_last_error(NULL): the calling thread's last creation error
+static thread_local std::string g_create_error;   // mi355_last_error(NULL): the calling thread's last creation error (or ctx-less call's error)
+
+void mi_set_host_error(const std::string& s) { g_create_error = s; }
 
 extern "C" void mi355_default_params(mi355_params* p) {
     if (!p) return;

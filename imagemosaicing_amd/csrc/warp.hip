@@ -18,6 +18,7 @@
 // contiguous run of the source row pair, so the 6-byte neighbourhood loads hit the same cache lines.
 #include "common.h"
 #include "hmath.h"
+#include "mosaic_frame.h"
 #include <memory>
 
 namespace {
@@ -31,37 +32,6 @@ struct WarpArgs {
     float dx, dy;                               // mode 0: xs = (float)xD - dx
     float sx, sy; int x0, y0;                   // mode 1 (chips): ((float)xD - dx) - sx + (float)x0
 };
-
-template <int CH>
-__device__ __forceinline__ void load_pair(const uint8_t* s, float& a, float& b, float& c, float& a1, float& b1, float& c1);
-
-// 6 bytes (two BGR pixels) with one dword + one ushort load; the device handles unaligned addresses.
-template <>
-__device__ __forceinline__ void load_pair<3>(const uint8_t* s, float& b0, float& g0, float& r0, float& b1, float& g1, float& r1) {
-    uint32_t lo; uint16_t hi;
-    __builtin_memcpy(&lo, s, 4);
-    __builtin_memcpy(&hi, s + 4, 2);
-    b0 = (float)(lo & 0xff); g0 = (float)((lo >> 8) & 0xff); r0 = (float)((lo >> 16) & 0xff);
-    b1 = (float)(lo >> 24);  g1 = (float)(hi & 0xff);        r1 = (float)(hi >> 8);
-}
-
-// the two BGR pixel pairs of a 2 x 2 neighbourhood (rows s and s + ws): one 8-byte load per row where 8 bytes from s still lie inside the row's
-// pitch (6 are used), else the 4 + 2 byte form -- half the load instructions of a sample (the canvas kernel is bound by their number)
-__device__ __forceinline__ void load_quad3(const uint8_t* s, int ws, bool wide, float& b00, float& g00, float& r00, float& b01, float& g01, float& r01,
-                                           float& b10, float& g10, float& r10, float& b11, float& g11, float& r11) {
-    if (wide) {
-        uint64_t q0, q1;
-        __builtin_memcpy(&q0, s, 8);
-        __builtin_memcpy(&q1, s + ws, 8);
-        b00 = (float)(q0 & 0xff); g00 = (float)((q0 >> 8) & 0xff); r00 = (float)((q0 >> 16) & 0xff);
-        b01 = (float)((q0 >> 24) & 0xff); g01 = (float)((q0 >> 32) & 0xff); r01 = (float)((q0 >> 40) & 0xff);
-        b10 = (float)(q1 & 0xff); g10 = (float)((q1 >> 8) & 0xff); r10 = (float)((q1 >> 16) & 0xff);
-        b11 = (float)((q1 >> 24) & 0xff); g11 = (float)((q1 >> 32) & 0xff); r11 = (float)((q1 >> 40) & 0xff);
-    } else {
-        load_pair<3>(s, b00, g00, r00, b01, g01, r01);
-        load_pair<3>(s + ws, b10, g10, r10, b11, g11, r11);
-    }
-}
 
 // PART (chips only): 0 = pixels and validity mask, 1 = the validity mask alone (no source read), 2 = the pixels alone (the mask bytes
 // hold the ownership by then and stay as they are)
@@ -224,12 +194,7 @@ extern "C" int mi355_mosaic_layout(const int* w, const int* h, int n, const floa
 // 2 x 2 neighbourhoods and one write per canvas pixel instead of one read + one write per covering image (3.1 covering images per
 // pixel in the C3 survey, ~60 at C5) and no clearing pass (pixels nobody covers are stored as zeros).  All images go through
 // one launch; the result does not depend on any execution order.
-struct FrameDev {
-    const uint8_t* src; int w, h, ws;
-    int begX, endX, begY, endY;                 // clipped canvas bounding box the reference visits for this image (:2276-2306)
-    float inv[9];
-    int unit_den;                               // affine with m8 = 1: the two divisions are by exactly 1.0f
-};
+// (FrameDev, the map and the sample: mosaic_frame.h)
 #ifndef MT_RPL_V
 #define MT_RPL_V 2
 #endif
@@ -336,6 +301,38 @@ __global__ __launch_bounds__(256) void mosaic_tile_kernel(const FrameDev* fr, in
     }
 }
 
+int mi_frame_dev_setup(const float* m, int w, int h, const float dG[2], int cw, int ch, int row0, int rows, FrameDev& f) {
+    memset(&f, 0, sizeof(f));
+    if (m[8] == 0.0f) return 0;                                         // MosaicWithoutPos.cpp:2205, 4646-4652
+    if (mi_inverse_matrix_host(m, 3, f.inv, 1e-12f) != 1) return 0;    // MosaicWithoutPos.cpp:2275 (reference: garbage invH)
+    float bminX = big(), bminY = big(), bmaxX = -big(), bmaxY = -big();
+    {
+        const float cx[4] = {0.0f, (float)(w - 1), (float)(w - 1), 0.0f};
+        const float cy[4] = {0.0f, 0.0f, (float)(h - 1), (float)(h - 1)};
+        for (int i = 0; i < 4; i++) {
+            float X, Y;
+            hm::apply_div9(m, cx[i], cy[i], X, Y);
+            X = X + (0.0f + dG[0]); Y = Y + (0.0f + dG[1]);
+            if (X < bminX) bminX = X;
+            if (X > bmaxX) bmaxX = X;
+            if (Y < bminY) bminY = Y;
+            if (Y > bmaxY) bmaxY = Y;
+        }
+    }
+    int begY = (int)(bminY - 0.5f), endY = (int)(bmaxY + 0.5f);       // :2305-2306
+    int begX = (int)(bminX - 0.5f), endX = (int)(bmaxX + 0.5f);
+    if (begX < 0) begX = 0;
+    if (begY < 0) begY = 0;
+    if (endX > cw - 1) endX = cw - 1;
+    if (endY > ch - 1) endY = ch - 1;
+    if (begY < row0) begY = row0;                                   // canvas stripe
+    if (endY > row0 + rows - 1) endY = row0 + rows - 1;
+    if (endX < begX || endY < begY) return 0;
+    f.begX = begX; f.endX = endX; f.begY = begY; f.endY = endY;
+    f.unit_den = (f.inv[6] == 0.0f && f.inv[7] == 0.0f && f.inv[8] == 1.0f) ? 1 : 0;
+    return 1;
+}
+
 // cover_only != NULL: cover_only[k] = 1 for the frames this call would read (the stripe's cover list, mi355_mosaic_stripe_cover), nothing is
 // rendered.  cover_exact == 0: every frame whose clipped canvas box meets the rows (host geometry alone: a superset); != 0: the frames that
 // give at least one pixel its sample -- the tile kernel's walk without its loads (what the rendering pass really dereferences).
@@ -354,33 +351,8 @@ int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
     fr.reserve(n);
     for (int k = 0; k < n; k++) {                  // ascending image order = overwrite order (MosaicWithoutPos.cpp:2254)
         const float* m = h9s + 9 * k;
-        if (m[8] == 0.0f) continue;
         FrameDev f;
-        memset(&f, 0, sizeof(f));
-        if (mi_inverse_matrix_host(m, 3, f.inv, 1e-12f) != 1) continue;   // MosaicWithoutPos.cpp:2275 (reference: garbage invH)
-        float bminX = big(), bminY = big(), bmaxX = -big(), bmaxY = -big();
-        {
-            const float cx[4] = {0.0f, (float)(w[k] - 1), (float)(w[k] - 1), 0.0f};
-            const float cy[4] = {0.0f, 0.0f, (float)(h[k] - 1), (float)(h[k] - 1)};
-            for (int i = 0; i < 4; i++) {
-                float X, Y;
-                hm::apply_div9(m, cx[i], cy[i], X, Y);
-                X = X + (0.0f + dG[0]); Y = Y + (0.0f + dG[1]);
-                if (X < bminX) bminX = X;
-                if (X > bmaxX) bmaxX = X;
-                if (Y < bminY) bminY = Y;
-                if (Y > bmaxY) bmaxY = Y;
-            }
-        }
-        int begY = (int)(bminY - 0.5f), endY = (int)(bmaxY + 0.5f);       // :2305-2306
-        int begX = (int)(bminX - 0.5f), endX = (int)(bmaxX + 0.5f);
-        if (begX < 0) begX = 0;
-        if (begY < 0) begY = 0;
-        if (endX > cw - 1) endX = cw - 1;
-        if (endY > ch - 1) endY = ch - 1;
-        if (begY < row0) begY = row0;                                   // canvas stripe
-        if (endY > row0 + rows - 1) endY = row0 + rows - 1;
-        if (endX < begX || endY < begY) continue;
+        if (!mi_frame_dev_setup(m, w[k], h[k], dG, cw, ch, row0, rows, f)) continue;
         if (cover_only && !cover_exact) { cover_only[k] = 1; continue; }
         if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) { ctx->set_error("mosaic_refined: bad image geometry"); return MI355_ERR_ARG; }
         // d_imgs[k] == NULL: the caller holds no copy of this image (owner-only frames, mi355_exchange_frames): it says the rows do not read
@@ -389,8 +361,6 @@ int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
         if (!cover_only && !d_imgs[k]) { withheld.push_back(k); continue; }
         f.src = cover_only ? nullptr : d_imgs[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k];
         frame_of.push_back(k);
-        f.begX = begX; f.endX = endX; f.begY = begY; f.endY = endY;
-        f.unit_den = (f.inv[6] == 0.0f && f.inv[7] == 0.0f && f.inv[8] == 1.0f) ? 1 : 0;
         fr.push_back(f);
     }
     if (cover_only && !cover_exact) return MI355_OK;

@@ -509,6 +509,72 @@ int  mi355_mosaic_stripe_cover(mi355_ctx* ctx, int mode, const int* w, const int
 int  mi355_exchange_frames(mi355_ctx* ctx, const uint8_t* const* d_frames, const int* h, const int* ws, int n, const int32_t* owner,
                            const uint8_t* need, int flags, const uint8_t** d_out, uint64_t* bytes_recv, uint64_t* bytes_sent);
 
+/* ---- exposure gain compensation (opt-in; csrc/gain.hip) ------------------------------------------------------------------------
+ * One gain per frame and channel, solved from the frames' overlaps and applied to the frames' texels before a render; the renders
+ * themselves are unchanged (GainCompensator's place between alignment and blending, OpenCV detail::GainCompensator).
+ *
+ * Frames: as mi355_mosaic_refined_dev takes them -- d_imgs (device, BGR8 rows of ws bytes), w, h, ws, n, h9s.  Frame k takes part only if
+ * h9s[9k+8] != 0 and its inverse exists, exactly as in the refined render; d_imgs[k] of a frame that takes no part may be NULL.  The canvas
+ * is mi355_mosaic_layout's for the same arguments (cw, ch, dGxy).
+ * Lattice: the canvas pixels (x, y) with x % step == 0 and y % step == 0, 1 <= step <= 64 (default 8).
+ * Cover and sample: frame k covers a lattice point, and has a sample there, exactly when the refined render would give that canvas pixel
+ *   frame k's sample if k were the top frame: the point lies inside k's clipped canvas box, the source coordinate (same unit_den /
+ *   apply_div9 choice) lies in [0, w-1) x [0, h-1), and the sample is the render's hm::bilin byte per channel.  Samples come from each
+ *   frame's own pixels whatever covers the point in the canvas.
+ * Statistics (integers: exact, independent of execution order):
+ *   frame_cover[k] = N_k, the lattice points frame k covers;
+ *   per listed pair (a, b) of positions: n = the lattice points both cover, sum_a[c] / sum_b[c] = frame a's / frame b's samples of channel
+ *   c (0 B, 1 G, 2 R) summed over those points.
+ * Gains: alpha = 1 / sigma_n^2, beta = 1 / sigma_g^2.  Per channel c (channels == 3), or once on the channel mean (channels == 1:
+ *   I = sum_c sum / (3 n)), with I_ab = sum_a / n, I_ba = sum_b / n, in double, for each listed pair with n > 0:
+ *     A[a][a] += 2 alpha I_ab^2 n + beta n      A[b][b] += 2 alpha I_ba^2 n + beta n
+ *     A[a][b] -= 2 alpha I_ab I_ba n            A[b][a] -= 2 alpha I_ab I_ba n
+ *     rhs[a]  += beta n                         rhs[b]  += beta n
+ *   and for every frame k: A[k][k] += beta N_k, rhs[k] += beta N_k (GainCompensator::singleFeed restricted to the listed pairs).  g solves
+ *   A g = rhs within 1e-9 relative (infinity norm) of the exact solution; a frame without an equation (A[k][k] == 0: skipped, or N_k == 0
+ *   and no listed pair with n > 0) gets g = 1 exactly.  gains: float[n][3] (channels == 1: the one gain in all three).  The solve is
+ *   single-threaded double arithmetic in a fixed order: bit-identical from call to call, across thread counts and contexts, so every rank of
+ *   a multi-GPU run solves the same records to the same bits.
+ * Apply: LUT_kc[v] = clamp(floor((double)g[k][c] * v + 0.5), 0, 255); bytes [0, 3w) of every row of dst[k] become LUT(src[k]), the pitch
+ *   padding of dst is left untouched.  dst[k] may equal src[k] (in place); a frame whose three gains are 1.0f gives identical bytes.  Gains
+ *   act on texels before sampling: a compensated canvas is, byte for byte, the render (refined or blended) of the compensated frames.
+ * Errors (MI355_ERR_ARG, the message names the index or value): a == b, a position outside [0, n), an unordered pair listed twice; step
+ *   outside [1, 64]; channels not 1 or 3; sigma_n or sigma_g <= 0 (or not finite); n > 65535; a dst range that overlaps a src or dst range
+ *   other than its own src range exactly; a taking-part frame with a NULL pointer or w < 2, h < 2, ws < 3 w. */
+typedef struct {
+    int32_t a, b;               /* positions in the frame list */
+    int64_t n;                  /* lattice points both frames cover */
+    int64_t sum_a[3], sum_b[3]; /* B, G, R samples of frame a / frame b summed over those points */
+} mi355_gain_pair_stats;        /* 64 B */
+typedef struct {
+    float sigma_n, sigma_g;     /* OpenCV GainCompensator: 10, 0.1 */
+    int32_t channels;           /* 3: a gain per channel; 1: one gain on the channel mean, copied to all three */
+    int32_t step;               /* lattice step in canvas pixels, 1..64 */
+} mi355_gain_params;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_gain_pair_stats) == 64, "mi355_gain_pair_stats is 64 bytes");
+static_assert(sizeof(mi355_gain_params) == 16, "mi355_gain_params is 16 bytes");
+#else
+_Static_assert(sizeof(mi355_gain_pair_stats) == 64, "mi355_gain_pair_stats is 64 bytes");
+_Static_assert(sizeof(mi355_gain_params) == 16, "mi355_gain_params is 16 bytes");
+#endif
+/* sigma_n = 10, sigma_g = 0.1, channels = 3, step = 8 */
+void mi355_default_gain_params(mi355_gain_params* p);
+/* the statistics (one launch over all pairs and frames; complete on return): pair_stats (HOST, n_pairs records, a / b filled in) and
+ * frame_cover (HOST, n values; may be NULL).  pairs_ab: 2 x n_pairs positions. */
+int  mi355_gain_stats_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                          const int32_t* pairs_ab, int n_pairs, int step, mi355_gain_pair_stats* pair_stats, int64_t* frame_cover);
+/* the gains from the statistics (host only, no ctx, no device); p NULL: defaults (p->step is not used here).  Errors: mi355_last_error(NULL). */
+int  mi355_solve_gains(const mi355_gain_pair_stats* pair_stats, int n_pairs, const int64_t* frame_cover, int n, const mi355_gain_params* p,
+                       float* gains /* n x 3 */);
+/* dst[k] = LUT_k(src[k]) for every k (one launch; enqueued on the ctx stream).  gains: HOST, n x 3.  Kept frames (mi355_get_frame_dev) may
+ * be sources; they stay immutable, so their output goes to caller buffers. */
+int  mi355_apply_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n,
+                           const float* gains);
+/* statistics at p->step, solve, apply in place on d_imgs; gains_out (HOST, n x 3; may be NULL) receives the gains.  p NULL: defaults. */
+int  mi355_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                               const int32_t* pairs_ab, int n_pairs, const mi355_gain_params* p, float* gains_out);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

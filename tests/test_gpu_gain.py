@@ -103,6 +103,33 @@ def test_apply_equals_lut(case):
     ctx.ApplyGainsDev(sp2, sp2, w2, h2, ws2, g)
     for k in range(n):
         assert np.array_equal(_host(src2[k], w2[k]), gr.apply_lut(imgs[k], g[k])), k
+    # ragged frames in one launch: rows shorter than the 16-byte head, heights off the 16-row blocks, unequal block counts, mixed pitches
+    # and base pointers (tests/pitched.py; padding and the gaps between frames are garbage that must stay as it is)
+    from tests import pitched as pf
+    from tests.synth import texture
+    sizes = [(1, 1), (2, 17), (5, 15), (7, 241), (320, 33), (333, 257)]
+    rimgs = [texture(w, h, seed=60 + k) for k, (w, h) in enumerate(sizes)]
+    rg = rng.uniform(0.6, 1.5, (len(sizes), 3)).astype(np.float32)
+    pitches = [pf.pitch_kinds(w)[k % 5] for k, (w, h) in enumerate(sizes)]
+    fs = pf.PitchedFrames(rimgs, pitches, offsets=[k % 4 for k in range(len(sizes))], seed=7)
+    fd = pf.PitchedFrames([np.zeros_like(i) for i in rimgs], pitches, offsets=[(k + 1) % 4 for k in range(len(sizes))], seed=8)
+    ts, sp3 = fs.to_device(torch)
+    td, dp3 = fd.to_device(torch)
+    rw, rh, rws = fs.geom()
+    pix_s, pix_d = np.zeros(fs.nbytes, bool), np.zeros(fd.nbytes, bool)
+    for k in range(len(sizes)):
+        fs.view(k, pix_s)[:, :fs.row_bytes(k)] = True
+        fd.view(k, pix_d)[:, :fd.row_bytes(k)] = True
+    ctx.ApplyGainsDev(sp3, dp3, rw, rh, rws, rg)
+    got_s, got_d = fs.device_bytes(ts), fd.device_bytes(td)
+    for k in range(len(sizes)):
+        assert np.array_equal(fd.pixels(k, got_d), gr.apply_lut(rimgs[k], rg[k])), sizes[k]
+    assert np.array_equal(got_d[~pix_d], fd.buf[~pix_d]) and np.array_equal(got_s, fs.buf)
+    ctx.ApplyGainsDev(sp3, sp3, rw, rh, rws, rg)
+    got_s = fs.device_bytes(ts)
+    for k in range(len(sizes)):
+        assert np.array_equal(fs.pixels(k, got_s), gr.apply_lut(rimgs[k], rg[k])), sizes[k]
+    assert np.array_equal(got_s[~pix_s], fs.buf[~pix_s])
     ctx.close()
 
 

@@ -60,6 +60,17 @@ def test_warp_vs_oracle_random(ctx, oracle):
             rc, ref = oracle.image_projection_transform(img, h9)
             buf, dw, dh, dws = ctx.ImageProjectionTransform(img, h9)
             assert (dw, dh, dws) == ref[1:] and np.array_equal(buf, ref[0])
+    # one channel (CH == 1), odd and tiny sizes: rows of w bytes, odd pitches
+    for (w, h) in [(333, 257), (201, 150), (7, 5), (2, 9), (9, 2), (2, 2)]:
+        img = np.ascontiguousarray(texture(w, h, seed=w + h)[..., 1])
+        for _ in range(3):
+            H = np.eye(3) + rng.normal(0, 0.06, (3, 3))
+            H[0, 2] = rng.uniform(-20, 20); H[1, 2] = rng.uniform(-20, 20)
+            H[2, 0] = rng.normal(0, 1e-4); H[2, 1] = rng.normal(0, 1e-4); H[2, 2] = 1
+            h9 = H.reshape(9).astype(np.float32)
+            rc, ref = oracle.image_projection_transform(img, h9)
+            buf, dw, dh, dws = ctx.ImageProjectionTransform(img, h9)
+            assert (dw, dh, dws) == ref[1:] and np.array_equal(buf, ref[0]), (w, h)
 
 
 def test_mosaic_stripes_equal_whole(ctx):

@@ -131,7 +131,15 @@ void mi355_free(void* p);                               /* frees host buffers re
  * 0..255 like OpenCV's SIFT; either output may be NULL).  Features stay device-resident under img_id for
  * mi355_match_pairs (the reference round-trips them through d:/feature_temp files instead).  With kp, desc128 and n_kp all
  * NULL nothing is waited for: the frame is copied into a staging ring in HBM (bgr may be reused on return) and joins a
- * batch like a device frame -- the fast way to feed host images. */
+ * batch like a device frame -- the fast way to feed host images.
+ * Sizes: w and h are at least 16 (smaller: MI355_ERR_ARG, decided on the host before any launch; the ctx stays usable) and below 2^20,
+ * keep-all frames at most 16384 x 16384.  Octave 0 is the image itself; cv::SIFT's count is cvRound(log2(min(w, h)) - 2), and octaves are
+ * built while both sides have at least 12 samples (no keypoint fits a smaller one: 5 border samples a side) -- for every size the 12-sample
+ * stop comes first, so octave o exists exactly when min(w, h) >> o >= 12.
+ * Ties at the cut: like KeyPointsFilter::retainBest, every keypoint whose |response| equals the nfeatures-th is kept; a feature record
+ * holds 2048 rows, and a frame whose tie group reaches past them (periodic content: identical structures by the hundred) fails with
+ * MI355_ERR_FAILED ("... overflow ...") instead of being cut short -- nothing is stored under img_id, the ctx stays usable, and keep-all
+ * mode (nfeatures <= 0) takes such frames. */
 int  mi355_sift_extract(mi355_ctx* ctx, int img_id, const uint8_t* bgr, int w, int h, int width_step,
                         mi355_keypoint* kp, float* desc128, int max_kp, int* n_kp);
 /* Same, image already in HBM (device pointer); nothing is copied back.  With n_kp == NULL the call returns at once and

@@ -100,6 +100,9 @@ int  orc_sift(const uint8_t* bgr, int w, int h, int ws, int nfeatures, orc_keypo
  * (a measuring instrument, see oracle_sift.c).  Process-wide switch: set it, call orc_sift, set it back. */
 void orc_sift_set_mode(int mode);
 int  orc_sift_get_mode(void);
+/* octave counts of the latest orc_sift call in this process: cvRound(log2(min(w, h)) - 2), and the octaves actually built (the loop stops
+ * below 12 samples) */
+void orc_sift_last_octaves(int* formula, int* built);
 void orc_cv_exp32f(const float* x, float* y, int n);      /* OpenCV 2.4.0 cv::exp over an array, as opencv_core240.dll runs it */
 const double* orc_cv_exp_table(void);                     /* its 64-entry table 2^(k/64) * A0 */
 

@@ -152,6 +152,9 @@ static inline void det_sincosdeg(float deg, float* sn, float* cs)
 static int g_sift_mode = 0;
 void orc_sift_set_mode(int mode) { g_sift_mode = mode; }
 int orc_sift_get_mode(void) { return g_sift_mode; }
+/* octave counts of the latest orc_sift call (process-wide, for tests): what the cvRound formula gives, and how many octaves were built */
+static int g_last_noct_formula = 0, g_last_noct_built = 0;
+void orc_sift_last_octaves(int* formula, int* built) { *formula = g_last_noct_formula; *built = g_last_noct_built; }
 
 #define EXPPOLY_A0 .9670371139572337719125840413672004409288e-2
 static double g_exp_tab[64];
@@ -535,6 +538,7 @@ int orc_sift(const uint8_t* bgr, int w, int h, int ws, int nfeatures, orc_keypoi
         no = o + 1;
     }
     free(up); free(tmp);
+    g_last_noct_formula = nOct; g_last_noct_built = no;
     /* 4-6: extrema -> refined keypoints with orientations */
     const int threshold = (int)floor(0.5 * 0.01 / N_LAYERS * 255 * FIXPT_SCALE);          /* 20 */
     size_t cap = 1 << 16, ncand = 0;

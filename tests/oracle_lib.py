@@ -248,6 +248,13 @@ class Oracle:
         n = self.L.orc_sift(_p(bgr), w, h, bgr.strides[0], nfeatures, _p(kp), _p(desc), max_kp)
         return kp[:n].copy(), desc[:n].copy()
 
+    def sift_last_octaves(self):
+        """(octave count by cv::SIFT's formula, octaves built) of the latest sift() call"""
+        a, b = C.c_int(0), C.c_int(0)
+        self.L.orc_sift_last_octaves.restype = None
+        self.L.orc_sift_last_octaves(C.byref(a), C.byref(b))
+        return a.value, b.value
+
 
     # ---- SURF variant (row f4) ---------------------------------------------------------------------
     def surf(self, bgr, hessian=50.0, max_kp=4096):

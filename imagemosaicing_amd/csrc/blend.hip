@@ -292,8 +292,12 @@ __device__ __forceinline__ void blend_lap_accumulate_body(const short* coarse, i
     int he[3][3], ho[3][3];                               // horizontal EXPAND values at fine columns 2x (even) and 2x + 1 (odd), per row and channel
 #pragma unroll
     for (int r = 0; r < 3; r++) up_h_pair(rows[r], w, x, he[r], ho[r]);
-    // the two fine pixels of a row are 12 contiguous bytes (4-byte aligned: the fine column 2x, the region offset ox and the row pitches are
-    // even): three 32-bit loads / stores instead of six 16-bit ones, the weights as one 64-bit access
+    // the two fine pixels of a row are 12 contiguous bytes: three 32-bit loads / stores instead of six 16-bit ones, the weights as one
+    // 64-bit access.  On the canvas side they are naturally aligned (the fine column 2x, the region offset ox and the row pitches are even).
+    // On the chip side they need not be: ChipP::tmp is a running sum of level sizes and a chip whose top level is odd x odd (224 x 160 at
+    // five bands: 7 x 5) leaves every level of the next chips at an odd pixel offset -- 2 bytes off for the 32-bit words, 4 bytes off for the
+    // float2.  Global memory on gfx950 takes unaligned vector accesses and the values are the same ones (tests/test_gpu_blend_edges.py,
+    // odd_offsets: 40 chips, odd offsets inside both batches).
 #pragma unroll
     for (int dy = 0; dy < 2; dy++) {
         const int Y = 2 * y + dy;

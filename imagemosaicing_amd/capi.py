@@ -45,6 +45,10 @@ class GainParams(C.Structure):
     _fields_ = [("sigma_n", C.c_float), ("sigma_g", C.c_float), ("channels", C.c_int32), ("step", C.c_int32)]
 
 
+class FeatherParams(C.Structure):
+    _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 # mi355_gain_pair_stats: the overlap statistics of one listed pair (positions a, b in the frame list)
 GAIN_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)), ("sum_b", "<i8", (3,))])
 assert GAIN_PAIR_STATS.itemsize == 64
@@ -608,6 +612,45 @@ class Context:
         self._chk(self.L.mi355_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
         return g
 
+    # ---- weighted (feather) blending (mi355_mosaic_feathered*, csrc/feather.hip) -------------------------------------------
+    def MosaicFeathered(self, imgs, h9s, params=None, want_pixels=True, **kw):
+        """mi355_mosaic_feathered: host images in, (canvas rows x cws, cw, ch, cws) out.  params: FeatherParams (feather_params()) or its
+        keyword fields (ramp)."""
+        n = len(imgs)
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
+        w = np.array([i.shape[1] for i in imgs], np.int32)
+        h = np.array([i.shape[0] for i in imgs], np.int32)
+        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else feather_params(**kw)
+        canvas = C.c_void_p()
+        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_mosaic_feathered(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
+                                                C.byref(cws)))
+        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value) if want_pixels else None
+        self.L.mi355_free(canvas)
+        return buf, cw.value, ch.value, cws.value
+
+    def MosaicFeatheredDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, params=None, **kw):
+        """mi355_mosaic_feathered_dev: device frames (0 / None: withheld) into the device canvas, rows [row0, row0 + rows); complete on return"""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else feather_params(**kw)
+        self._chk(self.L.mi355_mosaic_feathered_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas)),
+                                                    int(cw), int(ch), int(cws), int(row0), int(rows if rows >= 0 else ch)))
+
+    def MosaicFeatheredInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
+        """mi355_mosaic_feathered_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else feather_params(**kw)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_feathered_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
+                                                     C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
     # ---- frames kept in HBM after extraction, renders into caller memory -------------------------------------------------
     def DropFrames(self, img_id=-1):
         """releases the kept frame of img_id (set_option("keep_frames", 1)); img_id < 0: all of them"""
@@ -763,6 +806,15 @@ def gain_params(sigma_n=None, sigma_g=None, channels=None, step=None):
         p.channels = int(channels)
     if step is not None:
         p.step = int(step)
+    return p
+
+
+def feather_params(ramp=None):
+    """mi355_feather_params: the library's defaults (mi355_default_feather_params: ramp 0 = a full tent per frame) with the given fields replaced"""
+    p = FeatherParams()
+    load_library().mi355_default_feather_params(C.byref(p))
+    if ramp is not None:
+        p.ramp = int(ramp)
     return p
 
 

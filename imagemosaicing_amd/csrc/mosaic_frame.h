@@ -17,6 +17,12 @@ struct FrameDev {
 // the frame (h9[8] == 0, no inverse, or a clipped box that misses the rows), 1 otherwise.  src / w / h / ws are left to the caller.
 int mi_frame_dev_setup(const float* h9, int w, int h, const float dG[2], int cw, int ch, int row0, int rows, FrameDev& f);
 
+// The per-block candidate lists of the one-pass renders (warp.hip: mosaic_lists_kernel), enqueued on the ctx stream: for every MOSAIC_LIST_BLOCK x
+// MOSAIC_LIST_BLOCK block of the canvas rows from row0 on (bx_n x by_n blocks, row-major) the frames of d_fr[0 .. nf) whose box meets it, highest
+// index first, at d_lists[block * nf ..], their number in d_counts[block].
+constexpr int MOSAIC_LIST_BLOCK = 256;
+void mi_mosaic_lists_launch(mi355_ctx* ctx, const FrameDev* d_fr, int nf, int bx_n, int by_n, int row0, uint16_t* d_lists, int* d_counts);
+
 namespace {
 
 template <int CH>

@@ -407,6 +407,12 @@ int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
     return MI355_OK;
 }
 
+// the candidate lists for a render that lives in another file (feather.hip): the launch above, nothing else
+static_assert(MT_COARSE == MOSAIC_LIST_BLOCK, "mosaic_frame.h states the list block size");
+void mi_mosaic_lists_launch(mi355_ctx* ctx, const FrameDev* d_fr, int nf, int bx_n, int by_n, int row0, uint16_t* d_lists, int* d_counts) {
+    hipLaunchKernelGGL(mosaic_lists_kernel, dim3((bx_n * by_n + 255) / 256), dim3(256), 0, ctx->stream, d_fr, nf, bx_n, by_n, row0, d_lists, d_counts);
+}
+
 int mi_warp_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, int ch, const float* h9,
                   uint8_t** dst, int* dw, int* dh, int* dws) {
     if (!src || !h9 || !dst || w < 2 || h < 2 || (ch != 1 && ch != 3) || ws < w * ch) { ctx->set_error("warp_image: bad arguments"); return MI355_ERR_ARG; }

@@ -346,12 +346,10 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
     return rc;
 }
 
-// int CMosaicByPose::MosaicImagesRefined(const ImagePoseInfo* pImgPoses, const int nImages, const ImageTransform* pRectified)
-//                                                                                              MosaicWithoutPos.cpp:2194-2352
-// The member writes m_pMosaicResult; here it is the last argument (released first when not NULL, like a second call would leak in
-// the reference).  PoseT is the reference's ImagePoseInfo (only .pImg is read).  Returns 0 / -1 / -2 like the reference.
+namespace detail {
+// the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into) or weighted (mi355_mosaic_feathered_into, default ramp)
 template <class PoseT>
-inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
+inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, bool weighted) {
     if (NULL == pImgPoses || NULL == pRectified || nImages <= 0) return -1;
     mi355_ctx* c = context();
     if (!c) return -2;
@@ -372,11 +370,30 @@ inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const 
     if (rc != MI355_OK) return rc == MI355_ERR_ARG ? -1 : -2;
     MI355_NS IplImage* out = MI355_CREATE_IMAGE_8U(cw, ch, 3);          // :2246-2248; the library renders straight into its rows
     if (!out) return -2;
-    rc = mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
+    rc = weighted ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
+                  : mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
     if (rc != MI355_OK) { cvReleaseImage(&out); return rc == MI355_ERR_ARG ? -1 : -2; }
     if (pMosaicResult) cvReleaseImage(&pMosaicResult);
     pMosaicResult = out;
     return 0;
+}
+}  // namespace detail
+
+// int CMosaicByPose::MosaicImagesRefined(const ImagePoseInfo* pImgPoses, const int nImages, const ImageTransform* pRectified)
+//                                                                                              MosaicWithoutPos.cpp:2194-2352
+// The member writes m_pMosaicResult; here it is the last argument (released first when not NULL, like a second call would leak in
+// the reference).  PoseT is the reference's ImagePoseInfo (only .pImg is read).  Returns 0 / -1 / -2 like the reference.
+template <class PoseT>
+inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, false);
+}
+
+// UavMatchParam.blending == 1, "weighted blending" (MosaicWithoutPos.h:65): the mode the reference's driver sends down the unblended branch
+// (MosaicWithoutPos.cpp:4666-4672).  MosaicImagesRefined's signature, ownership and return values; the canvas is mi355_mosaic_feathered's
+// (include/mi355_mosaic.h, "weighted (feather) blending") with the default ramp.  Kept frames are used under MI355_ADAPTOR_KEEP_FRAMES.
+template <class PoseT>
+inline int MosaicImagesWeighted(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, true);
 }
 
 // IplImage* LaplacianPyramidBlending(IplImage** pImages, int imagesNum, ProjectMat* pImgT, int band, float resScale)

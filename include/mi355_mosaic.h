@@ -197,6 +197,39 @@ int  mi355_mosaic_layout(const int* w, const int* h, int n, const float* h9s, in
 int  mi355_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n,
                               const float* h9s, uint8_t* d_canvas, int cw, int ch, int cws, int row0, int rows);
 
+/* ---- weighted (feather) blending: the third one-pass render (csrc/feather.hip) -----------------------------------------------------
+ * UavMatchParam.blending = 1 (MosaicWithoutPos.h:65: 0 none, 1 weighted, 2 multiband).  The reference declares the mode and renders it
+ * unblended (MosaicWithoutPos.cpp:4666-4672); its MergeMultiImages2 is unreachable and order-dependent and is NOT what is computed here.
+ * Definition (exact integers; the bytes do not depend on frame order, tile shape or stripe cut):
+ *   Canvas geometry, frames and skipping are mi355_mosaic_refined_dev's: canvas = mi355_mosaic_layout; frames with h9[8] == 0 or without an
+ *   inverse are skipped.  "Frame k gives canvas pixel (x, y) a sample" is the refined render's own statement: the pixel lies in k's clipped
+ *   canvas box, the source coordinate (xs, ys) (unit_den / two-division choice as there) lies in [0, w-1) x [0, h-1), and the sample s_k[c],
+ *   c = B, G, R, is hm::bilin of the 2 x 2 texels at xi = (int)xs, yi = (int)ys with p = ys - yi, q = xs - xi.
+ *   Weight of a w x h frame with ramp R >= 1 (source pixels), for texel (i, j):
+ *     d(i, j)  = min(i, w-1-i, j, h-1-j)                       integer border distance
+ *     Wk(i, j) = (254 * min(d, R)) / R                         integer division, in [0, 254]
+ *     omega_k  = 1 + hm::bilin(Wk(xi,yi), Wk(xi+1,yi), Wk(xi,yi+1), Wk(xi+1,yi+1), p, q)          in [1, 255]
+ *   i.e. omega_k - 1 is the byte the refined render would take from a frame whose pixels are Wk.  Wk is evaluated arithmetically; no weight
+ *   image is stored.  params.ramp > 0: R = ramp for every frame; ramp == 0 (default): per frame R = (min(w, h) + 1) / 2, a full tent.
+ *   out[c] = (sum_k omega_k * s_k[c] + (sum_k omega_k) / 2) / sum_k omega_k                        integer division
+ *   over every frame k that gives the pixel a sample; a pixel no frame covers is 0; row padding [3 cw, cws) is 0.  With n <= 65535 every sum
+ *   fits 32 unsigned bits (255 * 255 * 65535 + 255 * 65535 / 2 < 2^32).
+ * Consequences: where exactly one frame covers a pixel the byte is the refined render's; every byte lies between the smallest and the
+ *   largest contributing sample; after mi355_gain_compensate_dev the canvas is the feathered render of the compensated frames.
+ * Cost: one launch over canvas tiles, no chips, masks or pyramids; every covering frame is sampled (C5: ~60 per pixel).  No cap on layers.
+ * Stripes: row0, rows, and the whole canvas's cw, ch, cws, as mi355_mosaic_refined_dev; a canvas row depends only on the frames whose box
+ *   meets it, so MI355_COVER_REFINED is exactly the set of frames a stripe reads.  d_imgs[k] == NULL for such a frame is MI355_ERR_ARG
+ *   whatever "strict_frames" says (there is no "lies under later frames" case); NULL for a frame outside the cover is fine.
+ * Errors: as the refined twins (argument checks, n <= 1 -> MI355_ERR_FAILED in the host forms, n > 65535, canvas geometry); params NULL =
+ *   defaults; ramp < 0 -> MI355_ERR_ARG; a contributing frame wider or higher than 2^20 -> MI355_ERR_ARG. */
+typedef struct { int32_t ramp; int32_t reserved[3]; } mi355_feather_params;
+void mi355_default_feather_params(mi355_feather_params* p);          /* ramp = 0, reserved = 0 */
+int  mi355_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n,
+                                const float* h9s, const mi355_feather_params* params, uint8_t* d_canvas, int cw, int ch, int cws, int row0, int rows);
+/* host images in, *canvas allocated by the library -> mi355_free (mi355_mosaic_refined's form) */
+int  mi355_mosaic_feathered(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
+                            const float* h9s, const mi355_feather_params* params, uint8_t** canvas, int* cw, int* ch, int* cws);
+
 /* LaplacianPyramidBlending warp stage (MosaicImage.cpp:2233-2460) + FindMasksByDistMap (:1761-1881):
  * per kept image a tight chip (3ch u8; the reference then converts to CV_16S), its validity mask and, with
  * find_masks!=0, the exclusive distance-map ownership masks.  h9s must carry the resScale multiplication of
@@ -271,6 +304,9 @@ int  mi355_get_frame_dev(mi355_ctx* ctx, int img_id, const uint8_t** d_frame, in
  * MI355_ERR_FAILED, as mi355_mosaic_refined. */
 int  mi355_mosaic_refined_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, uint8_t* dst, int dst_pitch, int cw, int ch);
+/* mi355_mosaic_feathered with mi355_mosaic_refined_into's sources (kept frames / host images), destination and download */
+int  mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                                 int n, const float* h9s, const mi355_feather_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
 int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 
@@ -487,7 +523,8 @@ int  mi355_global_affine_align_moments(const mi355_pair_moments* m, int n, int n
  * hold is sent by its owner over xGMI.  Replaces "every rank holds all N frames" (72 GB per GPU at C5; 8 x the PCIe upload). */
 /* need[k] = 1 when rendering canvas rows [row0, row0 + rows) reads frame k.  mode:
  *   MI355_COVER_REFINED        mi355_mosaic_refined_dev, by host geometry alone: every frame whose clipped canvas box meets the rows (a superset
- *                              of what is read: a frame lying entirely under later frames is in it);
+ *                              of what is read: a frame lying entirely under later frames is in it).  For mi355_mosaic_feathered_dev this box
+ *                              cover is the cover: every frame in it takes part in the walk, and a NULL pointer for one of them is an error there;
  *   MI355_COVER_BLENDED        mi355_mosaic_blended_rows_dev (keep, band as there): the chips that reach the rows plus the blender pyramids' reach;
  *   MI355_COVER_REFINED_EXACT  mi355_mosaic_refined_dev, exactly: the frames that GIVE at least one pixel of the rows its sample -- the tile
  *                              kernel's own walk (descending image index, first valid sample wins, MosaicWithoutPos.cpp:2254-2348 read backwards)

@@ -110,6 +110,15 @@ const double* orc_cv_exp_table(void);                     /* its 64-entry table 
 /* SURF(hessianThreshold, 4 octaves, 2 layers, extended, oriented) detect + compute (:5313-5335): the strongest max_kp keypoints,
  * ordered by (response descending, octave, layer, row, column); desc: n x 128 floats of unit norm.  returns n */
 int  orc_surf(const uint8_t* bgr, int w, int h, int ws, float hessian_threshold, orc_keypoint* kp, float* desc, int max_kp);
+/* what the latest orc_surf call of the calling thread saw (thread-local: concurrent calls on other threads do not disturb it):
+ *   maxima     Hessian maxima accepted after interpolation, before the max_kp cut (the count the HIP path holds against its candidate list)
+ *   kept       min(maxima, max_kp): the keypoints that went on to orientation
+ *   dropped    of those, the ones without any orientation sample inside the frame (not returned)
+ *   short_ori  returned keypoints with fewer than the disc's 113 orientation samples
+ *   clamped    returned keypoints with a descriptor-window pixel clamped at a frame edge
+ *   layer_mask per octave, bit l set when filter size (9 + 6 l) << o fits the frame */
+typedef struct { int64_t maxima, kept, dropped, short_ori, clamped; int32_t layer_mask[4]; } orc_surf_stats;
+void orc_surf_last_stats(orc_surf_stats* out);
 void orc_surf_set_mode(int mode);      /* 1: det / trace evaluated as the reference's binary does on the x87 unit (measuring instrument, oracle_surf.c) */
 /* exact 1-NN in L2 on float descriptors (what FlannBasedMatcher approximates, :5389-5391); distance = sqrt(sum of squares) */
 void orc_bf_match_f32(const float* d1, int n1, const float* d2, int n2, int32_t* nn_idx, float* nn_dist);

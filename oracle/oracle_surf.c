@@ -178,10 +178,16 @@ static void surf_solve3(float A[3][3], float b[3], float x[3])
     x[0] = ((b[p[0]] - A[p[0]][1] * x[1]) - A[p[0]][2] * x[2]) / A[p[0]][0];
 }
 
-/* orientation + descriptor of one keypoint.  Returns 0 when the keypoint has no orientation sample (dropped). */
+/* what the latest orc_surf call of the calling thread saw (orc_surf_last_stats): counting only, no value above depends on it */
+static _Thread_local orc_surf_stats g_last_stats;
+void orc_surf_last_stats(orc_surf_stats* out) { *out = g_last_stats; }
+
+/* orientation + descriptor of one keypoint.  Returns 0 when the keypoint has no orientation sample (dropped).
+ * info[0] = orientation samples inside the frame (of 113), info[1] = 1 when a pixel of the descriptor window was clamped at a frame edge */
 static int surf_describe(const uint8_t* gray, int w, int h, const uint32_t* S, float kx, float ky, float ksize,
-                         const float* aptw, const int* aptx, const int* apty, int napt, const float* DW, float* angle_out, float* desc)
+                         const float* aptw, const int* aptx, const int* apty, int napt, const float* DW, float* angle_out, float* desc, int* info)
 {
+    info[0] = 0; info[1] = 0;
     const int sw = w + 1;
     const float s = ksize * 1.2f / 9.0f;
     const int gws = 2 * (int)rintf(2.0f * s);                     /* Haar wavelet size of the orientation samples */
@@ -199,6 +205,7 @@ static int surf_describe(const uint8_t* gray, int w, int h, const uint32_t* S, f
         ang[na] = surf_atan2deg(Y[na], X[na]);
         na++;
     }
+    info[0] = na;
     if (na == 0) return 0;
     float bestx = 0.0f, besty = 0.0f, best_mod = 0.0f;
     for (int i = 0; i < 360; i += ORI_SEARCH_INC) {
@@ -239,6 +246,7 @@ static int surf_describe(const uint8_t* gray, int w, int h, const uint32_t* S, f
                     const float px = (start_x + (float)i * sin_dir) + (float)j * cos_dir;
                     const float py = (start_y + (float)i * cos_dir) - (float)j * sin_dir;
                     int xi = (int)rintf(px), yi = (int)rintf(py);
+                    if (xi < 0 || xi > w - 1 || yi < 0 || yi > h - 1) info[1] = 1;
                     xi = xi < 0 ? 0 : (xi > w - 1 ? w - 1 : xi);
                     yi = yi < 0 ? 0 : (yi > h - 1 ? h - 1 : yi);
                     acc = fmaf((float)gray[(size_t)yi * w + xi], wgt, acc);
@@ -276,6 +284,7 @@ static int surf_describe(const uint8_t* gray, int w, int h, const uint32_t* S, f
 /* kp_out: orc_keypoint (x, y, size, angle, response, octave, class_id = sign of the Laplacian); desc_out: n x 128 floats */
 int orc_surf(const uint8_t* bgr, int w, int h, int ws, float hessian_threshold, orc_keypoint* kp_out, float* desc_out, int max_kp)
 {
+    memset(&g_last_stats, 0, sizeof(g_last_stats));
     if (w < 16 || h < 16 || max_kp <= 0) return 0;
     const int sw = w + 1, sh = h + 1;
     uint8_t* gray = (uint8_t*)malloc((size_t)w * h);
@@ -300,6 +309,7 @@ int orc_surf(const uint8_t* bgr, int w, int h, int ws, float hessian_threshold, 
             q->det = (float*)calloc((size_t)q->rows * q->cols + 1, sizeof(float));
             q->trace = (float*)calloc((size_t)q->rows * q->cols + 1, sizeof(float));
             if (q->size > sh - 1 || q->size > sw - 1) continue;
+            g_last_stats.layer_mask[o] |= 1 << l;
             surf_box dx[3], dy[3], dxy[4];
             stretch(DX_P, 3, 9, q->size, dx); stretch(DY_P, 3, 9, q->size, dy); stretch(DXY_P, 4, 9, q->size, dxy);
             const surf_box* dxy_boxes = dxy;
@@ -389,10 +399,14 @@ int orc_surf(const uint8_t* bgr, int w, int h, int ws, float hessian_threshold, 
     /* the strongest max_kp candidates are described; one without any orientation sample is dropped from the output */
     int n = 0;
     const size_t lim = nc < (size_t)max_kp ? nc : (size_t)max_kp;
+    g_last_stats.maxima = (int64_t)nc; g_last_stats.kept = (int64_t)lim;
     for (size_t q = 0; q < lim; q++) {
         const surf_cand* k = &cand[q];
         float ang = 0.0f;
-        if (!surf_describe(gray, w, h, S, k->x, k->y, k->size, aptw, aptx, apty, napt, DW, &ang, desc_out + (size_t)n * 128)) continue;
+        int info[2];
+        if (!surf_describe(gray, w, h, S, k->x, k->y, k->size, aptw, aptx, apty, napt, DW, &ang, desc_out + (size_t)n * 128, info)) { g_last_stats.dropped++; continue; }
+        if (info[0] < napt) g_last_stats.short_ori++;
+        if (info[1]) g_last_stats.clamped++;
         kp_out[n].x = k->x; kp_out[n].y = k->y; kp_out[n].size = k->size; kp_out[n].angle = ang; kp_out[n].response = k->response;
         kp_out[n].octave = k->octave; kp_out[n].class_id = k->lap;
         n++;

@@ -17,6 +17,8 @@ KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 CHIPINFO = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("img", "<i4"),
                      ("sx", "<f4"), ("sy", "<f4"), ("quad", "<f4", (8,))])
 
+SURF_STATS = np.dtype([("maxima", "<i8"), ("kept", "<i8"), ("dropped", "<i8"), ("short_ori", "<i8"), ("clamped", "<i8"), ("layer_mask", "<i4", (4,))])
+
 fp = C.POINTER(C.c_float)
 ip = C.POINTER(C.c_int)
 u8p = C.POINTER(C.c_uint8)
@@ -265,6 +267,21 @@ class Oracle:
         self.L.orc_surf.restype = C.c_int
         n = self.L.orc_surf(_p(bgr), w, h, bgr.strides[0], C.c_float(hessian), _p(kp), _p(desc), max_kp)
         return kp[:n].copy(), desc[:n].copy()
+
+    def surf_last_stats(self):
+        """counters of the latest surf() call made on this thread (oracle.h orc_surf_stats): dict of maxima, kept, dropped, short_ori,
+        clamped and layer_mask (four per-octave bit masks of the filter sizes that fitted)"""
+        st = np.zeros(1, SURF_STATS)
+        self.L.orc_surf_last_stats.restype = None
+        self.L.orc_surf_last_stats(_p(st))
+        out = {k: int(st[0][k]) for k in ("maxima", "kept", "dropped", "short_ori", "clamped")}
+        out["layer_mask"] = tuple(int(v) for v in st[0]["layer_mask"])
+        return out
+
+    def surf_with_stats(self, bgr, hessian=50.0, max_kp=4096):
+        """surf() and its counters in one step (safe under parallel_map: both calls run on the caller's thread)"""
+        kp, d = self.surf(bgr, hessian, max_kp)
+        return kp, d, self.surf_last_stats()
 
     def bf_match_f32(self, d1, d2):
         d1 = np.ascontiguousarray(d1, np.float32); d2 = np.ascontiguousarray(d2, np.float32)

@@ -49,6 +49,10 @@ class FeatherParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class SeamlineParams(C.Structure):
+    _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 # mi355_gain_pair_stats: the overlap statistics of one listed pair (positions a, b in the frame list)
 GAIN_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)), ("sum_b", "<i8", (3,))])
 assert GAIN_PAIR_STATS.itemsize == 64
@@ -651,6 +655,64 @@ class Context:
                                                      C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
         return out, cw, ch
 
+    # ---- seamline render (mi355_mosaic_seamline*, csrc/seamline.hip) -------------------------------------------------------
+    def MosaicSeamline(self, imgs, h9s, params=None, want_owner=False, **kw):
+        """mi355_mosaic_seamline: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_owner (canvas, cw, ch, cws, owner [ch, cw]
+        uint16: owning frame + 1, 0 where nothing covers).  params: SeamlineParams (seamline_params()) or its keyword fields (ramp)."""
+        n = len(imgs)
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
+        w = np.array([i.shape[1] for i in imgs], np.int32)
+        h = np.array([i.shape[0] for i in imgs], np.int32)
+        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamline_params(**kw)
+        canvas, owner = C.c_void_p(), C.c_void_p()
+        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_mosaic_seamline(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
+                                               C.byref(cws), C.byref(owner) if want_owner else None))
+        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
+        self.L.mi355_free(canvas)
+        if not want_owner:
+            return buf, cw.value, ch.value, cws.value
+        own = _copy_out(owner, 2 * ch.value * cw.value, np.uint16).reshape(ch.value, cw.value)
+        self.L.mi355_free(owner)
+        return buf, cw.value, ch.value, cws.value, own
+
+    def MosaicSeamlineDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_owner=0, d_count=0, params=None, **kw):
+        """mi355_mosaic_seamline_dev: device frames (0 / None: withheld; d_imgs None when d_canvas is 0) into the device canvas and / or the
+        uint16 [ch, cw] maps d_owner, d_count (0: not wanted), rows [row0, row0 + rows); complete on return"""
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        n = len(w)
+        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
+        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamline_params(**kw)
+        self._chk(self.L.mi355_mosaic_seamline_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas or 0) or None),
+                                                   int(cw), int(ch), int(cws), C.c_void_p(int(d_owner or 0) or None), C.c_void_p(int(d_count or 0) or None),
+                                                   int(row0), int(rows if rows >= 0 else ch)))
+
+    def MosaicSeamlineInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
+        """mi355_mosaic_seamline_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamline_params(**kw)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_seamline_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
+                                                    C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
+    def SeamlineCover(self, w, h, h9s, row0=0, rows=-1, params=None, **kw):
+        """mi355_mosaic_seamline_cover: need[k] = 1 exactly for the frames that own at least one pixel of canvas rows [row0, row0 + rows)"""
+        n = len(w)
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamline_params(**kw)
+        need = np.zeros(n, np.uint8)
+        self._chk(self.L.mi355_mosaic_seamline_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
+        return need
+
     # ---- frames kept in HBM after extraction, renders into caller memory -------------------------------------------------
     def DropFrames(self, img_id=-1):
         """releases the kept frame of img_id (set_option("keep_frames", 1)); img_id < 0: all of them"""
@@ -813,6 +875,15 @@ def feather_params(ramp=None):
     """mi355_feather_params: the library's defaults (mi355_default_feather_params: ramp 0 = a full tent per frame) with the given fields replaced"""
     p = FeatherParams()
     load_library().mi355_default_feather_params(C.byref(p))
+    if ramp is not None:
+        p.ramp = int(ramp)
+    return p
+
+
+def seamline_params(ramp=None):
+    """mi355_seamline_params: the library's defaults (mi355_default_seamline_params: ramp 0 = a full tent per frame) with the given fields replaced"""
+    p = SeamlineParams()
+    load_library().mi355_default_seamline_params(C.byref(p))
     if ramp is not None:
         p.ramp = int(ramp)
     return p

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "hmath.h"
 #include "mosaic_frame.h"
+#include "ramp.h"
 
 namespace {
 
@@ -23,26 +24,7 @@ namespace {
 #endif
 constexpr int FT_W = 128, FT_RPL = FT_RPL_V, FT_H = 8 * FT_RPL;   // canvas tile of one workgroup: 256 lanes x 4 pixels x FT_RPL rows
 static_assert(MOSAIC_LIST_BLOCK % FT_W == 0 && MOSAIC_LIST_BLOCK % FT_H == 0, "a tile lies inside one list block");
-constexpr int FEATHER_MAX_SIDE = 1 << 20;       // frames up to 2^20 a side: 254 * (border distance) < 2^28, the range ramp_div is exact on
-
-// frame k's ramp: R and the constants of n / R for 0 <= n < 2^28 (Granlund & Montgomery 1994, theorem 4.2: with l = ceil(log2 R) and
-// mul = ceil(2^(28 + l) / R), floor(n mul / 2^(28 + l)) = floor(n / R) for every n < 2^28; mul <= 2^29)
-struct RampDev { uint32_t R, mul, shift, _pad; };
-
-RampDev ramp_setup(uint32_t R) {
-    uint32_t l = 0;
-    while (((uint64_t)1 << l) < R) l++;
-    RampDev r;
-    r.R = R; r.shift = 28 + l; r._pad = 0;
-    r.mul = (uint32_t)((((uint64_t)1 << r.shift) + R - 1) / R);
-    return r;
-}
-
-// Wk along one axis: (254 min(d, R)) / R for the border distance d of a texel row or column
-__device__ __forceinline__ unsigned ramp_weight(int d, const RampDev& r) {
-    const unsigned m = (unsigned)d < r.R ? (unsigned)d : r.R;
-    return (unsigned)(((unsigned long long)(254u * m) * r.mul) >> r.shift);
-}
+// (RampDev, ramp_weight and the weight omega_k itself: ramp.h, shared with seamline.hip)
 
 __global__ __launch_bounds__(256) void feather_tile_kernel(const FrameDev* fr, const RampDev* ramps, int n, const uint16_t* lists, const int* counts, int bx_n,
                                                            uint8_t* canvas, int cw, int cws, int row0, int row_end, float dGx, float dGy) {
@@ -79,15 +61,7 @@ __global__ __launch_bounds__(256) void feather_tile_kernel(const FrameDev* fr, c
                 if (!(yin && xD >= f.begX && xD <= f.endX && src_inside(xs, ys, w1, h1))) continue;
                 unsigned vb, vg, vr;
                 frame_sample3(f, xs, ys, vb, vg, vr);
-                // the weight through the same xi, yi, p, q: Wk of a texel = min over the two axes of the axis ramp (the quotient is monotone in d)
-                const int xi = (int)xs, yi = (int)ys;
-                const float p = ys - (float)yi, q = xs - (float)xi;
-                const int ax = f.w - 1 - xi, ay = f.h - 1 - yi;
-                const unsigned wx0 = ramp_weight(xi < ax ? xi : ax, r), wx1 = ramp_weight(xi + 1 < ax - 1 ? xi + 1 : ax - 1, r);
-                const unsigned wy0 = ramp_weight(yi < ay ? yi : ay, r), wy1 = ramp_weight(yi + 1 < ay - 1 ? yi + 1 : ay - 1, r);
-                const float W00 = (float)(wx0 < wy0 ? wx0 : wy0), W01 = (float)(wx1 < wy0 ? wx1 : wy0);
-                const float W10 = (float)(wx0 < wy1 ? wx0 : wy1), W11 = (float)(wx1 < wy1 ? wx1 : wy1);
-                const unsigned om = 1u + hm::bilin(W00, W01, W10, W11, p, q);
+                const unsigned om = ramp_omega(f, r, xs, ys);        // the weight through the sample's own xi, yi, p, q (ramp.h)
                 acc[j][k][0] += om * vb; acc[j][k][1] += om * vg; acc[j][k][2] += om * vr; acc[j][k][3] += om;
             }
         }
@@ -145,13 +119,12 @@ int mi_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const 
     for (int k = 0; k < n; k++) {
         FrameDev f;
         if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], dG, cw, ch, row0, rows, f)) continue;
-        if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k] || w[k] > FEATHER_MAX_SIDE || h[k] > FEATHER_MAX_SIDE) { ctx->set_error("mosaic_feathered: bad image geometry"); return MI355_ERR_ARG; }
+        if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k] || w[k] > RAMP_MAX_SIDE || h[k] > RAMP_MAX_SIDE) { ctx->set_error("mosaic_feathered: bad image geometry"); return MI355_ERR_ARG; }
         // every frame whose box meets the rows is read: there is no "lies under later frames" case here
         if (!d_imgs[k]) { ctx->set_error("mosaic_feathered: the box of image " + std::to_string(k) + " meets these canvas rows but no pointer to it was given"); return MI355_ERR_ARG; }
         f.src = d_imgs[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k];
         fr.push_back(f);
-        const int side = w[k] < h[k] ? w[k] : h[k];
-        ramps.push_back(ramp_setup((uint32_t)(params->ramp > 0 ? params->ramp : (side + 1) / 2)));
+        ramps.push_back(ramp_of_frame(w[k], h[k], params->ramp));
     }
     const int nf = (int)fr.size();
     const int bx_n = (cw + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK, by_n = (rows + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK;

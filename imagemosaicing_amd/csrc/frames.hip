@@ -1,6 +1,6 @@
 // csrc/frames.hip -- host frames kept in HBM after their extraction (option "keep_frames") and the render calls that write straight
-// into caller memory (mi355_mosaic_refined_into / mi355_mosaic_feathered_into / mi355_mosaic_blended_into).  Host code only: the canvases come
-// from the kernels of warp.hip / feather.hip / blend.hip; what is new is where their inputs come from and how the canvas reaches the caller's rows.
+// into caller memory (mi355_mosaic_refined_into / mi355_mosaic_feathered_into / mi355_mosaic_seamline_into / mi355_mosaic_blended_into).  Host code only: the canvases come
+// from the kernels of warp.hip / feather.hip / seamline.hip / blend.hip; what is new is where their inputs come from and how the canvas reaches the caller's rows.
 #include "common.h"
 #include <thread>
 
@@ -247,6 +247,29 @@ extern "C" int mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const*
     DevBuf& dcan = ctx->buf("into_canvas");
     MI_HIP(dcan.reserve((size_t)lws * lh));
     rc = mi_mosaic_feathered_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
+    if (rc != MI355_OK) return rc;
+    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+}
+
+extern "C" int mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                           const int* ws, int n, const float* h9s, const mi355_seamline_params* params, uint8_t* dst, int dst_pitch,
+                                           int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_seamline_into: bad arguments"); return MI355_ERR_ARG; }
+    if (n <= 1) { ctx->set_error("mosaic_seamline_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
+    int lw, lh, lws;
+    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
+    if (rc != MI355_OK) { ctx->set_error("mosaic_seamline_into: empty canvas"); return rc; }
+    rc = check_dst(ctx, "mosaic_seamline_into", dst, dst_pitch, cw, ch, lw, lh);
+    if (rc != MI355_OK) return rc;
+    std::vector<char> skip((size_t)n);
+    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
+    std::vector<const uint8_t*> dptr;
+    rc = render_sources(ctx, "mosaic_seamline_into", imgs, img_ids, w, h, ws, n, skip, dptr);
+    if (rc != MI355_OK) return rc;
+    DevBuf& dcan = ctx->buf("into_canvas");
+    MI_HIP(dcan.reserve((size_t)lws * lh));
+    rc = mi_mosaic_seamline_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
     if (rc != MI355_OK) return rc;
     return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
 }

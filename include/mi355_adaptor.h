@@ -347,9 +347,11 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
 }
 
 namespace detail {
-// the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into) or weighted (mi355_mosaic_feathered_into, default ramp)
+// the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into), weighted (mi355_mosaic_feathered_into, default ramp) or
+// seamline (mi355_mosaic_seamline_into, default ramp)
+enum OnePass { ONE_PASS_UNBLENDED, ONE_PASS_WEIGHTED, ONE_PASS_SEAMLINE };
 template <class PoseT>
-inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, bool weighted) {
+inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, OnePass mode) {
     if (NULL == pImgPoses || NULL == pRectified || nImages <= 0) return -1;
     mi355_ctx* c = context();
     if (!c) return -2;
@@ -370,8 +372,9 @@ inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI35
     if (rc != MI355_OK) return rc == MI355_ERR_ARG ? -1 : -2;
     MI355_NS IplImage* out = MI355_CREATE_IMAGE_8U(cw, ch, 3);          // :2246-2248; the library renders straight into its rows
     if (!out) return -2;
-    rc = weighted ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
-                  : mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
+    rc = mode == ONE_PASS_WEIGHTED ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
+       : mode == ONE_PASS_SEAMLINE ? mi355_mosaic_seamline_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
+                                   : mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
     if (rc != MI355_OK) { cvReleaseImage(&out); return rc == MI355_ERR_ARG ? -1 : -2; }
     if (pMosaicResult) cvReleaseImage(&pMosaicResult);
     pMosaicResult = out;
@@ -385,7 +388,7 @@ inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI35
 // the reference).  PoseT is the reference's ImagePoseInfo (only .pImg is read).  Returns 0 / -1 / -2 like the reference.
 template <class PoseT>
 inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
-    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, false);
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_UNBLENDED);
 }
 
 // UavMatchParam.blending == 1, "weighted blending" (MosaicWithoutPos.h:65): the mode the reference's driver sends down the unblended branch
@@ -393,7 +396,15 @@ inline int MosaicImagesRefined(const PoseT* pImgPoses, const int nImages, const 
 // (include/mi355_mosaic.h, "weighted (feather) blending") with the default ramp.  Kept frames are used under MI355_ADAPTOR_KEEP_FRAMES.
 template <class PoseT>
 inline int MosaicImagesWeighted(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
-    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, true);
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_WEIGHTED);
+}
+
+// The seamline render (include/mi355_mosaic.h, "seamline render") with the default ramp: every canvas pixel from the one frame in which it lies
+// deepest -- as sharp as MosaicImagesRefined, with the seams in the middle of the overlaps.  The reference has no such mode; the signature,
+// ownership and return values are MosaicImagesRefined's.  Kept frames are used under MI355_ADAPTOR_KEEP_FRAMES.
+template <class PoseT>
+inline int MosaicImagesSeamline(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_SEAMLINE);
 }
 
 // IplImage* LaplacianPyramidBlending(IplImage** pImages, int imagesNum, ProjectMat* pImgT, int band, float resScale)

@@ -230,6 +230,42 @@ int  mi355_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, co
 int  mi355_mosaic_feathered(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
                             const float* h9s, const mi355_feather_params* params, uint8_t** canvas, int* cw, int* ch, int* cws);
 
+/* ---- seamline render: the fourth one-pass render, each canvas pixel from its deepest frame (csrc/seamline.hip) -----------------------
+ * What orthomosaic tools call a Voronoi seamline: every canvas pixel is taken from exactly ONE frame, the frame in which it lies deepest, so
+ * the canvas is as sharp as the unblended render while its seams run through the middle of the overlaps, not along the outlines of late frames.
+ * Definition (exact integers; bytes, owner and count do not depend on walk order, tile shape or stripe cut):
+ *   Canvas geometry, frame skipping, "frame k gives canvas pixel (x, y) a sample", the sample s_k[c] and the weight omega_k in [1, 255] are
+ *   exactly the feathered render's (above), including params.ramp, the default R = (min(w, h) + 1) / 2 and the 2^20 side limit.
+ *   owner   = argmax over the contributing frames k of (omega_k, k): the largest weight wins, among equal weights the largest index k (the
+ *             position in the caller's arrays) -- the direction of "later frames overwrite" in the refined render;
+ *   out[c]  = s_owner[c]; a pixel no frame covers is 0; row padding [3 cw, cws) is 0;
+ *   d_owner (optional): uint16_t, the whole canvas's ch x cw at a pitch of cw elements: owner + 1, or 0 where nothing covers the pixel;
+ *   d_count (optional): same layout: the number of contributing frames (count > 0 is the no-data mask of all three one-pass renders).
+ *   n <= 65535.  Only rows [row0, row0 + rows) of the canvas and of either map are written.
+ * Consequences: where count == 1 the bytes are those of the refined render and of the feathered render; count > 0 is exactly the set of pixels
+ *   the refined and feathered renders cover; after mi355_gain_compensate_dev the canvas is the seamline render of the compensated frames.
+ * Cost: one launch over canvas tiles; the ownership walk maps, tests and weighs every covering frame and loads no texel, then ONE frame is
+ *   sampled per pixel.
+ * Pointers: d_canvas, d_owner, d_count may each be NULL, at least one must not be.  d_canvas == NULL: nothing is sampled, d_imgs (and ws) may be
+ *   NULL altogether.  d_canvas != NULL: a frame that owns no pixel of the rows may have d_imgs[k] == NULL; NULL for a frame that does own one is
+ *   MI355_ERR_ARG naming the frame, found before any sample is taken (one extra ownership pass, paid only when some pointer is NULL); no
+ *   invalid pointer is dereferenced and the ctx stays usable.
+ * mi355_mosaic_seamline_cover: need[k] = 1 exactly for the frames that own at least one pixel of the rows -- the ownership walk with nothing
+ *   sampled; what a rank must hold to render the stripe (feeds mi355_exchange_frames with MI355_EXCHANGE_NEED_IS_LOCAL, as
+ *   MI355_COVER_REFINED_EXACT does for the refined render).  mi355_mosaic_stripe_cover is unchanged.
+ * Errors: as the feathered twins (argument checks, n <= 1 -> MI355_ERR_FAILED in the host forms, n > 65535, canvas geometry, ramp < 0, frame
+ *   geometry); params NULL = defaults. */
+typedef struct { int32_t ramp; int32_t reserved[3]; } mi355_seamline_params;   /* ramp as in mi355_feather_params */
+void mi355_default_seamline_params(mi355_seamline_params* p);        /* ramp = 0, reserved = 0 */
+int  mi355_mosaic_seamline_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n,
+                               const float* h9s, const mi355_seamline_params* params, uint8_t* d_canvas, int cw, int ch, int cws,
+                               uint16_t* d_owner, uint16_t* d_count, int row0, int rows);
+/* host images in; *canvas and, when owner != NULL, *owner (ch x cw) are allocated by the library -> mi355_free */
+int  mi355_mosaic_seamline(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
+                           const float* h9s, const mi355_seamline_params* params, uint8_t** canvas, int* cw, int* ch, int* cws, uint16_t** owner);
+int  mi355_mosaic_seamline_cover(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const mi355_seamline_params* params,
+                                 int row0, int rows, uint8_t* need);
+
 /* LaplacianPyramidBlending warp stage (MosaicImage.cpp:2233-2460) + FindMasksByDistMap (:1761-1881):
  * per kept image a tight chip (3ch u8; the reference then converts to CV_16S), its validity mask and, with
  * find_masks!=0, the exclusive distance-map ownership masks.  h9s must carry the resScale multiplication of
@@ -307,6 +343,9 @@ int  mi355_mosaic_refined_into(mi355_ctx* ctx, const uint8_t* const* imgs, const
 /* mi355_mosaic_feathered with mi355_mosaic_refined_into's sources (kept frames / host images), destination and download */
 int  mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                  int n, const float* h9s, const mi355_feather_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
+/* mi355_mosaic_seamline's canvas with mi355_mosaic_feathered_into's sources, destination and download */
+int  mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                                int n, const float* h9s, const mi355_seamline_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
 int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 

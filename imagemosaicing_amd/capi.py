@@ -53,6 +53,13 @@ class SeamlineParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class PreviewParams(C.Structure):
+    _fields_ = [("render", C.c_int32), ("ramp", C.c_int32), ("level", C.c_int32), ("nodata", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+NODATA_NONE, NODATA_ZERO, NODATA_MAP = 0, 1, 2
+
+
 # mi355_gain_pair_stats: the overlap statistics of one listed pair (positions a, b in the frame list)
 GAIN_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)), ("sum_b", "<i8", (3,))])
 assert GAIN_PAIR_STATS.itemsize == 64
@@ -713,6 +720,61 @@ class Context:
         self._chk(self.L.mi355_mosaic_seamline_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
         return need
 
+    # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
+    def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
+        """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
+        whole device buffer of level l (overview_layout), d_covers None or a list whose entries may be 0.  Enqueued on the ctx stream."""
+        def arr(v):
+            if v is None:
+                return None
+            a = (C.c_void_p * len(v))()
+            for k, x in enumerate(v):
+                a[k] = int(x or 0) or None
+            return a
+        self._chk(self.L.mi355_mosaic_overview_dev(self._h, C.c_void_p(int(d_rows or 0) or None), int(cw), int(ch), int(cws),
+                                                   C.c_void_p(int(d_valid_rows or 0) or None), int(nodata), int(levels), arr(d_levels), arr(d_covers),
+                                                   int(row0), int(rows)))
+
+    def MosaicOverview(self, canvas, cw, levels, valid=None, nodata=NODATA_NONE, want_covers=False):
+        """mi355_mosaic_overview: a host canvas [ch, cws] uint8 (and a [ch, cw] uint16 map for NODATA_MAP) in, the list of level arrays
+        [oh_l, ows_l] out -- with want_covers (levels, covers), covers[l - 1] a [oh_l, ow_l] uint16 array."""
+        canvas = np.ascontiguousarray(canvas, np.uint8)
+        ch, cws = canvas.shape
+        v = None if valid is None else np.ascontiguousarray(valid, np.uint16)
+        lv, cv = C.POINTER(C.c_void_p)(), C.POINTER(C.c_void_p)()
+        self._chk(self.L.mi355_mosaic_overview(self._h, _p(canvas), int(cw), int(ch), int(cws), _p(v), int(nodata), int(levels), C.byref(lv),
+                                               C.byref(cv) if want_covers else None))
+        geo = overview_layout(cw, ch, levels)
+
+        def take(arr, l, nbytes, dtype, shape):
+            a = _copy_out(C.c_void_p(arr[l]), nbytes, dtype).reshape(shape)
+            self.L.mi355_free(C.c_void_p(arr[l]))
+            return a
+        outs = [take(lv, l, geo[l][2] * geo[l][1], np.uint8, (geo[l][1], geo[l][2])) for l in range(levels)]
+        self.L.mi355_free(lv)
+        if not want_covers:
+            return outs
+        covs = [take(cv, l, 2 * geo[l][0] * geo[l][1], np.uint16, (geo[l][1], geo[l][0])) for l in range(levels)]
+        self.L.mi355_free(cv)
+        return outs, covs
+
+    def MosaicPreviewInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, want_cover=False, dims=None, **kw):
+        """mi355_mosaic_preview_into: level `level` of the named render (render 0 refined, 1 feathered, 2 seamline), sources as
+        MosaicImagesRefinedInto.  Returns (out, ow, oh), with want_cover (out, ow, oh, cover [oh, ow] uint16).  dims: (ow, oh) to pass in place
+        of the layout's (the library refuses any other)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else preview_params(**kw)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        ow, oh, _ = overview_layout(cw, ch, p.level)[-1] if 1 <= p.level <= 7 else (cw, ch, 0)      # a bad level is the library's to refuse
+        if dims is not None:
+            ow, oh = dims
+        out, pitch = self._out_array(out, pitch, ow, oh)
+        cover = np.zeros((oh, ow), np.uint16) if want_cover else None
+        self._chk(self.L.mi355_mosaic_preview_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
+                                                   C.c_void_p(out.ctypes.data), int(pitch), _p(cover), int(ow), int(oh)))
+        return (out, ow, oh, cover) if want_cover else (out, ow, oh)
+
     # ---- frames kept in HBM after extraction, renders into caller memory -------------------------------------------------
     def DropFrames(self, img_id=-1):
         """releases the kept frame of img_id (set_option("keep_frames", 1)); img_id < 0: all of them"""
@@ -887,6 +949,27 @@ def seamline_params(ramp=None):
     if ramp is not None:
         p.ramp = int(ramp)
     return p
+
+
+def preview_params(render=None, ramp=None, level=None, nodata=None):
+    """mi355_preview_params: the library's defaults (refined render, ramp 0, level 3, exact coverage) with the given fields replaced"""
+    p = PreviewParams()
+    load_library().mi355_default_preview_params(C.byref(p))
+    for name, v in (("render", render), ("ramp", ramp), ("level", level), ("nodata", nodata)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def overview_layout(cw, ch, levels):
+    """mi355_overview_layout: [(ow_l, oh_l, ows_l) for l = 1 .. levels]"""
+    n = max(int(levels), 0)
+    ow, oh, ows = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    L = load_library()
+    rc = L.mi355_overview_layout(int(cw), int(ch), int(levels), _p(ow), _p(oh), _p(ows))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"overview_layout").decode())
+    return [(int(ow[l]), int(oh[l]), int(ows[l])) for l in range(n)]
 
 
 def solve_gains(pair_stats, frame_cover, params=None, **kw):

@@ -441,6 +441,11 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
         return MI355_OK;
     }
     if (std::string(name) == "download_threads") { ctx->download_threads = value < 1 ? 1 : (value > 16 ? 16 : value); return MI355_OK; }
+    if (std::string(name) == "preview_stripe_rows") {
+        if (value < 0) { ctx->set_error("set_option: preview_stripe_rows must be >= 0"); return MI355_ERR_ARG; }
+        ctx->preview_stripe_rows = value;
+        return MI355_OK;
+    }
     if (std::string(name) == "download_mode") { ctx->download_mode = value < 0 || value > 2 ? 0 : value; return MI355_OK; }
     if (std::string(name) == "sift_flush") return mi_sift_flush(ctx);      // close the batch that is collecting frames now (no wait): the caller shapes the batches of a short survey
     if (std::string(name) == "blur_stream") { ctx->blur_stream = value ? 1 : 0; return MI355_OK; }

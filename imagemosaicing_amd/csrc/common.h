@@ -144,7 +144,8 @@ struct mi355_ctx {
     std::unordered_map<int, KeptFrame> kept_frames;
     size_t download_chunk = (size_t)64 << 20;          // option "download_chunk_mb": bytes per chunk of the _into calls' canvas download
     int download_threads = 4;                          // option "download_threads" (1..16): host threads copying a pinned chunk into the caller's rows
-    int download_mode = 0;                             // option "download_mode" (measurement): 0 pinned double buffer, 1 hipMemcpy2DAsync into dst, 2 hipHostRegister(dst) + 2D copy
+    int preview_stripe_rows = 1024;                    // option "preview_stripe_rows": canvas rows per stripe of mi355_mosaic_preview_into (0: the whole canvas)
+    int download_mode = 0;                            // option "download_mode" (measurement): 0 pinned double buffer, 1 hipMemcpy2DAsync into dst, 2 hipHostRegister(dst) + 2D copy
     hipStream_t dl_stream = nullptr;                   // copy stream of those downloads
     hipEvent_t dl_ev[3] = {nullptr, nullptr, nullptr}; // [0], [1]: the pinned halves filled; [2]: the render finished on ctx->stream
     int cascade = 3;                                   // octaves >= 2000 px wide: 3 (default) = the first three levels ({gray | L0} -> L0/L1 L2) in one pass (pyr_chain), the rest per level; 2 = also L3..L5 in one pass; 1 = all six in one pass (pyr_cascade); 0 = every level on its own. Same bits; option "sift_cascade"
@@ -196,6 +197,8 @@ int mi_mosaic_feathered_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int*
 int mi_mosaic_seamline_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                            const mi355_seamline_params* params, uint8_t* d_canvas, int cw, int ch, int cws, uint16_t* d_owner, uint16_t* d_count,
                            int row0, int rows, uint8_t* cover_only);      // seamline.hip
+int mi_mosaic_overview_dev(mi355_ctx*, const uint8_t* d_rows, int cw, int ch, int cws, const uint16_t* d_valid_rows, int nodata, int levels,
+                           uint8_t* const* d_levels, uint16_t* const* d_covers, int row0, int rows, int only_level = 0);      // overview.hip; only_level = l: d_levels / d_covers entries other than l - 1 may be NULL (the preview)
 int mi_sift_flush(mi355_ctx*);                               // enqueues every partly filled batch (no wait)
 int mi_sift_flush_if_parked(mi355_ctx*, hipEvent_t ev);   // launches the batch still holding a parked frame with this event
 int mi_chips_and_masks_dev(mi355_ctx*, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,

@@ -1,6 +1,7 @@
 // csrc/frames.hip -- host frames kept in HBM after their extraction (option "keep_frames") and the render calls that write straight
 // into caller memory (mi355_mosaic_refined_into / mi355_mosaic_feathered_into / mi355_mosaic_seamline_into / mi355_mosaic_blended_into).  Host code only: the canvases come
 // from the kernels of warp.hip / feather.hip / seamline.hip / blend.hip; what is new is where their inputs come from and how the canvas reaches the caller's rows.
+// Last, mi355_mosaic_preview_into: the same sources, rendered stripe by stripe and reduced by overview.hip, one overview level reaching the caller.
 #include "common.h"
 #include <thread>
 
@@ -295,4 +296,79 @@ extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* i
     rc = mi_mosaic_blended_dev(ctx, dptr.data(), w, h, ws, n, h9s, keep, band, dcan.as<uint8_t>(), lw, lh, lws);
     if (rc != MI355_OK) return rc;
     return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+}
+
+// ---- striped preview ------------------------------------------------------------------------------------------------------
+// Level `level` of a render's canvas without that canvas: the survey is rendered stripe by stripe into ONE stripe buffer, each stripe is
+// reduced by the overview kernel (overview.hip) into the level's buffer, and only that level comes back.  The render launchers address the
+// canvas as base + y * pitch with y a row of the whole canvas, so a stripe buffer is handed to them as the base the whole canvas would have
+// had: buffer - row0 * pitch.  Only rows [row0, row0 + rows) are ever touched through it.
+template <class T> static T* stripe_base(T* buf, int row0, size_t pitch_elems) {
+    return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(buf) - (uintptr_t)row0 * pitch_elems * sizeof(T));
+}
+
+extern "C" int mi355_mosaic_preview_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                         const int* ws, int n, const float* h9s, const mi355_preview_params* params, uint8_t* dst, int dst_pitch,
+                                         uint16_t* cover, int ow, int oh) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_preview_into: bad arguments"); return MI355_ERR_ARG; }
+    mi355_preview_params dp;
+    if (!params) { mi355_default_preview_params(&dp); params = &dp; }
+    if (params->render < 0 || params->render > 2) { ctx->set_error("mosaic_preview_into: render=" + std::to_string(params->render) + " outside 0..2"); return MI355_ERR_ARG; }
+    if (params->level < 1 || params->level > 7) { ctx->set_error("mosaic_preview_into: level=" + std::to_string(params->level) + " outside 1..7"); return MI355_ERR_ARG; }
+    if (params->nodata < 0 || params->nodata > 2) { ctx->set_error("mosaic_preview_into: nodata=" + std::to_string(params->nodata) + " outside 0..2"); return MI355_ERR_ARG; }
+    if (params->ramp < 0) { ctx->set_error("mosaic_preview_into: ramp=" + std::to_string(params->ramp) + " < 0"); return MI355_ERR_ARG; }
+    if (n <= 1) { ctx->set_error("mosaic_preview_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
+    const int level = params->level;
+    int lw, lh, lws;
+    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
+    if (rc != MI355_OK) { ctx->set_error("mosaic_preview_into: empty canvas"); return rc; }
+    int aw[7], ah[7], aws[7];
+    mi355_overview_layout(lw, lh, level, aw, ah, aws);
+    const int low = aw[level - 1], loh = ah[level - 1], lows = aws[level - 1];
+    rc = check_dst(ctx, "mosaic_preview_into", dst, dst_pitch, ow, oh, low, loh);
+    if (rc != MI355_OK) return rc;
+    std::vector<char> skip((size_t)n);
+    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
+    std::vector<const uint8_t*> dptr;
+    rc = render_sources(ctx, "mosaic_preview_into", imgs, img_ids, w, h, ws, n, skip, dptr);
+    if (rc != MI355_OK) return rc;
+    const int unit = 1 << level;
+    long srows = ctx->preview_stripe_rows > 0 ? ((long)ctx->preview_stripe_rows + unit - 1) / unit * unit : lh;
+    if (srows > lh) srows = lh;                            // one stripe: it ends the canvas
+    const bool use_map = params->nodata == MI355_NODATA_MAP;
+    DevBuf& dstripe = ctx->buf("preview_stripe");
+    DevBuf& dmap = ctx->buf("preview_map");
+    DevBuf& dlev = ctx->buf("preview_level");
+    DevBuf& dcov = ctx->buf("preview_cover");
+    MI_HIP(dstripe.reserve((size_t)lws * srows));
+    if (use_map) MI_HIP(dmap.reserve(sizeof(uint16_t) * (size_t)lw * srows));
+    MI_HIP(dlev.reserve((size_t)lows * loh));
+    if (cover) MI_HIP(dcov.reserve(sizeof(uint16_t) * (size_t)low * loh));
+    uint8_t* d_lv[7] = {nullptr};
+    uint16_t* d_cv[7] = {nullptr};
+    d_lv[level - 1] = dlev.as<uint8_t>();
+    d_cv[level - 1] = cover ? dcov.as<uint16_t>() : nullptr;
+    mi355_feather_params fp;
+    mi355_seamline_params sp;
+    mi355_default_feather_params(&fp); fp.ramp = params->ramp;
+    mi355_default_seamline_params(&sp); sp.ramp = params->ramp;
+    for (int row0 = 0; row0 < lh; row0 += (int)srows) {
+        const int rows = lh - row0 < srows ? lh - row0 : (int)srows;
+        uint8_t* base = stripe_base(dstripe.as<uint8_t>(), row0, (size_t)lws);
+        uint16_t* mbase = use_map ? stripe_base(dmap.as<uint16_t>(), row0, (size_t)lw) : nullptr;
+        if (params->render == 0) rc = mi_mosaic_refined_dev(ctx, dptr.data(), w, h, ws, n, h9s, base, lw, lh, lws, row0, rows);
+        else if (params->render == 1) rc = mi_mosaic_feathered_dev(ctx, dptr.data(), w, h, ws, n, h9s, &fp, base, lw, lh, lws, row0, rows);
+        else rc = mi_mosaic_seamline_dev(ctx, dptr.data(), w, h, ws, n, h9s, &sp, base, lw, lh, lws, nullptr, mbase, row0, rows, nullptr);
+        // exact coverage of the refined and feathered renders: the seamline ownership walk's count, nothing sampled
+        if (rc == MI355_OK && use_map && params->render != 2)
+            rc = mi_mosaic_seamline_dev(ctx, nullptr, w, h, nullptr, n, h9s, &sp, nullptr, lw, lh, lws, nullptr, mbase, row0, rows, nullptr);
+        if (rc != MI355_OK) return rc;
+        rc = mi_mosaic_overview_dev(ctx, dstripe.as<uint8_t>(), lw, lh, lws, use_map ? dmap.as<uint16_t>() : nullptr, params->nodata, level, d_lv, d_cv,
+                                    row0, rows, level);
+        if (rc != MI355_OK) return rc;
+    }
+    rc = download_rows(ctx, dlev.as<uint8_t>(), (size_t)lows, dst, (size_t)dst_pitch, (size_t)3 * low, loh);
+    if (rc != MI355_OK || !cover) return rc;
+    return download_rows(ctx, dcov.as<uint8_t>(), sizeof(uint16_t) * (size_t)low, (uint8_t*)cover, sizeof(uint16_t) * (size_t)low, sizeof(uint16_t) * (size_t)low, loh);
 }

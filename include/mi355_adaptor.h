@@ -348,10 +348,12 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
 
 namespace detail {
 // the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into), weighted (mi355_mosaic_feathered_into, default ramp) or
-// seamline (mi355_mosaic_seamline_into, default ramp)
+// seamline (mi355_mosaic_seamline_into, default ramp); with level >= 1 the image is that level of the render `render` instead
+// (mi355_mosaic_preview_into, exact coverage, default ramp): the full-size canvas is never made
 enum OnePass { ONE_PASS_UNBLENDED, ONE_PASS_WEIGHTED, ONE_PASS_SEAMLINE };
 template <class PoseT>
-inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, OnePass mode) {
+inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, OnePass mode,
+                           int level = 0, int render = 0) {
     if (NULL == pImgPoses || NULL == pRectified || nImages <= 0) return -1;
     mi355_ctx* c = context();
     if (!c) return -2;
@@ -370,9 +372,19 @@ inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI35
     int cw = 0, ch = 0, cws = 0;
     int rc = mi355_mosaic_layout(&w[0], &h[0], nImages, &h9[0], &cw, &ch, &cws, NULL);
     if (rc != MI355_OK) return rc == MI355_ERR_ARG ? -1 : -2;
+    mi355_preview_params pp;
+    mi355_default_preview_params(&pp);
+    if (level != 0) {
+        if (level < 1 || level > 7 || render < 0 || render > 2) return -1;
+        int ow[7], oh[7];
+        if (mi355_overview_layout(cw, ch, level, ow, oh, NULL) != MI355_OK) return -1;
+        cw = ow[level - 1]; ch = oh[level - 1];
+        pp.level = level; pp.render = render;
+    }
     MI355_NS IplImage* out = MI355_CREATE_IMAGE_8U(cw, ch, 3);          // :2246-2248; the library renders straight into its rows
     if (!out) return -2;
-    rc = mode == ONE_PASS_WEIGHTED ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
+    rc = level != 0 ? mi355_mosaic_preview_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], &pp, (uint8_t*)out->imageData, out->widthStep, NULL, cw, ch)
+       : mode == ONE_PASS_WEIGHTED ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
        : mode == ONE_PASS_SEAMLINE ? mi355_mosaic_seamline_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
                                    : mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
     if (rc != MI355_OK) { cvReleaseImage(&out); return rc == MI355_ERR_ARG ? -1 : -2; }
@@ -405,6 +417,18 @@ inline int MosaicImagesWeighted(const PoseT* pImgPoses, const int nImages, const
 template <class PoseT>
 inline int MosaicImagesSeamline(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
     return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_SEAMLINE);
+}
+
+// A reduced-size mosaic (include/mi355_mosaic.h, "overview levels" / the preview): level `level` in 1..7 -- 1 / 2^level of the size -- of the
+// render `render` (0 MosaicImagesRefined's, 1 MosaicImagesWeighted's, 2 MosaicImagesSeamline's canvas), averaged over the pixels the survey
+// covers only, so that the empty surround does not darken the edge.  The survey is rendered in stripes on the device and only the small image
+// comes back.  The reference has no such mode; allocation, ownership and return values are MosaicImagesSeamline's (-1 also for a level or a
+// render outside its range).  Kept frames are used under MI355_ADAPTOR_KEEP_FRAMES.
+template <class PoseT>
+inline int MosaicImagesPreview(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, int level, int render,
+                               MI355_NS IplImage*& pMosaicResult) {
+    if (level < 1 || level > 7 || render < 0 || render > 2) return -1;
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_UNBLENDED, level, render);
 }
 
 // IplImage* LaplacianPyramidBlending(IplImage** pImages, int imagesNum, ProjectMat* pImgT, int band, float resScale)

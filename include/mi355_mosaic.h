@@ -349,6 +349,59 @@ int  mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, cons
 int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 
+/* ---- overview levels of a canvas and the striped preview render (csrc/overview.hip) ------------------------------------------------
+ * The reduced-size levels every orthomosaic product carries (GeoTIFF overviews, tile pyramids), made from a rendered canvas -- refined,
+ * feathered, seamline or blended -- in ONE pass that knows which pixels hold data, so that the zero surround is not averaged into the
+ * survey's edge.  Definition (exact integers; the bytes do not depend on tile shape, walk order or stripe cut):
+ *   Input: the level-0 canvas, cw x ch BGR u8 at pitch cws (cws >= 3 cw, a multiple of 4; the row pointer 4-byte aligned).
+ *   Valid map V(x, y) by `nodata`: MI355_NODATA_NONE every pixel is valid; MI355_NODATA_ZERO a pixel is invalid when B = G = R = 0 (what
+ *   every render leaves where nothing covers); MI355_NODATA_MAP valid where a caller's uint16_t map (pitch cw elements) is non-zero -- the
+ *   seamline render's count map and its owner map both qualify.
+ *   Levels l = 1 .. levels, 1 <= levels <= 7: ow_l = (cw + 2^l - 1) >> l, oh_l = (ch + 2^l - 1) >> l, ows_l = (3 ow_l + 3) & ~3
+ *   (mi355_overview_layout).  Pixel (X, Y) of level l owns the level-0 block [X 2^l, (X+1) 2^l) x [Y 2^l, (Y+1) 2^l) clipped to the canvas;
+ *   n = the number of valid level-0 pixels of the block, S[c] = the sum of their channel c;
+ *   out[c] = n ? (S[c] + n / 2) / n : 0 (integer division); row padding [3 ow_l, ows_l) is 0;
+ *   cover (optional, per level): uint16_t, oh_l x ow_l at pitch ow_l, the value n (n <= 4^7 = 16384; 255 * 16384 + 8192 < 2^32).
+ *   Every level is defined on level 0 directly, never as an average of averages.
+ * Consequences: a block with n = 4^l under MI355_NODATA_NONE gives the rounded box mean; every byte lies between the smallest and the
+ *   largest valid sample of its block; n > 0 at level l is the OR of V over the block; a constant valid region stays constant right up to
+ *   the survey's edge.
+ * Stripes: d_rows points at canvas row row0 and d_valid_rows at map row row0 (a stripe buffer serves as well as a whole canvas); cw, ch
+ *   are the whole canvas's.  row0 must be a multiple of 2^levels, and so must rows unless row0 + rows == ch (rows < 0: the rest of the
+ *   canvas).  Level l receives exactly its rows [row0 >> l, (row0 + rows + 2^l - 1) >> l); other rows of the outputs are left untouched.
+ *   Stripes put side by side give the bytes of the whole call.
+ * Cost: one launch makes all levels; canvas and map are read once; the higher levels come from sums carried in registers and LDS; no atomics.
+ * d_levels[l - 1] / d_covers[l - 1]: the WHOLE buffer of level l (oh_l x ows_l bytes / oh_l x ow_l uint16_t).  d_covers may be NULL, and so may
+ *   single entries of it.  Enqueued on the ctx stream like the other _dev forms.
+ * MI355_ERR_ARG: levels outside 1..7, nodata outside 0..2, MI355_NODATA_MAP without a map, a misaligned row0 / rows, rows outside the canvas,
+ *   NULL d_levels or a NULL entry in it, cw or ch < 1, cws < 3 cw or not a multiple of 4, a row pointer that is not 4-byte aligned. */
+#define MI355_NODATA_NONE 0
+#define MI355_NODATA_ZERO 1
+#define MI355_NODATA_MAP  2
+/* host geometry (no ctx): ow, oh, ows each hold `levels` entries (any of the three may be NULL) */
+int  mi355_overview_layout(int cw, int ch, int levels, int* ow, int* oh, int* ows);
+int  mi355_mosaic_overview_dev(mi355_ctx* ctx, const uint8_t* d_rows, int cw, int ch, int cws, const uint16_t* d_valid_rows, int nodata, int levels,
+                               uint8_t* const* d_levels, uint16_t* const* d_covers, int row0, int rows);
+/* host form: canvas (and valid, for MI355_NODATA_MAP) in host memory; *out_levels and, when out_covers != NULL, *out_covers are arrays of
+ * `levels` buffers, all library-allocated: free each buffer and the arrays with mi355_free */
+int  mi355_mosaic_overview(mi355_ctx* ctx, const uint8_t* canvas, int cw, int ch, int cws, const uint16_t* valid, int nodata, int levels,
+                           uint8_t*** out_levels, uint16_t*** out_covers);
+/* The preview: level `level` of the named render's canvas without that canvas.  render: 0 refined, 1 feathered, 2 seamline; ramp as in
+ * mi355_feather_params; nodata as above, where 2 stands for exact coverage: the render's count > 0, which the seamline ownership walk yields
+ * without a sample.  Sources, img_ids and refusals are those of mi355_mosaic_refined_into and of the render named; n <= 1 is MI355_ERR_FAILED.
+ * ow, oh must be what mi355_mosaic_layout followed by mi355_overview_layout give for `level` (else MI355_ERR_ARG).  dst: oh rows of
+ * dst_pitch >= 3 ow bytes, bytes [0, 3 ow) of each written; cover (NULL ok): oh x ow uint16_t at pitch ow, the level's n.
+ * The survey is rendered stripe by stripe in HBM, every stripe is reduced by the overview kernel, and the one level comes back through the
+ * ctx's pinned download buffers.  Stripe height: option "preview_stripe_rows" (default 1024, rounded up to a multiple of 2^level; 0: the
+ * whole canvas in one stripe).  Work memory is ONE stripe of canvas (and of map, for nodata 2) plus the one output level: the full-size
+ * canvas is never allocated and never crosses to the host.  The bytes are those of level `level` of mi355_mosaic_overview_dev applied to
+ * the whole canvas of the render, whatever the stripe height. */
+typedef struct { int32_t render; int32_t ramp; int32_t level; int32_t nodata; int32_t reserved[4]; } mi355_preview_params;
+void mi355_default_preview_params(mi355_preview_params* p);          /* render 0, ramp 0, level 3, nodata MI355_NODATA_MAP */
+int  mi355_mosaic_preview_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                               int n, const float* h9s, const mi355_preview_params* params, uint8_t* dst, int dst_pitch, uint16_t* cover,
+                               int ow, int oh);
+
 /* ---- callers / formats either side of the path ("next" rows f1, f2 of SURVEY 8f) ---------------------- */
 /* matchPairs.match: int32 n + n x 40-byte records (WriteMatchPairs / LoadMatchPairs, MosaicWithoutPos.cpp:4736-4797) */
 int  mi355_write_match_pairs(const char* path, const mi355_match_point_pairs* v, int n);

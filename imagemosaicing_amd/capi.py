@@ -321,12 +321,7 @@ class Context:
     def MosaicImagesRefined(self, imgs, h9s, want_pixels=True):
         """CMosaicByPose::MosaicImagesRefined (float), MosaicWithoutPos.cpp:2194-2352.  want_pixels=False: the canvas the library returns is
         released without the numpy copy (bench.py times the C call, not this binding)."""
-        n = len(imgs)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
         h9s = np.ascontiguousarray(h9s, np.float32)
         canvas = C.c_void_p()
         cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
@@ -590,6 +585,16 @@ class Context:
         return n, ptrs, np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32), np.ascontiguousarray(ws, np.int32)
 
     @staticmethod
+    def _host_args(imgs):
+        """n, the images as contiguous uint8 arrays (alive over the call), their pointers, w, h, ws"""
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+        ptrs = (C.c_void_p * len(imgs))(*[i.ctypes.data for i in imgs])
+        w = np.array([i.shape[1] for i in imgs], np.int32)
+        h = np.array([i.shape[0] for i in imgs], np.int32)
+        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        return len(imgs), imgs, ptrs, w, h, ws
+
+    @staticmethod
     def _pairs_ab(pairs):
         ab = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
         return ab, len(ab)
@@ -627,12 +632,7 @@ class Context:
     def MosaicFeathered(self, imgs, h9s, params=None, want_pixels=True, **kw):
         """mi355_mosaic_feathered: host images in, (canvas rows x cws, cw, ch, cws) out.  params: FeatherParams (feather_params()) or its
         keyword fields (ramp)."""
-        n = len(imgs)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
         h9s = np.ascontiguousarray(h9s, np.float32)
         p = params if params is not None else feather_params(**kw)
         canvas = C.c_void_p()
@@ -666,12 +666,7 @@ class Context:
     def MosaicSeamline(self, imgs, h9s, params=None, want_owner=False, **kw):
         """mi355_mosaic_seamline: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_owner (canvas, cw, ch, cws, owner [ch, cw]
         uint16: owning frame + 1, 0 where nothing covers).  params: SeamlineParams (seamline_params()) or its keyword fields (ramp)."""
-        n = len(imgs)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
         h9s = np.ascontiguousarray(h9s, np.float32)
         p = params if params is not None else seamline_params(**kw)
         canvas, owner = C.c_void_p(), C.c_void_p()

@@ -2,6 +2,7 @@
 // locking, host<->device staging around the kernels of warp.hip / ransac.hip / match.hip / sift.hip.
 // There is no CPU compute path in this library: without a usable gfx950 device mi355_create fails.
 #include "common.h"
+#include "mosaic_frame.h"
 #include <new>
 
 static thread_local std::string g_create_error;   // mi355_last_error(NULL): the calling thread's last creation error (or ctx-less call's error)
@@ -298,33 +299,13 @@ extern "C" int mi355_mosaic_refined(mi355_ctx* ctx, const uint8_t* const* imgs, 
                                     const float* h9s, uint8_t** canvas, int* cw, int* ch, int* cws) {
     LOCKED_PROLOGUE
     if (!imgs || !w || !h || !ws || !h9s || !canvas || !cw || !ch || !cws) return MI355_ERR_ARG;
-    if (n <= 1) { ctx->set_error("mosaic_refined: needs more than one image"); return MI355_ERR_FAILED; }   // MergeImagesRefined convention (:2164-2167)
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_refined: empty canvas"); return rc; }
-    // stage every contributing image in HBM (frames stay resident: 288 GB), then composite in index order
-    size_t total = 0;
-    std::vector<size_t> off(n, 0);
-    for (int k = 0; k < n; k++) { if (h9s[9 * k + 8] == 0.0f) continue; if (!imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) return MI355_ERR_ARG; off[k] = total; total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255; }
-    DevBuf& dall = ctx->buf("mosaic_srcs");
-    DevBuf& dcan = ctx->buf("mosaic_canvas");
-    MI_HIP(dall.reserve(total + 16));
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    std::vector<const uint8_t*> dptr(n, nullptr);
-    for (int k = 0; k < n; k++) {
-        if (h9s[9 * k + 8] == 0.0f) continue;
-        dptr[k] = dall.as<uint8_t>() + off[k];
-        MI_HIP(hipMemcpyAsync((void*)dptr[k], imgs[k], (size_t)ws[k] * h[k], hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = mi_mosaic_refined_dev(ctx, dptr.data(), w, h, ws, n, h9s, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
+    std::vector<const uint8_t*> d_imgs;
+    uint8_t* d_canvas;
+    int rc = mi_render_host_begin(ctx, "mosaic_refined", imgs, w, h, ws, n, h9s, &lw, &lh, &lws, d_imgs, &d_canvas);
+    if (rc == MI355_OK) rc = mi_mosaic_refined_dev(ctx, d_imgs.data(), w, h, ws, n, h9s, d_canvas, lw, lh, lws, 0, lh);
     if (rc != MI355_OK) return rc;
-    uint8_t* out = (uint8_t*)malloc((size_t)lws * lh);
-    if (!out) return MI355_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(out, dcan.p, (size_t)lws * lh, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(out); ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
-    *canvas = out; *cw = lw; *ch = lh; *cws = lws;
-    return MI355_OK;
+    return mi_render_host_end(ctx, lw, lh, lws, canvas, cw, ch, cws);
 }
 
 extern "C" int mi355_chips_and_masks(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,

@@ -12,6 +12,8 @@
 //                         frame record, its ramp constants and the box test are uniform over the workgroup (scalar loads).  The epilogue
 //                         divides (three exact unsigned divisions per pixel) and stores 12 bytes per row like the unblended render.
 //                         Integer sums: the bytes do not depend on the walk order, the tile shape or the stripe cut.
+// The lane / tile prologue and the row store (tile_lane, store_row12) and the host path around the launch -- entry check, frame table, lists,
+// the host form -- are mosaic_frame.h's, shared with warp.hip and seamline.hip; the walk is spelt out here (mosaic_frame.h says why).
 #include "common.h"
 #include "hmath.h"
 #include "mosaic_frame.h"
@@ -23,38 +25,29 @@ namespace {
 #define FT_RPL_V 2
 #endif
 constexpr int FT_W = 128, FT_RPL = FT_RPL_V, FT_H = 8 * FT_RPL;   // canvas tile of one workgroup: 256 lanes x 4 pixels x FT_RPL rows
-static_assert(MOSAIC_LIST_BLOCK % FT_W == 0 && MOSAIC_LIST_BLOCK % FT_H == 0, "a tile lies inside one list block");
-// (RampDev, ramp_weight and the weight omega_k itself: ramp.h, shared with seamline.hip)
+// (ramp_weight and the weight omega_k itself: ramp.h, shared with seamline.hip)
 
 __global__ __launch_bounds__(256) void feather_tile_kernel(const FrameDev* fr, const RampDev* ramps, int n, const uint16_t* lists, const int* counts, int bx_n,
                                                            uint8_t* canvas, int cw, int cws, int row0, int row_end, float dGx, float dGy) {
-    const int tid = threadIdx.x;
-    const int tx0 = blockIdx.x * FT_W, ty0 = row0 + blockIdx.y * FT_H;
-    // a lane owns 4 adjacent pixels in each of FT_RPL rows (rows ty0 + (tid >> 5) + 8 j), as in mosaic_tile_kernel
-    const int xg = tx0 + 4 * (tid & 31), yB = ty0 + (tid >> 5);
-    const int cb = ((ty0 - row0) / MOSAIC_LIST_BLOCK) * bx_n + tx0 / MOSAIC_LIST_BLOCK;
-    const uint16_t* list = lists + (size_t)cb * n;
-    const int cnt = counts[cb];
+    const TileLane t = tile_lane<FT_W, FT_RPL>(lists, counts, n, bx_n, cw, row0, row_end);
     unsigned acc[FT_RPL][4][4];                          // per pixel: sum omega B, sum omega G, sum omega R, sum omega
 #pragma unroll
     for (int j = 0; j < FT_RPL; j++)
 #pragma unroll
         for (int k = 0; k < 4; k++) { acc[j][k][0] = 0; acc[j][k][1] = 0; acc[j][k][2] = 0; acc[j][k][3] = 0; }
-    const int tx1 = tx0 + FT_W - 1 < cw - 1 ? tx0 + FT_W - 1 : cw - 1;
-    const int ty1 = ty0 + FT_H - 1 < row_end - 1 ? ty0 + FT_H - 1 : row_end - 1;
-    for (int e = 0; e < cnt; e++) {
-        const FrameDev& f = fr[list[e]];                 // uniform over the workgroup: scalar loads
-        if (f.begX > tx1 || f.endX < tx0 || f.begY > ty1 || f.endY < ty0) continue;
-        const RampDev r = ramps[list[e]];
+    for (int e = 0; e < t.cnt; e++) {
+        const FrameDev& f = fr[t.list[e]];               // uniform over the workgroup: scalar loads
+        if (f.begX > t.tx1 || f.endX < t.tx0 || f.begY > t.ty1 || f.endY < t.ty0) continue;
+        const RampDev r = ramps[t.list[e]];
         const float w1 = (float)(f.w - 1), h1 = (float)(f.h - 1);
 #pragma unroll
         for (int j = 0; j < FT_RPL; j++) {
-            const int yD = yB + 8 * j;
+            const int yD = t.yB + 8 * j;
             const bool yin = yD >= f.begY && yD <= f.endY;           // the box is clipped to the canvas and to the rows of this call
             const float yf = (float)yD - dGy;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const int xD = xg + k;
+                const int xD = t.xg + k;
                 const float xf = (float)xD - dGx;
                 float xs, ys;
                 frame_src(f, xf, yf, xs, ys);
@@ -66,10 +59,10 @@ __global__ __launch_bounds__(256) void feather_tile_kernel(const FrameDev* fr, c
             }
         }
     }
-    if (xg >= cw) return;
+    if (t.xg >= cw) return;
 #pragma unroll
     for (int j = 0; j < FT_RPL; j++) {
-        const int yD = yB + 8 * j;
+        const int yD = t.yB + 8 * j;
         if (yD >= row_end) continue;
         uint32_t out[3] = {0, 0, 0};                     // 12 bytes: B G R of the 4 pixels
 #pragma unroll
@@ -83,18 +76,7 @@ __global__ __launch_bounds__(256) void feather_tile_kernel(const FrameDev* fr, c
                 out[(3 * k + c) >> 2] |= v << (8 * ((3 * k + c) & 3));      // static positions
             }
         }
-        uint8_t* drow = canvas + (size_t)yD * cws + 3 * (size_t)xg;
-        if (xg + 3 < cw) {
-            uint32_t* d32 = reinterpret_cast<uint32_t*>(drow);
-            d32[0] = out[0]; d32[1] = out[1]; d32[2] = out[2];
-        } else {
-#pragma unroll
-            for (int b = 0; b < 9; b++)                  // at most 3 pixels
-                if (xg + b / 3 < cw) drow[b] = (uint8_t)(out[b >> 2] >> (8 * (b & 3)));
-        }
-        // row padding [3 cw, cws): zero, as in the unblended render
-        if (xg + 4 >= cw)
-            for (int b = 3 * cw; b < cws; b++) canvas[(size_t)yD * cws + b] = 0;
+        store_row12(canvas, cw, cws, t.xg, yD, out);
     }
 }
 
@@ -105,17 +87,10 @@ int mi_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const 
     mi355_feather_params dp;
     if (!params) { mi355_default_feather_params(&dp); params = &dp; }
     if (params->ramp < 0) { ctx->set_error("mosaic_feathered: ramp=" + std::to_string(params->ramp) + " < 0"); return MI355_ERR_ARG; }
-    int lw, lh, lws; float dG[2];
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, dG);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_feathered: no image with h[8] != 0 / empty canvas"); return rc; }
-    if (lw != cw || lh != ch || cws < cw * 3 || (cws & 3)) { ctx->set_error("mosaic_feathered: canvas geometry does not match mi355_mosaic_layout"); return MI355_ERR_ARG; }
-    if (row0 < 0) row0 = 0;
-    if (rows < 0 || row0 + rows > ch) rows = ch - row0;
-    if (rows <= 0) return MI355_OK;
-    if (n > 65535) { ctx->set_error("mosaic_feathered: at most 65535 images"); return MI355_ERR_ARG; }      // 16-bit lists; 255 * 255 * 65535 + 255 * 65535 / 2 < 2^32
-    std::vector<FrameDev> fr;
-    std::vector<RampDev> ramps;
-    fr.reserve(n); ramps.reserve(n);
+    float dG[2]; bool go;
+    const int rc = mi_render_entry(ctx, "mosaic_feathered", w, h, n, h9s, false, true, cw, ch, cws, row0, rows, dG, go);     // n <= 65535: 255 * 255 * 65535 + 255 * 65535 / 2 < 2^32
+    if (rc != MI355_OK || !go) return rc;
+    FrameTable t;
     for (int k = 0; k < n; k++) {
         FrameDev f;
         if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], dG, cw, ch, row0, rows, f)) continue;
@@ -123,31 +98,18 @@ int mi_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const 
         // every frame whose box meets the rows is read: there is no "lies under later frames" case here
         if (!d_imgs[k]) { ctx->set_error("mosaic_feathered: the box of image " + std::to_string(k) + " meets these canvas rows but no pointer to it was given"); return MI355_ERR_ARG; }
         f.src = d_imgs[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k];
-        fr.push_back(f);
-        ramps.push_back(ramp_of_frame(w[k], h[k], params->ramp));
+        t.add(f, k);
+        t.ramps.push_back(ramp_of_frame(w[k], h[k], params->ramp));
     }
-    const int nf = (int)fr.size();
-    const int bx_n = (cw + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK, by_n = (rows + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK;
-    DevBuf& dfr = ctx->buf("mosaic_frames");
-    DevBuf& dl = ctx->buf("mosaic_lists");
-    DevBuf& dc = ctx->buf("mosaic_counts");
-    DevBuf& dr = ctx->buf("feather_ramps");
-    MI_HIP(dfr.reserve(sizeof(FrameDev) * (size_t)(nf > 0 ? nf : 1)));
-    MI_HIP(dr.reserve(sizeof(RampDev) * (size_t)(nf > 0 ? nf : 1)));
-    MI_HIP(dl.reserve(sizeof(uint16_t) * (size_t)bx_n * by_n * (size_t)(nf > 0 ? nf : 1)));
-    MI_HIP(dc.reserve(sizeof(int) * (size_t)bx_n * by_n));
-    if (nf > 0) {
-        MI_HIP(hipMemcpyAsync(dfr.p, fr.data(), sizeof(FrameDev) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-        MI_HIP(hipMemcpyAsync(dr.p, ramps.data(), sizeof(RampDev) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    }
-    mi_mosaic_lists_launch(ctx, dfr.as<FrameDev>(), nf, bx_n, by_n, row0, dl.as<uint16_t>(), dc.as<int>());
+    const int rc2 = mi_frame_table_upload(ctx, t, true, false, cw, rows, row0);
+    if (rc2 != MI355_OK) return rc2;
     {
         ProfScope ps(ctx, "feather", 0.0);
         hipLaunchKernelGGL(feather_tile_kernel, dim3((cw + FT_W - 1) / FT_W, (rows + FT_H - 1) / FT_H), dim3(256), 0, ctx->stream,
-                           dfr.as<FrameDev>(), dr.as<RampDev>(), nf, dl.as<uint16_t>(), dc.as<int>(), bx_n, d_canvas, cw, cws, row0, row0 + rows, dG[0], dG[1]);
+                           t.d_fr, t.d_ramps, t.nf, t.d_lists, t.d_counts, t.bx_n, d_canvas, cw, cws, row0, row0 + rows, dG[0], dG[1]);
     }
     MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // `fr` and `ramps` go out of scope
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // the table goes out of scope
     return MI355_OK;
 }
 
@@ -163,35 +125,16 @@ extern "C" int mi355_mosaic_feathered_dev(mi355_ctx* ctx, const uint8_t* const* 
     return mi_mosaic_feathered_dev(ctx, d_imgs, w, h, ws, n, h9s, params, d_canvas, cw, ch, cws, row0, rows);
 }
 
-// the host form: mi355_mosaic_refined's staging, the feathered render in its place
+// the host form (mi_render_host_begin / _end, frames.hip)
 extern "C" int mi355_mosaic_feathered(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                       const mi355_feather_params* params, uint8_t** canvas, int* cw, int* ch, int* cws) {
     LOCKED_PROLOGUE
     if (!imgs || !w || !h || !ws || !h9s || !canvas || !cw || !ch || !cws) return MI355_ERR_ARG;
-    if (n <= 1) { ctx->set_error("mosaic_feathered: needs more than one image"); return MI355_ERR_FAILED; }
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_feathered: empty canvas"); return rc; }
-    size_t total = 0;
-    std::vector<size_t> off(n, 0);
-    for (int k = 0; k < n; k++) { if (h9s[9 * k + 8] == 0.0f) continue; if (!imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) return MI355_ERR_ARG; off[k] = total; total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255; }
-    DevBuf& dall = ctx->buf("mosaic_srcs");
-    DevBuf& dcan = ctx->buf("mosaic_canvas");
-    MI_HIP(dall.reserve(total + 16));
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    std::vector<const uint8_t*> dptr(n, nullptr);
-    for (int k = 0; k < n; k++) {
-        if (h9s[9 * k + 8] == 0.0f) continue;
-        dptr[k] = dall.as<uint8_t>() + off[k];
-        MI_HIP(hipMemcpyAsync((void*)dptr[k], imgs[k], (size_t)ws[k] * h[k], hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = mi_mosaic_feathered_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
+    std::vector<const uint8_t*> d_imgs;
+    uint8_t* d_canvas;
+    int rc = mi_render_host_begin(ctx, "mosaic_feathered", imgs, w, h, ws, n, h9s, &lw, &lh, &lws, d_imgs, &d_canvas);
+    if (rc == MI355_OK) rc = mi_mosaic_feathered_dev(ctx, d_imgs.data(), w, h, ws, n, h9s, params, d_canvas, lw, lh, lws, 0, lh);
     if (rc != MI355_OK) return rc;
-    uint8_t* out = (uint8_t*)malloc((size_t)lws * lh);
-    if (!out) return MI355_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(out, dcan.p, (size_t)lws * lh, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(out); ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
-    *canvas = out; *cw = lw; *ch = lh; *cws = lws;
-    return MI355_OK;
+    return mi_render_host_end(ctx, lw, lh, lws, canvas, cw, ch, cws);
 }

@@ -1,8 +1,11 @@
-// csrc/frames.hip -- host frames kept in HBM after their extraction (option "keep_frames") and the render calls that write straight
-// into caller memory (mi355_mosaic_refined_into / mi355_mosaic_feathered_into / mi355_mosaic_seamline_into / mi355_mosaic_blended_into).  Host code only: the canvases come
-// from the kernels of warp.hip / feather.hip / seamline.hip / blend.hip; what is new is where their inputs come from and how the canvas reaches the caller's rows.
-// Last, mi355_mosaic_preview_into: the same sources, rendered stripe by stripe and reduced by overview.hip, one overview level reaching the caller.
+// csrc/frames.hip -- where the renders' inputs come from and how their canvas reaches the caller.  Host code only: the canvases come from the
+// kernels of warp.hip / feather.hip / seamline.hip / blend.hip.  Host frames kept in HBM after their extraction (option "keep_frames");
+// render_sources, the staging every form shares; the host forms of the one-pass renders (mi_render_host_begin / _end: a malloc'd canvas) and the calls
+// that write straight into caller memory (render_into: mi355_mosaic_refined_into / _feathered_into / _seamline_into / _blended_into).
+// Last, mi355_mosaic_preview_into: the same sources, rendered stripe by stripe and reduced by overview.hip, one overview level reaching the
+// caller.
 #include "common.h"
+#include "mosaic_frame.h"
 #include <thread>
 
 // ---- kept frames ------------------------------------------------------------------------------------------------------
@@ -103,10 +106,20 @@ extern "C" int mi355_get_frame_dev(mi355_ctx* ctx, int img_id, const uint8_t** d
 }
 
 // ---- the render calls' sources --------------------------------------------------------------------------------------------
-// Device pointers of the images a render reads: kept frames where img_ids names one, the host images staged in "into_srcs" otherwise.
-// Images the render skips (skip[k]) are neither read nor checked.
+// n <= 1 and the layout of the one-pass renders' host-image forms (MergeImagesRefined's convention, MosaicWithoutPos.cpp:2164-2167)
+static int render_layout(mi355_ctx* ctx, const char* who, const int* w, const int* h, int n, const float* h9s, int* lw, int* lh, int* lws) {
+    if (n <= 1) { ctx->set_error(std::string(who) + ": needs more than one image"); return MI355_ERR_FAILED; }
+    const int rc = mi355_mosaic_layout(w, h, n, h9s, lw, lh, lws, nullptr);
+    if (rc != MI355_OK) ctx->set_error(std::string(who) + ": empty canvas");
+    return rc;
+}
+
+// Device pointers of the images a render reads: kept frames where img_ids (may be NULL) names one, the host images staged in the ctx buffer
+// `staging` otherwise.  Images the render skips (h9[8] == 0, or keep[k] == 0 where keep is given) are neither read nor checked.
 static int render_sources(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
-                          const int* ws, int n, const std::vector<char>& skip, std::vector<const uint8_t*>& dptr) {
+                          const int* ws, int n, const float* h9s, const uint8_t* keep, const char* staging, std::vector<const uint8_t*>& dptr) {
+    std::vector<char> skip((size_t)n);
+    for (int k = 0; k < n; k++) skip[k] = (keep && !keep[k]) || h9s[9 * k + 8] == 0.0f;
     dptr.assign((size_t)n, nullptr);
     std::vector<size_t> off((size_t)n, 0);
     size_t total = 0;
@@ -136,7 +149,7 @@ static int render_sources(mi355_ctx* ctx, const char* who, const uint8_t* const*
         total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255;
     }
     if (total == 0) return MI355_OK;
-    DevBuf& dall = ctx->buf("into_srcs");
+    DevBuf& dall = ctx->buf(staging);
     MI_HIP(dall.reserve(total + 16));
     for (int k = 0; k < n; k++) {
         if (skip[k] || dptr[k]) continue;
@@ -206,27 +219,59 @@ static int check_dst(mi355_ctx* ctx, const char* who, const uint8_t* dst, int ds
     return MI355_OK;
 }
 
+// ---- the host forms: host images in, a malloc'd canvas out ---------------------------------------------------------------------
+int mi_render_host_begin(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                         int* lw, int* lh, int* lws, std::vector<const uint8_t*>& d_imgs, uint8_t** d_canvas) {
+    int rc = render_layout(ctx, who, w, h, n, h9s, lw, lh, lws);
+    if (rc != MI355_OK) return rc;
+    rc = render_sources(ctx, who, imgs, nullptr, w, h, ws, n, h9s, nullptr, "mosaic_srcs", d_imgs);     // every contributing image staged in HBM (frames stay resident: 288 GB)
+    if (rc != MI355_OK) return rc;
+    DevBuf& dcan = ctx->buf("mosaic_canvas");
+    MI_HIP(dcan.reserve((size_t)*lws * *lh));
+    *d_canvas = dcan.as<uint8_t>();
+    return MI355_OK;
+}
+
+int mi_render_host_end(mi355_ctx* ctx, int lw, int lh, int lws, uint8_t** canvas, int* cw, int* ch, int* cws, const void* d_map, size_t map_bytes, void** map) {
+    const size_t cbytes = (size_t)lws * lh;
+    void* out = malloc(cbytes);
+    void* m = map ? malloc(map_bytes) : nullptr;
+    if (!out || (map && !m)) { free(out); free(m); return MI355_ERR_NOMEM; }
+    hipError_t e = hipMemcpyAsync(out, ctx->buf("mosaic_canvas").p, cbytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && map) e = hipMemcpyAsync(m, d_map, map_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { free(out); free(m); ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
+    *canvas = (uint8_t*)out; *cw = lw; *ch = lh; *cws = lws;
+    if (map) *map = m;
+    return MI355_OK;
+}
+
 // ---- render into caller memory --------------------------------------------------------------------------------------------
+// sources (kept frames / "into_srcs"), render(d_imgs, d_canvas) into "into_canvas", the canvas's rows into dst
+template <class Render>
+static int render_into(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                       int n, const float* h9s, const uint8_t* keep, uint8_t* dst, int dst_pitch, int cw, int ch, int lw, int lh, int lws, Render render) {
+    int rc = check_dst(ctx, who, dst, dst_pitch, cw, ch, lw, lh);
+    if (rc != MI355_OK) return rc;
+    std::vector<const uint8_t*> dptr;
+    rc = render_sources(ctx, who, imgs, img_ids, w, h, ws, n, h9s, keep, "into_srcs", dptr);
+    if (rc != MI355_OK) return rc;
+    DevBuf& dcan = ctx->buf("into_canvas");
+    MI_HIP(dcan.reserve((size_t)lws * lh));
+    rc = render(dptr.data(), dcan.as<uint8_t>());
+    if (rc != MI355_OK) return rc;
+    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+}
+
 extern "C" int mi355_mosaic_refined_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
                                          const int* ws, int n, const float* h9s, uint8_t* dst, int dst_pitch, int cw, int ch) {
     LOCKED_PROLOGUE
     if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_refined_into: bad arguments"); return MI355_ERR_ARG; }
-    if (n <= 1) { ctx->set_error("mosaic_refined_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_refined_into: empty canvas"); return rc; }
-    rc = check_dst(ctx, "mosaic_refined_into", dst, dst_pitch, cw, ch, lw, lh);
+    const int rc = render_layout(ctx, "mosaic_refined_into", w, h, n, h9s, &lw, &lh, &lws);
     if (rc != MI355_OK) return rc;
-    std::vector<char> skip((size_t)n);
-    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
-    std::vector<const uint8_t*> dptr;
-    rc = render_sources(ctx, "mosaic_refined_into", imgs, img_ids, w, h, ws, n, skip, dptr);
-    if (rc != MI355_OK) return rc;
-    DevBuf& dcan = ctx->buf("into_canvas");
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    rc = mi_mosaic_refined_dev(ctx, dptr.data(), w, h, ws, n, h9s, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
-    if (rc != MI355_OK) return rc;
-    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+    return render_into(ctx, "mosaic_refined_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws,
+                       [&](const uint8_t* const* d, uint8_t* dc) { return mi_mosaic_refined_dev(ctx, d, w, h, ws, n, h9s, dc, lw, lh, lws, 0, lh); });
 }
 
 extern "C" int mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
@@ -234,22 +279,11 @@ extern "C" int mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const*
                                            int cw, int ch) {
     LOCKED_PROLOGUE
     if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_feathered_into: bad arguments"); return MI355_ERR_ARG; }
-    if (n <= 1) { ctx->set_error("mosaic_feathered_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_feathered_into: empty canvas"); return rc; }
-    rc = check_dst(ctx, "mosaic_feathered_into", dst, dst_pitch, cw, ch, lw, lh);
+    const int rc = render_layout(ctx, "mosaic_feathered_into", w, h, n, h9s, &lw, &lh, &lws);
     if (rc != MI355_OK) return rc;
-    std::vector<char> skip((size_t)n);
-    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
-    std::vector<const uint8_t*> dptr;
-    rc = render_sources(ctx, "mosaic_feathered_into", imgs, img_ids, w, h, ws, n, skip, dptr);
-    if (rc != MI355_OK) return rc;
-    DevBuf& dcan = ctx->buf("into_canvas");
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    rc = mi_mosaic_feathered_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, 0, lh);
-    if (rc != MI355_OK) return rc;
-    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+    return render_into(ctx, "mosaic_feathered_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws,
+                       [&](const uint8_t* const* d, uint8_t* dc) { return mi_mosaic_feathered_dev(ctx, d, w, h, ws, n, h9s, params, dc, lw, lh, lws, 0, lh); });
 }
 
 extern "C" int mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
@@ -257,22 +291,12 @@ extern "C" int mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* 
                                            int cw, int ch) {
     LOCKED_PROLOGUE
     if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_seamline_into: bad arguments"); return MI355_ERR_ARG; }
-    if (n <= 1) { ctx->set_error("mosaic_seamline_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_seamline_into: empty canvas"); return rc; }
-    rc = check_dst(ctx, "mosaic_seamline_into", dst, dst_pitch, cw, ch, lw, lh);
+    const int rc = render_layout(ctx, "mosaic_seamline_into", w, h, n, h9s, &lw, &lh, &lws);
     if (rc != MI355_OK) return rc;
-    std::vector<char> skip((size_t)n);
-    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
-    std::vector<const uint8_t*> dptr;
-    rc = render_sources(ctx, "mosaic_seamline_into", imgs, img_ids, w, h, ws, n, skip, dptr);
-    if (rc != MI355_OK) return rc;
-    DevBuf& dcan = ctx->buf("into_canvas");
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    rc = mi_mosaic_seamline_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
-    if (rc != MI355_OK) return rc;
-    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+    return render_into(ctx, "mosaic_seamline_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws, [&](const uint8_t* const* d, uint8_t* dc) {
+        return mi_mosaic_seamline_dev(ctx, d, w, h, ws, n, h9s, params, dc, lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
+    });
 }
 
 extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
@@ -281,21 +305,11 @@ extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* i
     LOCKED_PROLOGUE
     if (!w || !h || !ws || !h9s || n <= 0 || (!imgs && !img_ids)) { ctx->set_error("mosaic_blended_into: bad arguments"); return MI355_ERR_ARG; }
     int lw = 0, lh = 0;
-    int rc = mi_blend_layout(w, h, n, h9s, keep, &lw, &lh);
+    const int rc = mi_blend_layout(w, h, n, h9s, keep, &lw, &lh);
     if (rc != MI355_OK) return rc;
     const int lws = (lw * 3 + 3) & ~3;
-    rc = check_dst(ctx, "mosaic_blended_into", dst, dst_pitch, cw, ch, lw, lh);
-    if (rc != MI355_OK) return rc;
-    std::vector<char> skip((size_t)n);
-    for (int k = 0; k < n; k++) skip[k] = (keep && !keep[k]) || h9s[9 * k + 8] == 0.0f;
-    std::vector<const uint8_t*> dptr;
-    rc = render_sources(ctx, "mosaic_blended_into", imgs, img_ids, w, h, ws, n, skip, dptr);
-    if (rc != MI355_OK) return rc;
-    DevBuf& dcan = ctx->buf("into_canvas");
-    MI_HIP(dcan.reserve((size_t)lws * lh));
-    rc = mi_mosaic_blended_dev(ctx, dptr.data(), w, h, ws, n, h9s, keep, band, dcan.as<uint8_t>(), lw, lh, lws);
-    if (rc != MI355_OK) return rc;
-    return download_rows(ctx, dcan.as<uint8_t>(), (size_t)lws, dst, (size_t)dst_pitch, (size_t)3 * lw, lh);
+    return render_into(ctx, "mosaic_blended_into", imgs, img_ids, w, h, ws, n, h9s, keep, dst, dst_pitch, cw, ch, lw, lh, lws,
+                       [&](const uint8_t* const* d, uint8_t* dc) { return mi_mosaic_blended_dev(ctx, d, w, h, ws, n, h9s, keep, band, dc, lw, lh, lws); });
 }
 
 // ---- striped preview ------------------------------------------------------------------------------------------------------
@@ -318,20 +332,17 @@ extern "C" int mi355_mosaic_preview_into(mi355_ctx* ctx, const uint8_t* const* i
     if (params->level < 1 || params->level > 7) { ctx->set_error("mosaic_preview_into: level=" + std::to_string(params->level) + " outside 1..7"); return MI355_ERR_ARG; }
     if (params->nodata < 0 || params->nodata > 2) { ctx->set_error("mosaic_preview_into: nodata=" + std::to_string(params->nodata) + " outside 0..2"); return MI355_ERR_ARG; }
     if (params->ramp < 0) { ctx->set_error("mosaic_preview_into: ramp=" + std::to_string(params->ramp) + " < 0"); return MI355_ERR_ARG; }
-    if (n <= 1) { ctx->set_error("mosaic_preview_into: needs more than one image"); return MI355_ERR_FAILED; }   // as mi355_mosaic_refined
     const int level = params->level;
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_preview_into: empty canvas"); return rc; }
+    int rc = render_layout(ctx, "mosaic_preview_into", w, h, n, h9s, &lw, &lh, &lws);
+    if (rc != MI355_OK) return rc;
     int aw[7], ah[7], aws[7];
     mi355_overview_layout(lw, lh, level, aw, ah, aws);
     const int low = aw[level - 1], loh = ah[level - 1], lows = aws[level - 1];
     rc = check_dst(ctx, "mosaic_preview_into", dst, dst_pitch, ow, oh, low, loh);
     if (rc != MI355_OK) return rc;
-    std::vector<char> skip((size_t)n);
-    for (int k = 0; k < n; k++) skip[k] = h9s[9 * k + 8] == 0.0f;
     std::vector<const uint8_t*> dptr;
-    rc = render_sources(ctx, "mosaic_preview_into", imgs, img_ids, w, h, ws, n, skip, dptr);
+    rc = render_sources(ctx, "mosaic_preview_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, "into_srcs", dptr);
     if (rc != MI355_OK) return rc;
     const int unit = 1 << level;
     long srows = ctx->preview_stripe_rows > 0 ? ((long)ctx->preview_stripe_rows + unit - 1) / unit * unit : lh;

@@ -1,7 +1,11 @@
-// csrc/mosaic_frame.h -- one frame of the refined render as its kernels see it: the FrameDev record and its host setup (the clipped canvas box
-// and the inverse, warp.hip: mi_frame_dev_setup), the 2 x 2 texel loads, and "frame f gives canvas pixel (x, y) this sample" as device helpers
-// (gain.hip).  mosaic_tile_kernel spells the same map / bounds / hm::bilin steps inline, unchanged, so that its code object stays what it
-// was; tests/test_gpu_gain.py pins the helpers against the render (per-frame samples and cover equal the oracle's refined canvas).
+// csrc/mosaic_frame.h -- what the one-pass canvas renders (refined: warp.hip, feathered: feather.hip, seamline: seamline.hip) share.
+// Host side: the FrameDev record and its setup (the clipped canvas box and the inverse), the entry check of the _dev launchers, the frame
+// table with its upload and candidate lists, the "which table entries were used" pass (all warp.hip), and the host forms' staging and
+// download (frames.hip).  Device side: the 2 x 2 texel loads, "frame f gives canvas pixel (x, y) this sample" (also gain.hip), and the
+// lane / tile prologue and 12-byte row store of feather_tile_kernel and seamline_tile_kernel.  mosaic_tile_kernel spells the same
+// map / bounds / hm::bilin / store steps inline, unchanged, so that its code object stays what it was (one more VGPR than its 72 would cost
+// it a wave per SIMD); tests/test_gpu_gain.py pins the helpers against the render (per-frame samples and cover equal the oracle's refined
+// canvas).
 #pragma once
 #include "common.h"
 #include "hmath.h"
@@ -17,11 +21,48 @@ struct FrameDev {
 // the frame (h9[8] == 0, no inverse, or a clipped box that misses the rows), 1 otherwise.  src / w / h / ws are left to the caller.
 int mi_frame_dev_setup(const float* h9, int w, int h, const float dG[2], int cw, int ch, int row0, int rows, FrameDev& f);
 
-// The per-block candidate lists of the one-pass renders (warp.hip: mosaic_lists_kernel), enqueued on the ctx stream: for every MOSAIC_LIST_BLOCK x
-// MOSAIC_LIST_BLOCK block of the canvas rows from row0 on (bx_n x by_n blocks, row-major) the frames of d_fr[0 .. nf) whose box meets it, highest
-// index first, at d_lists[block * nf ..], their number in d_counts[block].
+// a frame's feather ramp (ramp.h: ramp_of_frame, ramp_weight)
+struct RampDev { uint32_t R, mul, shift, _pad; };
+
+// ---- the host path of the one-pass renders ------------------------------------------------------------------------------------------
+// The entry check of a _dev launcher (`who` prefixes its messages): the layout of the survey must be the caller's cw x ch (and, where a canvas
+// is written, cws a multiple of 4 that holds a row) -- a cover call (cover) has no canvas and takes the layout's; row0 / rows are clamped to
+// the canvas, dG is the layout's shift.  go = 0: no rows, nothing to do.
+int mi_render_entry(mi355_ctx* ctx, const char* who, const int* w, const int* h, int n, const float* h9s, bool cover, bool want_canvas,
+                    int& cw, int& ch, int& cws, int& row0, int& rows, float dG[2], bool& go);
+
+// The frames a render walks: fr[q] is the caller's image frame_of[q] (ascending), ramps[q] its ramp where the render weighs.  Which frames
+// enter, and what a withheld pointer means, is the render's own loop over mi_frame_dev_setup.
 constexpr int MOSAIC_LIST_BLOCK = 256;
-void mi_mosaic_lists_launch(mi355_ctx* ctx, const FrameDev* d_fr, int nf, int bx_n, int by_n, int row0, uint16_t* d_lists, int* d_counts);
+struct FrameTable {
+    std::vector<FrameDev> fr;
+    std::vector<int> frame_of;
+    std::vector<RampDev> ramps;
+    void add(const FrameDev& f, int k) { fr.push_back(f); frame_of.push_back(k); }
+    // filled by mi_frame_table_upload
+    int nf = 0, bx_n = 0;
+    const FrameDev* d_fr = nullptr; const RampDev* d_ramps = nullptr; const int* d_frame_of = nullptr;
+    const uint16_t* d_lists = nullptr; const int* d_counts = nullptr;
+};
+
+// The table into the ctx buffers "mosaic_frames" (with_ramps: "feather_ramps", with_frame_of: "seamline_frame_of") and its per-block candidate
+// lists (mosaic_lists_kernel into "mosaic_lists" / "mosaic_counts"), enqueued on the ctx stream: for every MOSAIC_LIST_BLOCK x MOSAIC_LIST_BLOCK
+// block of the canvas rows from row0 on (bx_n blocks a row, row-major) the frames whose box meets it, highest index first, at d_lists[block *
+// nf ..], their number in d_counts[block].  The host vectors must outlive the copies (the renders end with a stream synchronise).
+int mi_frame_table_upload(mi355_ctx* ctx, FrameTable& t, bool with_ramps, bool with_frame_of, int cw, int rows, int row0);
+
+// used[q] != 0 for the table entries a pass marked: _begin zeroes "mosaic_used" and hands it out, the caller enqueues the pass that sets
+// d_used[q] on the ctx stream, _end copies the flags back (complete on return).
+int mi_frame_table_used_begin(mi355_ctx* ctx, const FrameTable& t, int** d_used);
+int mi_frame_table_used_end(mi355_ctx* ctx, const FrameTable& t, std::vector<int>& used);
+
+// The host form of a render (frames.hip).  _begin: n <= 1 and the layout, the images with h9[8] != 0 staged in "mosaic_srcs" (d_imgs), and
+// "mosaic_canvas" sized for the layout.  The caller renders.  _end: the canvas -- and d_map, map_bytes of a second output where asked for --
+// handed back in malloc'd memory, complete on return; on failure no output is touched.
+int mi_render_host_begin(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                         int* lw, int* lh, int* lws, std::vector<const uint8_t*>& d_imgs, uint8_t** d_canvas);
+int mi_render_host_end(mi355_ctx* ctx, int lw, int lh, int lws, uint8_t** canvas, int* cw, int* ch, int* cws, const void* d_map = nullptr,
+                       size_t map_bytes = 0, void** map = nullptr);
 
 namespace {
 
@@ -80,6 +121,45 @@ __device__ __forceinline__ void frame_sample3(const FrameDev& f, float xs, float
     const uint8_t* g0 = f.src + (size_t)yi * f.ws + 3 * (size_t)xi;
     load_quad3(g0, f.ws, 3 * xi + 8 <= f.ws, b00, g00, r00, b01, g01, r01, b10, g10, r10, b11, g11, r11);
     vb = hm::bilin(b00, b01, b10, b11, p, q); vg = hm::bilin(g00, g01, g10, g11, p, q); vr = hm::bilin(r00, r01, r10, r11, p, q);
+}
+
+// ---- the tile prologue and row store of feather_tile_kernel / seamline_tile_kernel ----------------------------------------------------
+// (mosaic_tile_kernel keeps its own spelling, see the file head.  The walk between the two stays spelt out in both kernels: as a helper
+// taking the per-sample step as a functor it cost feather_tile_kernel 16 VGPRs, 99 against 83, and with them a wave per SIMD.)
+// What a lane of the 256-lane workgroup of a TW x 8 RPL canvas tile (TW = 128) works on: 4 adjacent pixels from column xg in each of the RPL rows
+// yB + 8 j, the candidate list of the tile's block, and the tile's corners clipped to the canvas and the rows of the call.
+struct TileLane { int tx0, ty0, tx1, ty1, xg, yB, cnt; const uint16_t* list; };
+
+template <int TW, int RPL>
+__device__ __forceinline__ TileLane tile_lane(const uint16_t* lists, const int* counts, int n, int bx_n, int cw, int row0, int row_end) {
+    constexpr int TH = 8 * RPL;
+    static_assert(MOSAIC_LIST_BLOCK % TW == 0 && MOSAIC_LIST_BLOCK % TH == 0, "a tile lies inside one list block");
+    const int tid = threadIdx.x;
+    TileLane t;
+    t.tx0 = blockIdx.x * TW; t.ty0 = row0 + blockIdx.y * TH;
+    t.xg = t.tx0 + 4 * (tid & 31); t.yB = t.ty0 + (tid >> 5);
+    const int cb = ((t.ty0 - row0) / MOSAIC_LIST_BLOCK) * bx_n + t.tx0 / MOSAIC_LIST_BLOCK;
+    t.list = lists + (size_t)cb * n;
+    t.cnt = counts[cb];
+    t.tx1 = t.tx0 + TW - 1 < cw - 1 ? t.tx0 + TW - 1 : cw - 1;
+    t.ty1 = t.ty0 + TH - 1 < row_end - 1 ? t.ty0 + TH - 1 : row_end - 1;
+    return t;
+}
+
+// The 12 bytes (B G R of 4 pixels) of a lane's group in canvas row yD: three dwords where the group is whole, bytes where the row ends inside
+// it; the lane that owns the row's last group clears the padding [3 cw, cws), as the unblended render does.
+__device__ __forceinline__ void store_row12(uint8_t* canvas, int cw, int cws, int xg, int yD, const uint32_t out[3]) {
+    uint8_t* drow = canvas + (size_t)yD * cws + 3 * (size_t)xg;
+    if (xg + 3 < cw) {
+        uint32_t* d32 = reinterpret_cast<uint32_t*>(drow);
+        d32[0] = out[0]; d32[1] = out[1]; d32[2] = out[2];
+    } else {
+#pragma unroll
+        for (int b = 0; b < 9; b++)                      // at most 3 pixels
+            if (xg + b / 3 < cw) drow[b] = (uint8_t)(out[b >> 2] >> (8 * (b & 3)));
+    }
+    if (xg + 4 >= cw)
+        for (int b = 3 * cw; b < cws; b++) canvas[(size_t)yD * cws + b] = 0;
 }
 
 }  // namespace

@@ -10,7 +10,7 @@ constexpr int RAMP_MAX_SIDE = 1 << 20;          // frames up to 2^20 a side: 254
 
 // frame k's ramp: R and the constants of n / R for 0 <= n < 2^28 (Granlund & Montgomery 1994, theorem 4.2: with l = ceil(log2 R) and
 // mul = ceil(2^(28 + l) / R), floor(n mul / 2^(28 + l)) = floor(n / R) for every n < 2^28; mul <= 2^29)
-struct RampDev { uint32_t R, mul, shift, _pad; };
+// (struct RampDev { R, mul, shift }: mosaic_frame.h, beside the frame record it travels with)
 
 inline RampDev ramp_setup(uint32_t R) {
     uint32_t l = 0;

@@ -18,6 +18,8 @@
 //                         recomputation is a handful of multiply-adds per pixel, once (-DSL_KEEP_XY_V=1 builds the other form).
 //                         <false>: phase 2 is left out -- the maps alone (d_canvas == NULL) or the per-frame "owns a pixel" flags (the cover
 //                         call, and the check that precedes a render some of whose frames came without a pointer).
+// The lane / tile prologue and the row store (tile_lane, store_row12) and the host path around the launches -- entry check, frame table,
+// lists, used flags, the host form -- are mosaic_frame.h's, shared with warp.hip and feather.hip; the walk is spelt out here.
 #include "common.h"
 #include "hmath.h"
 #include "mosaic_frame.h"
@@ -32,7 +34,6 @@ namespace {
 #define SL_KEEP_XY_V 0                          // 1: keep the winner's xs, ys from phase 1 (kernel A/B builds)
 #endif
 constexpr int SL_W = 128, SL_RPL = SL_RPL_V, SL_H = 8 * SL_RPL;   // canvas tile of one workgroup: 256 lanes x 4 pixels x SL_RPL rows
-static_assert(MOSAIC_LIST_BLOCK % SL_W == 0 && MOSAIC_LIST_BLOCK % SL_H == 0, "a tile lies inside one list block");
 
 // four 16-bit map entries of a lane's pixel group: 8 bytes at once where the group is whole
 __device__ __forceinline__ void store_map4(uint16_t* row, int xg, int cw, const unsigned v[4]) {
@@ -50,13 +51,8 @@ template <bool SAMPLE>
 __global__ __launch_bounds__(256) void seamline_tile_kernel(const FrameDev* fr, const RampDev* ramps, const int* frame_of, int n, const uint16_t* lists,
                                                             const int* counts, int bx_n, uint8_t* canvas, uint16_t* owner, uint16_t* count, int* used,
                                                             int cw, int cws, int row0, int row_end, float dGx, float dGy) {
-    const int tid = threadIdx.x;
-    const int tx0 = blockIdx.x * SL_W, ty0 = row0 + blockIdx.y * SL_H;
-    // a lane owns 4 adjacent pixels in each of SL_RPL rows (rows ty0 + (tid >> 5) + 8 j), as in mosaic_tile_kernel
-    const int xg = tx0 + 4 * (tid & 31), yB = ty0 + (tid >> 5);
-    const int cb = ((ty0 - row0) / MOSAIC_LIST_BLOCK) * bx_n + tx0 / MOSAIC_LIST_BLOCK;
-    const uint16_t* list = lists + (size_t)cb * n;
-    const int cnt = counts[cb];
+    const TileLane t = tile_lane<SL_W, SL_RPL>(lists, counts, n, bx_n, cw, row0, row_end);
+    const int xg = t.xg;
     unsigned key[SL_RPL][4], cov[SL_RPL][4];             // per pixel: max of omega << 16 | q (0: no frame), the number of contributing frames
 #if SL_KEEP_XY_V
     float kx[SL_RPL][4], ky[SL_RPL][4];
@@ -65,18 +61,16 @@ __global__ __launch_bounds__(256) void seamline_tile_kernel(const FrameDev* fr, 
     for (int j = 0; j < SL_RPL; j++)
 #pragma unroll
         for (int k = 0; k < 4; k++) { key[j][k] = 0; cov[j][k] = 0; }
-    const int tx1 = tx0 + SL_W - 1 < cw - 1 ? tx0 + SL_W - 1 : cw - 1;
-    const int ty1 = ty0 + SL_H - 1 < row_end - 1 ? ty0 + SL_H - 1 : row_end - 1;
     // ---- phase 1: who owns each pixel ----
-    for (int e = 0; e < cnt; e++) {
-        const unsigned q = list[e];
+    for (int e = 0; e < t.cnt; e++) {
+        const unsigned q = t.list[e];
         const FrameDev& f = fr[q];                       // uniform over the workgroup: scalar loads
-        if (f.begX > tx1 || f.endX < tx0 || f.begY > ty1 || f.endY < ty0) continue;
+        if (f.begX > t.tx1 || f.endX < t.tx0 || f.begY > t.ty1 || f.endY < t.ty0) continue;
         const RampDev r = ramps[q];
         const float w1 = (float)(f.w - 1), h1 = (float)(f.h - 1);
 #pragma unroll
         for (int j = 0; j < SL_RPL; j++) {
-            const int yD = yB + 8 * j;
+            const int yD = t.yB + 8 * j;
             const bool yin = yD >= f.begY && yD <= f.endY;           // the box is clipped to the canvas and to the rows of this call
             const float yf = (float)yD - dGy;
 #pragma unroll
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(256) void seamline_tile_kernel(const FrameDev* fr, 
     if (xg >= cw) return;
 #pragma unroll
     for (int j = 0; j < SL_RPL; j++) {
-        const int yD = yB + 8 * j;
+        const int yD = t.yB + 8 * j;
         if (yD >= row_end) continue;
         // a pixel at or beyond cw lies in no frame's box: its key stays 0
         if (used) {
@@ -133,45 +127,25 @@ __global__ __launch_bounds__(256) void seamline_tile_kernel(const FrameDev* fr, 
 #pragma unroll
                 for (int c = 0; c < 3; c++) out[(3 * k + c) >> 2] |= v[c] << (8 * ((3 * k + c) & 3));      // static positions
             }
-            uint8_t* drow = canvas + (size_t)yD * cws + 3 * (size_t)xg;
-            if (xg + 3 < cw) {
-                uint32_t* d32 = reinterpret_cast<uint32_t*>(drow);
-                d32[0] = out[0]; d32[1] = out[1]; d32[2] = out[2];
-            } else {
-#pragma unroll
-                for (int b = 0; b < 9; b++)              // at most 3 pixels
-                    if (xg + b / 3 < cw) drow[b] = (uint8_t)(out[b >> 2] >> (8 * (b & 3)));
-            }
-            // row padding [3 cw, cws): zero, as in the unblended render
-            if (xg + 4 >= cw)
-                for (int b = 3 * cw; b < cws; b++) canvas[(size_t)yD * cws + b] = 0;
+            store_row12(canvas, cw, cws, xg, yD, out);
         }
     }
 }
 
 }  // namespace
 
-// cover_only != NULL: cover_only[k] = 1 for the frames that own at least one pixel of the rows; nothing is sampled or stored (d_imgs, ws and the
-// three outputs are not looked at)
+// cover_only != NULL (with the three outputs NULL): cover_only[k] = 1 for the frames that own at least one pixel of the rows; nothing is
+// sampled or stored, and cw, ch, cws are the layout's whatever the caller passes
 int mi_mosaic_seamline_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                            const mi355_seamline_params* params, uint8_t* d_canvas, int cw, int ch, int cws, uint16_t* d_owner, uint16_t* d_count,
                            int row0, int rows, uint8_t* cover_only) {
     mi355_seamline_params dp;
     if (!params) { mi355_default_seamline_params(&dp); params = &dp; }
     if (params->ramp < 0) { ctx->set_error("mosaic_seamline: ramp=" + std::to_string(params->ramp) + " < 0"); return MI355_ERR_ARG; }
-    int lw, lh, lws; float dG[2];
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, dG);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_seamline: no image with h[8] != 0 / empty canvas"); return rc; }
-    if (cover_only) { cw = lw; ch = lh; cws = lws; d_canvas = nullptr; d_owner = d_count = nullptr; }
-    if (lw != cw || lh != ch || (d_canvas && (cws < cw * 3 || (cws & 3)))) { ctx->set_error("mosaic_seamline: canvas geometry does not match mi355_mosaic_layout"); return MI355_ERR_ARG; }
-    if (row0 < 0) row0 = 0;
-    if (rows < 0 || row0 + rows > ch) rows = ch - row0;
-    if (rows <= 0) return MI355_OK;
-    if (n > 65535) { ctx->set_error("mosaic_seamline: at most 65535 images"); return MI355_ERR_ARG; }      // 16-bit lists, keys and maps (owner + 1 <= 65535)
-    std::vector<FrameDev> fr;
-    std::vector<RampDev> ramps;
-    std::vector<int> frame_of;                           // the caller's k of table entry q, ascending: (omega, q) orders as (omega, k)
-    fr.reserve(n); ramps.reserve(n); frame_of.reserve(n);
+    float dG[2]; bool go;
+    const int rc = mi_render_entry(ctx, "mosaic_seamline", w, h, n, h9s, cover_only != nullptr, d_canvas != nullptr, cw, ch, cws, row0, rows, dG, go);     // n <= 65535: 16-bit lists, keys and maps (owner + 1 <= 65535)
+    if (rc != MI355_OK || !go) return rc;
+    FrameTable t;                                        // frame_of ascending: (omega, q) orders as (omega, k)
     bool withheld = false;
     for (int k = 0; k < n; k++) {
         FrameDev f;
@@ -179,68 +153,42 @@ int mi_mosaic_seamline_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const i
         if (w[k] < 2 || h[k] < 2 || (d_canvas && ws[k] < 3 * w[k]) || w[k] > RAMP_MAX_SIDE || h[k] > RAMP_MAX_SIDE) { ctx->set_error("mosaic_seamline: bad image geometry"); return MI355_ERR_ARG; }
         f.src = d_canvas ? d_imgs[k] : nullptr; f.w = w[k]; f.h = h[k]; f.ws = d_canvas ? ws[k] : 0;
         if (d_canvas && !f.src) withheld = true;         // fine as long as the frame owns no pixel of the rows: checked below, before any sample
-        fr.push_back(f);
-        ramps.push_back(ramp_of_frame(w[k], h[k], params->ramp));
-        frame_of.push_back(k);
+        t.add(f, k);
+        t.ramps.push_back(ramp_of_frame(w[k], h[k], params->ramp));
     }
-    const int nf = (int)fr.size();
-    if (cover_only && nf == 0) return MI355_OK;
-    const int bx_n = (cw + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK, by_n = (rows + MOSAIC_LIST_BLOCK - 1) / MOSAIC_LIST_BLOCK;
-    const size_t nf1 = (size_t)(nf > 0 ? nf : 1);
-    DevBuf& dfr = ctx->buf("mosaic_frames");
-    DevBuf& dl = ctx->buf("mosaic_lists");
-    DevBuf& dc = ctx->buf("mosaic_counts");
-    DevBuf& dr = ctx->buf("feather_ramps");
-    DevBuf& dk = ctx->buf("seamline_frame_of");
-    MI_HIP(dfr.reserve(sizeof(FrameDev) * nf1));
-    MI_HIP(dr.reserve(sizeof(RampDev) * nf1));
-    MI_HIP(dk.reserve(sizeof(int) * nf1));
-    MI_HIP(dl.reserve(sizeof(uint16_t) * (size_t)bx_n * by_n * nf1));
-    MI_HIP(dc.reserve(sizeof(int) * (size_t)bx_n * by_n));
-    if (nf > 0) {
-        MI_HIP(hipMemcpyAsync(dfr.p, fr.data(), sizeof(FrameDev) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-        MI_HIP(hipMemcpyAsync(dr.p, ramps.data(), sizeof(RampDev) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-        MI_HIP(hipMemcpyAsync(dk.p, frame_of.data(), sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    }
-    mi_mosaic_lists_launch(ctx, dfr.as<FrameDev>(), nf, bx_n, by_n, row0, dl.as<uint16_t>(), dc.as<int>());
+    if (cover_only && t.fr.empty()) return MI355_OK;
+    const int rc2 = mi_frame_table_upload(ctx, t, true, true, cw, rows, row0);
+    if (rc2 != MI355_OK) return rc2;
     const dim3 grid((cw + SL_W - 1) / SL_W, (rows + SL_H - 1) / SL_H);
+    auto launch = [&](auto kernel, uint8_t* canvas, uint16_t* owner, uint16_t* count, int* used) {
+        ProfScope ps(ctx, "seamline", 0.0);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, t.d_fr, t.d_ramps, t.d_frame_of, t.nf, t.d_lists, t.d_counts, t.bx_n, canvas, owner,
+                           count, used, cw, cws, row0, row0 + rows, dG[0], dG[1]);
+    };
     if (cover_only || withheld) {
         // the ownership walk alone, one flag per table entry: the cover call's answer, and what tells a withheld frame that owns nothing
         // (left out by the caller with reason) from one the render would dereference.  Paid only when a pointer is missing.
-        DevBuf& du = ctx->buf("mosaic_used");
-        MI_HIP(du.reserve(sizeof(int) * nf1));
-        MI_HIP(hipMemsetAsync(du.p, 0, sizeof(int) * nf1, ctx->stream));
-        {
-            ProfScope ps(ctx, "seamline", 0.0);
-            hipLaunchKernelGGL(seamline_tile_kernel<false>, grid, dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), dr.as<RampDev>(), dk.as<int>(), nf,
-                               dl.as<uint16_t>(), dc.as<int>(), bx_n, (uint8_t*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, du.as<int>(), cw, cws,
-                               row0, row0 + rows, dG[0], dG[1]);
-        }
-        MI_HIP(hipGetLastError());
-        std::vector<int> used(nf1, 0);
-        MI_HIP(hipMemcpyAsync(used.data(), du.p, sizeof(int) * nf1, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        if (cover_only) {
-            for (int q = 0; q < nf; q++) if (used[q]) cover_only[frame_of[q]] = 1;
-            return MI355_OK;
-        }
-        for (int q = 0; q < nf; q++)
-            if (used[q] && !fr[q].src) {
-                ctx->set_error("mosaic_seamline: image " + std::to_string(frame_of[q]) + " owns pixels of these canvas rows but no pointer to it was given");
+        std::vector<int> used;
+        int* d_used;
+        int rc3 = mi_frame_table_used_begin(ctx, t, &d_used);
+        if (rc3 != MI355_OK) return rc3;
+        launch(seamline_tile_kernel<false>, nullptr, nullptr, nullptr, d_used);
+        rc3 = mi_frame_table_used_end(ctx, t, used);
+        if (rc3 != MI355_OK) return rc3;
+        for (int q = 0; q < t.nf; q++) {
+            if (!used[q]) continue;
+            if (cover_only) cover_only[t.frame_of[q]] = 1;
+            else if (!t.fr[q].src) {
+                ctx->set_error("mosaic_seamline: image " + std::to_string(t.frame_of[q]) + " owns pixels of these canvas rows but no pointer to it was given");
                 return MI355_ERR_ARG;
             }
+        }
+        if (cover_only) return MI355_OK;
     }
-    {
-        ProfScope ps(ctx, "seamline", 0.0);
-        if (d_canvas)
-            hipLaunchKernelGGL(seamline_tile_kernel<true>, grid, dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), dr.as<RampDev>(), dk.as<int>(), nf,
-                               dl.as<uint16_t>(), dc.as<int>(), bx_n, d_canvas, d_owner, d_count, (int*)nullptr, cw, cws, row0, row0 + rows, dG[0], dG[1]);
-        else
-            hipLaunchKernelGGL(seamline_tile_kernel<false>, grid, dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), dr.as<RampDev>(), dk.as<int>(), nf,
-                               dl.as<uint16_t>(), dc.as<int>(), bx_n, (uint8_t*)nullptr, d_owner, d_count, (int*)nullptr, cw, cws, row0, row0 + rows, dG[0], dG[1]);
-    }
+    if (d_canvas) launch(seamline_tile_kernel<true>, d_canvas, d_owner, d_count, nullptr);
+    else launch(seamline_tile_kernel<false>, nullptr, d_owner, d_count, nullptr);
     MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // `fr`, `ramps` and `frame_of` go out of scope
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // the table goes out of scope
     return MI355_OK;
 }
 
@@ -267,41 +215,20 @@ extern "C" int mi355_mosaic_seamline_cover(mi355_ctx* ctx, const int* w, const i
     return mi_mosaic_seamline_dev(ctx, nullptr, w, h, nullptr, n, h9s, params, nullptr, 0, 0, 0, nullptr, nullptr, row0, rows, need);
 }
 
-// the host form: mi355_mosaic_refined's staging, the seamline render in its place; the owner map comes back when asked for
+// the host form (mi_render_host_begin / _end, frames.hip); the owner map comes back when asked for
 extern "C" int mi355_mosaic_seamline(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                      const mi355_seamline_params* params, uint8_t** canvas, int* cw, int* ch, int* cws, uint16_t** owner) {
     LOCKED_PROLOGUE
     if (!imgs || !w || !h || !ws || !h9s || !canvas || !cw || !ch || !cws) return MI355_ERR_ARG;
-    if (n <= 1) { ctx->set_error("mosaic_seamline: needs more than one image"); return MI355_ERR_FAILED; }
     int lw, lh, lws;
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, nullptr);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_seamline: empty canvas"); return rc; }
-    size_t total = 0;
-    std::vector<size_t> off(n, 0);
-    for (int k = 0; k < n; k++) { if (h9s[9 * k + 8] == 0.0f) continue; if (!imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) return MI355_ERR_ARG; off[k] = total; total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255; }
-    const size_t cbytes = (size_t)lws * lh, obytes = owner ? sizeof(uint16_t) * (size_t)lw * lh : 0;
-    DevBuf& dall = ctx->buf("mosaic_srcs");
-    DevBuf& dcan = ctx->buf("mosaic_canvas");
-    DevBuf& down = ctx->buf("seamline_owner");
-    MI_HIP(dall.reserve(total + 16));
-    MI_HIP(dcan.reserve(cbytes));
-    if (owner) MI_HIP(down.reserve(obytes));
-    std::vector<const uint8_t*> dptr(n, nullptr);
-    for (int k = 0; k < n; k++) {
-        if (h9s[9 * k + 8] == 0.0f) continue;
-        dptr[k] = dall.as<uint8_t>() + off[k];
-        MI_HIP(hipMemcpyAsync((void*)dptr[k], imgs[k], (size_t)ws[k] * h[k], hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = mi_mosaic_seamline_dev(ctx, dptr.data(), w, h, ws, n, h9s, params, dcan.as<uint8_t>(), lw, lh, lws, owner ? down.as<uint16_t>() : nullptr, nullptr, 0, lh, nullptr);
+    std::vector<const uint8_t*> d_imgs;
+    uint8_t* d_canvas;
+    int rc = mi_render_host_begin(ctx, "mosaic_seamline", imgs, w, h, ws, n, h9s, &lw, &lh, &lws, d_imgs, &d_canvas);
     if (rc != MI355_OK) return rc;
-    uint8_t* out = (uint8_t*)malloc(cbytes);
-    uint16_t* own = owner ? (uint16_t*)malloc(obytes) : nullptr;
-    if (!out || (owner && !own)) { free(out); free(own); return MI355_ERR_NOMEM; }
-    hipError_t e = hipMemcpyAsync(out, dcan.p, cbytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && owner) e = hipMemcpyAsync(own, down.p, obytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(out); free(own); ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
-    *canvas = out; *cw = lw; *ch = lh; *cws = lws;
-    if (owner) *owner = own;
-    return MI355_OK;
+    DevBuf& down = ctx->buf("seamline_owner");
+    const size_t obytes = sizeof(uint16_t) * (size_t)lw * lh;
+    if (owner) MI_HIP(down.reserve(obytes));
+    rc = mi_mosaic_seamline_dev(ctx, d_imgs.data(), w, h, ws, n, h9s, params, d_canvas, lw, lh, lws, owner ? down.as<uint16_t>() : nullptr, nullptr, 0, lh, nullptr);
+    if (rc != MI355_OK) return rc;
+    return mi_render_host_end(ctx, lw, lh, lws, canvas, cw, ch, cws, down.p, obytes, (void**)owner);
 }

@@ -194,7 +194,7 @@ extern "C" int mi355_mosaic_layout(const int* w, const int* h, int n, const floa
 // 2 x 2 neighbourhoods and one write per canvas pixel instead of one read + one write per covering image (3.1 covering images per
 // pixel in the C3 survey, ~60 at C5) and no clearing pass (pixels nobody covers are stored as zeros).  All images go through
 // one launch; the result does not depend on any execution order.
-// (FrameDev, the map and the sample: mosaic_frame.h)
+// (FrameDev, the map and the sample, and the host path this render shares with feather.hip / seamline.hip: mosaic_frame.h)
 #ifndef MT_RPL_V
 #define MT_RPL_V 2
 #endif
@@ -333,26 +333,78 @@ int mi_frame_dev_setup(const float* m, int w, int h, const float dG[2], int cw, 
     return 1;
 }
 
+int mi_render_entry(mi355_ctx* ctx, const char* who, const int* w, const int* h, int n, const float* h9s, bool cover, bool want_canvas,
+                    int& cw, int& ch, int& cws, int& row0, int& rows, float dG[2], bool& go) {
+    go = false;
+    int lw, lh, lws;
+    const int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, dG);
+    if (rc != MI355_OK) { ctx->set_error(std::string(who) + ": no image with h[8] != 0 / empty canvas"); return rc; }
+    if (cover) { cw = lw; ch = lh; cws = lws; }
+    else if (lw != cw || lh != ch || (want_canvas && (cws < cw * 3 || (cws & 3)))) { ctx->set_error(std::string(who) + ": canvas geometry does not match mi355_mosaic_layout"); return MI355_ERR_ARG; }
+    if (row0 < 0) row0 = 0;
+    if (rows < 0 || row0 + rows > ch) rows = ch - row0;
+    if (rows <= 0) return MI355_OK;
+    if (n > 65535) { ctx->set_error(std::string(who) + ": at most 65535 images"); return MI355_ERR_ARG; }      // 16-bit candidate lists
+    go = true;
+    return MI355_OK;
+}
+
+static_assert(MT_COARSE == MOSAIC_LIST_BLOCK, "mosaic_frame.h states the list block size");
+int mi_frame_table_upload(mi355_ctx* ctx, FrameTable& t, bool with_ramps, bool with_frame_of, int cw, int rows, int row0) {
+    t.nf = (int)t.fr.size();
+    t.bx_n = (cw + MT_COARSE - 1) / MT_COARSE;
+    const int by_n = (rows + MT_COARSE - 1) / MT_COARSE;
+    const size_t nf = (size_t)t.nf, nf1 = nf > 0 ? nf : 1, blocks = (size_t)t.bx_n * by_n;
+    auto put = [&](DevBuf& b, const void* src, size_t elem) -> int {
+        MI_HIP(b.reserve(elem * nf1));
+        if (nf > 0) MI_HIP(hipMemcpyAsync(b.p, src, elem * nf, hipMemcpyHostToDevice, ctx->stream));
+        return MI355_OK;
+    };
+    DevBuf& dfr = ctx->buf("mosaic_frames");
+    int rc = put(dfr, t.fr.data(), sizeof(FrameDev));
+    t.d_fr = dfr.as<FrameDev>();
+    if (rc == MI355_OK && with_ramps) { DevBuf& b = ctx->buf("feather_ramps"); rc = put(b, t.ramps.data(), sizeof(RampDev)); t.d_ramps = b.as<RampDev>(); }
+    if (rc == MI355_OK && with_frame_of) { DevBuf& b = ctx->buf("seamline_frame_of"); rc = put(b, t.frame_of.data(), sizeof(int)); t.d_frame_of = b.as<int>(); }
+    if (rc != MI355_OK) return rc;
+    DevBuf& dl = ctx->buf("mosaic_lists");
+    DevBuf& dc = ctx->buf("mosaic_counts");
+    MI_HIP(dl.reserve(sizeof(uint16_t) * blocks * nf1));
+    MI_HIP(dc.reserve(sizeof(int) * blocks));
+    t.d_lists = dl.as<uint16_t>(); t.d_counts = dc.as<int>();
+    hipLaunchKernelGGL(mosaic_lists_kernel, dim3((t.bx_n * by_n + 255) / 256), dim3(256), 0, ctx->stream, t.d_fr, t.nf, t.bx_n, by_n, row0, dl.as<uint16_t>(), dc.as<int>());
+    return MI355_OK;
+}
+
+int mi_frame_table_used_begin(mi355_ctx* ctx, const FrameTable& t, int** d_used) {
+    const size_t bytes = sizeof(int) * (size_t)(t.nf > 0 ? t.nf : 1);
+    DevBuf& du = ctx->buf("mosaic_used");
+    MI_HIP(du.reserve(bytes));
+    MI_HIP(hipMemsetAsync(du.p, 0, bytes, ctx->stream));
+    *d_used = du.as<int>();
+    return MI355_OK;
+}
+
+int mi_frame_table_used_end(mi355_ctx* ctx, const FrameTable& t, std::vector<int>& used) {
+    MI_HIP(hipGetLastError());
+    used.assign((size_t)(t.nf > 0 ? t.nf : 1), 0);
+    MI_HIP(hipMemcpyAsync(used.data(), ctx->buf("mosaic_used").p, sizeof(int) * used.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    return MI355_OK;
+}
+
 // cover_only != NULL: cover_only[k] = 1 for the frames this call would read (the stripe's cover list, mi355_mosaic_stripe_cover), nothing is
 // rendered.  cover_exact == 0: every frame whose clipped canvas box meets the rows (host geometry alone: a superset); != 0: the frames that
 // give at least one pixel its sample -- the tile kernel's walk without its loads (what the rendering pass really dereferences).
 int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n,
                           const float* h9s, uint8_t* d_canvas, int cw, int ch, int cws, int row0, int rows, uint8_t* cover_only, int cover_exact) {
-    int lw, lh, lws; float dG[2];
-    int rc = mi355_mosaic_layout(w, h, n, h9s, &lw, &lh, &lws, dG);
-    if (rc != MI355_OK) { ctx->set_error("mosaic_refined: no image with h[8] != 0 / empty canvas"); return rc; }
-    if (lw != cw || lh != ch || cws < cw * 3 || (cws & 3)) { ctx->set_error("mosaic_refined: canvas geometry does not match mi355_mosaic_layout"); return MI355_ERR_ARG; }
-    if (row0 < 0) row0 = 0;
-    if (rows < 0 || row0 + rows > ch) rows = ch - row0;
-    if (rows <= 0) return MI355_OK;
-    if (n > 65535) { ctx->set_error("mosaic_refined: at most 65535 images"); return MI355_ERR_ARG; }
-    std::vector<FrameDev> fr;
-    std::vector<int> frame_of, withheld;           // image index of fr[q]; images whose box meets the rows and that came without a pointer
-    fr.reserve(n);
+    float dG[2]; bool go;
+    const int rc = mi_render_entry(ctx, "mosaic_refined", w, h, n, h9s, false, true, cw, ch, cws, row0, rows, dG, go);
+    if (rc != MI355_OK || !go) return rc;
+    FrameTable t;
+    std::vector<int> withheld;                     // images whose box meets the rows and that came without a pointer
     for (int k = 0; k < n; k++) {                  // ascending image order = overwrite order (MosaicWithoutPos.cpp:2254)
-        const float* m = h9s + 9 * k;
         FrameDev f;
-        if (!mi_frame_dev_setup(m, w[k], h[k], dG, cw, ch, row0, rows, f)) continue;
+        if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], dG, cw, ch, row0, rows, f)) continue;
         if (cover_only && !cover_exact) { cover_only[k] = 1; continue; }
         if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) { ctx->set_error("mosaic_refined: bad image geometry"); return MI355_ERR_ARG; }
         // d_imgs[k] == NULL: the caller holds no copy of this image (owner-only frames, mi355_exchange_frames): it says the rows do not read
@@ -360,8 +412,7 @@ int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
         // IS read).  Such a frame is left out of the walk; with option "strict_frames" the statement is checked first (one cover pass).
         if (!cover_only && !d_imgs[k]) { withheld.push_back(k); continue; }
         f.src = cover_only ? nullptr : d_imgs[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k];
-        frame_of.push_back(k);
-        fr.push_back(f);
+        t.add(f, k);
     }
     if (cover_only && !cover_exact) return MI355_OK;
     if (!withheld.empty() && ctx->strict_frames) {       // the caller's statement "these rows do not read the images I withhold", checked: one cover pass
@@ -370,47 +421,33 @@ int mi_mosaic_refined_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
         if (rc2 != MI355_OK) return rc2;
         for (int k : withheld) if (read[k]) { ctx->set_error("mosaic_refined: these canvas rows read image " + std::to_string(k) + " but no pointer to it was given"); return MI355_ERR_ARG; }
     }
-    const int nf = (int)fr.size();
-    if (cover_only && nf == 0) return MI355_OK;
-    const int bx_n = (cw + MT_COARSE - 1) / MT_COARSE, by_n = (rows + MT_COARSE - 1) / MT_COARSE;
-    DevBuf& dfr = ctx->buf("mosaic_frames");
-    DevBuf& dl = ctx->buf("mosaic_lists");
-    DevBuf& dc = ctx->buf("mosaic_counts");
-    MI_HIP(dfr.reserve(sizeof(FrameDev) * (size_t)(nf > 0 ? nf : 1)));
-    MI_HIP(dl.reserve(sizeof(uint16_t) * (size_t)bx_n * by_n * (size_t)(nf > 0 ? nf : 1)));
-    MI_HIP(dc.reserve(sizeof(int) * (size_t)bx_n * by_n));
-    if (nf > 0) MI_HIP(hipMemcpyAsync(dfr.p, fr.data(), sizeof(FrameDev) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(mosaic_lists_kernel, dim3((bx_n * by_n + 255) / 256), dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), nf, bx_n, by_n, row0, dl.as<uint16_t>(), dc.as<int>());
+    if (cover_only && t.fr.empty()) return MI355_OK;
+    const int rc3 = mi_frame_table_upload(ctx, t, false, false, cw, rows, row0);
+    if (rc3 != MI355_OK) return rc3;
+    const dim3 grid((cw + MT_W - 1) / MT_W, (rows + MT_H - 1) / MT_H);
     if (cover_only) {
-        DevBuf& du = ctx->buf("mosaic_used");
-        MI_HIP(du.reserve(sizeof(int) * (size_t)nf));
-        MI_HIP(hipMemsetAsync(du.p, 0, sizeof(int) * (size_t)nf, ctx->stream));
-        hipLaunchKernelGGL(mosaic_tile_kernel<true>, dim3((cw + MT_W - 1) / MT_W, (rows + MT_H - 1) / MT_H), dim3(256), 0, ctx->stream,
-                           dfr.as<FrameDev>(), nf, dl.as<uint16_t>(), dc.as<int>(), bx_n, (uint8_t*)nullptr, cw, cws, row0, row0 + rows, dG[0], dG[1], du.as<int>());
-        MI_HIP(hipGetLastError());
-        std::vector<int> used((size_t)nf);
-        MI_HIP(hipMemcpyAsync(used.data(), du.p, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        for (int q = 0; q < nf; q++) if (used[q]) cover_only[frame_of[q]] = 1;
+        std::vector<int> used;
+        int* d_used;
+        int rc4 = mi_frame_table_used_begin(ctx, t, &d_used);
+        if (rc4 != MI355_OK) return rc4;
+        hipLaunchKernelGGL(mosaic_tile_kernel<true>, grid, dim3(256), 0, ctx->stream, t.d_fr, t.nf, t.d_lists, t.d_counts, t.bx_n, (uint8_t*)nullptr, cw, cws, row0,
+                           row0 + rows, dG[0], dG[1], d_used);
+        rc4 = mi_frame_table_used_end(ctx, t, used);
+        if (rc4 != MI355_OK) return rc4;
+        for (int q = 0; q < t.nf; q++) if (used[q]) cover_only[t.frame_of[q]] = 1;
         return MI355_OK;
     }
     {
         // SURVEY 8(d) algorithmic figure: every image read once and written once (6 P per image)
         double bytes = 0.0;
-        for (const FrameDev& f : fr) bytes += 6.0 * (double)f.w * f.h;
+        for (const FrameDev& f : t.fr) bytes += 6.0 * (double)f.w * f.h;
         ProfScope ps(ctx, "warp", bytes);
-        hipLaunchKernelGGL(mosaic_tile_kernel<false>, dim3((cw + MT_W - 1) / MT_W, (rows + MT_H - 1) / MT_H), dim3(256), 0, ctx->stream,
-                           dfr.as<FrameDev>(), nf, dl.as<uint16_t>(), dc.as<int>(), bx_n, d_canvas, cw, cws, row0, row0 + rows, dG[0], dG[1], (int*)nullptr);
+        hipLaunchKernelGGL(mosaic_tile_kernel<false>, grid, dim3(256), 0, ctx->stream, t.d_fr, t.nf, t.d_lists, t.d_counts, t.bx_n, d_canvas, cw, cws, row0,
+                           row0 + rows, dG[0], dG[1], (int*)nullptr);
     }
     MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // `fr` goes out of scope
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // the table goes out of scope
     return MI355_OK;
-}
-
-// the candidate lists for a render that lives in another file (feather.hip): the launch above, nothing else
-static_assert(MT_COARSE == MOSAIC_LIST_BLOCK, "mosaic_frame.h states the list block size");
-void mi_mosaic_lists_launch(mi355_ctx* ctx, const FrameDev* d_fr, int nf, int bx_n, int by_n, int row0, uint16_t* d_lists, int* d_counts) {
-    hipLaunchKernelGGL(mosaic_lists_kernel, dim3((bx_n * by_n + 255) / 256), dim3(256), 0, ctx->stream, d_fr, nf, bx_n, by_n, row0, d_lists, d_counts);
 }
 
 int mi_warp_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, int ch, const float* h9,

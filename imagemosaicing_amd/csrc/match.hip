@@ -649,6 +649,16 @@ int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float 
     if (n_pairs <= 0) return MI355_OK;
     if (!pairs || !d_out) return MI355_ERR_ARG;
     if (ctx->p.grid_x * ctx->p.grid_y > 64 || ctx->p.grid_x < 1 || ctx->p.grid_y < 1 || ctx->p.max_selected > MI355_MAX_SELECTED) { ctx->set_error("match_pairs: grid > 64 cells or max_selected > 400"); return MI355_ERR_ARG; }
+    // an image i narrower than the grid gives stepX = 0 and the cell (int)(x / 0.0f), which host and device convert differently: refused like
+    // select_grid's width < gx, before anything is launched (a frame still in flight has its size already; an unknown id is build_pair_table's to report)
+    for (int p = 0; p < n_pairs; p++) {
+        const auto fi = ctx->feats.find(pairs[2 * p]);
+        if (fi != ctx->feats.end() && (fi->second.w < ctx->p.grid_x || fi->second.h < ctx->p.grid_y)) {
+            ctx->set_error("match_pairs: bad arguments (image " + std::to_string(pairs[2 * p]) + " is " + std::to_string(fi->second.w) + "x" + std::to_string(fi->second.h) +
+                           ", smaller than the " + std::to_string(ctx->p.grid_x) + "x" + std::to_string(ctx->p.grid_y) + " grid)");
+            return MI355_ERR_ARG;
+        }
+    }
     const int BATCH = 32768;                                  // bounds the nn workspaces (32768 x 2048 x 12 B = 768 MiB of the 288 GB); every batch boundary drains the stream
     std::vector<PairDesc> pd;
     { const int rc = mi_ransac_tables(ctx, seed, nullptr); if (rc != MI355_OK) return rc; }      // a new seed's draw tables are built beside the matcher

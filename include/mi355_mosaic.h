@@ -52,7 +52,10 @@ typedef struct { int32_t queryIdx, trainIdx, imgIdx; float distance; } mi355_dma
 typedef struct { float m[9]; int32_t fixed; } mi355_image_transform;
 
 /* Result of one image pair (i,j): what GetMatchedPairsOneToAllSIFTThread appends (MosaicWithoutPos.cpp:5201-5221)
- * plus the homography Ransac2D returned.  Fixed size (9664 B) so that ranks can all-gather arrays of it. */
+ * plus the homography Ransac2D returned.  Fixed size (9664 B) so that ranks can all-gather arrays of it.
+ * A pair that is not accepted (n_in <= min_inliers) still carries its real n_in and the inliers of the winning hypothesis in a[0 .. n_in) and
+ * b[0 .. n_in); match_pairs skips Ransac2D's closing refinement for it, so its H is all zero and its ok is 0.  The list entries from n_in on
+ * are zero in every record. */
 typedef struct {
     int32_t i, j;            /* image indices (ptA_i, ptB_i) */
     int32_t n_in;            /* inlier count; the reference accepts the pair iff n_in > min_inliers (30) */

@@ -17,6 +17,7 @@ import imagemosaicing_amd as im  # noqa: E402
 from tests import oracle_lib as ol  # noqa: E402
 from tests import test_oracle_vs_ref as t_vs  # noqa: E402
 from tests import test_overlap as t_ov  # noqa: E402
+from tests import test_match_patterns_oracle as t_mp  # noqa: E402
 from tests import test_warp_patterns_oracle as t_wp  # noqa: E402
 
 
@@ -26,6 +27,7 @@ def run_all(orc, ref):
     t_ov.test_resample_by_overlap_vs_reference(im, ref)
     t_ov.test_oracle_chips_and_masks_vs_reference(orc, ref)
     t_wp.check_all_vs_reference(orc, ref)          # the warp stage's edge cases (tests/warp_patterns.py) where the reference's code is defined
+    t_mp.check_select_vs_reference(orc, ref)       # the grid walk on cell-edge and cell-filling patterns (tests/match_patterns.py), inside the label array
 
 
 def main():

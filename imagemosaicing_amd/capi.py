@@ -45,6 +45,11 @@ class GainParams(C.Structure):
     _fields_ = [("sigma_n", C.c_float), ("sigma_g", C.c_float), ("channels", C.c_int32), ("step", C.c_int32)]
 
 
+class BlockGainParams(C.Structure):
+    _fields_ = [("sigma_n", C.c_float), ("sigma_g", C.c_float), ("channels", C.c_int32), ("step", C.c_int32), ("grid_x", C.c_int32),
+                ("grid_y", C.c_int32), ("smooth", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FeatherParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -63,6 +68,10 @@ NODATA_NONE, NODATA_ZERO, NODATA_MAP = 0, 1, 2
 # mi355_gain_pair_stats: the overlap statistics of one listed pair (positions a, b in the frame list)
 GAIN_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)), ("sum_b", "<i8", (3,))])
 assert GAIN_PAIR_STATS.itemsize == 64
+# mi355_block_gain_stats: the statistics of one (cell_a, cell_b) of listed pair `pair` (an index into the pair list)
+BLOCK_GAIN_STATS = np.dtype([("pair", "<i4"), ("cell_a", "<i4"), ("cell_b", "<i4"), ("reserved", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)),
+                             ("sum_b", "<i8", (3,))])
+assert BLOCK_GAIN_STATS.itemsize == 72 and C.sizeof(BlockGainParams) == 32
 
 
 class Mi355Error(RuntimeError):
@@ -628,6 +637,46 @@ class Context:
         self._chk(self.L.mi355_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
         return g
 
+    # ---- block gain compensation (mi355_block_gain_*, csrc/gain.hip) -------------------------------------------------------
+    def BlockGainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, grid_x=8, grid_y=6):
+        """per-cell overlap statistics of the listed pairs: (BLOCK_GAIN_STATS records sorted by (pair, cell_a, cell_b), cell cover int64
+        [n, grid_y * grid_x])"""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        cover = np.zeros((n, max(int(grid_x) * int(grid_y), 0)), np.int64)
+        recs, nrec = C.c_void_p(), C.c_int64(0)
+        self._chk(self.L.mi355_block_gain_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), int(grid_x), int(grid_y),
+                                                    C.byref(recs), C.byref(nrec), _p(cover)))
+        st = np.zeros(nrec.value, BLOCK_GAIN_STATS)
+        if nrec.value:
+            C.memmove(st.ctypes.data, recs, st.nbytes)
+        self.L.mi355_free(recs)
+        return st, cover
+
+    def ApplyBlockGainsDev(self, d_src, d_dst, w, h, ws, gains):
+        """d_dst[k] = d_src[k] times its interpolated gain map (d_dst[k] may be d_src[k]); gains [n, grid_y, grid_x, 3] float32.  Complete
+        on return."""
+        n, sp, w, h, ws = self._frame_args(d_src, w, h, ws)
+        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        g = np.ascontiguousarray(gains, np.float32)
+        if g.ndim != 4 or g.shape[0] != n or g.shape[3] != 3:
+            raise ValueError("gains must be [n, grid_y, grid_x, 3]")
+        self._chk(self.L.mi355_apply_block_gains_dev(self._h, sp, dp, _p(w), _p(h), _p(ws), n, int(g.shape[2]), int(g.shape[1]), _p(g)))
+
+    def BlockGainCompensateDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
+        """statistics, solve, smoothing and in-place apply on the device frames; returns the gain maps [n, grid_y, grid_x, 3] float32.
+        params: BlockGainParams (block_gain_params()) or keyword fields of it."""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else block_gain_params(**kw)
+        g = np.zeros((n, max(p.grid_y, 0), max(p.grid_x, 0), 3), np.float32)
+        if g.size > (1 << 28):
+            g = np.zeros((n, 1, 1, 3), np.float32)                # a grid the library refuses
+        self._chk(self.L.mi355_block_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
+        return g
+
     # ---- weighted (feather) blending (mi355_mosaic_feathered*, csrc/feather.hip) -------------------------------------------
     def MosaicFeathered(self, imgs, h9s, params=None, want_pixels=True, **kw):
         """mi355_mosaic_feathered: host images in, (canvas rows x cws, cw, ch, cws) out.  params: FeatherParams (feather_params()) or its
@@ -928,6 +977,19 @@ def gain_params(sigma_n=None, sigma_g=None, channels=None, step=None):
     return p
 
 
+def block_gain_params(sigma_n=None, sigma_g=None, channels=None, step=None, grid_x=None, grid_y=None, smooth=None):
+    """mi355_block_gain_params: the library's defaults (mi355_default_block_gain_params: 10, 0.1, 3, 8, 8 x 6, 2) with the given fields replaced"""
+    p = BlockGainParams()
+    load_library().mi355_default_block_gain_params(C.byref(p))
+    for name, v in (("sigma_n", sigma_n), ("sigma_g", sigma_g)):
+        if v is not None:
+            setattr(p, name, float(v))
+    for name, v in (("channels", channels), ("step", step), ("grid_x", grid_x), ("grid_y", grid_y), ("smooth", smooth)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
 def feather_params(ramp=None):
     """mi355_feather_params: the library's defaults (mi355_default_feather_params: ramp 0 = a full tent per frame) with the given fields replaced"""
     p = FeatherParams()
@@ -976,6 +1038,26 @@ def solve_gains(pair_stats, frame_cover, params=None, **kw):
     p = params if params is not None else gain_params(**kw)
     g = np.zeros((max(n, 0), 3), np.float32)
     rc = L.mi355_solve_gains(_p(st), len(st), _p(cover), n, C.byref(p), _p(g))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return g
+
+
+def solve_block_gains(records, pairs, cell_cover, params=None, **kw):
+    """mi355_solve_block_gains (host only): smoothed gain maps [n, grid_y, grid_x, 3] float32 from BLOCK_GAIN_STATS records, the pair list
+    they index and the cell cover [n, grid_y * grid_x]"""
+    L = load_library()
+    st = np.ascontiguousarray(records, BLOCK_GAIN_STATS)
+    ab = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    cover = np.ascontiguousarray(cell_cover, np.int64)
+    n = len(cover)
+    p = params if params is not None else block_gain_params(**kw)
+    gx, gy = p.grid_x, p.grid_y
+    ok = 1 <= gx <= 16 and 1 <= gy <= 16
+    if ok and cover.size != n * gx * gy:
+        raise ValueError("cell_cover must hold n x grid_y * grid_x values")
+    g = np.zeros((n, gy, gx, 3) if ok else (n, 1, 1, 3), np.float32)
+    rc = L.mi355_solve_block_gains(_p(st), C.c_int64(len(st)), _p(ab), len(ab), _p(cover), n, C.byref(p), _p(g))
     if rc < 0:
         raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
     return g

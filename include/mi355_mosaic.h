@@ -715,6 +715,82 @@ int  mi355_apply_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t*
 int  mi355_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                const int32_t* pairs_ab, int n_pairs, const mi355_gain_params* p, float* gains_out);
 
+/* ---- block gain compensation (opt-in; csrc/gain.hip) -----------------------------------------------------------------------------
+ * A gain MAP per frame and channel on a grid of grid_x x grid_y cells over the frame's own pixels, for what one gain per frame cannot
+ * remove: vignetting and uneven light (OpenCV detail::BlocksGainCompensator's place).  Solved from the overlaps like the per-frame gains,
+ * smoothed, and applied to the texels with bilinear interpolation between cell centres.  Everything the section above says about frames,
+ * taking part, canvas, lattice, cover and sample holds unchanged.
+ *
+ * Grid: 1 <= grid_x, grid_y <= 16; a taking-part frame needs grid_x <= w and grid_y <= h (and w, h <= 2^20).  cells = grid_x * grid_y, the
+ *   cell index is cy * grid_x + cx.
+ * Cell of a sample: frame k's sample at a lattice point has the source coordinate (xs, ys) the render maps it to; xi = (int)xs,
+ *   yi = (int)ys, cx = (xi * grid_x) / w, cy = (yi * grid_y) / h by integer division.
+ * Statistics (integers: exact, independent of tile shape, walk order and launch geometry):
+ *   cell_cover[k][cell] = the lattice points frame k covers whose sample falls in that cell;
+ *   per listed pair (a, b) and per (cell_a, cell_b) with at least one common lattice point: n, sum_a[3], sum_b[3] as in
+ *   mi355_gain_pair_stats, in records sorted by (pair, cell_a, cell_b); only records with n > 0 exist.  pair is the index into pairs_ab.
+ *   Summing a pair's records gives mi355_gain_stats_dev's record of that pair at the same step, field for field; summing cell_cover[k]
+ *   over the cells gives frame_cover[k].
+ * Solve (host, no ctx): the unknowns are the nodes (k, cell), n * cells of them; the equations are those of the section above with every
+ *   record a pair between node (a, cell_a) and node (b, cell_b) and N_node = cell_cover; same alpha, beta and channels.  A node without an
+ *   equation gets exactly 1.  Within 1e-9 relative (infinity norm) of the exact solution, single-threaded double arithmetic in a fixed
+ *   order: the same bits on every call, thread count and context.  (The factorisation of mi355_solve_gains where its envelope is small --
+ *   grid 1 x 1 then gives mi355_solve_gains' values --, a diagonally preconditioned conjugate gradient with a proven error bound where it
+ *   is not; a system on which that bound cannot be met in double, a weak prior on a very large graph, is MI355_ERR_FAILED.)
+ * Smoothing: after the solve, per frame and channel on the grid_y x grid_x map in double: `smooth` passes (0..8) of the separable
+ *   [1/4, 1/2, 1/4] filter, x then y, edges replicated.  The smoothed maps cast to float are gains[n][grid_y][grid_x][3].
+ * Apply (integers only): q[cy][cx] = clamp((int)floor((double)g * 4096 + 0.5), 0, 32767) per channel (Q12: gains lie in [0, 8)).  For
+ *   column x of a frame of width w: num = (2x + 1) grid_x - w clamped to [0, 2w (grid_x - 1)], i0 = num / (2w), rem = num % (2w),
+ *   fx = (rem * 256) / (2w), i1 = min(i0 + 1, grid_x - 1); row y gives j0, j1, fy likewise from h and grid_y.  Then in uint32_t:
+ *     R_i = (256 - fy) q[j0][i] + fy q[j1][i]  (i = i0, i1),   G = (256 - fx) R_i0 + fx R_i1  (Q28, below 2^31),
+ *     Gq = (G + 128) >> 8  (Q20),   out = min(255, (Gq * v + (1 << 19)) >> 20).
+ *   A map that is 1.0f everywhere gives identical bytes.  Bytes [0, 3w) of each row are written, the pitch padding is untouched; the
+ *   in-place and overlap rules are those of mi355_apply_gains_dev.  With grid 1 x 1 the bytes are NOT promised to equal the per-frame
+ *   LUT's: this is a Q12 gain in integers, that one a double product.
+ * Errors: as in the section above, plus grid_x, grid_y outside [1, 16], a taking-part frame smaller than the grid (the message names the
+ *   frame, its size and the grid), smooth outside [0, 8], w or h above 2^20, a gain that is not finite; in the solve also a record whose
+ *   pair or cell index is out of range or whose n < 0, and a cell_cover < 0. */
+typedef struct {
+    int32_t pair;               /* index into pairs_ab */
+    int32_t cell_a, cell_b;     /* cell of frame a's / frame b's sample */
+    int32_t reserved;
+    int64_t n;                  /* common lattice points with these two cells */
+    int64_t sum_a[3], sum_b[3]; /* B, G, R samples of frame a / frame b summed over those points */
+} mi355_block_gain_stats;       /* 72 B */
+typedef struct {
+    float sigma_n, sigma_g;     /* as mi355_gain_params */
+    int32_t channels;           /* 3 or 1 */
+    int32_t step;               /* lattice step, 1..64 */
+    int32_t grid_x, grid_y;     /* cells per frame, 1..16 each */
+    int32_t smooth;             /* passes of [1/4, 1/2, 1/4], 0..8 */
+    int32_t reserved;
+} mi355_block_gain_params;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_block_gain_stats) == 72, "mi355_block_gain_stats is 72 bytes");
+static_assert(sizeof(mi355_block_gain_params) == 32, "mi355_block_gain_params is 32 bytes");
+#else
+_Static_assert(sizeof(mi355_block_gain_stats) == 72, "mi355_block_gain_stats is 72 bytes");
+_Static_assert(sizeof(mi355_block_gain_params) == 32, "mi355_block_gain_params is 32 bytes");
+#endif
+/* sigma_n = 10, sigma_g = 0.1, channels = 3, step = 8, grid 8 x 6, smooth = 2 */
+void mi355_default_block_gain_params(mi355_block_gain_params* p);
+/* the statistics (complete on return): *records (HOST, *n_records of them, released with mi355_free; NULL when there are none) and
+ * cell_cover (HOST, n x cells values; may be NULL). */
+int  mi355_block_gain_stats_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                const int32_t* pairs_ab, int n_pairs, int step, int grid_x, int grid_y,
+                                mi355_block_gain_stats** records, int64_t* n_records, int64_t* cell_cover);
+/* the smoothed gain maps from the statistics (host only, no ctx, no device); p NULL: defaults (p->step is not used here).  gains: HOST,
+ * n x grid_y x grid_x x 3.  Errors: mi355_last_error(NULL). */
+int  mi355_solve_block_gains(const mi355_block_gain_stats* records, int64_t n_records, const int32_t* pairs_ab, int n_pairs, const int64_t* cell_cover,
+                             int n, const mi355_block_gain_params* p, float* gains);
+/* dst[k] = src[k] times its interpolated map, for every k (one launch; complete on return).  gains: HOST, n x grid_y x grid_x x 3. */
+int  mi355_apply_block_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n,
+                                 int grid_x, int grid_y, const float* gains);
+/* statistics at p->step, solve, apply in place on d_imgs; gains_out (HOST, n x grid_y x grid_x x 3; may be NULL) receives the maps.  Frames
+ * the render skips are not touched and may be NULL.  p NULL: defaults. */
+int  mi355_block_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                     const int32_t* pairs_ab, int n_pairs, const mi355_block_gain_params* p, float* gains_out);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

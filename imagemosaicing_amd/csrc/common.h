@@ -241,6 +241,6 @@ int  mi_kept_frame_slot(mi355_ctx*, int img_id, int w, int h, int ws, const char
 void mi_frames_release(mi355_ctx*);
 
 // host helpers
-void mi_set_host_error(const std::string& s);                                        // api.hip: what mi355_last_error(NULL) returns (calls without a ctx)
+#include "host_error.h"
 int  mi_inverse_matrix_host(const float* src, int order, float* dst, float eps);   // matrix.h:147-296 (host side of the warps)
 void mi_glibc_draw_table(uint32_t seed, int n, int max_draws, uint16_t* out4);       // mosaicimage.h:1777-1813

@@ -12,22 +12,25 @@
 //   gain_apply_kernel   a row-streaming LUT pass over every frame in one launch: a workgroup builds its frame's 3 x 256 table in LDS from
 //                       the gains (in double) and streams 16 rows, 16 B in and 16 B out per lane where the row is aligned, bytes at the ends.
 //                       Its roofline is HBM: 2 x 3 w h bytes per frame.
-//   mi355_solve_gains   host, single-threaded double: the normal equations over the frames that have one, reverse Cuthill-McKee order, an
-//                       envelope Cholesky factor and one step of iterative refinement.  Fixed order throughout: the same bits every call.
-// Block gains (a gain map per frame on a grid of cells; header section "block gain compensation") follow further down with their own kernels;
-// they share the work list, the map and sample, the node solve (solve_nodes) and the apply's frame check with the per-frame stage.
+// Block gains (a gain map per frame on a grid of cells; header section "block gain compensation") follow further down with their own kernels.
+// The two apply kernels are one row streamer (stream_rows) around different middles: how a byte becomes an output byte (a LUT read, or the
+// Q12 interpolation).  The two stats kernels keep their sample walk inline (see the note above gain_stats_kernel).  On the host the stages
+// share the stats' checks, frame table and work list (stats_setup), the apply's frame check and launch (check_apply_frames, launch_apply)
+// and the compensate calls' choice of frames (NonUnit).  The parameter checks and both solves are host-only: gain_solve.cpp (gain.h).
 #include "common.h"
+#include "gain.h"
 #include "hmath.h"
 #include "mosaic_frame.h"
 #include <algorithm>
 #include <cmath>
-#include <unordered_map>
+#include <cstddef>
 
 namespace {
 
+using namespace mi_gain;
+
 constexpr int GT_X = 64, GT_Y = 16;           // lattice columns x rows of a stats tile (256 lanes: 64 x 4, 4 rows each)
 constexpr int AP_NT = 256, AP_ROWS = 16;      // apply: lanes and frame rows per workgroup
-constexpr int GAIN_MAX_FRAMES = 65535;
 
 struct GainTile { int a, b, rec; int lx0, ly0, lx1, ly1; int _pad; };   // b < 0: cover tile of frame a (rec = a); else pair record rec
 
@@ -37,6 +40,10 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+// The two stats kernels carry the same walk over a tile's samples (lane to lattice point, frame_src, src_inside, frame_sample3) spelled out
+// twice.  A shared walk that hands each sample to a callable was tried, as one function and as a cover and a pair walk: with it the compiler
+// schedules the unrolled rows differently and block_gain_stats_kernel grows from 3235 to 3540 instructions (v_pk_* 114 -> 71).  So, as with
+// mosaic_tile_kernel in mosaic_frame.h, the walk stays inline: a fix to one copy goes into the other as well.
 __global__ __launch_bounds__(256) void gain_stats_kernel(const FrameDev* fr, const GainTile* tiles, int step, float dGx, float dGy,
                                                          unsigned long long* pair_acc, unsigned long long* cover_acc) {
     const GainTile t = tiles[blockIdx.x];
@@ -91,32 +98,33 @@ __global__ __launch_bounds__(256) void gain_stats_kernel(const FrameDev* fr, con
     }
 }
 
-struct ApplyFrame { const uint8_t* src; uint8_t* dst; int w, h, ws, first_block; float g[3]; int _pad; };
+// One record per frame an apply launch works on.  Both forms begin alike: frame_of_block, stream_rows and launch_apply read that part.
+struct ApplyHead { const uint8_t* src; uint8_t* dst; int w, h, ws, first_block; };
+struct ApplyFrame : ApplyHead { float g[3]; int _pad; };
+struct BlockApplyFrame : ApplyHead { int q_off; int _pad; };
+static_assert(offsetof(ApplyHead, first_block) == 28 && sizeof(ApplyHead) == 32 && sizeof(ApplyFrame) == 48 && sizeof(BlockApplyFrame) == 40, "apply record layout");
 
-__global__ __launch_bounds__(AP_NT) void gain_apply_kernel(const ApplyFrame* frames, int nf) {
-    __shared__ uint8_t lut[3 * 256];
+// the record of this workgroup's frame: the last k with first_block <= blockIdx.x (first_block ascends).  Ends in a barrier.
+template <class Rec>
+__device__ __forceinline__ const Rec& frame_of_block(const Rec* frames, int nf) {
     __shared__ int s_k;
-    // the frame of this workgroup: the last k with first_block <= blockIdx.x (first_block ascends)
     if (threadIdx.x == 0) {
         int lo = 0, hi = nf - 1;
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (frames[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
         s_k = lo;
     }
     __syncthreads();
-    const ApplyFrame& f = frames[s_k];
-    {
-        const int v = threadIdx.x;                                  // AP_NT == 256: one table entry per lane and channel
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            double o = floor((double)f.g[c] * (double)v + 0.5);
-            o = o < 0.0 ? 0.0 : (o > 255.0 ? 255.0 : o);
-            lut[c * 256 + v] = (uint8_t)(int)o;
-        }
-    }
-    __syncthreads();
-    const int y0 = ((int)blockIdx.x - f.first_block) * AP_ROWS;
+    return frames[s_k];
+}
+
+// Rows y0 .. y0 + AP_ROWS - 1 of frame f from src to dst: 16 B in and 16 B out per lane where the row is aligned, bytes at its ends.  What a
+// byte becomes is the cursor's business: cursor_of_row(y - y0) gives a row's cursor, seek(off) puts it at byte offset off of the row, map(v)
+// is the output byte for input byte v there, next() moves it one byte on.
+template <class RowCursor>
+__device__ __forceinline__ void stream_rows(const ApplyHead& f, int y0, RowCursor cursor_of_row) {
     const int nb = 3 * f.w;
     for (int y = y0; y < y0 + AP_ROWS && y < f.h; y++) {
+        auto cur = cursor_of_row(y - y0);
         const uint8_t* srow = f.src + (size_t)y * f.ws;
         uint8_t* drow = f.dst + (size_t)y * f.ws;
         int head = (int)((16 - ((uintptr_t)srow & 15)) & 15);
@@ -129,14 +137,14 @@ __global__ __launch_bounds__(AP_NT) void gain_apply_kernel(const ApplyFrame* fra
             const uint4 in = *reinterpret_cast<const uint4*>(srow + off);
             const unsigned w4[4] = {in.x, in.y, in.z, in.w};
             unsigned o4[4];
-            int c = off % 3;
+            cur.seek(off);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 unsigned o = 0;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    o |= (unsigned)lut[c * 256 + ((w4[q] >> (8 * j)) & 0xffu)] << (8 * j);
-                    c = c == 2 ? 0 : c + 1;
+                    o |= cur.map((w4[q] >> (8 * j)) & 0xffu) << (8 * j);
+                    cur.next();
                 }
                 o4[q] = o;
             }
@@ -144,41 +152,33 @@ __global__ __launch_bounds__(AP_NT) void gain_apply_kernel(const ApplyFrame* fra
         }
         // the row's ends (or the whole row where src and dst are not aligned alike): bytes
         const int nhead = vec ? head : nb;
-        for (int i = threadIdx.x; i < nhead; i += AP_NT) drow[i] = lut[(i % 3) * 256 + srow[i]];
+        for (int i = threadIdx.x; i < nhead; i += AP_NT) { cur.seek(i); drow[i] = (uint8_t)cur.map(srow[i]); }
         if (vec)
-            for (int i = tail + (int)threadIdx.x; i < nb; i += AP_NT) drow[i] = lut[(i % 3) * 256 + srow[i]];
+            for (int i = tail + (int)threadIdx.x; i < nb; i += AP_NT) { cur.seek(i); drow[i] = (uint8_t)cur.map(srow[i]); }
     }
 }
 
-std::string pair_str(int p, int a, int b) { return "pair " + std::to_string(p) + " (" + std::to_string(a) + ", " + std::to_string(b) + ")"; }
+struct LutCursor {
+    const uint8_t* lut; int c;                                  // the 3 x 256 table; the channel of the byte the cursor is at
+    __device__ __forceinline__ void seek(int off) { c = off % 3; }
+    __device__ __forceinline__ unsigned map(unsigned v) const { return lut[c * 256 + v]; }
+    __device__ __forceinline__ void next() { c = c == 2 ? 0 : c + 1; }
+};
 
-// a == b, a position out of range, an unordered pair listed twice
-bool check_pairs(const int32_t* ab, int n_pairs, int n, std::string& err) {
-    std::unordered_map<uint64_t, int> seen;
-    seen.reserve((size_t)n_pairs * 2 + 1);
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = ab[2 * p], b = ab[2 * p + 1];
-        if (a < 0 || a >= n || b < 0 || b >= n) { err = pair_str(p, a, b) + ": position outside [0, " + std::to_string(n) + ")"; return false; }
-        if (a == b) { err = pair_str(p, a, b) + ": a == b"; return false; }
-        const uint64_t key = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
-        auto it = seen.find(key);
-        if (it != seen.end()) { err = pair_str(p, a, b) + " repeats pair " + std::to_string(it->second); return false; }
-        seen.emplace(key, p);
+__global__ __launch_bounds__(AP_NT) void gain_apply_kernel(const ApplyFrame* frames, int nf) {
+    __shared__ uint8_t lut[3 * 256];
+    const ApplyFrame& f = frame_of_block(frames, nf);
+    {
+        const int v = threadIdx.x;                                  // AP_NT == 256: one table entry per lane and channel
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            double o = floor((double)f.g[c] * (double)v + 0.5);
+            o = o < 0.0 ? 0.0 : (o > 255.0 ? 255.0 : o);
+            lut[c * 256 + v] = (uint8_t)(int)o;
+        }
     }
-    return true;
-}
-
-bool check_frames_n(int n, std::string& err) {
-    if (n < 1 || n > GAIN_MAX_FRAMES) { err = "n=" + std::to_string(n) + " outside [1, 65535]"; return false; }
-    return true;
-}
-
-bool check_params(const mi355_gain_params& p, bool need_step, std::string& err) {
-    if (need_step && (p.step < 1 || p.step > 64)) { err = "step=" + std::to_string(p.step) + " outside [1, 64]"; return false; }
-    if (p.channels != 1 && p.channels != 3) { err = "channels=" + std::to_string(p.channels) + " (need 1 or 3)"; return false; }
-    if (!(p.sigma_n > 0.0f) || !std::isfinite(p.sigma_n)) { err = "sigma_n=" + std::to_string(p.sigma_n) + " must be > 0"; return false; }
-    if (!(p.sigma_g > 0.0f) || !std::isfinite(p.sigma_g)) { err = "sigma_g=" + std::to_string(p.sigma_g) + " must be > 0"; return false; }
-    return true;
+    __syncthreads();
+    stream_rows(f, ((int)blockIdx.x - f.first_block) * AP_ROWS, [&](int) __attribute__((always_inline)) { return LutCursor{lut, 0}; });
 }
 
 int lattice_lo(int x0, int step) { return (x0 + step - 1) / step; }       // x0 >= 0
@@ -195,38 +195,68 @@ void push_tiles(std::vector<GainTile>& tiles, int a, int b, int rec, int x0, int
         }
 }
 
+// What a stats launcher knows after stats_setup: the frame table (also on the device, ctx buffer "gain_frames"), which frames take part,
+// the canvas offset, and from them the work list.
+struct StatsFrames {
+    std::vector<FrameDev> fr;
+    std::vector<char> part;
+    float dG[2];
+    const FrameDev* d_fr;
+    void push_cover_tiles(std::vector<GainTile>& tiles, int step) const {
+        for (size_t k = 0; k < fr.size(); k++)
+            if (part[k]) push_tiles(tiles, (int)k, -1, (int)k, fr[k].begX, fr[k].endX, fr[k].begY, fr[k].endY, step);
+    }
+    // tiles over the intersection of the two canvas boxes; none where either frame takes no part
+    void push_pair_tiles(std::vector<GainTile>& tiles, int a, int b, int rec, int step) const {
+        if (!part[a] || !part[b]) return;
+        const FrameDev &A = fr[a], &B = fr[b];
+        push_tiles(tiles, a, b, rec, std::max(A.begX, B.begX), std::min(A.endX, B.endX), std::max(A.begY, B.begY), std::min(A.endY, B.endY), step);
+    }
+};
+
+constexpr int BG_MAX_DIM = 1 << 20;           // block gains: the widest and tallest frame (bg_cell, bg_axis)
+
+// The argument checks, the canvas layout and the frame table of both stats launchers; who ("gain_stats: ") prefixes the refusals.  grid
+// (grid_x, grid_y; NULL for the per-frame stage) adds the block stage's limits: the grid's range, no side above BG_MAX_DIM, no frame that
+// takes part smaller than the grid.  s.fr must stay until the stream has been synchronised.
+int stats_setup(mi355_ctx* ctx, const std::string& who, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                const int32_t* pairs_ab, int n_pairs, int step, const int* grid, StatsFrames& s) {
+    std::string err;
+    if (!d_imgs || !w || !h || !ws || !h9s || (n_pairs > 0 && !pairs_ab) || n_pairs < 0) { ctx->set_error(who + "NULL argument or n_pairs < 0"); return MI355_ERR_ARG; }
+    if (!check_frames_n(n, err) || !check_pairs(flat_pairs(pairs_ab), n_pairs, n, err) || (grid && !check_grid(grid[0], grid[1], err))) { ctx->set_error(who + err); return MI355_ERR_ARG; }
+    if (step < 1 || step > 64) { ctx->set_error(who + "step=" + std::to_string(step) + " outside [1, 64]"); return MI355_ERR_ARG; }
+    int cw, ch, cws;
+    if (mi355_mosaic_layout(w, h, n, h9s, &cw, &ch, &cws, s.dG) != MI355_OK) { ctx->set_error(who + "no image with h[8] != 0 / empty canvas"); return MI355_ERR_FAILED; }
+    s.fr.assign((size_t)n, FrameDev());
+    s.part.assign((size_t)n, 0);
+    for (int k = 0; k < n; k++) {
+        if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], s.dG, cw, ch, 0, ch, s.fr[k])) continue;
+        const std::string fk = who + "frame " + std::to_string(k);
+        if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k] || (grid && (w[k] > BG_MAX_DIM || h[k] > BG_MAX_DIM))) { ctx->set_error(fk + ": bad geometry w=" + std::to_string(w[k]) + " h=" + std::to_string(h[k]) + " ws=" + std::to_string(ws[k])); return MI355_ERR_ARG; }
+        if (grid && (w[k] < grid[0] || h[k] < grid[1])) { ctx->set_error(fk + " (" + std::to_string(w[k]) + "x" + std::to_string(h[k]) + ") is smaller than the " + std::to_string(grid[0]) + "x" + std::to_string(grid[1]) + " grid"); return MI355_ERR_ARG; }
+        if (!d_imgs[k]) { ctx->set_error(fk + " takes part but its pointer is NULL"); return MI355_ERR_ARG; }
+        s.fr[k].src = d_imgs[k]; s.fr[k].w = w[k]; s.fr[k].h = h[k]; s.fr[k].ws = ws[k];
+        s.part[k] = 1;
+    }
+    DevBuf& dfr = ctx->buf("gain_frames");
+    MI_HIP(dfr.reserve(sizeof(FrameDev) * (size_t)n));
+    MI_HIP(hipMemcpyAsync(dfr.p, s.fr.data(), sizeof(FrameDev) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    s.d_fr = dfr.as<FrameDev>();
+    return MI355_OK;
+}
+
 int gain_stats(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                const int32_t* pairs_ab, int n_pairs, int step, mi355_gain_pair_stats* pair_stats, int64_t* frame_cover) {
-    std::string err;
-    if (!d_imgs || !w || !h || !ws || !h9s || (n_pairs > 0 && (!pairs_ab || !pair_stats)) || n_pairs < 0) { ctx->set_error("gain_stats: NULL argument or n_pairs < 0"); return MI355_ERR_ARG; }
-    if (!check_frames_n(n, err) || !check_pairs(pairs_ab, n_pairs, n, err)) { ctx->set_error("gain_stats: " + err); return MI355_ERR_ARG; }
-    if (step < 1 || step > 64) { ctx->set_error("gain_stats: step=" + std::to_string(step) + " outside [1, 64]"); return MI355_ERR_ARG; }
-    int cw, ch, cws; float dG[2];
-    if (mi355_mosaic_layout(w, h, n, h9s, &cw, &ch, &cws, dG) != MI355_OK) { ctx->set_error("gain_stats: no image with h[8] != 0 / empty canvas"); return MI355_ERR_FAILED; }
-    std::vector<FrameDev> fr((size_t)n);
-    std::vector<char> part((size_t)n, 0);
-    for (int k = 0; k < n; k++) {
-        if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], dG, cw, ch, 0, ch, fr[k])) continue;
-        if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) { ctx->set_error("gain_stats: frame " + std::to_string(k) + ": bad geometry w=" + std::to_string(w[k]) + " h=" + std::to_string(h[k]) + " ws=" + std::to_string(ws[k])); return MI355_ERR_ARG; }
-        if (!d_imgs[k]) { ctx->set_error("gain_stats: frame " + std::to_string(k) + " takes part but its pointer is NULL"); return MI355_ERR_ARG; }
-        fr[k].src = d_imgs[k]; fr[k].w = w[k]; fr[k].h = h[k]; fr[k].ws = ws[k];
-        part[k] = 1;
-    }
+    if (n_pairs > 0 && !pair_stats) { ctx->set_error("gain_stats: NULL argument or n_pairs < 0"); return MI355_ERR_ARG; }
+    StatsFrames s;
+    { const int rc = stats_setup(ctx, "gain_stats: ", d_imgs, w, h, ws, n, h9s, pairs_ab, n_pairs, step, nullptr, s); if (rc != MI355_OK) return rc; }
     std::vector<GainTile> tiles;
-    for (int k = 0; k < n; k++)
-        if (part[k]) push_tiles(tiles, k, -1, k, fr[k].begX, fr[k].endX, fr[k].begY, fr[k].endY, step);
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = pairs_ab[2 * p], b = pairs_ab[2 * p + 1];
-        if (!part[a] || !part[b]) continue;
-        const FrameDev &A = fr[a], &B = fr[b];
-        push_tiles(tiles, a, b, p, std::max(A.begX, B.begX), std::min(A.endX, B.endX), std::max(A.begY, B.begY), std::min(A.endY, B.endY), step);
-    }
+    s.push_cover_tiles(tiles, step);
+    for (int p = 0; p < n_pairs; p++) s.push_pair_tiles(tiles, pairs_ab[2 * p], pairs_ab[2 * p + 1], p, step);
     const size_t n_acc = (size_t)n_pairs * 7 + (size_t)n;
-    DevBuf& dfr = ctx->buf("gain_frames"); DevBuf& dt = ctx->buf("gain_tiles"); DevBuf& dacc = ctx->buf("gain_acc");
-    MI_HIP(dfr.reserve(sizeof(FrameDev) * (size_t)n));
+    DevBuf& dt = ctx->buf("gain_tiles"); DevBuf& dacc = ctx->buf("gain_acc");
     MI_HIP(dt.reserve(sizeof(GainTile) * std::max<size_t>(tiles.size(), 1)));
     MI_HIP(dacc.reserve(sizeof(unsigned long long) * n_acc));
-    MI_HIP(hipMemcpyAsync(dfr.p, fr.data(), sizeof(FrameDev) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if (!tiles.empty()) MI_HIP(hipMemcpyAsync(dt.p, tiles.data(), sizeof(GainTile) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
     MI_HIP(hipMemsetAsync(dacc.p, 0, sizeof(unsigned long long) * n_acc, ctx->stream));
     unsigned long long* pair_acc = dacc.as<unsigned long long>();
@@ -234,216 +264,21 @@ int gain_stats(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const
     for (size_t t0 = 0; t0 < tiles.size(); t0 += (size_t)1 << 30) {     // grid.x < 2^31
         const size_t nt = std::min(tiles.size() - t0, (size_t)1 << 30);
         ProfScope ps(ctx, "gain_stats", 0.0);
-        hipLaunchKernelGGL(gain_stats_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), dt.as<GainTile>() + t0, step,
-                           dG[0], dG[1], pair_acc, cover_acc);
+        hipLaunchKernelGGL(gain_stats_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, s.d_fr, dt.as<GainTile>() + t0, step, s.dG[0], s.dG[1], pair_acc,
+                           cover_acc);
         MI_HIP(hipGetLastError());
     }
     std::vector<unsigned long long> acc(n_acc);
     MI_HIP(hipMemcpyAsync(acc.data(), dacc.p, sizeof(unsigned long long) * n_acc, hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipStreamSynchronize(ctx->stream));                 // fr / tiles are locals
+    MI_HIP(hipStreamSynchronize(ctx->stream));                 // s.fr / tiles are locals
     for (int p = 0; p < n_pairs; p++) {
-        mi355_gain_pair_stats& s = pair_stats[p];
-        s.a = pairs_ab[2 * p]; s.b = pairs_ab[2 * p + 1];
-        s.n = (int64_t)acc[7 * (size_t)p];
-        for (int c = 0; c < 3; c++) { s.sum_a[c] = (int64_t)acc[7 * (size_t)p + 1 + c]; s.sum_b[c] = (int64_t)acc[7 * (size_t)p + 4 + c]; }
+        mi355_gain_pair_stats& st = pair_stats[p];
+        st.a = pairs_ab[2 * p]; st.b = pairs_ab[2 * p + 1];
+        st.n = (int64_t)acc[7 * (size_t)p];
+        for (int c = 0; c < 3; c++) { st.sum_a[c] = (int64_t)acc[7 * (size_t)p + 1 + c]; st.sum_b[c] = (int64_t)acc[7 * (size_t)p + 4 + c]; }
     }
     if (frame_cover)
         for (int k = 0; k < n; k++) frame_cover[k] = (int64_t)acc[(size_t)n_pairs * 7 + k];
-    return MI355_OK;
-}
-
-// ---- host solve -----------------------------------------------------------------------------------------------------------------------
-constexpr double ENVELOPE_WORK_MAX = 2e9;     // multiply-adds of one envelope factorisation above which solve_nodes may iterate instead
-constexpr int PCG_MAX_ITER = 2000;
-
-// One channel of solve_nodes by conjugate gradients with the diagonal as preconditioner, from x = 1, every sum in index or pair-list order.
-// Unknowns are the active ones (positions in node); diag / off / rhs are the channel's system in pair-list order.
-// The stop is a bound, not a guess.  Every pair term 2 alpha n (I_ab e_a - I_ba e_b)(...)^T is positive semidefinite, so A >= beta diag(M) with
-// M_i = N_i + the n of i's live pairs (integers >= 1).  With e = x - x*, r = rhs - A x:  e^T A e = r^T A^-1 r <= sum r_i^2 / (beta M_i)  and
-// e^T A e >= beta min(M) |e|_inf^2, hence |e|_inf <= sqrt(sum r_i^2 / (beta M_i) / (beta min M)).  The iteration ends when that bound, taken on
-// the residual computed afresh from x, is below 5e-10 max|x| (so below 1e-9 |x*|_inf); a system on which double arithmetic cannot bring the
-// residual that low (a weak prior on a large graph) is refused.
-int solve_pcg(const mi355_gain_pair_stats* ps, const std::vector<int>& live, const std::vector<int>& idx, const std::vector<int>& node, const int64_t* cover,
-              const std::vector<double>& diag, const std::vector<double>& off, const std::vector<double>& rhs, double beta, std::vector<double>& x,
-              std::string& err) {
-    const int m = (int)node.size();
-    std::vector<double> M((size_t)m), r((size_t)m), z((size_t)m), p((size_t)m), Ap((size_t)m);
-    for (int i = 0; i < m; i++) M[i] = (double)cover[node[i]];
-    for (int q : live) { M[idx[ps[q].a]] += (double)ps[q].n; M[idx[ps[q].b]] += (double)ps[q].n; }
-    double mmin = M[0];
-    for (int i = 1; i < m; i++) mmin = std::min(mmin, M[i]);
-    auto matvec = [&](const std::vector<double>& v, std::vector<double>& y) {
-        for (int i = 0; i < m; i++) y[i] = diag[i] * v[i];
-        for (size_t q = 0; q < live.size(); q++) {
-            const int a = idx[ps[live[q]].a], b = idx[ps[live[q]].b];
-            y[a] += off[q] * v[b]; y[b] += off[q] * v[a];
-        }
-    };
-    auto dot = [&](const std::vector<double>& a, const std::vector<double>& b) { double s = 0.0; for (int i = 0; i < m; i++) s += a[i] * b[i]; return s; };
-    auto error_bound = [&]() { double s = 0.0; for (int i = 0; i < m; i++) s += r[i] * r[i] / (beta * M[i]); return std::sqrt(s / (beta * mmin)); };
-    auto restart = [&]() {                                     // r, z, p from x
-        matvec(x, Ap);
-        for (int i = 0; i < m; i++) { r[i] = rhs[i] - Ap[i]; z[i] = r[i] / diag[i]; p[i] = z[i]; }
-        return dot(r, z);
-    };
-    std::fill(x.begin(), x.end(), 1.0);
-    double rho = restart();
-    for (int it = 0; it < PCG_MAX_ITER; it++) {
-        double xmax = 0.0;
-        for (int i = 0; i < m; i++) xmax = std::max(xmax, std::fabs(x[i]));
-        if (error_bound() <= 2.5e-10 * xmax) {
-            rho = restart();                                   // the recurrence's residual drifts from the true one: decide on the true one
-            if (error_bound() <= 5e-10 * xmax) return MI355_OK;
-        }
-        matvec(p, Ap);
-        const double a = rho / dot(p, Ap);
-        for (int i = 0; i < m; i++) { x[i] += a * p[i]; r[i] -= a * Ap[i]; z[i] = r[i] / diag[i]; }
-        const double rho2 = dot(r, z);
-        const double b = rho2 / rho;
-        for (int i = 0; i < m; i++) p[i] = z[i] + b * p[i];
-        rho = rho2;
-    }
-    err = "the iterative solve of " + std::to_string(m) + " unknowns did not reach 1e-9 in " + std::to_string(PCG_MAX_ITER) + " steps (prior too weak for a graph this large)";
-    return MI355_ERR_FAILED;
-}
-
-// The normal equations of the header over n unknowns ("frames" for mi355_solve_gains, the nodes (frame, cell) for the block gains): ps[p].a / .b
-// are unknowns, cover[k] is N_k.  x3: n x 3 doubles, 1 for an unknown without an equation (channels == 1: the one value in all three).
-// The factorisation is the envelope Cholesky below.  may_iterate (block gains only): where its envelope would cost more than ENVELOPE_WORK_MAX
-// multiply-adds per channel, a Jacobi-preconditioned conjugate gradient in the same fixed order takes its place; it stops on a bound of the
-// error that it can prove (see there) and fails rather than return less.  unit names an unknown in the messages.
-int solve_nodes(const mi355_gain_pair_stats* ps, int n_pairs, const int64_t* cover, int n, const mi355_gain_params& prm, const char* unit, bool may_iterate,
-                double* x3, std::string& err) {
-    const double alpha = 1.0 / ((double)prm.sigma_n * (double)prm.sigma_n), beta = 1.0 / ((double)prm.sigma_g * (double)prm.sigma_g);
-    // the frames with an equation and the graph of the pairs with n > 0 (the same for every channel)
-    std::vector<char> active((size_t)n, 0);
-    for (int k = 0; k < n; k++) if (cover[k] > 0) active[k] = 1;
-    std::vector<int> live;                                    // pairs that add terms
-    for (int p = 0; p < n_pairs; p++) if (ps[p].n > 0) { live.push_back(p); active[ps[p].a] = 1; active[ps[p].b] = 1; }
-    std::vector<int> idx((size_t)n, -1), node;
-    for (int k = 0; k < n; k++) if (active[k]) { idx[k] = (int)node.size(); node.push_back(k); }
-    const int m = (int)node.size();
-    std::fill(x3, x3 + 3 * (size_t)n, 1.0);
-    if (m == 0) return MI355_OK;
-    std::vector<std::vector<int>> adj((size_t)m);
-    for (int p : live) { const int u = idx[ps[p].a], v = idx[ps[p].b]; adj[u].push_back(v); adj[v].push_back(u); }
-    for (auto& l : adj) std::sort(l.begin(), l.end());
-    // reverse Cuthill-McKee: per component, start at the unvisited node of least degree (lowest index on ties), neighbours by (degree, index)
-    std::vector<int> order; order.reserve(m);
-    std::vector<char> seen((size_t)m, 0);
-    std::vector<int> by_deg(m);
-    for (int i = 0; i < m; i++) by_deg[i] = i;
-    std::stable_sort(by_deg.begin(), by_deg.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
-    for (int s : by_deg) {
-        if (seen[s]) continue;
-        size_t head = order.size();
-        order.push_back(s); seen[s] = 1;
-        std::vector<int> nb;
-        while (head < order.size()) {
-            const int u = order[head++];
-            nb.clear();
-            for (int v : adj[u]) if (!seen[v]) { nb.push_back(v); seen[v] = 1; }
-            std::stable_sort(nb.begin(), nb.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
-            order.insert(order.end(), nb.begin(), nb.end());
-        }
-    }
-    std::reverse(order.begin(), order.end());
-    std::vector<int> pos((size_t)m);
-    for (int i = 0; i < m; i++) pos[order[i]] = i;
-    // envelope: row i (permuted) holds columns fst[i] .. i
-    std::vector<int> fst((size_t)m);
-    for (int i = 0; i < m; i++) { int f = i; for (int v : adj[order[i]]) f = std::min(f, pos[v]); fst[i] = f; }
-    std::vector<size_t> rp((size_t)m + 1, 0);
-    for (int i = 0; i < m; i++) rp[i + 1] = rp[i] + (size_t)(i - fst[i] + 1);
-    double work = 0.0;
-    for (int i = 0; i < m; i++) work += (double)(i - fst[i]) * (double)(i - fst[i]);
-    const bool iterate = may_iterate && work > ENVELOPE_WORK_MAX;
-    std::vector<double> E(iterate ? 0 : rp[m]), diag((size_t)m), rhs((size_t)m), x((size_t)m), r((size_t)m), d((size_t)m);
-    std::vector<double> off((size_t)live.size());
-    auto at = [&](int i, int j) -> double& { return E[rp[i] + (size_t)(j - fst[i])]; };   // j in [fst[i], i]
-    const int nch = prm.channels;
-    for (int c = 0; c < nch; c++) {
-        // the normal equations in pair-list order
-        for (int i = 0; i < m; i++) { diag[i] = beta * (double)cover[node[i]]; rhs[i] = beta * (double)cover[node[i]]; }
-        for (size_t q = 0; q < live.size(); q++) {
-            const mi355_gain_pair_stats& s = ps[live[q]];
-            const double nn = (double)s.n;
-            double Iab, Iba;
-            if (nch == 3) { Iab = (double)s.sum_a[c] / nn; Iba = (double)s.sum_b[c] / nn; }
-            else { Iab = (double)(s.sum_a[0] + s.sum_a[1] + s.sum_a[2]) / (3.0 * nn); Iba = (double)(s.sum_b[0] + s.sum_b[1] + s.sum_b[2]) / (3.0 * nn); }
-            const int u = idx[s.a], v = idx[s.b];
-            diag[u] += 2.0 * alpha * Iab * Iab * nn + beta * nn;
-            diag[v] += 2.0 * alpha * Iba * Iba * nn + beta * nn;
-            off[q] = -2.0 * alpha * Iab * Iba * nn;
-            rhs[u] += beta * nn; rhs[v] += beta * nn;
-        }
-        if (iterate) {
-            const int rc = solve_pcg(ps, live, idx, node, cover, diag, off, rhs, beta, x, err);
-            if (rc != MI355_OK) return rc;
-            for (int i = 0; i < m; i++) {
-                if (nch == 3) x3[3 * (size_t)node[i] + c] = x[i];
-                else x3[3 * (size_t)node[i]] = x3[3 * (size_t)node[i] + 1] = x3[3 * (size_t)node[i] + 2] = x[i];
-            }
-            continue;
-        }
-        std::fill(E.begin(), E.end(), 0.0);
-        for (int i = 0; i < m; i++) at(pos[i], pos[i]) = diag[i];
-        for (size_t q = 0; q < live.size(); q++) {
-            const int u = pos[idx[ps[live[q]].a]], v = pos[idx[ps[live[q]].b]];
-            if (u > v) at(u, v) += off[q]; else at(v, u) += off[q];
-        }
-        // envelope Cholesky, row by row
-        for (int i = 0; i < m; i++) {
-            for (int j = fst[i]; j < i; j++) {
-                double s = at(i, j);
-                for (int k = std::max(fst[i], fst[j]); k < j; k++) s -= at(i, k) * at(j, k);
-                at(i, j) = s / at(j, j);
-            }
-            double s = at(i, i);
-            for (int k = fst[i]; k < i; k++) s -= at(i, k) * at(i, k);
-            if (!(s > 0.0)) { err = std::string("the normal equations are not positive definite at ") + unit + " " + std::to_string(node[order[i]]); return MI355_ERR_FAILED; }
-            at(i, i) = std::sqrt(s);
-        }
-        auto lsolve = [&](std::vector<double>& b) {              // b := (L L^T)^-1 b, permuted positions
-            for (int i = 0; i < m; i++) { double s = b[i]; for (int k = fst[i]; k < i; k++) s -= at(i, k) * b[k]; b[i] = s / at(i, i); }
-            for (int i = m - 1; i >= 0; i--) { b[i] /= at(i, i); const double bi = b[i]; for (int k = fst[i]; k < i; k++) b[k] -= at(i, k) * bi; }
-        };
-        for (int i = 0; i < m; i++) x[pos[i]] = rhs[i];
-        lsolve(x);
-        // one step of iterative refinement on the unfactored system: r = rhs - A x
-        for (int i = 0; i < m; i++) r[pos[i]] = rhs[i] - diag[i] * x[pos[i]];
-        for (size_t q = 0; q < live.size(); q++) {
-            const int u = pos[idx[ps[live[q]].a]], v = pos[idx[ps[live[q]].b]];
-            r[u] -= off[q] * x[v]; r[v] -= off[q] * x[u];
-        }
-        d = r;
-        lsolve(d);
-        for (int i = 0; i < m; i++) x[i] += d[i];
-        for (int i = 0; i < m; i++) {
-            const double g = x[pos[i]];
-            if (nch == 3) x3[3 * (size_t)node[i] + c] = g;
-            else x3[3 * (size_t)node[i]] = x3[3 * (size_t)node[i] + 1] = x3[3 * (size_t)node[i] + 2] = g;
-        }
-    }
-    return MI355_OK;
-}
-
-int solve_gains(const mi355_gain_pair_stats* ps, int n_pairs, const int64_t* cover, int n, const mi355_gain_params& prm, float* gains, std::string& err) {
-    if (!check_frames_n(n, err) || !check_params(prm, false, err)) return MI355_ERR_ARG;
-    if (n_pairs < 0 || (n_pairs > 0 && !ps) || !cover || !gains) { err = "NULL argument or n_pairs < 0"; return MI355_ERR_ARG; }
-    {
-        std::vector<int32_t> ab((size_t)n_pairs * 2);
-        for (int p = 0; p < n_pairs; p++) { ab[2 * p] = ps[p].a; ab[2 * p + 1] = ps[p].b; }
-        if (!check_pairs(ab.data(), n_pairs, n, err)) return MI355_ERR_ARG;
-    }
-    for (int p = 0; p < n_pairs; p++)
-        if (ps[p].n < 0) { err = pair_str(p, ps[p].a, ps[p].b) + ": n=" + std::to_string(ps[p].n) + " < 0"; return MI355_ERR_ARG; }
-    for (int k = 0; k < n; k++)
-        if (cover[k] < 0) { err = "frame " + std::to_string(k) + ": frame_cover=" + std::to_string(cover[k]) + " < 0"; return MI355_ERR_ARG; }
-    std::vector<double> x3((size_t)n * 3);
-    const int rc = solve_nodes(ps, n_pairs, cover, n, prm, "frame", false, x3.data(), err);
-    if (rc != MI355_OK) return rc;
-    for (size_t i = 0; i < x3.size(); i++) gains[i] = (float)x3[i];
     return MI355_OK;
 }
 
@@ -479,39 +314,75 @@ int check_apply_frames(mi355_ctx* ctx, const std::string& who, const uint8_t* co
     return MI355_OK;
 }
 
-int apply_gains(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n, const float* gains) {
-    std::string err;
-    if (!d_src || !d_dst || !w || !h || !ws || !gains) { ctx->set_error("apply_gains: NULL argument"); return MI355_ERR_ARG; }
-    if (!check_frames_n(n, err)) { ctx->set_error("apply_gains: " + err); return MI355_ERR_ARG; }
-    { const int rc = check_apply_frames(ctx, "apply_gains", d_src, d_dst, w, h, ws, n, gains, 3); if (rc != MI355_OK) return rc; }
-    std::vector<ApplyFrame> af;
+bool all_one(const float* g, int per) {
+    bool unit = true;
+    for (int i = 0; i < per; i++) unit = unit && g[i] == 1.0f;
+    return unit;
+}
+
+// One apply launch over checked frames with `per` gains each: a record for every frame but those in place with gains all 1 (their bytes stay
+// as they are), AP_ROWS rows per workgroup, the records in ctx buffer buf, the kernel's time under scope.  fill(rec, gains of the frame) sets
+// the form's own fields; launch(records on the device, their number, workgroups) uploads what else the form needs and starts its kernel.
+template <class Rec, class Fill, class Launch>
+int launch_apply(mi355_ctx* ctx, const char* buf, const char* scope, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws,
+                 int n, const float* gains, int per, Fill fill, Launch launch) {
+    std::vector<Rec> af;
     int blocks = 0;
     double bytes = 0.0;
     for (int k = 0; k < n; k++) {
-        const bool unit = gains[3 * k] == 1.0f && gains[3 * k + 1] == 1.0f && gains[3 * k + 2] == 1.0f;
-        if (unit && d_src[k] == d_dst[k]) continue;                       // in place with gains 1: the bytes stay as they are
-        ApplyFrame f;
+        const float* g = gains + (size_t)per * k;
+        if (all_one(g, per) && d_src[k] == d_dst[k]) continue;
+        Rec f;
         f.src = d_src[k]; f.dst = d_dst[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k]; f.first_block = blocks; f._pad = 0;
-        for (int c = 0; c < 3; c++) f.g[c] = gains[3 * k + c];
+        fill(f, g);
         af.push_back(f);
         blocks += (h[k] + AP_ROWS - 1) / AP_ROWS;
         bytes += 6.0 * (double)w[k] * h[k];
     }
     if (af.empty()) return MI355_OK;
-    DevBuf& daf = ctx->buf("gain_apply_frames");
-    MI_HIP(daf.reserve(sizeof(ApplyFrame) * af.size()));
-    MI_HIP(hipMemcpyAsync(daf.p, af.data(), sizeof(ApplyFrame) * af.size(), hipMemcpyHostToDevice, ctx->stream));
+    DevBuf& daf = ctx->buf(buf);
+    MI_HIP(daf.reserve(sizeof(Rec) * af.size()));
+    MI_HIP(hipMemcpyAsync(daf.p, af.data(), sizeof(Rec) * af.size(), hipMemcpyHostToDevice, ctx->stream));
     {
-        ProfScope ps(ctx, "gain_apply", bytes);
-        hipLaunchKernelGGL(gain_apply_kernel, dim3(blocks), dim3(AP_NT), 0, ctx->stream, daf.as<ApplyFrame>(), (int)af.size());
+        ProfScope ps(ctx, scope, bytes);
+        MI_HIP(launch(daf.as<Rec>(), (int)af.size(), blocks));
         MI_HIP(hipGetLastError());
     }
-    MI_HIP(hipStreamSynchronize(ctx->stream));                 // af is a local
+    MI_HIP(hipStreamSynchronize(ctx->stream));                 // af and what fill gathered are locals
     return MI355_OK;
 }
 
+int apply_gains(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n, const float* gains) {
+    std::string err;
+    if (!d_src || !d_dst || !w || !h || !ws || !gains) { ctx->set_error("apply_gains: NULL argument"); return MI355_ERR_ARG; }
+    if (!check_frames_n(n, err)) { ctx->set_error("apply_gains: " + err); return MI355_ERR_ARG; }
+    { const int rc = check_apply_frames(ctx, "apply_gains", d_src, d_dst, w, h, ws, n, gains, 3); if (rc != MI355_OK) return rc; }
+    return launch_apply<ApplyFrame>(ctx, "gain_apply_frames", "gain_apply", d_src, d_dst, w, h, ws, n, gains, 3,
+        [](ApplyFrame& f, const float* g) { for (int c = 0; c < 3; c++) f.g[c] = g[c]; },
+        [&](const ApplyFrame* d_af, int nf, int blocks) {
+            hipLaunchKernelGGL(gain_apply_kernel, dim3(blocks), dim3(AP_NT), 0, ctx->stream, d_af, nf);
+            return hipSuccess;
+        });
+}
+
+// the frames whose `per` gains are not all 1: what a compensate call applies in place.  The others (the frames the render skips; their
+// pointers may be NULL) are left out and so not touched.
+struct NonUnit {
+    std::vector<uint8_t*> img;
+    std::vector<int> w, h, ws;
+    std::vector<float> g;
+    NonUnit(uint8_t* const* d_imgs, const int* w_, const int* h_, const int* ws_, int n, const float* gains, int per) {
+        for (int k = 0; k < n; k++) {
+            if (all_one(gains + (size_t)per * k, per)) continue;
+            img.push_back(d_imgs[k]); w.push_back(w_[k]); h.push_back(h_[k]); ws.push_back(ws_[k]);
+            g.insert(g.end(), gains + (size_t)per * k, gains + (size_t)per * (k + 1));
+        }
+    }
+    const uint8_t* const* src() const { return (const uint8_t* const*)img.data(); }
+};
+
 // ---- block gains: a gain map per frame (include/mi355_mosaic.h, "block gain compensation") ------------------------------------------------
-//   block_gain_stats_kernel    gain_stats_kernel's work list, map and samples; the sums are binned by (cell_a, cell_b).  A lane adds up its four
+//   block_gain_stats_kernel    gain_stats_kernel's work list and walk; the sums are binned by (cell_a, cell_b).  A lane adds up its four
 //                              points in registers while their key stays the same; a wave whose lanes all end with one and the same key (the
 //                              usual tile: a cell is hundreds of canvas pixels wide) reduces with shuffles as gain_stats_kernel does, every
 //                              other lane adds its run to an LDS table keyed by hashing (BG_SLOTS = 1024 slots for at most 1024 points of a
@@ -521,10 +392,9 @@ int apply_gains(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_d
 //   block_gain_compact_kernel  the table's entries with n > 0 become records (order arbitrary: the host sorts them).  The record buffer holds
 //                              sum over the batch's pairs of min(cells^2, lattice points of the pair's tiles), which no batch can exceed;
 //                              the kernel checks the slot all the same and the launcher fails on the flag.
-//   block_gain_apply_kernel    gain_apply_kernel's row streaming with the header's integer interpolation in the LUT's place: per workgroup the
+//   block_gain_apply_kernel    gain_apply_kernel's stream_rows with the header's integer interpolation in the LUT's place: per workgroup the
 //                              16 rows' R_i (grid_x x 3 each) and the columns' (i0, fx) in LDS, so the divisions happen once per 16 rows.
-constexpr int BG_MAX_GRID = 16, BG_SLOTS = 1024, BG_MAX_SMOOTH = 8;
-constexpr int BG_MAX_DIM = 1 << 20;
+constexpr int BG_SLOTS = 1024;
 constexpr size_t BG_TABLE_BYTES = (size_t)32 << 20;
 constexpr int BA_COLS = 8192;                   // widest frame whose column table fits; wider frames compute (i0, fx) per pixel
 
@@ -537,6 +407,7 @@ __device__ __forceinline__ int bg_cell(int xi, int g, int w, float rw) {
     return q;
 }
 
+// a lane's run v (NV fields) into key's slot of the LDS table
 template <int NV>
 __device__ __forceinline__ void bg_flush(int* s_key, int (*s_val)[BG_SLOTS], int key, const int (&v)[7]) {
     unsigned s = ((unsigned)key * 2654435761u) >> 22;                    // 10 bits
@@ -671,8 +542,6 @@ __global__ __launch_bounds__(256) void block_gain_compact_kernel(const unsigned 
     out[slot] = r;
 }
 
-struct BlockApplyFrame { const uint8_t* src; uint8_t* dst; int w, h, ws, first_block; int q_off; int _pad; };
-
 // the header's i0 and fx (or j0 and fy) of pixel x along an axis of w pixels and g cells
 __device__ __forceinline__ void bg_axis(int x, int g, int w, unsigned& i0, unsigned& f) {
     int num = (2 * x + 1) * g - w;
@@ -683,17 +552,31 @@ __device__ __forceinline__ void bg_axis(int x, int g, int w, unsigned& i0, unsig
     f = (((unsigned)num - i0 * d) * 256u) / d;
 }
 
+// the block form's cursor: pixel x and channel c of the current byte, and the pixel's column (offsets of R_i0, R_i1 in the row's R, and fx),
+// loaded anew whenever x changes
+struct BlockCursor {
+    const uint32_t* R; const uint16_t* cols; bool table; int w, gx;       // the row's R_i; the column table (i0 << 8 | fx) where table
+    int x, c; unsigned o0, o1, fx;
+    __device__ __forceinline__ void column() {
+        const int xc = x < w ? x : w - 1;
+        unsigned i0;
+        if (table) { const unsigned e = cols[xc]; i0 = e >> 8; fx = e & 255u; }
+        else bg_axis(xc, gx, w, i0, fx);
+        o0 = 3u * i0; o1 = 3u * min(i0 + 1u, (unsigned)gx - 1u);
+    }
+    __device__ __forceinline__ void seek(int off) { x = off / 3; c = off - 3 * x; column(); }
+    __device__ __forceinline__ unsigned map(unsigned v) const {
+        const unsigned G = (256u - fx) * R[o0 + c] + fx * R[o1 + c];
+        const unsigned o = (((G + 128u) >> 8) * v + (1u << 19)) >> 20;
+        return o > 255u ? 255u : o;
+    }
+    __device__ __forceinline__ void next() { if (c == 2) { c = 0; x++; column(); } else c++; }
+};
+
 __global__ __launch_bounds__(AP_NT) void block_gain_apply_kernel(const BlockApplyFrame* frames, int nf, const uint16_t* qs, int gx, int gy) {
     __shared__ uint16_t s_col[BA_COLS];                         // i0 << 8 | fx
-    __shared__ uint32_t s_R[AP_ROWS][BG_MAX_GRID * 3];          // R_i of the workgroup's rows, [i][channel]
-    __shared__ int s_k;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = nf - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (frames[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-        s_k = lo;
-    }
-    __syncthreads();
-    const BlockApplyFrame& f = frames[s_k];
+    __shared__ uint32_t s_R[AP_ROWS][MAX_GRID * 3];             // R_i of the workgroup's rows, [i][channel]
+    const BlockApplyFrame& f = frame_of_block(frames, nf);
     const int y0 = ((int)blockIdx.x - f.first_block) * AP_ROWS;
     const int g3 = gx * 3;
     for (int e = threadIdx.x; e < AP_ROWS * g3; e += AP_NT) {
@@ -713,123 +596,35 @@ __global__ __launch_bounds__(AP_NT) void block_gain_apply_kernel(const BlockAppl
             s_col[x] = (uint16_t)(i0 << 8 | fx);
         }
     __syncthreads();
-    const int nb = 3 * f.w;
-    const unsigned glast = (unsigned)gx - 1u;
-    auto column = [&](int x, unsigned& o0, unsigned& o1, unsigned& fx) {      // offsets of R_i0, R_i1 in a row of s_R
-        x = x < f.w ? x : f.w - 1;
-        unsigned i0;
-        if (table) { const unsigned e = s_col[x]; i0 = e >> 8; fx = e & 255u; }
-        else bg_axis(x, gx, f.w, i0, fx);
-        o0 = 3u * i0; o1 = 3u * min(i0 + 1u, glast);
-    };
-    auto gain = [&](const uint32_t* R, unsigned o0, unsigned o1, unsigned fx, int c, unsigned v) {
-        const unsigned G = (256u - fx) * R[o0 + c] + fx * R[o1 + c];
-        const unsigned o = (((G + 128u) >> 8) * v + (1u << 19)) >> 20;
-        return o > 255u ? 255u : o;
-    };
-    auto byte_at = [&](const uint32_t* R, int i, unsigned v) {
-        const int x = i / 3;
-        unsigned o0, o1, fx;
-        column(x, o0, o1, fx);
-        return (uint8_t)gain(R, o0, o1, fx, i - 3 * x, v);
-    };
-    for (int y = y0; y < y0 + AP_ROWS && y < f.h; y++) {
-        const uint32_t* R = s_R[y - y0];
-        const uint8_t* srow = f.src + (size_t)y * f.ws;
-        uint8_t* drow = f.dst + (size_t)y * f.ws;
-        int head = (int)((16 - ((uintptr_t)srow & 15)) & 15);
-        if (head > nb) head = nb;
-        const bool vec = (((uintptr_t)(drow + head)) & 15) == 0;
-        const int nvec = vec ? (nb - head) >> 4 : 0;
-        const int tail = head + 16 * nvec;
-        for (int i = threadIdx.x; i < nvec; i += AP_NT) {
-            const int off = head + 16 * i;
-            const uint4 in = *reinterpret_cast<const uint4*>(srow + off);
-            const unsigned w4[4] = {in.x, in.y, in.z, in.w};
-            unsigned o4[4];
-            int x = off / 3, c = off - 3 * x;
-            unsigned o0, o1, fx;
-            column(x, o0, o1, fx);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                unsigned o = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    o |= gain(R, o0, o1, fx, c, (w4[q] >> (8 * j)) & 0xffu) << (8 * j);
-                    if (c == 2) { c = 0; x++; column(x, o0, o1, fx); } else c++;
-                }
-                o4[q] = o;
-            }
-            *reinterpret_cast<uint4*>(drow + off) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-        }
-        // the row's ends (or the whole row where src and dst are not aligned alike): bytes
-        const int nhead = vec ? head : nb;
-        for (int i = threadIdx.x; i < nhead; i += AP_NT) drow[i] = byte_at(R, i, srow[i]);
-        if (vec)
-            for (int i = tail + (int)threadIdx.x; i < nb; i += AP_NT) drow[i] = byte_at(R, i, srow[i]);
-    }
-}
-
-bool check_grid(int gx, int gy, std::string& err) {
-    if (gx < 1 || gx > BG_MAX_GRID || gy < 1 || gy > BG_MAX_GRID) { err = "grid " + std::to_string(gx) + "x" + std::to_string(gy) + " outside [1, 16] x [1, 16]"; return false; }
-    return true;
-}
-
-bool check_block_params(const mi355_block_gain_params& p, bool need_step, std::string& err) {
-    mi355_gain_params g;
-    g.sigma_n = p.sigma_n; g.sigma_g = p.sigma_g; g.channels = p.channels; g.step = p.step;
-    if (!check_params(g, need_step, err) || !check_grid(p.grid_x, p.grid_y, err)) return false;
-    if (p.smooth < 0 || p.smooth > BG_MAX_SMOOTH) { err = "smooth=" + std::to_string(p.smooth) + " outside [0, 8]"; return false; }
-    return true;
+    stream_rows(f, y0, [&](int r) __attribute__((always_inline)) { return BlockCursor{s_R[r], s_col, table, f.w, gx, 0, 0, 0u, 0u, 0u}; });
 }
 
 int block_gain_stats(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s, const int32_t* pairs_ab,
                      int n_pairs, int step, int gx, int gy, std::vector<mi355_block_gain_stats>& recs, int64_t* cell_cover) {
     const std::string who = "block_gain_stats: ";
-    std::string err;
     recs.clear();
-    if (!d_imgs || !w || !h || !ws || !h9s || (n_pairs > 0 && !pairs_ab) || n_pairs < 0) { ctx->set_error(who + "NULL argument or n_pairs < 0"); return MI355_ERR_ARG; }
-    if (!check_frames_n(n, err) || !check_pairs(pairs_ab, n_pairs, n, err) || !check_grid(gx, gy, err)) { ctx->set_error(who + err); return MI355_ERR_ARG; }
-    if (step < 1 || step > 64) { ctx->set_error(who + "step=" + std::to_string(step) + " outside [1, 64]"); return MI355_ERR_ARG; }
-    int cw, ch, cws; float dG[2];
-    if (mi355_mosaic_layout(w, h, n, h9s, &cw, &ch, &cws, dG) != MI355_OK) { ctx->set_error(who + "no image with h[8] != 0 / empty canvas"); return MI355_ERR_FAILED; }
-    std::vector<FrameDev> fr((size_t)n);
-    std::vector<char> part((size_t)n, 0);
-    for (int k = 0; k < n; k++) {
-        if (!mi_frame_dev_setup(h9s + 9 * k, w[k], h[k], dG, cw, ch, 0, ch, fr[k])) continue;
-        const std::string fk = who + "frame " + std::to_string(k);
-        if (w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k] || w[k] > BG_MAX_DIM || h[k] > BG_MAX_DIM) { ctx->set_error(fk + ": bad geometry w=" + std::to_string(w[k]) + " h=" + std::to_string(h[k]) + " ws=" + std::to_string(ws[k])); return MI355_ERR_ARG; }
-        if (w[k] < gx || h[k] < gy) { ctx->set_error(fk + " (" + std::to_string(w[k]) + "x" + std::to_string(h[k]) + ") is smaller than the " + std::to_string(gx) + "x" + std::to_string(gy) + " grid"); return MI355_ERR_ARG; }
-        if (!d_imgs[k]) { ctx->set_error(fk + " takes part but its pointer is NULL"); return MI355_ERR_ARG; }
-        fr[k].src = d_imgs[k]; fr[k].w = w[k]; fr[k].h = h[k]; fr[k].ws = ws[k];
-        part[k] = 1;
-    }
+    StatsFrames s;
+    const int grid[2] = {gx, gy};
+    { const int rc = stats_setup(ctx, who, d_imgs, w, h, ws, n, h9s, pairs_ab, n_pairs, step, grid, s); if (rc != MI355_OK) return rc; }
     const int cells = gx * gy;
     const size_t c2 = (size_t)cells * cells;
     const int per_batch = (int)std::max<size_t>(1, BG_TABLE_BYTES / (c2 * 7 * sizeof(unsigned long long)));
     const size_t n_cover = (size_t)n * cells;
-    DevBuf& dfr = ctx->buf("gain_frames"); DevBuf& dt = ctx->buf("gain_tiles"); DevBuf& dacc = ctx->buf("block_gain_acc");
+    DevBuf& dt = ctx->buf("gain_tiles"); DevBuf& dacc = ctx->buf("block_gain_acc");
     DevBuf& dcov = ctx->buf("block_gain_cover"); DevBuf& dout = ctx->buf("block_gain_records"); DevBuf& dcnt = ctx->buf("block_gain_count");
-    MI_HIP(dfr.reserve(sizeof(FrameDev) * (size_t)n));
     MI_HIP(dcov.reserve(sizeof(unsigned long long) * n_cover));
     MI_HIP(dcnt.reserve(2 * sizeof(unsigned)));
-    MI_HIP(hipMemcpyAsync(dfr.p, fr.data(), sizeof(FrameDev) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     MI_HIP(hipMemsetAsync(dcov.p, 0, sizeof(unsigned long long) * n_cover, ctx->stream));
     std::vector<GainTile> tiles;
     for (int p0 = 0; p0 == 0 || p0 < n_pairs; p0 += per_batch) {
         const int np = std::min(per_batch, n_pairs - p0);
         const size_t plane = (size_t)std::max(np, 0) * c2;
         tiles.clear();
-        if (p0 == 0)
-            for (int k = 0; k < n; k++)
-                if (part[k]) push_tiles(tiles, k, -1, k, fr[k].begX, fr[k].endX, fr[k].begY, fr[k].endY, step);
+        if (p0 == 0) s.push_cover_tiles(tiles, step);
         size_t cap = 0;                                                // records this batch can give
         for (int p = p0; p < p0 + np; p++) {
-            const int a = pairs_ab[2 * p], b = pairs_ab[2 * p + 1];
-            if (!part[a] || !part[b]) continue;
-            const FrameDev &A = fr[a], &B = fr[b];
             const size_t t0 = tiles.size();
-            push_tiles(tiles, a, b, p - p0, std::max(A.begX, B.begX), std::min(A.endX, B.endX), std::max(A.begY, B.begY), std::min(A.endY, B.endY), step);
+            s.push_pair_tiles(tiles, pairs_ab[2 * p], pairs_ab[2 * p + 1], p - p0, step);
             size_t pts = 0;
             for (size_t t = t0; t < tiles.size(); t++) pts += (size_t)(tiles[t].lx1 - tiles[t].lx0 + 1) * (size_t)(tiles[t].ly1 - tiles[t].ly0 + 1);
             cap += std::min(pts, c2);
@@ -844,8 +639,8 @@ int block_gain_stats(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w,
         MI_HIP(hipMemsetAsync(dcnt.p, 0, 2 * sizeof(unsigned), ctx->stream));
         {
             ProfScope ps(ctx, "block_gain_stats", 0.0);
-            hipLaunchKernelGGL(block_gain_stats_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, ctx->stream, dfr.as<FrameDev>(), dt.as<GainTile>(), step,
-                               dG[0], dG[1], gx, gy, dacc.as<unsigned long long>(), plane, dcov.as<unsigned long long>());
+            hipLaunchKernelGGL(block_gain_stats_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, ctx->stream, s.d_fr, dt.as<GainTile>(), step, s.dG[0], s.dG[1],
+                               gx, gy, dacc.as<unsigned long long>(), plane, dcov.as<unsigned long long>());
             MI_HIP(hipGetLastError());
         }
         unsigned cnt[2] = {0, 0};
@@ -877,51 +672,6 @@ int block_gain_stats(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w,
     return MI355_OK;
 }
 
-int solve_block_gains(const mi355_block_gain_stats* rs, int64_t n_recs, const int32_t* pairs_ab, int n_pairs, const int64_t* cell_cover, int n,
-                      const mi355_block_gain_params& prm, float* gains, std::string& err) {
-    if (!check_frames_n(n, err) || !check_block_params(prm, false, err)) return MI355_ERR_ARG;
-    if (n_recs < 0 || n_pairs < 0 || (n_recs > 0 && !rs) || (n_pairs > 0 && !pairs_ab) || !cell_cover || !gains) { err = "NULL argument or a count < 0"; return MI355_ERR_ARG; }
-    if (!check_pairs(pairs_ab, n_pairs, n, err)) return MI355_ERR_ARG;
-    const int gx = prm.grid_x, gy = prm.grid_y, cells = gx * gy;
-    if (n_recs > (int64_t)0x7fffffff) { err = "n_records=" + std::to_string(n_recs) + " too large"; return MI355_ERR_ARG; }
-    std::vector<mi355_gain_pair_stats> edges((size_t)n_recs);
-    for (int64_t i = 0; i < n_recs; i++) {
-        const mi355_block_gain_stats& r = rs[i];
-        const std::string ri = "record " + std::to_string(i);
-        if (r.pair < 0 || r.pair >= n_pairs) { err = ri + ": pair=" + std::to_string(r.pair) + " outside [0, " + std::to_string(n_pairs) + ")"; return MI355_ERR_ARG; }
-        if (r.cell_a < 0 || r.cell_a >= cells || r.cell_b < 0 || r.cell_b >= cells) { err = ri + ": cell (" + std::to_string(r.cell_a) + ", " + std::to_string(r.cell_b) + ") outside [0, " + std::to_string(cells) + ")"; return MI355_ERR_ARG; }
-        if (r.n < 0) { err = ri + ": n=" + std::to_string(r.n) + " < 0"; return MI355_ERR_ARG; }
-        mi355_gain_pair_stats& e = edges[(size_t)i];
-        e.a = pairs_ab[2 * r.pair] * cells + r.cell_a; e.b = pairs_ab[2 * r.pair + 1] * cells + r.cell_b; e.n = r.n;
-        for (int c = 0; c < 3; c++) { e.sum_a[c] = r.sum_a[c]; e.sum_b[c] = r.sum_b[c]; }
-    }
-    const int nodes = n * cells;
-    for (int i = 0; i < nodes; i++)
-        if (cell_cover[i] < 0) { err = "frame " + std::to_string(i / cells) + " cell " + std::to_string(i % cells) + ": cell_cover=" + std::to_string(cell_cover[i]) + " < 0"; return MI355_ERR_ARG; }
-    mi355_gain_params gp;
-    gp.sigma_n = prm.sigma_n; gp.sigma_g = prm.sigma_g; gp.channels = prm.channels; gp.step = prm.step;
-    std::vector<double> x3((size_t)nodes * 3);
-    const int rc = solve_nodes(edges.data(), (int)n_recs, cell_cover, nodes, gp, "node", true, x3.data(), err);
-    if (rc != MI355_OK) return rc;
-    // smoothing: per frame and channel, x then y, edges replicated
-    std::vector<double> a((size_t)cells), b((size_t)cells);
-    for (int k = 0; k < n; k++)
-        for (int c = 0; c < 3; c++) {
-            double* m = x3.data() + (size_t)k * cells * 3 + c;           // m[3 * cell]
-            for (int i = 0; i < cells; i++) a[i] = m[3 * i];
-            for (int s = 0; s < prm.smooth; s++) {
-                for (int y = 0; y < gy; y++)
-                    for (int x = 0; x < gx; x++)
-                        b[y * gx + x] = 0.25 * a[y * gx + std::max(x - 1, 0)] + 0.5 * a[y * gx + x] + 0.25 * a[y * gx + std::min(x + 1, gx - 1)];
-                for (int y = 0; y < gy; y++)
-                    for (int x = 0; x < gx; x++)
-                        a[y * gx + x] = 0.25 * b[std::max(y - 1, 0) * gx + x] + 0.5 * b[y * gx + x] + 0.25 * b[std::min(y + 1, gy - 1) * gx + x];
-            }
-            for (int i = 0; i < cells; i++) gains[((size_t)k * cells + i) * 3 + c] = (float)a[i];
-        }
-    return MI355_OK;
-}
-
 int apply_block_gains(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n, int gx, int gy,
                       const float* gains) {
     const std::string who = "apply_block_gains";
@@ -932,62 +682,31 @@ int apply_block_gains(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* cons
     { const int rc = check_apply_frames(ctx, who, d_src, d_dst, w, h, ws, n, gains, per); if (rc != MI355_OK) return rc; }
     for (int k = 0; k < n; k++)
         if (w[k] > BG_MAX_DIM || h[k] > BG_MAX_DIM) { ctx->set_error(who + ": frame " + std::to_string(k) + ": w=" + std::to_string(w[k]) + " h=" + std::to_string(h[k]) + " above 2^20"); return MI355_ERR_ARG; }
-    std::vector<BlockApplyFrame> af;
-    std::vector<uint16_t> qs;
-    int blocks = 0;
-    double bytes = 0.0;
-    for (int k = 0; k < n; k++) {
-        const float* g = gains + (size_t)per * k;
-        bool unit = true;
-        for (int i = 0; i < per; i++) unit = unit && g[i] == 1.0f;
-        if (unit && d_src[k] == d_dst[k]) continue;                       // in place with a map of 1: the bytes stay as they are
-        BlockApplyFrame f;
-        f.src = d_src[k]; f.dst = d_dst[k]; f.w = w[k]; f.h = h[k]; f.ws = ws[k]; f.first_block = blocks; f.q_off = (int)qs.size(); f._pad = 0;
-        for (int i = 0; i < per; i++) {
-            double q = std::floor((double)g[i] * 4096.0 + 0.5);
-            q = q < 0.0 ? 0.0 : (q > 32767.0 ? 32767.0 : q);
-            qs.push_back((uint16_t)(int)q);
-        }
-        af.push_back(f);
-        blocks += (h[k] + AP_ROWS - 1) / AP_ROWS;
-        bytes += 6.0 * (double)w[k] * h[k];
-    }
-    if (af.empty()) return MI355_OK;
-    DevBuf& daf = ctx->buf("block_gain_apply_frames"); DevBuf& dq = ctx->buf("block_gain_apply_q");
-    MI_HIP(daf.reserve(sizeof(BlockApplyFrame) * af.size()));
-    MI_HIP(dq.reserve(sizeof(uint16_t) * qs.size()));
-    MI_HIP(hipMemcpyAsync(daf.p, af.data(), sizeof(BlockApplyFrame) * af.size(), hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dq.p, qs.data(), sizeof(uint16_t) * qs.size(), hipMemcpyHostToDevice, ctx->stream));
-    {
-        ProfScope ps(ctx, "block_gain_apply", bytes);
-        hipLaunchKernelGGL(block_gain_apply_kernel, dim3(blocks), dim3(AP_NT), 0, ctx->stream, daf.as<BlockApplyFrame>(), (int)af.size(), dq.as<uint16_t>(), gx, gy);
-        MI_HIP(hipGetLastError());
-    }
-    MI_HIP(hipStreamSynchronize(ctx->stream));                 // af, qs are locals
-    return MI355_OK;
+    std::vector<uint16_t> qs;                                          // the Q12 maps of the frames that get a record
+    return launch_apply<BlockApplyFrame>(ctx, "block_gain_apply_frames", "block_gain_apply", d_src, d_dst, w, h, ws, n, gains, per,
+        [&](BlockApplyFrame& f, const float* g) {
+            f.q_off = (int)qs.size();
+            for (int i = 0; i < per; i++) {
+                double q = std::floor((double)g[i] * 4096.0 + 0.5);
+                q = q < 0.0 ? 0.0 : (q > 32767.0 ? 32767.0 : q);
+                qs.push_back((uint16_t)(int)q);
+            }
+        },
+        [&](const BlockApplyFrame* d_af, int nf, int blocks) {
+            DevBuf& dq = ctx->buf("block_gain_apply_q");
+            hipError_t e = dq.reserve(sizeof(uint16_t) * qs.size());
+            if (e == hipSuccess) e = hipMemcpyAsync(dq.p, qs.data(), sizeof(uint16_t) * qs.size(), hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess) hipLaunchKernelGGL(block_gain_apply_kernel, dim3(blocks), dim3(AP_NT), 0, ctx->stream, d_af, nf, dq.as<uint16_t>(), gx, gy);
+            return e;
+        });
 }
 
 }  // namespace
-
-extern "C" void mi355_default_gain_params(mi355_gain_params* p) {
-    if (!p) return;
-    p->sigma_n = 10.0f; p->sigma_g = 0.1f; p->channels = 3; p->step = 8;
-}
 
 extern "C" int mi355_gain_stats_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                     const int32_t* pairs_ab, int n_pairs, int step, mi355_gain_pair_stats* pair_stats, int64_t* frame_cover) {
     LOCKED_PROLOGUE
     return gain_stats(ctx, d_imgs, w, h, ws, n, h9s, pairs_ab, n_pairs, step, pair_stats, frame_cover);
-}
-
-extern "C" int mi355_solve_gains(const mi355_gain_pair_stats* pair_stats, int n_pairs, const int64_t* frame_cover, int n, const mi355_gain_params* p,
-                                 float* gains) {
-    mi355_gain_params dp;
-    if (!p) { mi355_default_gain_params(&dp); p = &dp; }
-    std::string err;
-    const int rc = solve_gains(pair_stats, n_pairs, frame_cover, n, *p, gains, err);
-    if (rc != MI355_OK) mi_set_host_error("solve_gains: " + err);
-    return rc;
 }
 
 extern "C" int mi355_apply_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n,
@@ -1002,7 +721,7 @@ extern "C" int mi355_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs,
     mi355_gain_params dp;
     if (!p) { mi355_default_gain_params(&dp); p = &dp; }
     std::string err;
-    if (!check_params(*p, true, err)) { ctx->set_error("gain_compensate: " + err); return MI355_ERR_ARG; }
+    if (!check_params(p->sigma_n, p->sigma_g, p->channels, &p->step, err)) { ctx->set_error("gain_compensate: " + err); return MI355_ERR_ARG; }
     if (!check_frames_n(n, err)) { ctx->set_error("gain_compensate: " + err); return MI355_ERR_ARG; }
     std::vector<mi355_gain_pair_stats> st((size_t)std::max(n_pairs, 1));
     std::vector<int64_t> cover((size_t)n);
@@ -1011,26 +730,11 @@ extern "C" int mi355_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs,
     std::vector<float> g((size_t)n * 3);
     rc = solve_gains(st.data(), n_pairs, cover.data(), n, *p, g.data(), err);
     if (rc != MI355_OK) { ctx->set_error("gain_compensate: " + err); return rc; }
-    // frames the render skips keep gain 1 and are not touched (their pointers may be NULL)
-    std::vector<const uint8_t*> src((size_t)n);
-    std::vector<uint8_t*> dst((size_t)n);
-    std::vector<int> ww((size_t)n), hh((size_t)n), ss((size_t)n);
-    std::vector<float> gg;
-    int m = 0;
-    for (int k = 0; k < n; k++) {
-        if (g[3 * k] == 1.0f && g[3 * k + 1] == 1.0f && g[3 * k + 2] == 1.0f) continue;
-        src[m] = d_imgs[k]; dst[m] = d_imgs[k]; ww[m] = w[k]; hh[m] = h[k]; ss[m] = ws[k];
-        gg.insert(gg.end(), g.begin() + 3 * k, g.begin() + 3 * k + 3);
-        m++;
-    }
-    if (m > 0) { rc = apply_gains(ctx, src.data(), dst.data(), ww.data(), hh.data(), ss.data(), m, gg.data()); if (rc != MI355_OK) return rc; }
+    const NonUnit nu(d_imgs, w, h, ws, n, g.data(), 3);
+    if (!nu.img.empty()) rc = apply_gains(ctx, nu.src(), nu.img.data(), nu.w.data(), nu.h.data(), nu.ws.data(), (int)nu.img.size(), nu.g.data());
+    if (rc != MI355_OK) return rc;
     if (gains_out) std::copy(g.begin(), g.end(), gains_out);
     return MI355_OK;
-}
-
-extern "C" void mi355_default_block_gain_params(mi355_block_gain_params* p) {
-    if (!p) return;
-    p->sigma_n = 10.0f; p->sigma_g = 0.1f; p->channels = 3; p->step = 8; p->grid_x = 8; p->grid_y = 6; p->smooth = 2; p->reserved = 0;
 }
 
 extern "C" int mi355_block_gain_stats_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
@@ -1047,16 +751,6 @@ extern "C" int mi355_block_gain_stats_dev(mi355_ctx* ctx, const uint8_t* const* 
     std::copy(recs.begin(), recs.end(), out);
     *records = out; *n_records = (int64_t)recs.size();
     return MI355_OK;
-}
-
-extern "C" int mi355_solve_block_gains(const mi355_block_gain_stats* records, int64_t n_records, const int32_t* pairs_ab, int n_pairs, const int64_t* cell_cover,
-                                       int n, const mi355_block_gain_params* p, float* gains) {
-    mi355_block_gain_params dp;
-    if (!p) { mi355_default_block_gain_params(&dp); p = &dp; }
-    std::string err;
-    const int rc = solve_block_gains(records, n_records, pairs_ab, n_pairs, cell_cover, n, *p, gains, err);
-    if (rc != MI355_OK) mi_set_host_error("solve_block_gains: " + err);
-    return rc;
 }
 
 extern "C" int mi355_apply_block_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws, int n,
@@ -1080,19 +774,9 @@ extern "C" int mi355_block_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d
     std::vector<float> g((size_t)n * per);
     rc = solve_block_gains(recs.data(), (int64_t)recs.size(), pairs_ab, n_pairs, cover.data(), n, *p, g.data(), err);
     if (rc != MI355_OK) { ctx->set_error("block_gain_compensate: " + err); return rc; }
-    // frames the render skips keep a map of 1 and are not touched (their pointers may be NULL)
-    std::vector<const uint8_t*> src;
-    std::vector<uint8_t*> dst;
-    std::vector<int> ww, hh, ss;
-    std::vector<float> gg;
-    for (int k = 0; k < n; k++) {
-        bool unit = true;
-        for (int i = 0; i < per; i++) unit = unit && g[(size_t)per * k + i] == 1.0f;
-        if (unit) continue;
-        src.push_back(d_imgs[k]); dst.push_back(d_imgs[k]); ww.push_back(w[k]); hh.push_back(h[k]); ss.push_back(ws[k]);
-        gg.insert(gg.end(), g.begin() + (size_t)per * k, g.begin() + (size_t)per * (k + 1));
-    }
-    if (!src.empty()) { rc = apply_block_gains(ctx, src.data(), dst.data(), ww.data(), hh.data(), ss.data(), (int)src.size(), p->grid_x, p->grid_y, gg.data()); if (rc != MI355_OK) return rc; }
+    const NonUnit nu(d_imgs, w, h, ws, n, g.data(), per);
+    if (!nu.img.empty()) rc = apply_block_gains(ctx, nu.src(), nu.img.data(), nu.w.data(), nu.h.data(), nu.ws.data(), (int)nu.img.size(), p->grid_x, p->grid_y, nu.g.data());
+    if (rc != MI355_OK) return rc;
     if (gains_out) std::copy(g.begin(), g.end(), gains_out);
     return MI355_OK;
 }

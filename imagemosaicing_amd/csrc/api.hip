@@ -3,6 +3,7 @@
 // There is no CPU compute path in this library: without a usable gfx950 device mi355_create fails.
 #include "common.h"
 #include "mosaic_frame.h"
+#include <memory>
 #include <new>
 
 static thread_local std::string g_create_error;   // mi355_last_error(NULL): the calling thread's last creation error (or ctx-less call's error)
@@ -266,18 +267,16 @@ extern "C" int mi355_ransac2d(mi355_ctx* ctx, const mi355_sfpoint* p1, const mi3
     int rc = mi_ransac_batch(ctx, d1.as<mi355_sfpoint>(), d2.as<mi355_sfpoint>(), dn.as<int>(), &n, 1, MI355_MAX_SELECTED, dist, sample_times, seed,
                              dres.as<mi355_pair_result>());
     if (rc != MI355_OK) return rc;
-    mi355_pair_result* r = (mi355_pair_result*)malloc(sizeof(mi355_pair_result));
+    const std::unique_ptr<mi355_pair_result> r(new (std::nothrow) mi355_pair_result);      // 10 KB: not on the caller's stack
     if (!r) return MI355_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(r, dres.p, sizeof(mi355_pair_result), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = hipMemcpyAsync(r.get(), dres.p, sizeof(mi355_pair_result), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(r); ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
+    if (e != hipSuccess) { ctx->set_error(hipGetErrorString(e)); return MI355_ERR_DEVICE; }
     *n_in = r->n_in;
     if (in1) memcpy(in1, r->a, sizeof(mi355_sfpoint) * r->n_in);
     if (in2) memcpy(in2, r->b, sizeof(mi355_sfpoint) * r->n_in);
     memcpy(H, r->H, sizeof(float) * 9);
-    const int ok = r->ok;
-    free(r);
-    return ok;
+    return r->ok;
 }
 
 // ---- warps ------------------------------------------------------------------------------------------------------

@@ -421,6 +421,11 @@ __global__ void desc_u8_to_f32_kernel(const uint8_t* d8, float* f, size_t count)
     if (i < count) f[i] = (float)d8[i];
 }
 
+// ---- host side ----------------------------------------------------------------------------------------------
+constexpr int chunks_of(int n) { return n > 0 ? (n + KSTRIDE - 1) / KSTRIDE : 1; }                  // chunks of KSTRIDE rows an image is matched in: one at least
+constexpr int row_pad(int n) { return n > 0 ? (n + ROWPAD - 1) / ROWPAD * ROWPAD : ROWPAD; }        // rows of a descriptor matrix: a multiple of ROWPAD, one at least
+inline int pow2_pad(int n) { int m = 64; while (m < n) m <<= 1; return m; }                         // keys select_big_kernel sorts: the next power of two, one wave's step at least
+
 int build_pair_table(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, std::vector<PairDesc>& pd) {
     {                                                       // wait for the frames of THESE pairs only: later batches keep running
         std::vector<int> ids(pairs, pairs + 2 * (size_t)n_pairs);
@@ -445,13 +450,99 @@ int build_pair_table(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, std::vec
     return MI355_OK;
 }
 
+bool pair_is_big(const PairDesc& d) { return d.n_i > KSTRIDE || d.n_j > KSTRIDE; }
+long long sub_pairs_of(const PairDesc& d) { return (long long)chunks_of(d.n_i) * chunks_of(d.n_j); }      // split_large_pairs' (query chunk, train chunk) sub-pairs of a pair
+
+hipError_t reserve_all(std::initializer_list<std::pair<DevBuf*, size_t>> want) {
+    for (const auto& w : want) { const hipError_t e = w.first->reserve(w.second); if (e != hipSuccess) return e; }
+    return hipSuccess;
+}
+
+// The workspaces of the pair stage by role, bound once per call: the names are spelt here and nowhere else in this file (ctx->buf makes the buffer it does
+// not find, so a name spelt differently in two places would be two buffers).  "sel1" / "sel2" / "nsel" are also what SURF's pair stage selects into.
+struct NnBufs {                                           // the 1-NN arrays of a run, indexed alike: train index, squared distance, second-best squared distance
+    DevBuf &idx, &d2, &d2nd;
+    hipError_t reserve(size_t n) { return reserve_all({{&idx, n * 4}, {&d2, n * 4}, {&d2nd, n * 4}}); }
+};
+struct NnView { const void *idx, *d2, *d2nd, *keys; size_t extent; };      // where a run left the results of its first pair, `extent` entries each (mi_bf_match reads them back)
+struct PairWs {
+    DevBuf &pairs, &sub, &big;                            // pair table of the run (finalize_kernel reads it too), sub-pair table, large-pair table
+    NnBufs nn, merged;                                    // KSTRIDE entries per (sub-)pair; large pairs merged over their train chunks, at BigPairDev::off
+    DevBuf &keys, &mkeys;                                 // sorted keys: KSTRIDE per pair (mi_bf_match only) / of the large pairs at BigPairDev::koff
+    DevBuf &sel1, &sel2, &nsel;                           // selected points and their count, by pair of the run
+    explicit PairWs(mi355_ctx* c)
+        : pairs(c->buf("pair_desc")), sub(c->buf("pair_desc_sub")), big(c->buf("big_pairs")),
+          nn{c->buf("nn_idx"), c->buf("nn_d2"), c->buf("nn_2nd")}, merged{c->buf("nnb_idx"), c->buf("nnb_d2"), c->buf("nnb_2nd")},
+          keys(c->buf("sorted_keys")), mkeys(c->buf("sorted_keys_big")), sel1(c->buf("sel1")), sel2(c->buf("sel2")), nsel(c->buf("nsel")) {}
+    // what every run needs: table and selection outputs of n pairs, 1-NN arrays of n_nn (sub-)pairs
+    hipError_t reserve_run(size_t n, size_t n_nn) {
+        const hipError_t e = reserve_all({{&pairs, sizeof(PairDesc) * n}, {&sel1, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * n}, {&sel2, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * n}, {&nsel, sizeof(int) * n}});
+        return e != hipSuccess ? e : nn.reserve(n_nn * KSTRIDE);
+    }
+    // what the large-pair form adds: n large pairs of n_sub sub-pairs, n_merged merged entries and n_keys keys in all
+    hipError_t reserve_big(size_t n, size_t n_sub, size_t n_merged, size_t n_keys) {
+        const hipError_t e = reserve_all({{&sub, sizeof(PairDesc) * n_sub}, {&big, sizeof(BigPairDev) * n}, {&mkeys, n_keys * 8}});
+        return e != hipSuccess ? e : merged.reserve(n_merged);
+    }
+    NnView view(bool large, size_t extent) const { const NnBufs& a = large ? merged : nn; return NnView{a.idx.p, a.d2.p, a.d2nd.p, (large ? mkeys : keys).p, extent}; }
+};
+
+BigPairDev big_pair(int n_i, int n_j, int sub0, long long off, long long koff) { return BigPairDev{n_i, n_j, chunks_of(n_j), sub0, off, koff, pow2_pad(n_i), 0}; }
+
+double match_bytes(const std::vector<PairDesc>& table) {       // algorithmic bytes of the "match" profile class
+    double bytes = 0.0;
+    for (const PairDesc& d : table) bytes += (double)(d.npad_i + d.npad_j) * 128.0 + 8.0 * d.n_i;
+    return bytes;
+}
+
+// bf_match_kernel on the n (sub-)pairs of a device table, nqt query tiles each, into ws.nn; `second`: mi355_bf_match reports the second-best distance, the ratio test reads it
+void launch_match(mi355_ctx* ctx, PairWs& ws, const PairDesc* table, int n, int nqt, bool second) {
+    const auto kernel = second ? bf_match_kernel<true> : bf_match_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nqt * (unsigned)n), dim3(BF_NT), 0, ctx->stream, table, nqt, ws.nn.idx.as<int>(), ws.nn.d2.as<int>(), ws.nn.d2nd.as<int>());
+}
+
+SelectParams select_params(const mi355_ctx* ctx) {
+    const auto& p = ctx->p;
+    return SelectParams{p.max_selected, p.select_fraction, p.grid_x, p.grid_y, p.ratio > 0.0f ? p.ratio * p.ratio : 0.0f};
+}
+
+// sort + grid walk of the n pairs of ws.pairs into ws.sel1 / sel2 / nsel: select_kernel on ws.nn (keys in LDS, kept in ws.keys on request) or, `large`,
+// select_big_kernel on ws.merged by ws.big (keys in ws.mkeys)
+void launch_select(mi355_ctx* ctx, PairWs& ws, int n, bool large, const SelectParams& sp, bool keep_keys) {
+    mi355_sfpoint *s1 = ws.sel1.as<mi355_sfpoint>(), *s2 = ws.sel2.as<mi355_sfpoint>();
+    if (large) hipLaunchKernelGGL(select_big_kernel, dim3(n), dim3(1024), 0, ctx->stream, ws.pairs.as<PairDesc>(), ws.big.as<BigPairDev>(), ws.merged.idx.as<int>(), ws.merged.d2.as<int>(),
+                                  ws.merged.d2nd.as<int>(), sp, ws.mkeys.as<unsigned long long>(), s1, s2, ws.nsel.as<int>());
+    else hipLaunchKernelGGL(select_kernel, dim3(n), dim3(256), 0, ctx->stream, ws.pairs.as<PairDesc>(), ws.nn.idx.as<int>(), ws.nn.d2.as<int>(), ws.nn.d2nd.as<int>(), sp, s1, s2, ws.nsel.as<int>(),
+                            keep_keys ? ws.keys.as<unsigned long long>() : (unsigned long long*)nullptr);
+}
+
+// The large-pair form's decomposition (described at merge_chunks_kernel): the (query chunk, train chunk) sub-pairs of every pair -- each a PairDesc whose pointers start at
+// its chunks -- and where the pair's merged results will lie; off / koff: the merged entries / keys of the run in all
+void split_large_pairs(const std::vector<PairDesc>& pd, std::vector<BigPairDev>& bp, std::vector<PairDesc>& sub, long long& off, long long& koff) {
+    auto chunk = [](const int8_t*& s8, const int*& n8, const float2*& xy, int& n, int& npad, int c) {      // one side of a sub-pair: the rows of chunk c
+        const int r0 = c * KSTRIDE;
+        s8 += (size_t)r0 * 128; n8 += r0; xy += r0;
+        n = std::min(std::max(n - r0, 0), KSTRIDE); npad = row_pad(n);
+    };
+    for (const PairDesc& d : pd) {
+        bp.push_back(big_pair(d.n_i, d.n_j, (int)sub.size(), off, koff));
+        off += d.n_i > 0 ? d.n_i : 1; koff += bp.back().mpad;
+        for (int qc = 0; qc < chunks_of(d.n_i); qc++)
+            for (int tc = 0; tc < chunks_of(d.n_j); tc++) {
+                PairDesc s = d;
+                chunk(s.s8_i, s.n8_i, s.xy_i, s.n_i, s.npad_i, qc);
+                chunk(s.s8_j, s.n8_j, s.xy_j, s.n_j, s.npad_j, tc);
+                sub.push_back(s);
+            }
+    }
+}
+
 }  // namespace
 
 int mi_finish_features(mi355_ctx* ctx, Features& f, const int* d_n, hipStream_t st) {
     if (!st) st = ctx->stream;
     const int nmax = d_n ? KSTRIDE : f.n;
-    f.npad = ((nmax + ROWPAD - 1) / ROWPAD) * ROWPAD;
-    if (f.npad == 0) f.npad = ROWPAD;
+    f.npad = row_pad(nmax);
     MI_HIP(f.xy.reserve(sizeof(float2) * (size_t)(nmax > 0 ? nmax : 1)));
     MI_HIP(f.s8.reserve((size_t)128 * (size_t)f.npad));
     MI_HIP(f.n8.reserve(sizeof(int) * (size_t)f.npad));
@@ -469,7 +560,7 @@ int mi_finish_features_batch(mi355_ctx* ctx, Features* const* fs, int nf, const 
     if (max_rows < KSTRIDE) max_rows = KSTRIDE;          // keep-all frames (nfeatures <= 0) carry up to ctx->keepall_max rows: the large-pair path reads them all
     FinishBatch fb;
     memset(&fb, 0, sizeof(fb));
-    const int npad = ((max_rows + ROWPAD - 1) / ROWPAD) * ROWPAD;
+    const int npad = row_pad(max_rows);
     for (int k = 0; k < nf; k++) {
         Features& f = *fs[k];
         f.npad = npad;
@@ -527,122 +618,43 @@ extern "C" int mi355_get_features(mi355_ctx* ctx, int img_id, mi355_keypoint* kp
     return MI355_OK;
 }
 
-static int run_match_select(mi355_ctx* ctx, const std::vector<PairDesc>& pd, int n_pairs, bool want_sorted_keys) {
-    DevBuf& dpd = ctx->buf("pair_desc");
-    DevBuf& didx = ctx->buf("nn_idx");
-    DevBuf& dd2 = ctx->buf("nn_d2");
-    DevBuf& d2nd = ctx->buf("nn_2nd");
-    DevBuf& ds1 = ctx->buf("sel1");
-    DevBuf& ds2 = ctx->buf("sel2");
-    DevBuf& dns = ctx->buf("nsel");
-    DevBuf& dkeys = ctx->buf("sorted_keys");
-    const size_t nn = (size_t)n_pairs * KSTRIDE;
-    MI_HIP(dpd.reserve(sizeof(PairDesc) * n_pairs));
-    MI_HIP(didx.reserve(nn * 4)); MI_HIP(dd2.reserve(nn * 4)); MI_HIP(d2nd.reserve(nn * 4));
-    MI_HIP(ds1.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * (size_t)n_pairs));
-    MI_HIP(ds2.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * (size_t)n_pairs));
-    MI_HIP(dns.reserve(sizeof(int) * n_pairs));
-    if (want_sorted_keys) MI_HIP(dkeys.reserve(nn * 8));
-    MI_HIP(hipMemcpyAsync(dpd.p, pd.data(), sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipStreamSynchronize(ctx->stream));
-    int max_ni = 1;
-    double flops_bytes = 0.0;
-    for (int p = 0; p < n_pairs; p++) { if (pd[p].n_i > max_ni) max_ni = pd[p].n_i; flops_bytes += (double)(pd[p].npad_i + pd[p].npad_j) * 128.0 + 8.0 * pd[p].n_i; }
-    {
-        ProfScope ps(ctx, "match", flops_bytes);
-        const int nqt = (max_ni + QTILE - 1) / QTILE;
-        const bool second = want_sorted_keys || ctx->p.ratio > 0.0f;      // mi355_bf_match reports it, the ratio test reads it
-        if (second) hipLaunchKernelGGL(bf_match_kernel<true>, dim3((unsigned)nqt * (unsigned)n_pairs), dim3(BF_NT), 0, ctx->stream,
-                                       dpd.as<PairDesc>(), nqt, didx.as<int>(), dd2.as<int>(), d2nd.as<int>());
-        else hipLaunchKernelGGL(bf_match_kernel<false>, dim3((unsigned)nqt * (unsigned)n_pairs), dim3(BF_NT), 0, ctx->stream,
-                                dpd.as<PairDesc>(), nqt, didx.as<int>(), dd2.as<int>(), d2nd.as<int>());
-    }
-    SelectParams sp;
-    sp.max_selected = ctx->p.max_selected; sp.fraction = ctx->p.select_fraction; sp.gx = ctx->p.grid_x; sp.gy = ctx->p.grid_y;
-    sp.ratio2 = ctx->p.ratio > 0.0f ? ctx->p.ratio * ctx->p.ratio : 0.0f;
-    {
-        ProfScope ps(ctx, "select", (double)n_pairs * (KSTRIDE * 12.0 + 9600.0));
-        hipLaunchKernelGGL(select_kernel, dim3(n_pairs), dim3(256), 0, ctx->stream, dpd.as<PairDesc>(), didx.as<int>(), dd2.as<int>(), d2nd.as<int>(),
-                           sp, ds1.as<mi355_sfpoint>(), ds2.as<mi355_sfpoint>(), dns.as<int>(),
-                           want_sorted_keys ? dkeys.as<unsigned long long>() : (unsigned long long*)nullptr);
-    }
-    MI_HIP(hipGetLastError());
-    return MI355_OK;
-}
-
-// The large-pair form of run_match_select (an image of the pair has more than 2048 keypoints): same outputs -- sel1 / sel2 / nsel by pair of the
-// run, "pair_desc" for finalize_kernel -- through the sub-pair decomposition described at merge_chunks_kernel.  The merged 1-NN arrays stay in
-// "nnb_idx" / "nnb_d2" / "nnb_2nd" at off[p] and the sorted keys in "sorted_keys_big" at koff[p] (mi_bf_match reads them back).
-static int run_match_select_big(mi355_ctx* ctx, const std::vector<PairDesc>& pd, int n_pairs, bool want_second, std::vector<BigPairDev>* layout_out = nullptr) {
-    std::vector<BigPairDev> bp(n_pairs);
+// One run of pairs of one kind: match and select.  Leaves sel1 / sel2 / nsel by pair of the run and the pair table for finalize_kernel.  The live path (every image
+// <= 2048 keypoints) matches the plain table, a pair per KSTRIDE entries of ws.nn.  A run of large pairs matches the sub-pairs of split_large_pairs instead and merges
+// them: the merged 1-NN arrays stay in ws.merged at off[p], the sorted keys in ws.mkeys at koff[p].  for_bf_match: the second-best distance and the sorted keys are kept.
+static int run_match_select(mi355_ctx* ctx, PairWs& ws, const std::vector<PairDesc>& pd, bool for_bf_match, NnView* at = nullptr) {
+    const int n_pairs = (int)pd.size();
+    const bool large = pair_is_big(pd[0]);
+    std::vector<BigPairDev> bp;
     std::vector<PairDesc> sub;
     long long off = 0, koff = 0;
+    if (large) split_large_pairs(pd, bp, sub, off, koff);
+    const std::vector<PairDesc>& table = large ? sub : pd;          // what the matcher runs on
+    const int n_table = (int)table.size();
     int max_ni = 1;
-    for (int p = 0; p < n_pairs; p++) {
-        const PairDesc& d = pd[p];
-        const int qc_n = d.n_i > 0 ? (d.n_i + KSTRIDE - 1) / KSTRIDE : 1, tc_n = d.n_j > 0 ? (d.n_j + KSTRIDE - 1) / KSTRIDE : 1;
-        BigPairDev& b = bp[p];
-        b.n_i = d.n_i; b.n_j = d.n_j; b.tc_n = tc_n; b.sub0 = (int)sub.size(); b.off = off; b.koff = koff; b._pad = 0;
-        int mp = 64; while (mp < d.n_i) mp <<= 1;
-        b.mpad = mp;
-        off += d.n_i > 0 ? d.n_i : 1; koff += mp;
-        if (d.n_i > max_ni) max_ni = d.n_i;
-        for (int qc = 0; qc < qc_n; qc++)
-            for (int tc = 0; tc < tc_n; tc++) {
-                PairDesc s = d;
-                const int q0 = qc * KSTRIDE, t0 = tc * KSTRIDE;
-                s.s8_i = d.s8_i + (size_t)q0 * 128; s.n8_i = d.n8_i + q0; s.xy_i = d.xy_i + q0;
-                s.n_i = d.n_i - q0 < KSTRIDE ? (d.n_i - q0 > 0 ? d.n_i - q0 : 0) : KSTRIDE;
-                s.npad_i = ((s.n_i + ROWPAD - 1) / ROWPAD) * ROWPAD; if (s.npad_i == 0) s.npad_i = ROWPAD;
-                s.s8_j = d.s8_j + (size_t)t0 * 128; s.n8_j = d.n8_j + t0; s.xy_j = d.xy_j + t0;
-                s.n_j = d.n_j - t0 < KSTRIDE ? (d.n_j - t0 > 0 ? d.n_j - t0 : 0) : KSTRIDE;
-                s.npad_j = ((s.n_j + ROWPAD - 1) / ROWPAD) * ROWPAD; if (s.npad_j == 0) s.npad_j = ROWPAD;
-                sub.push_back(s);
-            }
+    for (const PairDesc& d : pd) if (d.n_i > max_ni) max_ni = d.n_i;
+    MI_HIP(ws.reserve_run(n_pairs, n_table));
+    if (large) MI_HIP(ws.reserve_big(n_pairs, n_table, (size_t)off, (size_t)koff));
+    else if (for_bf_match) MI_HIP(ws.keys.reserve((size_t)n_pairs * KSTRIDE * 8));
+    MI_HIP(hipMemcpyAsync(ws.pairs.p, pd.data(), sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    if (large) {
+        MI_HIP(hipMemcpyAsync(ws.sub.p, sub.data(), sizeof(PairDesc) * n_table, hipMemcpyHostToDevice, ctx->stream));
+        MI_HIP(hipMemcpyAsync(ws.big.p, bp.data(), sizeof(BigPairDev) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     }
-    const int nsub = (int)sub.size();
-    DevBuf& dpd = ctx->buf("pair_desc"); DevBuf& dsub = ctx->buf("pair_desc_sub"); DevBuf& dbp = ctx->buf("big_pairs");
-    DevBuf& didx = ctx->buf("nn_idx"); DevBuf& dd2 = ctx->buf("nn_d2"); DevBuf& d2nd = ctx->buf("nn_2nd");
-    DevBuf& midx = ctx->buf("nnb_idx"); DevBuf& md2 = ctx->buf("nnb_d2"); DevBuf& m2nd = ctx->buf("nnb_2nd"); DevBuf& dkeys = ctx->buf("sorted_keys_big");
-    DevBuf& ds1 = ctx->buf("sel1"); DevBuf& ds2 = ctx->buf("sel2"); DevBuf& dns = ctx->buf("nsel");
-    const size_t nn = (size_t)nsub * KSTRIDE;
-    MI_HIP(dpd.reserve(sizeof(PairDesc) * n_pairs)); MI_HIP(dsub.reserve(sizeof(PairDesc) * nsub)); MI_HIP(dbp.reserve(sizeof(BigPairDev) * n_pairs));
-    MI_HIP(didx.reserve(nn * 4)); MI_HIP(dd2.reserve(nn * 4)); MI_HIP(d2nd.reserve(nn * 4));
-    MI_HIP(midx.reserve((size_t)off * 4)); MI_HIP(md2.reserve((size_t)off * 4)); MI_HIP(m2nd.reserve((size_t)off * 4)); MI_HIP(dkeys.reserve((size_t)koff * 8));
-    MI_HIP(ds1.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * (size_t)n_pairs));
-    MI_HIP(ds2.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * (size_t)n_pairs));
-    MI_HIP(dns.reserve(sizeof(int) * n_pairs));
-    MI_HIP(hipMemcpyAsync(dpd.p, pd.data(), sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dsub.p, sub.data(), sizeof(PairDesc) * nsub, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dbp.p, bp.data(), sizeof(BigPairDev) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // the host vectors are locals
-    const bool second = want_second || ctx->p.ratio > 0.0f;
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // the host vectors are the caller's and this function's locals
+    const bool second = for_bf_match || ctx->p.ratio > 0.0f;
     {
-        double bytes = 0.0;
-        for (const PairDesc& q : sub) bytes += (double)(q.npad_i + q.npad_j) * 128.0 + 8.0 * q.n_i;
-        ProfScope ps(ctx, "match", bytes);
-        const int nqt = KSTRIDE / QTILE;
-        if (second) hipLaunchKernelGGL(bf_match_kernel<true>, dim3((unsigned)nqt * (unsigned)nsub), dim3(BF_NT), 0, ctx->stream, dsub.as<PairDesc>(), nqt, didx.as<int>(), dd2.as<int>(), d2nd.as<int>());
-        else hipLaunchKernelGGL(bf_match_kernel<false>, dim3((unsigned)nqt * (unsigned)nsub), dim3(BF_NT), 0, ctx->stream, dsub.as<PairDesc>(), nqt, didx.as<int>(), dd2.as<int>(), d2nd.as<int>());
-        hipLaunchKernelGGL(merge_chunks_kernel, dim3((max_ni + 255) / 256, n_pairs), dim3(256), 0, ctx->stream, dbp.as<BigPairDev>(), didx.as<int>(), dd2.as<int>(), d2nd.as<int>(), second ? 1 : 0,
-                           midx.as<int>(), md2.as<int>(), m2nd.as<int>());
+        ProfScope ps(ctx, "match", match_bytes(table));
+        launch_match(ctx, ws, (large ? ws.sub : ws.pairs).as<PairDesc>(), n_table, large ? KSTRIDE / QTILE : (max_ni + QTILE - 1) / QTILE, second);
+        if (large) hipLaunchKernelGGL(merge_chunks_kernel, dim3((max_ni + 255) / 256, n_pairs), dim3(256), 0, ctx->stream, ws.big.as<BigPairDev>(), ws.nn.idx.as<int>(), ws.nn.d2.as<int>(),
+                                      ws.nn.d2nd.as<int>(), second ? 1 : 0, ws.merged.idx.as<int>(), ws.merged.d2.as<int>(), ws.merged.d2nd.as<int>());
     }
-    SelectParams sp;
-    sp.max_selected = ctx->p.max_selected; sp.fraction = ctx->p.select_fraction; sp.gx = ctx->p.grid_x; sp.gy = ctx->p.grid_y;
-    sp.ratio2 = ctx->p.ratio > 0.0f ? ctx->p.ratio * ctx->p.ratio : 0.0f;
     {
-        ProfScope ps(ctx, "select", (double)koff * 8.0);
-        hipLaunchKernelGGL(select_big_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, dpd.as<PairDesc>(), dbp.as<BigPairDev>(), midx.as<int>(), md2.as<int>(), m2nd.as<int>(), sp,
-                           dkeys.as<unsigned long long>(), ds1.as<mi355_sfpoint>(), ds2.as<mi355_sfpoint>(), dns.as<int>());
+        ProfScope ps(ctx, "select", large ? (double)koff * 8.0 : (double)n_pairs * (KSTRIDE * 12.0 + 9600.0));
+        launch_select(ctx, ws, n_pairs, large, select_params(ctx), for_bf_match);
     }
     MI_HIP(hipGetLastError());
-    if (layout_out) *layout_out = bp;
+    if (at) *at = ws.view(large, large ? (size_t)(pd[0].n_j > 0 && pd[0].n_i > 0 ? pd[0].n_i : 1) : (size_t)KSTRIDE);     // a large pair: its matches, one entry at least
     return MI355_OK;
-}
-
-static bool pair_is_big(const PairDesc& d) { return d.n_i > KSTRIDE || d.n_j > KSTRIDE; }
-static long long sub_pairs_of(const PairDesc& d) {      // run_match_select_big's (query chunk, train chunk) sub-pairs of a pair
-    return (long long)(d.n_i > 0 ? (d.n_i + KSTRIDE - 1) / KSTRIDE : 1) * (long long)(d.n_j > 0 ? (d.n_j + KSTRIDE - 1) / KSTRIDE : 1);
 }
 
 int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float dist, uint32_t seed, mi355_pair_result* d_out) {
@@ -661,6 +673,7 @@ int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float 
     }
     const int BATCH = 32768;                                  // bounds the nn workspaces (32768 x 2048 x 12 B = 768 MiB of the 288 GB); every batch boundary drains the stream
     std::vector<PairDesc> pd;
+    PairWs ws(ctx);
     { const int rc = mi_ransac_tables(ctx, seed, nullptr); if (rc != MI355_OK) return rc; }      // a new seed's draw tables are built beside the matcher
     for (int b0 = 0; b0 < n_pairs; b0 += BATCH) {
         const int nb = (n_pairs - b0) < BATCH ? (n_pairs - b0) : BATCH;
@@ -675,17 +688,13 @@ int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float 
             long long subs = big ? sub_pairs_of(pd[r0]) : 0;
             while (r1 < nb && pair_is_big(pd[r1]) == big && (!big || (r1 - r0 < 256 && subs + sub_pairs_of(pd[r1]) <= ctx->big_sub_max))) { if (big) subs += sub_pairs_of(pd[r1]); r1++; }
             const int nr = r1 - r0;
-            if (r0 == 0 && nr == nb && !big) rc = run_match_select(ctx, pd, nb, false);
-            else {
-                const std::vector<PairDesc> run(pd.begin() + r0, pd.begin() + r1);
-                rc = big ? run_match_select_big(ctx, run, nr, false) : run_match_select(ctx, run, nr, false);
-            }
+            if (r0 == 0 && nr == nb) rc = run_match_select(ctx, ws, pd, false);
+            else rc = run_match_select(ctx, ws, std::vector<PairDesc>(pd.begin() + r0, pd.begin() + r1), false);
             if (rc != MI355_OK) return rc;
-            rc = mi_ransac_batch(ctx, ctx->buf("sel1").as<mi355_sfpoint>(), ctx->buf("sel2").as<mi355_sfpoint>(), ctx->buf("nsel").as<int>(), nullptr,
+            rc = mi_ransac_batch(ctx, ws.sel1.as<mi355_sfpoint>(), ws.sel2.as<mi355_sfpoint>(), ws.nsel.as<int>(), nullptr,
                                  nr, MI355_MAX_SELECTED, dist, ctx->p.sample_times, seed, d_out + b0 + r0, ctx->p.min_inliers);
             if (rc != MI355_OK) return rc;
-            hipLaunchKernelGGL(finalize_kernel, dim3((nr + 255) / 256), dim3(256), 0, ctx->stream, ctx->buf("pair_desc").as<PairDesc>(), ctx->buf("nsel").as<int>(),
-                               nr, ctx->p.min_inliers, d_out + b0 + r0);
+            hipLaunchKernelGGL(finalize_kernel, dim3((nr + 255) / 256), dim3(256), 0, ctx->stream, ws.pairs.as<PairDesc>(), ws.nsel.as<int>(), nr, ctx->p.min_inliers, d_out + b0 + r0);
             MI_HIP(hipGetLastError());
             if (r1 < nb || b0 + BATCH < n_pairs) MI_HIP(hipStreamSynchronize(ctx->stream));     // workspaces are reused by the next run / batch
             r0 = r1;
@@ -699,17 +708,18 @@ int mi_bf_match(mi355_ctx* ctx, int img_i, int img_j, int sorted, mi355_dmatch* 
     std::vector<PairDesc> pd;
     int rc = build_pair_table(ctx, pr, 1, pd);
     if (rc != MI355_OK) return rc;
-    const bool big = pair_is_big(pd[0]);
-    rc = big ? run_match_select_big(ctx, pd, 1, true) : run_match_select(ctx, pd, 1, true);
+    PairWs ws(ctx);
+    NnView at;
+    rc = run_match_select(ctx, ws, pd, true, &at);
     if (rc != MI355_OK) return rc;
     const int M = pd[0].n_j > 0 ? pd[0].n_i : 0;
-    const size_t K = big ? (size_t)(M > 0 ? M : 1) : (size_t)KSTRIDE;        // the large-pair form keeps one pair at offset 0 of its merged arrays
+    const size_t K = at.extent;
     std::vector<int> idx(K), dd(K), d2nd(K);
     std::vector<unsigned long long> keys(K);
-    MI_HIP(hipMemcpyAsync(idx.data(), ctx->buf(big ? "nnb_idx" : "nn_idx").p, K * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dd.data(), ctx->buf(big ? "nnb_d2" : "nn_d2").p, K * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipMemcpyAsync(d2nd.data(), ctx->buf(big ? "nnb_2nd" : "nn_2nd").p, K * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipMemcpyAsync(keys.data(), ctx->buf(big ? "sorted_keys_big" : "sorted_keys").p, K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(idx.data(), at.idx, K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(dd.data(), at.d2, K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(d2nd.data(), at.d2nd, K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(keys.data(), at.keys, K * 8, hipMemcpyDeviceToHost, ctx->stream));
     MI_HIP(hipStreamSynchronize(ctx->stream));
     const int n = M < maxm ? M : maxm;
     for (int k = 0; k < n; k++) {
@@ -722,7 +732,7 @@ int mi_bf_match(mi355_ctx* ctx, int img_i, int img_j, int sorted, mi355_dmatch* 
     return MI355_OK;
 }
 
-// stand-alone SelectMatchPairs: host arrays in, the same select kernel on one synthetic "pair"
+// stand-alone SelectMatchPairs: host arrays in, the same select launch on one synthetic "pair"
 int mi_select_grid(mi355_ctx* ctx, const mi355_dmatch* sorted, int n, const float* kp1, int nk1, const float* kp2, int nk2,
                    int nMatch, int width, int height, int gx, int gy, mi355_sfpoint* v1, mi355_sfpoint* v2, int* n_out) {
     if (n < 0 || n > ctx->keepall_max || !kp1 || !kp2 || !v1 || !v2 || !n_out || gx < 1 || gy < 1 || gx * gy > 64 || width < gx || height < gy) { ctx->set_error("select_grid: bad arguments (at most keepall_max=" + std::to_string(ctx->keepall_max) + " matches)"); return MI355_ERR_ARG; }
@@ -739,42 +749,30 @@ int mi_select_grid(mi355_ctx* ctx, const mi355_dmatch* sorted, int n, const floa
         xy2[k] = make_float2(kp2[2 * t], kp2[2 * t + 1]);
         idx[k] = k; dd[k] = k;
     }
+    PairWs ws(ctx);
+    const BigPairDev bp = big_pair(n, 1, 0, 0, 0);          // one pair at offset 0 of the merged arrays
+    NnBufs& nn = big ? ws.merged : ws.nn;                   // where the select launch reads the 1-NN arrays of its form
     DevBuf& dx1 = ctx->buf("sg_xy1"); DevBuf& dx2 = ctx->buf("sg_xy2");
-    DevBuf& dpd = ctx->buf("pair_desc"); DevBuf& didx = ctx->buf(big ? "nnb_idx" : "nn_idx"); DevBuf& dd2 = ctx->buf(big ? "nnb_d2" : "nn_d2"); DevBuf& d2n = ctx->buf(big ? "nnb_2nd" : "nn_2nd");
-    DevBuf& ds1 = ctx->buf("sel1"); DevBuf& ds2 = ctx->buf("sel2"); DevBuf& dns = ctx->buf("nsel");
     MI_HIP(dx1.reserve(sizeof(float2) * xy1.size())); MI_HIP(dx2.reserve(sizeof(float2) * xy2.size()));
-    MI_HIP(dpd.reserve(sizeof(PairDesc))); MI_HIP(didx.reserve(K * 4)); MI_HIP(dd2.reserve(K * 4)); MI_HIP(d2n.reserve(K * 4));
-    MI_HIP(ds1.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED)); MI_HIP(ds2.reserve(sizeof(mi355_sfpoint) * MI355_MAX_SELECTED)); MI_HIP(dns.reserve(sizeof(int)));
+    MI_HIP(ws.reserve_run(1, big ? 0 : 1));               // a reservation of 0 bytes leaves its buffer alone (DevBuf::reserve): each form grows only what it reads
+    if (big) MI_HIP(ws.reserve_big(1, 0, K, (size_t)bp.mpad));
     PairDesc pd;
     memset(&pd, 0, sizeof(pd));
     pd.xy_i = dx1.as<float2>(); pd.xy_j = dx2.as<float2>(); pd.n_i = n; pd.n_j = n > 0 ? 1 : 0; pd.width = width; pd.height = height;
     MI_HIP(hipMemcpyAsync(dx1.p, xy1.data(), sizeof(float2) * xy1.size(), hipMemcpyHostToDevice, ctx->stream));
     MI_HIP(hipMemcpyAsync(dx2.p, xy2.data(), sizeof(float2) * xy2.size(), hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dpd.p, &pd, sizeof(pd), hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(didx.p, idx.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(dd2.p, dd.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP(hipMemcpyAsync(d2n.p, d2nd.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(ws.pairs.p, &pd, sizeof(pd), hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(nn.idx.p, idx.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(nn.d2.p, dd.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(nn.d2nd.p, d2nd.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (big) MI_HIP(hipMemcpyAsync(ws.big.p, &bp, sizeof(bp), hipMemcpyHostToDevice, ctx->stream));
     // nMatch is given by the caller here: choose (max_selected, fraction) that reproduce it: min(nMatch, 1.0*M)
-    SelectParams sp;
-    sp.max_selected = nMatch; sp.fraction = 1e9; sp.gx = gx; sp.gy = gy; sp.ratio2 = 0.0f;      // Min(nMatch, huge) = the caller's nMatch
-    BigPairDev bp;
-    memset(&bp, 0, sizeof(bp));
-    if (big) {
-        bp.n_i = n; bp.n_j = 1; bp.tc_n = 1; bp.mpad = 64; while (bp.mpad < n) bp.mpad <<= 1;
-        DevBuf& dbp = ctx->buf("big_pairs"); DevBuf& dkeys = ctx->buf("sorted_keys_big");
-        MI_HIP(dbp.reserve(sizeof(bp))); MI_HIP(dkeys.reserve((size_t)bp.mpad * 8));
-        MI_HIP(hipMemcpyAsync(dbp.p, &bp, sizeof(bp), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(select_big_kernel, dim3(1), dim3(1024), 0, ctx->stream, dpd.as<PairDesc>(), dbp.as<BigPairDev>(), didx.as<int>(), dd2.as<int>(), d2n.as<int>(), sp,
-                           dkeys.as<unsigned long long>(), ds1.as<mi355_sfpoint>(), ds2.as<mi355_sfpoint>(), dns.as<int>());
-    } else {
-        hipLaunchKernelGGL(select_kernel, dim3(1), dim3(256), 0, ctx->stream, dpd.as<PairDesc>(), didx.as<int>(), dd2.as<int>(), d2n.as<int>(),
-                           sp, ds1.as<mi355_sfpoint>(), ds2.as<mi355_sfpoint>(), dns.as<int>(), (unsigned long long*)nullptr);
-    }
+    launch_select(ctx, ws, 1, big, SelectParams{nMatch, 1e9, gx, gy, 0.0f}, false);          // Min(nMatch, huge) = the caller's nMatch
     int cnt = 0;
     std::vector<mi355_sfpoint> h1(MI355_MAX_SELECTED), h2(MI355_MAX_SELECTED);
-    MI_HIP(hipMemcpyAsync(&cnt, dns.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipMemcpyAsync(h1.data(), ds1.p, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED, hipMemcpyDeviceToHost, ctx->stream));
-    MI_HIP(hipMemcpyAsync(h2.data(), ds2.p, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(&cnt, ws.nsel.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(h1.data(), ws.sel1.p, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipMemcpyAsync(h2.data(), ws.sel2.p, sizeof(mi355_sfpoint) * MI355_MAX_SELECTED, hipMemcpyDeviceToHost, ctx->stream));
     MI_HIP(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < cnt; k++) {
         const int pos = h1[k].id;                       // position in the caller's sorted list

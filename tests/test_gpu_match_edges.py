@@ -284,3 +284,65 @@ def test_large_pair_runs_split_by_sub_pair_count(ctx, orc):
     _same_record(together[0], mp.record_of(orc, a, mp.DIST, 5), "1500 x 1500")
     _same_record(together[1], mp.record_of(orc, b, mp.DIST, 5), "300 x 2049")
     ctx.DropFeatures(-1)
+
+
+# ---- one context through every entry point ------------------------------------------------------------------------------------------------------
+def test_workspaces_shared_across_entry_points(orc):
+    """MatchPairs, BFMatch, SelectMatchPairs and SurfMatchPairs share workspaces (the pair table, the 1-NN arrays, sel1 / sel2 / nsel, the
+    records) and each sizes them for itself: a 300 x 300 pair, a 2049 x 300 pair (the smallest large pair: two query chunks), lists of 2049
+    and 100 matches and two SURF pairs, one after the other in ONE context, then the first two again.  Every output is, byte for byte, what
+    the same call gives in a context of its own, and the oracle's (the SURF records against surf -> surf_match_pair, as tests/test_gpu_surf_edges.py
+    checks them).  On the oracle: 90 and 396 selected, 37 and 211 inliers; 396 and 27 of the lists selected; 124 and 198 SURF correspondences
+    selected, 121 and 186 of them inliers"""
+    from tests import surf_patterns as su
+    a, b = mp.make_pair(71, 300, 300), mp.make_pair(72, 2049, 300)
+    sel = {p["tag"]: p for p in mp.fill_patterns()}["size_2049"]
+    frames = su.dup_pair()
+
+    def select_args(n):
+        return (sel["matches"][:n], sel["kp1"], sel["kp2"], int(min(400.0, 0.3 * n)), sel["w"], sel["h"], 3, 3)
+
+    def install(c):
+        assert (_set_pair(c, 0, a), _set_pair(c, 1, b)) == ((0, 1), (2, 3))
+        for k, f in enumerate(frames):
+            c.SurfExtract(10 + k, f, su.THR, su.KEEP_ALL)
+
+    calls = {"match small": lambda c: (c.MatchPairs([(0, 1)], mp.DIST, SEED),), "match large": lambda c: (c.MatchPairs([(2, 3)], mp.DIST, SEED),),
+             "bf large": lambda c: c.BFMatch(2, 3, True, 4096), "bf small": lambda c: c.BFMatch(0, 1, True, 4096),
+             "select 2049": lambda c: c.SelectMatchPairs(*select_args(2049)), "select 100": lambda c: c.SelectMatchPairs(*select_args(100)),
+             "surf": lambda c: (c.SurfMatchPairs([(10, 11), (11, 10)], mp.DIST, SEED),)}
+    order = ["match small", "match large", "bf large", "bf small", "select 2049", "select 100", "surf", "match small", "match large"]
+    assert set(order) == set(calls)
+
+    def as_bytes(out):
+        return [np.ascontiguousarray(x).tobytes() for x in out]
+
+    alone = {}
+    for name, call in calls.items():
+        with _context() as c:
+            install(c)
+            alone[name] = as_bytes(call(c))
+    got = {}
+    with _context() as c:
+        install(c)
+        for k, name in enumerate(order):
+            got[name] = calls[name](c)
+            assert as_bytes(got[name]) == alone[name], (k, name)
+    for name, p in (("match small", a), ("match large", b)):
+        _same_record(got[name][0][0], mp.record_of(orc, p, mp.DIST, SEED), name)
+    for name, p in (("bf small", a), ("bf large", b)):
+        idx, b1, b2 = orc.bf_match(p["d1"], p["d2"])
+        want = orc.sort_matches(idx, b1)
+        ms, s1, s2 = got[name]
+        assert len(ms) == len(p["d1"]), name
+        assert np.array_equal(np.stack([ms["queryIdx"], ms["trainIdx"]], 1), want) and np.array_equal(s1, b1[want[:, 0]]) and np.array_equal(s2, b2[want[:, 0]]), name
+    for n, kept in ((2049, 396), (100, 27)):
+        o1, o2 = orc.select(*select_args(n))
+        a1, a2 = got["select %d" % n]
+        assert len(o1) == kept and np.array_equal(a1, o1) and np.array_equal(a2, o2), n
+    F = [orc.surf(f, su.THR, su.KEEP_ALL) for f in frames]
+    for r, (i, j) in zip(got["surf"][0], ((0, 1), (1, 0))):
+        n_in, i1, i2, H, n_sel = orc.surf_match_pair(F[i], F[j], mp.DIST, SEED)
+        assert n_sel > 100 and n_in > 18, (i, j, n_sel, n_in)
+        assert (int(r["i"]), int(r["j"]), int(r["n_selected"]), int(r["n_in"]), int(r["accepted"])) == (10 + i, 10 + j, n_sel, n_in, 1), (i, j)
+        assert np.array_equal(r["a"][:n_in], i1[:n_in]) and np.array_equal(r["b"][:n_in], i2[:n_in]) and np.array_equal(bits(r["H"]), bits(H)), (i, j)

@@ -14,7 +14,7 @@ from .capi import (  # noqa: F401
     global_affine_align_results, select_connected_results, pair_moments_host, select_connected_moments, global_affine_align_moments, PAIR_MOMENTS, write_descriptors_xml, load_descriptors_xml,
     ScreenParams, screen_params, GainParams, GAIN_PAIR_STATS, gain_params, solve_gains,
     BlockGainParams, BLOCK_GAIN_STATS, block_gain_params, solve_block_gains,
-    FeatherParams, feather_params, SeamlineParams, seamline_params,
+    FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

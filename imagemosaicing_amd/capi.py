@@ -58,6 +58,10 @@ class SeamlineParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class MedianParams(C.Structure):
+    _fields_ = [("ramp", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class PreviewParams(C.Structure):
     _fields_ = [("render", C.c_int32), ("ramp", C.c_int32), ("level", C.c_int32), ("nodata", C.c_int32), ("reserved", C.c_int32 * 4)]
 
@@ -764,6 +768,61 @@ class Context:
         self._chk(self.L.mi355_mosaic_seamline_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
         return need
 
+    # ---- median render (mi355_mosaic_median*, csrc/median.hip) -------------------------------------------------------------
+    def MosaicMedian(self, imgs, h9s, params=None, want_spread=False, **kw):
+        """mi355_mosaic_median: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_spread (canvas, cw, ch, cws, spread [ch, cw]
+        uint8: the largest per-channel range of the selected samples).  params: MedianParams (median_params()) or its keyword fields (ramp,
+        depth)."""
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else median_params(**kw)
+        canvas, spread = C.c_void_p(), C.c_void_p()
+        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_mosaic_median(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
+                                             C.byref(cws), C.byref(spread) if want_spread else None))
+        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
+        self.L.mi355_free(canvas)
+        if not want_spread:
+            return buf, cw.value, ch.value, cws.value
+        spr = _copy_out(spread, ch.value * cw.value, np.uint8).reshape(ch.value, cw.value)
+        self.L.mi355_free(spread)
+        return buf, cw.value, ch.value, cws.value, spr
+
+    def MosaicMedianDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_spread=0, d_count=0, params=None, **kw):
+        """mi355_mosaic_median_dev: device frames (0 / None: withheld; d_imgs None when d_canvas and d_spread are 0) into the device canvas and /
+        or the maps d_spread (uint8 [ch, cw]) and d_count (uint16 [ch, cw]) (0: not wanted), rows [row0, row0 + rows); complete on return"""
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        n = len(w)
+        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
+        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else median_params(**kw)
+        self._chk(self.L.mi355_mosaic_median_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas or 0) or None),
+                                                 int(cw), int(ch), int(cws), C.c_void_p(int(d_spread or 0) or None), C.c_void_p(int(d_count or 0) or None),
+                                                 int(row0), int(rows if rows >= 0 else ch)))
+
+    def MosaicMedianInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
+        """mi355_mosaic_median_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else median_params(**kw)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_median_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
+                                                  C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
+    def MedianCover(self, w, h, h9s, row0=0, rows=-1, params=None, **kw):
+        """mi355_mosaic_median_cover: need[k] = 1 exactly for the frames that are among the selected of at least one pixel of canvas rows
+        [row0, row0 + rows)"""
+        n = len(w)
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else median_params(**kw)
+        need = np.zeros(n, np.uint8)
+        self._chk(self.L.mi355_mosaic_median_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
+        return need
+
     # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
@@ -1005,6 +1064,17 @@ def seamline_params(ramp=None):
     load_library().mi355_default_seamline_params(C.byref(p))
     if ramp is not None:
         p.ramp = int(ramp)
+    return p
+
+
+def median_params(ramp=None, depth=None):
+    """mi355_median_params: the library's defaults (mi355_default_median_params: ramp 0 = a full tent per frame, depth 0 = 5 frames) with the
+    given fields replaced"""
+    p = MedianParams()
+    load_library().mi355_default_median_params(C.byref(p))
+    for name, v in (("ramp", ramp), ("depth", depth)):
+        if v is not None:
+            setattr(p, name, int(v))
     return p
 
 

@@ -1,7 +1,7 @@
 // csrc/frames.hip -- where the renders' inputs come from and how their canvas reaches the caller.  Host code only: the canvases come from the
-// kernels of warp.hip / feather.hip / seamline.hip / blend.hip.  Host frames kept in HBM after their extraction (option "keep_frames");
+// kernels of warp.hip / feather.hip / seamline.hip / median.hip / blend.hip.  Host frames kept in HBM after their extraction (option "keep_frames");
 // render_sources, the staging every form shares; the host forms of the one-pass renders (mi_render_host_begin / _end: a malloc'd canvas) and the calls
-// that write straight into caller memory (render_into: mi355_mosaic_refined_into / _feathered_into / _seamline_into / _blended_into).
+// that write straight into caller memory (render_into: mi355_mosaic_refined_into / _feathered_into / _seamline_into / _median_into / _blended_into).
 // Last, mi355_mosaic_preview_into: the same sources, rendered stripe by stripe and reduced by overview.hip, one overview level reaching the
 // caller.
 #include "common.h"
@@ -296,6 +296,19 @@ extern "C" int mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* 
     if (rc != MI355_OK) return rc;
     return render_into(ctx, "mosaic_seamline_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws, [&](const uint8_t* const* d, uint8_t* dc) {
         return mi_mosaic_seamline_dev(ctx, d, w, h, ws, n, h9s, params, dc, lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
+    });
+}
+
+extern "C" int mi355_mosaic_median_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                         const int* ws, int n, const float* h9s, const mi355_median_params* params, uint8_t* dst, int dst_pitch,
+                                         int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_median_into: bad arguments"); return MI355_ERR_ARG; }
+    int lw, lh, lws;
+    const int rc = render_layout(ctx, "mosaic_median_into", w, h, n, h9s, &lw, &lh, &lws);
+    if (rc != MI355_OK) return rc;
+    return render_into(ctx, "mosaic_median_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws, [&](const uint8_t* const* d, uint8_t* dc) {
+        return mi_mosaic_median_dev(ctx, d, w, h, ws, n, h9s, params, dc, lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
     });
 }
 

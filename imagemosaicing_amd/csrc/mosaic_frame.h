@@ -1,8 +1,8 @@
-// csrc/mosaic_frame.h -- what the one-pass canvas renders (refined: warp.hip, feathered: feather.hip, seamline: seamline.hip) share.
+// csrc/mosaic_frame.h -- what the one-pass canvas renders (refined: warp.hip, feathered: feather.hip, seamline: seamline.hip, median: median.hip) share.
 // Host side: the FrameDev record and its setup (the clipped canvas box and the inverse), the entry check of the _dev launchers, the frame
 // table with its upload and candidate lists, the "which table entries were used" pass (all warp.hip), and the host forms' staging and
 // download (frames.hip).  Device side: the 2 x 2 texel loads, "frame f gives canvas pixel (x, y) this sample" (also gain.hip), and the
-// lane / tile prologue and 12-byte row store of feather_tile_kernel and seamline_tile_kernel.  mosaic_tile_kernel spells the same
+// lane / tile prologue and 12-byte row store of feather_tile_kernel, seamline_tile_kernel and median_tile_kernel.  mosaic_tile_kernel spells the same
 // map / bounds / hm::bilin / store steps inline, unchanged, so that its code object stays what it was (one more VGPR than its 72 would cost
 // it a wave per SIMD); tests/test_gpu_gain.py pins the helpers against the render (per-frame samples and cover equal the oracle's refined
 // canvas).
@@ -160,6 +160,18 @@ __device__ __forceinline__ void store_row12(uint8_t* canvas, int cw, int cws, in
     }
     if (xg + 4 >= cw)
         for (int b = 3 * cw; b < cws; b++) canvas[(size_t)yD * cws + b] = 0;
+}
+
+// four 16-bit map entries of a lane's pixel group (seamline.hip: owner, count; median.hip: count): 8 bytes at once where the group is whole
+__device__ __forceinline__ void store_map4(uint16_t* row, int xg, int cw, const unsigned v[4]) {
+    if (xg + 3 < cw) {
+        const uint32_t two[2] = {v[0] | (v[1] << 16), v[2] | (v[3] << 16)};
+        __builtin_memcpy(row + xg, two, 8);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++)                      // at most 3 pixels
+            if (xg + k < cw) row[xg + k] = (uint16_t)v[k];
+    }
 }
 
 }  // namespace

@@ -18,7 +18,7 @@
 //                         recomputation is a handful of multiply-adds per pixel, once (-DSL_KEEP_XY_V=1 builds the other form).
 //                         <false>: phase 2 is left out -- the maps alone (d_canvas == NULL) or the per-frame "owns a pixel" flags (the cover
 //                         call, and the check that precedes a render some of whose frames came without a pointer).
-// The lane / tile prologue and the row store (tile_lane, store_row12) and the host path around the launches -- entry check, frame table,
+// The lane / tile prologue and the row and map stores (tile_lane, store_row12, store_map4) and the host path around the launches -- entry check, frame table,
 // lists, used flags, the host form -- are mosaic_frame.h's, shared with warp.hip and feather.hip; the walk is spelt out here.
 #include "common.h"
 #include "hmath.h"
@@ -34,18 +34,6 @@ namespace {
 #define SL_KEEP_XY_V 0                          // 1: keep the winner's xs, ys from phase 1 (kernel A/B builds)
 #endif
 constexpr int SL_W = 128, SL_RPL = SL_RPL_V, SL_H = 8 * SL_RPL;   // canvas tile of one workgroup: 256 lanes x 4 pixels x SL_RPL rows
-
-// four 16-bit map entries of a lane's pixel group: 8 bytes at once where the group is whole
-__device__ __forceinline__ void store_map4(uint16_t* row, int xg, int cw, const unsigned v[4]) {
-    if (xg + 3 < cw) {
-        const uint32_t two[2] = {v[0] | (v[1] << 16), v[2] | (v[3] << 16)};
-        __builtin_memcpy(row + xg, two, 8);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++)                      // at most 3 pixels
-            if (xg + k < cw) row[xg + k] = (uint16_t)v[k];
-    }
-}
 
 template <bool SAMPLE>
 __global__ __launch_bounds__(256) void seamline_tile_kernel(const FrameDev* fr, const RampDev* ramps, const int* frame_of, int n, const uint16_t* lists,

@@ -347,10 +347,11 @@ inline int GetMatchedPairsOneToAllSurf(const PoseT* pImgPoses, const int nImages
 }
 
 namespace detail {
-// the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into), weighted (mi355_mosaic_feathered_into, default ramp) or
-// seamline (mi355_mosaic_seamline_into, default ramp); with level >= 1 the image is that level of the render `render` instead
+// the one-pass renders into a fresh IplImage: unblended (mi355_mosaic_refined_into), weighted (mi355_mosaic_feathered_into, default ramp),
+// seamline (mi355_mosaic_seamline_into, default ramp) or median (mi355_mosaic_median_into, default ramp and depth); with level >= 1 the image
+// is that level of the render `render` instead
 // (mi355_mosaic_preview_into, exact coverage, default ramp): the full-size canvas is never made
-enum OnePass { ONE_PASS_UNBLENDED, ONE_PASS_WEIGHTED, ONE_PASS_SEAMLINE };
+enum OnePass { ONE_PASS_UNBLENDED, ONE_PASS_WEIGHTED, ONE_PASS_SEAMLINE, ONE_PASS_MEDIAN };
 template <class PoseT>
 inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult, OnePass mode,
                            int level = 0, int render = 0) {
@@ -386,6 +387,7 @@ inline int render_one_pass(const PoseT* pImgPoses, const int nImages, const MI35
     rc = level != 0 ? mi355_mosaic_preview_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], &pp, (uint8_t*)out->imageData, out->widthStep, NULL, cw, ch)
        : mode == ONE_PASS_WEIGHTED ? mi355_mosaic_feathered_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
        : mode == ONE_PASS_SEAMLINE ? mi355_mosaic_seamline_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
+       : mode == ONE_PASS_MEDIAN   ? mi355_mosaic_median_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], NULL, (uint8_t*)out->imageData, out->widthStep, cw, ch)
                                    : mi355_mosaic_refined_into(c, &imgs[0], &ids[0], &w[0], &h[0], &ws[0], nImages, &h9[0], (uint8_t*)out->imageData, out->widthStep, cw, ch);
     if (rc != MI355_OK) { cvReleaseImage(&out); return rc == MI355_ERR_ARG ? -1 : -2; }
     if (pMosaicResult) cvReleaseImage(&pMosaicResult);
@@ -417,6 +419,15 @@ inline int MosaicImagesWeighted(const PoseT* pImgPoses, const int nImages, const
 template <class PoseT>
 inline int MosaicImagesSeamline(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
     return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_SEAMLINE);
+}
+
+// The median render (include/mi355_mosaic.h, "median render") with the default ramp and depth (5): every canvas pixel the per-channel median
+// of its deepest frames, so that what moved between exposures -- cars, people, shadows -- drops out of the overlaps instead of ghosting or
+// being cut at a seam.  The reference has no such mode; the signature, ownership and return values are MosaicImagesSeamline's.  Kept frames
+// are used under MI355_ADAPTOR_KEEP_FRAMES.
+template <class PoseT>
+inline int MosaicImagesMedian(const PoseT* pImgPoses, const int nImages, const MI355_NS ImageTransform* pRectified, MI355_NS IplImage*& pMosaicResult) {
+    return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_MEDIAN);
 }
 
 // A reduced-size mosaic (include/mi355_mosaic.h, "overview levels" / the preview): level `level` in 1..7 -- 1 / 2^level of the size -- of the

@@ -269,6 +269,48 @@ int  mi355_mosaic_seamline(mi355_ctx* ctx, const uint8_t* const* imgs, const int
 int  mi355_mosaic_seamline_cover(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const mi355_seamline_params* params,
                                  int row0, int rows, uint8_t* need);
 
+/* ---- median render: the fifth one-pass render, each canvas pixel the median of its deepest frames (csrc/median.hip) ------------------
+ * What moves between exposures -- a car on a road, a person, a drifting shadow -- shows in a minority of the looks a deep survey has at a piece
+ * of ground.  The feathered mean leaves a ghost of it, the seamline and refined renders cut it at a seam or print it once, multiband smears
+ * it over the low bands; a per-pixel median across the looks makes it drop out.  The reference has no such mode.
+ * Definition (exact integers; bytes and maps do not depend on walk order, tile shape or stripe cut):
+ *   Canvas geometry, frame skipping, "frame k gives canvas pixel (x, y) a sample", the sample s_k[c] and the weight omega_k in [1, 255] are
+ *   exactly the feathered render's (above), including params.ramp, the default R = (min(w, h) + 1) / 2, the 2^20 side limit and n <= 65535.
+ *   params.depth: 0 = the default, 5; 1 .. MI355_MEDIAN_MAX_DEPTH as given.
+ *   Per pixel: C = the set of contributing frames, m = min(|C|, depth), S = the m frames of C that are largest in the lexicographic order
+ *   (omega_k, k) -- the seamline order: the deepest frames first, equal weights by the larger caller index.  For each channel c the m values
+ *   s_k[c], k in S, sorted ascending are v_0 .. v_{m-1}.
+ *   out[c]   = (v[(m-1) >> 1] + v[m >> 1] + 1) >> 1: the median for odd m, the rounded mean of the two middle values for even m; a pixel no
+ *              frame covers is 0; row padding [3 cw, cws) is 0;
+ *   d_count  (optional): uint16_t, the whole canvas's ch x cw at a pitch of cw elements: |C| -- the seamline render's count map;
+ *   d_spread (optional): uint8_t, ch x cw at a pitch of cw bytes: max over c of (v_{m-1} - v_0), 0 where m <= 1: where the selected looks
+ *              disagree -- moving objects, misregistration, exposure.  The samples are in registers anyway.
+ *   Only rows [row0, row0 + rows) of the canvas and of either map are written.
+ * Consequences: with depth = 1 the canvas bytes are the seamline render's at the same ramp; where count == 1 the bytes are the refined
+ *   render's; every byte lies between the smallest and the largest selected sample; after mi355_gain_compensate_dev the canvas is the median
+ *   render of the compensated frames.
+ * Cost: one launch over canvas tiles; the selection walk maps, tests and weighs every covering frame and loads no texel, keeping a sorted
+ *   top-`depth` per pixel in registers; then at most `depth` frames are sampled per pixel.
+ * Pointers: d_canvas, d_spread, d_count may each be NULL, at least one must not be.  d_canvas == NULL and d_spread == NULL: nothing is sampled,
+ *   d_imgs (and ws) may be NULL altogether.  Otherwise a frame that is in S for no pixel of the rows may have d_imgs[k] == NULL; NULL for a frame
+ *   that is in S somewhere is MI355_ERR_ARG naming the frame, found before any sample is taken and before anything is written (one extra
+ *   selection pass, paid only when some pointer is NULL); no invalid pointer is dereferenced and the ctx stays usable.
+ * mi355_mosaic_median_cover: need[k] = 1 exactly for the frames that are in S for at least one pixel of the rows -- the selection walk with
+ *   nothing sampled; what a rank must hold to render the stripe (as mi355_mosaic_seamline_cover).
+ * Errors: as the seamline twins (argument checks, n <= 1 -> MI355_ERR_FAILED in the host forms, n > 65535, canvas geometry, ramp < 0, frame
+ *   geometry); depth < 0 or depth > MI355_MEDIAN_MAX_DEPTH -> MI355_ERR_ARG; params NULL = defaults. */
+#define MI355_MEDIAN_MAX_DEPTH 9
+typedef struct { int32_t ramp; int32_t depth; int32_t reserved[2]; } mi355_median_params;   /* ramp as in mi355_feather_params */
+void mi355_default_median_params(mi355_median_params* p);            /* ramp = 0, depth = 0 (5), reserved = 0 */
+int  mi355_mosaic_median_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n,
+                             const float* h9s, const mi355_median_params* params, uint8_t* d_canvas, int cw, int ch, int cws,
+                             uint8_t* d_spread, uint16_t* d_count, int row0, int rows);
+/* host images in; *canvas and, when spread != NULL, *spread (ch x cw bytes) are allocated by the library -> mi355_free */
+int  mi355_mosaic_median(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
+                         const float* h9s, const mi355_median_params* params, uint8_t** canvas, int* cw, int* ch, int* cws, uint8_t** spread);
+int  mi355_mosaic_median_cover(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const mi355_median_params* params,
+                               int row0, int rows, uint8_t* need);
+
 /* LaplacianPyramidBlending warp stage (MosaicImage.cpp:2233-2460) + FindMasksByDistMap (:1761-1881):
  * per kept image a tight chip (3ch u8; the reference then converts to CV_16S), its validity mask and, with
  * find_masks!=0, the exclusive distance-map ownership masks.  h9s must carry the resScale multiplication of
@@ -349,6 +391,9 @@ int  mi355_mosaic_feathered_into(mi355_ctx* ctx, const uint8_t* const* imgs, con
 /* mi355_mosaic_seamline's canvas with mi355_mosaic_feathered_into's sources, destination and download */
 int  mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                 int n, const float* h9s, const mi355_seamline_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
+/* mi355_mosaic_median's canvas with mi355_mosaic_seamline_into's sources, destination and download */
+int  mi355_mosaic_median_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                              int n, const float* h9s, const mi355_median_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
 int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 

@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     ScreenParams, screen_params, GainParams, GAIN_PAIR_STATS, gain_params, solve_gains,
     BlockGainParams, BLOCK_GAIN_STATS, block_gain_params, solve_block_gains,
     FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params,
+    Camera, UndistortParams, undistort_params, undistort_fit, undistort_map,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

@@ -62,6 +62,16 @@ class MedianParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class Camera(C.Structure):
+    """mi355_camera: a Brown-Conrady camera in pixels, OpenCV's coefficient order and signs"""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+class UndistortParams(C.Structure):
+    _fields_ = [("out_fx", C.c_double), ("out_fy", C.c_double), ("out_cx", C.c_double), ("out_cy", C.c_double), ("fill", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class PreviewParams(C.Structure):
     _fields_ = [("render", C.c_int32), ("ramp", C.c_int32), ("level", C.c_int32), ("nodata", C.c_int32), ("reserved", C.c_int32 * 4)]
 
@@ -76,6 +86,7 @@ assert GAIN_PAIR_STATS.itemsize == 64
 BLOCK_GAIN_STATS = np.dtype([("pair", "<i4"), ("cell_a", "<i4"), ("cell_b", "<i4"), ("reserved", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)),
                              ("sum_b", "<i8", (3,))])
 assert BLOCK_GAIN_STATS.itemsize == 72 and C.sizeof(BlockGainParams) == 32
+assert C.sizeof(Camera) == 72 and C.sizeof(UndistortParams) == 48
 
 
 class Mi355Error(RuntimeError):
@@ -823,6 +834,36 @@ class Context:
         self._chk(self.L.mi355_mosaic_median_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
         return need
 
+    # ---- lens undistortion (mi355_undistort_*, csrc/undistort.hip) ---------------------------------------------------------
+    def UndistortFramesDev(self, d_src, d_dst, w, h, ws_src, ws_dst, cam, params=None, **kw):
+        """mi355_undistort_frames_dev: device frames d_src resampled from the distorted camera `cam` (Camera) to the pinhole camera of params
+        (UndistortParams / undistort_params() keyword fields) into d_dst (d_dst[k] == d_src[k] with equal pitches: in place).  Complete on
+        return; returns n_outside, int64 [n]: the pixels of each frame without a sample."""
+        n, sp, w, h, ws_src = self._frame_args(d_src, w, h, ws_src)
+        if len(d_dst) != n:
+            raise ValueError("d_src and d_dst must list the same frames")
+        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        ws_dst = np.ascontiguousarray(ws_dst, np.int32)
+        p = params if params is not None else undistort_params(**kw)
+        out = np.zeros(n, np.int64)
+        self._chk(self.L.mi355_undistort_frames_dev(self._h, sp, dp, _p(w), _p(h), _p(ws_src), _p(ws_dst), n, C.byref(cam), C.byref(p), _p(out)))
+        return out
+
+    def UndistortImage(self, img, cam, params=None, out=None, **kw):
+        """mi355_undistort_image: a host BGR image [h, w, 3] uint8 resampled; out: the array to write (img itself is allowed), default a new
+        one.  Returns (out, n_outside)."""
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.strides[1:] != (3, 1):
+            raise ValueError("img must be [h, w, 3] uint8 with contiguous rows")
+        out = np.empty_like(img) if out is None else out
+        if out.dtype != np.uint8 or out.shape != img.shape or out.strides[1:] != (3, 1):
+            raise ValueError("out must have img's shape and contiguous rows")
+        h, w = img.shape[:2]
+        p = params if params is not None else undistort_params(**kw)
+        cnt = C.c_int64(0)
+        self._chk(self.L.mi355_undistort_image(self._h, C.c_void_p(img.ctypes.data), w, h, int(img.strides[0]), C.c_void_p(out.ctypes.data),
+                                               int(out.strides[0]), C.byref(cam), C.byref(p), C.byref(cnt)))
+        return out, int(cnt.value)
+
     # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
@@ -1076,6 +1117,41 @@ def median_params(ramp=None, depth=None):
         if v is not None:
             setattr(p, name, int(v))
     return p
+
+
+def undistort_params(out_fx=None, out_fy=None, out_cx=None, out_cy=None, fill=None):
+    """mi355_undistort_params: the library's defaults (mi355_default_undistort_params: the camera's own intrinsics, fill 0) with the given
+    fields replaced"""
+    p = UndistortParams()
+    load_library().mi355_default_undistort_params(C.byref(p))
+    for name, v in (("out_fx", out_fx), ("out_fy", out_fy), ("out_cx", out_cx), ("out_cy", out_cy)):
+        if v is not None:
+            setattr(p, name, float(v))
+    if fill is not None:
+        p.fill = int(fill)
+    return p
+
+
+def undistort_fit(cam, w, h):
+    """mi355_undistort_fit (host only): the UndistortParams of the widest pinhole camera whose w x h border lies inside the source"""
+    L = load_library()
+    p = UndistortParams()
+    rc = L.mi355_undistort_fit(C.byref(cam) if cam is not None else None, int(w), int(h), C.byref(p))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return p
+
+
+def undistort_map(cam, w, h, params=None, **kw):
+    """mi355_undistort_map (host only): (xs, ys), float32 [h, w] each: the source coordinate of every output pixel"""
+    L = load_library()
+    p = params if params is not None else undistort_params(**kw)
+    ok = 0 < int(w) <= 1 << 20 and 0 < int(h) <= 1 << 20
+    xs, ys = (np.zeros((int(h), int(w)) if ok else (1, 1), np.float32) for _ in range(2))
+    rc = L.mi355_undistort_map(C.byref(cam) if cam is not None else None, C.byref(p), int(w), int(h), _p(xs), _p(ys))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return xs, ys
 
 
 def preview_params(render=None, ramp=None, level=None, nodata=None):

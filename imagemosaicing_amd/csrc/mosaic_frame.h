@@ -123,6 +123,17 @@ __device__ __forceinline__ void frame_sample3(const FrameDev& f, float xs, float
     vb = hm::bilin(b00, b01, b10, b11, p, q); vg = hm::bilin(g00, g01, g10, g11, p, q); vr = hm::bilin(r00, r01, r10, r11, p, q);
 }
 
+// The same sample for a caller that chose the texel itself (undistort.hip: xi, yi clamped to w - 2, h - 2, so p or q may be exactly 1): the
+// B, G, R bytes from the 2 x 2 texels at (xi, yi) of a w-pixel-wide image with rows ws bytes apart.  The 8-byte form only where its 8 bytes
+// are pixels of the row (xi <= w - 3): no byte outside the image's pixels is read.  frame_sample3 stays as it is, and with it the code objects
+// of the kernels that call it.
+__device__ __forceinline__ void texel_sample3(const uint8_t* src, int w, int ws, int xi, int yi, float p, float q, unsigned& vb, unsigned& vg, unsigned& vr) {
+    float b00, g00, r00, b01, g01, r01, b10, g10, r10, b11, g11, r11;
+    const uint8_t* g0 = src + (size_t)yi * ws + 3 * (size_t)xi;
+    load_quad3(g0, ws, xi + 3 <= w, b00, g00, r00, b01, g01, r01, b10, g10, r10, b11, g11, r11);
+    vb = hm::bilin(b00, b01, b10, b11, p, q); vg = hm::bilin(g00, g01, g10, g11, p, q); vr = hm::bilin(r00, r01, r10, r11, p, q);
+}
+
 // ---- the tile prologue and row store of feather_tile_kernel / seamline_tile_kernel ----------------------------------------------------
 // (mosaic_tile_kernel keeps its own spelling, see the file head.  The walk between the two stays spelt out in both kernels: as a helper
 // taking the per-sample step as a functor it cost feather_tile_kernel 16 VGPRs, 99 against 83, and with them a wave per SIMD.)

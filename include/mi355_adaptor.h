@@ -430,6 +430,25 @@ inline int MosaicImagesMedian(const PoseT* pImgPoses, const int nImages, const M
     return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_MEDIAN);
 }
 
+// Lens undistortion (include/mi355_mosaic.h, "lens undistortion"): src, a frame of the distorted camera `cam`, resampled into dst for the
+// pinhole camera of `params` (0: the camera's own intrinsics; mi355_undistort_fit gives the widest one without empty rim pixels).  The
+// reference has no such step: its caller, which holds host IplImages, calls this just before SiftExtraction; dst may be
+// src.  Both images are 3-channel 8-bit of one size.  0 on success, -1 for bad arguments, else the C call's error; n_outside (may be 0)
+// receives the number of output pixels without a sample.
+inline int UndistortImage(const MI355_NS IplImage* src, MI355_NS IplImage* dst, const mi355_camera& cam, const mi355_undistort_params* params = 0,
+                          long long* n_outside = 0) {
+    if (!src || !dst || !src->imageData || !dst->imageData || src->nChannels != 3 || dst->nChannels != 3 || src->depth != 8 || dst->depth != 8 ||
+        src->width != dst->width || src->height != dst->height)
+        return -1;
+    mi355_ctx* ctx = context();
+    if (!ctx) return MI355_ERR_DEVICE;
+    int64_t cnt = 0;
+    const int rc = mi355_undistort_image(ctx, (const uint8_t*)src->imageData, src->width, src->height, src->widthStep, (uint8_t*)dst->imageData,
+                                         dst->widthStep, &cam, params, &cnt);
+    if (rc == MI355_OK && n_outside) *n_outside = (long long)cnt;
+    return rc;
+}
+
 // A reduced-size mosaic (include/mi355_mosaic.h, "overview levels" / the preview): level `level` in 1..7 -- 1 / 2^level of the size -- of the
 // render `render` (0 MosaicImagesRefined's, 1 MosaicImagesWeighted's, 2 MosaicImagesSeamline's canvas), averaged over the pixels the survey
 // covers only, so that the empty surround does not darken the edge.  The survey is rendered in stripes on the device and only the small image

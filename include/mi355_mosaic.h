@@ -836,6 +836,69 @@ int  mi355_apply_block_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, ui
 int  mi355_block_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                      const int32_t* pairs_ab, int n_pairs, const mi355_block_gain_params* p, float* gains_out);
 
+/* ---- lens undistortion (opt-in; csrc/undistort.hip, csrc/lens.h) ---------------------------------------------------------------------
+ * Every stage of this library relates two frames of flat ground by a homography, which holds for a pinhole camera only.  This pass
+ * resamples BGR u8 frames of a camera with Brown-Conrady distortion (OpenCV's model, coefficient order and signs: k1, k2, p1, p2, k3) to an
+ * ideal pinhole camera, in front of the extraction; undistorted frames are ordinary frames.  The reference has no such step.
+ *
+ * Constants, formed once on the host: the nine camera values and out_cx, out_cy cast to float (fx .. k3, ocx, ocy);
+ *   ifx = (float)(1.0 / out_fx), ify = (float)(1.0 / out_fy), each quotient taken in double.  out_fx = out_fy = out_cx = out_cy = 0 stands
+ *   for the camera's own fx, fy, cx, cy (the doubles).  Nothing is divided per pixel.
+ * Map: for output pixel (u, v) of a w x h frame, every operation a separately rounded f32 operation in exactly this order:
+ *     x = ((float)u - ocx) * ifx;   y = ((float)v - ocy) * ify;
+ *     xx = x*x;  yy = y*y;  xy = x*y;  r2 = xx + yy;  a1 = xy + xy;
+ *     t = r2*k3;  t = k2 + t;  t = r2*t;  t = k1 + t;  t = r2*t;  rad = 1.0f + t;
+ *     tx = (p1*a1) + (p2*(r2 + (xx + xx)));      ty = (p1*(r2 + (yy + yy))) + (p2*a1);
+ *     xd = (x*rad) + tx;   yd = (y*rad) + ty;
+ *     xs = (fx*xd) + cx;   ys = (fy*yd) + cy;
+ * Inside: the pixel has a sample iff xs >= 0 && xs <= (float)(w-1) && ys >= 0 && ys <= (float)(h-1), which also rejects NaN and
+ *   infinities.  The interval is closed -- on purpose not the renders' [0, w-1) --: an undistorted camera gives back its frame, last row
+ *   and column included.
+ * Sample: xi = min((int)xs, w-2), yi = min((int)ys, h-2), q = xs - (float)xi, p = ys - (float)yi (either may be exactly 1); each channel
+ *   is the renders' pixel expression (uchar)(s00 (1-p)(1-q) + s01 (1-p) q + s10 p (1-q) + s11 p q) of the 2 x 2 texels at (xi, yi).
+ * Outside: `fill` in all three channels, and the pixel counts towards the frame's n_outside.
+ * Sizes: 2 <= w, h <= 2^20.  Bytes [0, 3w) of each destination row are written; the row padding [3w, ws_dst) is not.
+ * Consequences: with k1 = k2 = p1 = p2 = k3 = 0, output intrinsics equal to the camera's, fx and fy powers of two and integer cx, cy the
+ *   output is the source byte for byte and n_outside = 0.  The bytes of a frame depend on nothing but its own pixels, its size and the
+ *   constants: not on its position in the call, the other frames, or the pitches.  In-place output equals out-of-place output.
+ * Errors (MI355_ERR_ARG before any launch, the message names the argument, the ctx stays usable): a NULL frame pointer or array; ws < 3w;
+ *   w or h below 2 or above 2^20; n < 0 or n > 65535; a camera or output value that is not finite; fx, fy, out_fx or out_fy <= 0 (out_* all
+ *   0 excepted); fill outside 0..255; a destination range that meets any source or destination range of the call other than in place. */
+typedef struct { double fx, fy, cx, cy, k1, k2, p1, p2, k3; } mi355_camera;            /* pixels; OpenCV's coefficient order and signs */
+typedef struct {
+    double out_fx, out_fy, out_cx, out_cy;  /* the pinhole camera of the output; all four 0: the camera's own fx, fy, cx, cy */
+    int32_t fill;                           /* byte written to all three channels where the source has no sample, 0..255 */
+    int32_t reserved[3];
+} mi355_undistort_params;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_camera) == 72, "mi355_camera is 72 bytes");
+static_assert(sizeof(mi355_undistort_params) == 48, "mi355_undistort_params is 48 bytes");
+#else
+_Static_assert(sizeof(mi355_camera) == 72, "mi355_camera is 72 bytes");
+_Static_assert(sizeof(mi355_undistort_params) == 48, "mi355_undistort_params is 48 bytes");
+#endif
+/* out_* = 0 (the camera's own), fill = 0, reserved = 0 */
+void mi355_default_undistort_params(mi355_undistort_params* p);
+/* The output camera with the widest field of view for which no rim pixel falls outside the source (host only, no ctx; errors:
+ * mi355_last_error(NULL)).  *out = the defaults with out_cx = cx, out_cy = cy, out_fx = s * (double)(float)fx, out_fy = s * (double)(float)fy,
+ * s = j / 256 for the smallest j in 128..1024 at which all 2 (w + h) - 4 border pixels of the w x h output are inside under the definition
+ * above.  The scan ascends, so the result is defined even where validity is not monotone in j.  No such j: MI355_ERR_FAILED.  Only the
+ * border is tested: n_outside of the pass itself tells the truth for pathological coefficients. */
+int  mi355_undistort_fit(const mi355_camera* cam, int w, int h, mi355_undistort_params* out);
+/* The two source-coordinate planes of the definition, xs[v * w + u] and ys[v * w + u] (host only, no ctx; p NULL: defaults): what a caller
+ * moves points with. */
+int  mi355_undistort_map(const mi355_camera* cam, const mi355_undistort_params* p, int w, int h, float* xs, float* ys);
+/* d_dst[k] = frame d_src[k] resampled, for every k: one camera per call, frames of any mix of sizes, one launch, complete on return.
+ * n_outside: HOST, n values, may be NULL.  p NULL: defaults.  d_dst[k] == d_src[k] with ws_dst[k] == ws_src[k] is in place: such frames go
+ * through a ctx-owned scratch buffer in groups of as many frames as 512 MB hold (at least one; one launch per group) and are copied back 3w
+ * bytes per row.  n = 0 is success with nothing done. */
+int  mi355_undistort_frames_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h,
+                                const int* ws_src, const int* ws_dst, int n, const mi355_camera* cam, const mi355_undistort_params* p,
+                                int64_t* n_outside);
+/* the host form: upload, the same kernel, download into the caller's rows (3w bytes each, dst_ws apart).  dst == src is allowed. */
+int  mi355_undistort_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, uint8_t* dst, int dst_ws, const mi355_camera* cam,
+                           const mi355_undistort_params* p, int64_t* n_outside);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

@@ -12,7 +12,10 @@
 // after the other, in chip order, because the float weight sums make the order per pixel part of the result: per chip 5 x Laplacian +
 // accumulate (a 2 x 2 fine block per thread, never stored) and the top level's accumulate.
 #include "common.h"
-#include <cmath>
+#include "chips.h"
+#include "blend_plan.h"
+
+namespace bp = blend_plan;
 
 namespace {
 
@@ -44,23 +47,13 @@ __global__ __launch_bounds__(256) void blend_prep_kernel(const uint8_t* chip, in
     w0[(size_t)y * rw + x] = w;
 }
 
-// one chip of a batch: where its pixels are, how its region lies on the chip, where its pyramid levels >= 1 live
-constexpr int MAX_BANDS = 16;
-struct Win { int x0, y0, x1, y1; };   // inclusive
-struct ChipP {
-    const uint8_t* chip; const uint8_t* mask;
-    int cw, ch, cws, mws;             // chip size, row pitches of chip (3 B / pixel) and mask
-    int left, top, rw, rh;            // chip origin inside its region, region size (multiples of 2^bands)
-    size_t tmp;                       // pixel offset of this chip's level 1 inside the batch's pyramid buffers
-    int tlx, tly;                     // the region's origin on the canvas
-    // Active windows (round 4).  With FindMasksByDistMap's masks a chip's weights are non-zero only over the cell of the mosaic it owns (+ the
-    // reach of the REDUCE filter per level), and a pixel of weight +0 adds nothing to the canvas: only the part of the pyramids that the
-    // non-zero weights can see is ever formed.  cwin[l], l = 1 .. bands: the pixels of level l (Gaussian and weight) that are computed --
-    // everything outside is never written and never read; twin[l], l = 0 .. bands: the threads of the accumulation of level l (one per
-    // 2 x 2 block of level l below the top level, one per pixel at the top level).  See chip_windows() for the derivation.
-    Win cwin[MAX_BANDS + 1];
-    Win twin[MAX_BANDS + 1];
-};
+// The geometry -- Win, ChipP, MAX_BANDS, chip_windows and the plan of a call -- is host code of its own: blend_plan.h.  The kernels keep a
+// parameter type of this name in this namespace: it is part of their names, "(anonymous namespace)::pyr_down0_batch_kernel((anonymous
+// namespace)::ChipP const*, short*, float*)", which profiles/ quote.
+using bp::MAX_BANDS;
+using bp::Win;
+struct ChipP : bp::ChipP {};
+static_assert(sizeof(ChipP) == sizeof(bp::ChipP), "the device array is filled from blend_plan::ChipP");
 // pixel offset of level l >= 1 behind tmp
 __device__ __forceinline__ size_t level_off(int rw, int rh, int l) { size_t o = 0; for (int m = 1; m < l; m++) o += (size_t)(rw >> m) * (rh >> m); return o; }
 
@@ -120,9 +113,6 @@ __device__ __forceinline__ void pyr_down_pair_body(const short* src, const float
         const float v = fr[o][2] * 6.0f + (fr[o][1] + fr[o][3]) * 4.0f + fr[o][0] + fr[o][4];
         dstw[(size_t)y * dw + x0 + o] = v * (1.0f / 256.0f);
     }
-}
-__global__ __launch_bounds__(256) void pyr_down_pair_kernel(const short* src, const float* srcw, int w, int h, short* dst, float* dstw) {
-    pyr_down_pair_body(src, srcw, w, h, dst, dstw, Win{0, 0, (w >> 1) - 1, (h >> 1) - 1});
 }
 // level l -> l + 1 (l >= 1) of every chip of a batch; the grid covers the largest chip
 __global__ __launch_bounds__(256) void pyr_down_pair_batch_kernel(const ChipP* cp, int l, short* g, float* wp) {
@@ -500,390 +490,223 @@ __global__ __launch_bounds__(256) void blend_finalize_kernel(const short* dl, co
 
 inline dim3 grid2(int w, int h) { return dim3((unsigned)((w + 255) / 256), (unsigned)h); }
 
-// Active windows of one chip (ChipP::cwin / twin), one axis at a time.  n_l = extent of level l, S_0 = the owned pixels' range in region
-// coordinates (bb == NULL: everything).  Every set is a superset of what is needed, so a window can only cost time, never change a value:
-//   S_l    where the weight of level l can be non-zero: REDUCE output q sees the inputs 2q - 2 .. 2q + 2 (reflected indices fall on inputs
-//          the unreflected ones already reach), so S_l+1 = [floor((a - 2) / 2) - 1, floor((b + 2) / 2) + 1], one more on each side for slack;
-//   T_l    the accumulation's threads: 2 x 2 blocks of level l below the top level ([a >> 1, b >> 1]), pixels at the top level;
-//   F_l    the pixels of level l those threads read (Gaussian + weight): the blocks themselves;
-//   E_l+1  the pixels of level l + 1 the EXPAND of those blocks reads: T_l widened by one;
-//   C_l    what is computed of level l >= 1: F_l, E_l and the inputs of the REDUCE that forms C_l+1 ([2a - 2, 2b + 2]).
-// Everything outside C_l stays unwritten in the batch's pyramid buffers and is never read (the pair kernels' second output may be formed
-// from such pixels when C_l+1 starts at an odd column; it lies outside C_l+1 and is never read either).
-// nlo / nhi (not NULL: a stripe of the canvas is blended): per level the canvas rows whose pyramid values the stripe's output depends on; the
-// accumulation windows are cut to them, a level whose window is empty then has y1 < y0 (and adds nothing to F / E / C).  Returns false when
-// no level of the chip is left: the chip adds nothing to the stripe.
-bool chip_windows(ChipP& c, int nb, const int* bb, const int* nlo = nullptr, const int* nhi = nullptr) {
-    const int L = nb < MAX_BANDS ? nb : MAX_BANDS;
-    if (!bb || nb > MAX_BANDS) {
-        for (int l = 0; l <= L; l++) {
-            c.cwin[l] = Win{0, 0, (c.rw >> l) - 1, (c.rh >> l) - 1};
-            c.twin[l] = l < nb ? Win{0, 0, (c.rw >> (l + 1)) - 1, (c.rh >> (l + 1)) - 1} : c.cwin[l];
-        }
-        return true;
-    }
-    bool any = false;
-    for (int axis = 0; axis < 2; axis++) {
-        const int dim = axis ? c.rh : c.rw, off = axis ? c.top : c.left;
-        int Sa[MAX_BANDS + 1], Sb[MAX_BANDS + 1], Ta[MAX_BANDS + 1], Tb[MAX_BANDS + 1], Fa[MAX_BANDS + 1], Fb[MAX_BANDS + 1], Ea[MAX_BANDS + 2], Eb[MAX_BANDS + 2];
-        int Ca[MAX_BANDS + 2], Cb[MAX_BANDS + 2];
-        auto clip = [](int& a, int& b, int n) { if (a < 0) a = 0; if (b > n - 1) b = n - 1; if (a > b) { a = a < n ? a : n - 1; b = a; } };
-        auto uni = [](int& a, int& b, int a2, int b2) { if (a2 > b2) return; if (a > b) { a = a2; b = b2; return; } a = a2 < a ? a2 : a; b = b2 > b ? b2 : b; };
-        Sa[0] = bb[axis] + off; Sb[0] = bb[2 + axis] + off;
-        clip(Sa[0], Sb[0], dim);
-        for (int l = 0; l < nb; l++) {
-            Sa[l + 1] = ((Sa[l] - 2) >> 1) - 1; Sb[l + 1] = ((Sb[l] + 2) >> 1) + 1;
-            clip(Sa[l + 1], Sb[l + 1], dim >> (l + 1));
-        }
-        for (int l = 0; l <= nb + 1; l++) { Ea[l] = 0; Eb[l] = -1; }
-        for (int l = 0; l <= nb; l++) {
-            if (l < nb) { Ta[l] = Sa[l] >> 1; Tb[l] = Sb[l] >> 1; } else { Ta[l] = Sa[l]; Tb[l] = Sb[l]; }
-            if (axis == 1 && nlo) {
-                // the threads whose canvas rows meet nlo[l] .. nhi[l]: thread t covers the level's rows 2t, 2t + 1 below the top level
-                const int oy = c.tly >> l, lo = nlo[l] - oy, hi = nhi[l] - oy;
-                const int ta = l < nb ? (lo >= 1 ? lo >> 1 : 0) : (lo > 0 ? lo : 0), tb = l < nb ? (hi >= 0 ? hi >> 1 : -1) : hi;
-                if (ta > Ta[l]) Ta[l] = ta;
-                if (tb < Tb[l]) Tb[l] = tb;
-            }
-            if (Ta[l] > Tb[l]) { Ta[l] = 0; Tb[l] = -1; Fa[l] = 0; Fb[l] = -1; continue; }
-            if (axis == 1) any = true;
-            if (l < nb) {
-                Fa[l] = 2 * Ta[l]; Fb[l] = 2 * Tb[l] + 1;
-                Ea[l + 1] = Ta[l] - 1; Eb[l + 1] = Tb[l] + 1;
-                clip(Ea[l + 1], Eb[l + 1], dim >> (l + 1));
-            } else { Fa[l] = Ta[l]; Fb[l] = Tb[l]; }
-        }
-        Ca[nb + 1] = 0; Cb[nb + 1] = -1;
-        for (int l = nb; l >= 1; l--) {
-            int a = 0, b = -1;
-            uni(a, b, Fa[l], Fb[l]); uni(a, b, Ea[l], Eb[l]);
-            if (l < nb && Ca[l + 1] <= Cb[l + 1]) uni(a, b, 2 * Ca[l + 1] - 2, 2 * Cb[l + 1] + 2);
-            if (a <= b) clip(a, b, dim >> l);
-            Ca[l] = a; Cb[l] = b;
-        }
-        Ca[0] = 0; Cb[0] = dim - 1;
-        for (int l = 0; l <= nb; l++) {
-            if (axis == 0) { c.cwin[l].x0 = Ca[l]; c.cwin[l].x1 = Cb[l]; c.twin[l].x0 = Ta[l]; c.twin[l].x1 = Tb[l]; }
-            else           { c.cwin[l].y0 = Ca[l]; c.cwin[l].y1 = Cb[l]; c.twin[l].y0 = Ta[l]; c.twin[l].y1 = Tb[l]; }
-        }
-    }
-    return any;
-}
+// where the finished canvas goes: the caller's device buffer (d_rows != NULL: rows of ws bytes, the first one is the plan's first output
+// row; nothing is copied to the host), or a malloc'd host canvas
+struct BlendOut { uint8_t* d_rows; int ws; uint8_t** host; int* ow; int* oh; int* ows; };
 
-}  // namespace
+// One blend: the plan, the chips that take part, and the device side -- the batch's chip pyramids (g, wp: levels >= 1) and the canvas
+// pyramids (dl, dw), which vlap / vwgt address by canvas coordinates.  set != NULL: the chip stage's set (the one-call forms: chips and
+// masks in HBM, FindMasksByDistMap's masks with their owned boxes, the pixels still to be made); NULL: the direct form's host chips,
+// staged one batch at a time.
+struct Blender {
+    mi355_ctx* ctx; const bp::Plan& p; chips::ChipSet* set; hipStream_t st;
+    std::vector<bp::ChipP> par;
+    short* g; float* wp; short* dl; float* dw; const ChipP* d_par;
+    bool lap0_batched;
+    short* vlap(int l) const { return dl + p.voff[l] * 3; }
+    float* vwgt(int l) const { return dw + p.voff[l]; }
 
-// The chip pixels a chip's windows read: the 2 x 2 blocks of the level-0 accumulation (twin[0]) and the inputs of the first REDUCE over
-// cwin[1] (both outputs of a thread, rows and columns 2q - 2 .. 2q + 2), taken through the two reflections the kernels apply (BORDER_REFLECT_101
-// at the region's border, then BORDER_REFLECT into the chip).  Chip coordinates, inclusive.
-static void chip_pixel_window(const ChipP& c, int& x0, int& y0, int& x1, int& y1) {
-    for (int axis = 0; axis < 2; axis++) {
-        const int rdim = axis ? c.rh : c.rw, cdim = axis ? c.ch : c.cw, off = axis ? c.top : c.left;
-        const int ta = axis ? c.twin[0].y0 : c.twin[0].x0, tb = axis ? c.twin[0].y1 : c.twin[0].x1;
-        int ca = axis ? c.cwin[1].y0 : (c.cwin[1].x0 & ~1), cb = axis ? c.cwin[1].y1 : (c.cwin[1].x1 | 1);
-        int a = 0, b = -1;                                    // (a stripe may leave either window empty: y1 < y0)
-        if (ta <= tb) { a = 2 * ta; b = 2 * tb + 1; }
-        if (ca <= cb) { if (a > b) { a = 2 * ca - 2; b = 2 * cb + 2; } else { a = a < 2 * ca - 2 ? a : 2 * ca - 2; b = b > 2 * cb + 2 ? b : 2 * cb + 2; } }
-        if (a > b) { if (axis == 0) { x0 = 0; x1 = -1; } else { y0 = 0; y1 = -1; } continue; }
-        if (a < 0) { b = b > -a ? b : -a; a = 0; }
-        if (b > rdim - 1) { const int m = 2 * (rdim - 1) - b; a = a < m ? a : m; b = rdim - 1; }
-        if (a < 0) a = 0;
-        a -= off; b -= off;
-        if (a < 0) { b = b > -a - 1 ? b : -a - 1; a = 0; }
-        if (b > cdim - 1) { const int m = 2 * cdim - 1 - b; a = a < m ? a : m; b = cdim - 1; }
-        if (a < 0) a = 0;
-        if (b < a) b = a;
-        if (axis == 0) { x0 = a; x1 = b; } else { y0 = a; y1 = b; }
+    // host chips of one batch to "blend_chip" / "blend_mask"; the batch's ChipP then point there
+    int stage_batch(const bp::Batch& bt) {
+        uint8_t* dchip = ctx->buf("blend_chip").as<uint8_t>();
+        uint8_t* dmask = ctx->buf("blend_mask").as<uint8_t>();
+        size_t co = 0, mo = 0;
+        for (int i = bt.b0; i < bt.b1; i++) {
+            const size_t cb = (size_t)par[i].cws * par[i].ch, mb = (size_t)par[i].mws * par[i].ch;
+            MI_HIP(hipMemcpyAsync(dchip + co, par[i].chip, cb, hipMemcpyHostToDevice, st));
+            MI_HIP(hipMemcpyAsync(dmask + mo, par[i].mask, mb, hipMemcpyHostToDevice, st));
+            par[i].chip = dchip + co; par[i].mask = dmask + mo;
+            co += (cb + 15) & ~(size_t)15; mo += (mb + 15) & ~(size_t)15;
+        }
+        return MI355_OK;
     }
-}
 
-// chips / masks: host pointers (staged one chip at a time) when on_device == 0, device pointers otherwise
-// The canvas rows of every pyramid level that the output rows row0 .. row0 + rows - 1 depend on (a stripe of the canvas: one rank's part of
-// LaplacianPyramidBlending).  The collapse forms level l from its Laplacian and EXPAND of level l + 1: fine row Y reads the coarse rows
-// (Y >> 1) - 1 .. (Y >> 1) + 1, so N_0 = the stripe, N_l+1 = [(a >> 1) - 1, (b >> 1) + 1]; below the top level the ranges are widened to whole
-// 2 x 2 blocks (the accumulation's threads).  Everything a rank forms is what the whole canvas holds there: the canvas geometry (padded
-// size, level count, the chips' regions) is the full canvas's, only rows are left out.
-static void stripe_levels(int row0, int rows, int nb, int Hp, std::vector<int>& nlo, std::vector<int>& nhi) {
-    nlo.assign(nb + 1, 0); nhi.assign(nb + 1, 0);
-    nlo[0] = row0; nhi[0] = row0 + rows - 1;
-    for (int l = 0; l <= nb; l++) {
-        const int hl = Hp >> l;
-        if (l > 0) { nlo[l] = (nlo[l - 1] >> 1) - 1; nhi[l] = (nhi[l - 1] >> 1) + 1; }
-        if (l < nb) { nlo[l] &= ~1; nhi[l] |= 1; }
-        if (nlo[l] < 0) nlo[l] = 0;
-        if (nhi[l] > hl - 1) nhi[l] = hl - 1;
+    // no pyramid: level 0 is the only level; it is materialised and accumulated (the path of bands = 0)
+    void accumulate_flat(const bp::Batch& bt) {
+        for (int i = bt.b0; i < bt.b1; i++) {
+            const bp::ChipP& c = par[i];
+            hipLaunchKernelGGL(blend_prep_kernel, grid2(c.rw, c.rh), dim3(256), 0, st, c.chip, c.cws, c.mask, c.mws, c.cw, c.ch, c.left, c.top, c.rw, c.rh, g + c.tmp * 3, wp + c.tmp);
+            hipLaunchKernelGGL(blend_accumulate_kernel, grid2(c.rw, c.rh), dim3(256), 0, st, g + c.tmp * 3, wp + c.tmp, c.rw, c.rh, c.tlx, c.tly, vlap(0), vwgt(0), p.Wp);
+        }
     }
-}
-// ... and the canvas rows whose ownership (FindMasksByDistMap) those values can depend on: a level-l value sees 2^l q -+ (2^(l+1) - 2) rows of
-// level 0 through its l REDUCE steps, its Laplacian one more level; 8 * 2^l on either side covers both with room to spare
-static void stripe_mask_rows(const std::vector<int>& nlo, const std::vector<int>& nhi, int H, int& r0, int& r1) {
-    r0 = nlo[0]; r1 = nhi[0];
-    for (size_t l = 0; l < nlo.size(); l++) {
-        const long long a = ((long long)nlo[l] << l) - (8ll << l), b = (((long long)nhi[l] + 1) << l) - 1 + (8ll << l);
-        if (a < r0) r0 = a < 0 ? 0 : (int)a;
-        if (b > r1) r1 = b > H - 1 ? H - 1 : (int)b;
-    }
-    if (r1 > H - 1) r1 = H - 1;
-}
 
-// chips / masks: host pointers (staged one chip at a time) when on_device == 0, device pointers otherwise
-static int blend_core(mi355_ctx* ctx, const uint8_t* const* chips, const uint8_t* const* masks, int on_device, const mi355_chip_info* info, int n,
-                      int W, int H, int band, uint8_t** out, int* ow, int* oh, int* ows_out, uint8_t* d_user = nullptr, int user_ws = 0,
-                      const int* owned_bbox = nullptr, int deferred_pixels = 0, int row0 = 0, int rows = -1) {
-    // deferred_pixels: the chips hold no pixels yet (mi_chips_and_masks_dev(.., defer_pixels)): each chip's are made here, inside the part
-    // of the chip its active windows read (chip_pixel_window)
-    // owned_bbox != NULL (the masks are FindMasksByDistMap's, made on this device): per chip the box of its non-zero mask bytes -- a chip
-    // that owns nothing is left out, the others work inside their active windows (chip_windows)
-    // d_user != NULL: the finished canvas goes to the caller's device buffer (rows of user_ws bytes) and nothing is copied to the host
-    // rows >= 0: only the canvas rows row0 .. row0 + rows - 1 are formed (d_user then starts at row row0); needs owned_bbox
-    if (n < 0 || (n > 0 && (!chips || !masks || !info)) || W <= 0 || H <= 0 || band < 0 || (!out && !d_user)) { ctx->set_error("multiband_blend: bad arguments"); return MI355_ERR_ARG; }
-    const hipStream_t st = ctx->stream;
-    int nb = (int)std::ceil(std::log((double)(W > H ? W : H)) / std::log(2.0));
-    if (nb > band) nb = band;
-    if (nb < 0) nb = 0;
-    const int al = 1 << nb;
-    const int Wp = (W + al - 1) / al * al, Hp = (H + al - 1) / al * al;
-    const bool striped = rows >= 0 && !(row0 == 0 && rows == H);
-    if (striped && (row0 < 0 || rows < 1 || row0 + rows > H || !owned_bbox || !d_user || nb > MAX_BANDS || nb < 1)) { ctx->set_error("multiband_blend: bad stripe"); return MI355_ERR_ARG; }
-    if (!striped) { row0 = 0; rows = H; }
-    // rows of level l held by the canvas pyramids: all of them, or the stripe's (stripe_levels).  loff: level offsets in pixels inside one
-    // pyramid buffer; voff: the same minus the rows left out above the stripe, so that canvas coordinates index the buffers unchanged
-    std::vector<int> nlo(nb + 1, 0), nhi(nb + 1, 0);
-    for (int l = 0; l <= nb; l++) nhi[l] = (Hp >> l) - 1;
-    if (striped) stripe_levels(row0, rows, nb, Hp, nlo, nhi);
-    std::vector<size_t> loff(nb + 2, 0);
-    std::vector<long long> voff(nb + 1, 0);
-    for (int l = 0; l <= nb; l++) {
-        loff[l + 1] = loff[l] + (size_t)(Wp >> l) * (size_t)(nhi[l] - nlo[l] + 1);
-        voff[l] = (long long)loff[l] - (long long)nlo[l] * (Wp >> l);
-    }
-    DevBuf& dlap = ctx->buf("blend_dst_lap");
-    DevBuf& dwgt = ctx->buf("blend_dst_w");
-    MI_HIP(dlap.reserve(loff[nb + 1] * 3 * sizeof(short)));
-    MI_HIP(dwgt.reserve(loff[nb + 1] * sizeof(float)));
-    auto vlap = [&](int l) { return dlap.as<short>() + voff[l] * 3; };      // level l of the canvas Laplacian / weight pyramid, addressed by canvas coordinates
-    auto vwgt = [&](int l) { return dwgt.as<float>() + voff[l]; };
-    DevBuf& dchip = ctx->buf("blend_chip");
-    DevBuf& dmask = ctx->buf("blend_mask");
-    DevBuf& glap = ctx->buf("blend_src_lap");
-    DevBuf& gwgt = ctx->buf("blend_src_w");
-    DevBuf& dpar = ctx->buf("blend_chip_params");
-    // geometry of every chip (MultiBandBlender::feed: gap 3 * 2^bands, corners snapped to the level grid, region pulled back inside the canvas)
-    struct Geo { int k, tlx, tly; };
-    std::vector<ChipP> par; std::vector<Geo> geo;
-    par.reserve(n); geo.reserve(n);
-    for (int k = 0; k < n; k++) {
-        const int cw = info[k].w, chh = info[k].h, x0 = info[k].x0, y0 = info[k].y0;
-        if (cw <= 0 || chh <= 0) continue;
-        if (owned_bbox && (owned_bbox[4 * k + 2] < owned_bbox[4 * k] || owned_bbox[4 * k + 3] < owned_bbox[4 * k + 1])) continue;      // all weights +0: adds nothing
-        const int gap = 3 * al;
-        int tlx = x0 - gap > 0 ? x0 - gap : 0, tly = y0 - gap > 0 ? y0 - gap : 0;
-        int brx = x0 + cw + gap < Wp ? x0 + cw + gap : Wp, bry = y0 + chh + gap < Hp ? y0 + chh + gap : Hp;
-        tlx = (tlx >> nb) << nb; tly = (tly >> nb) << nb;
-        int rw = brx - tlx, rh = bry - tly;
-        rw += (al - rw % al) % al;
-        rh += (al - rh % al) % al;
-        brx = tlx + rw; bry = tly + rh;
-        const int dx = brx - Wp > 0 ? brx - Wp : 0, dy = bry - Hp > 0 ? bry - Hp : 0;
-        tlx -= dx; tly -= dy;
-        if (tlx < 0 || tly < 0 || rw <= 0 || rh <= 0) { ctx->set_error("multiband_blend: chip outside the canvas"); return MI355_ERR_ARG; }
-        ChipP c; memset(&c, 0, sizeof(c));
-        c.chip = chips[k]; c.mask = masks[k];
-        c.cw = cw; c.ch = chh; c.cws = (cw * 3 + 3) & ~3; c.mws = (cw + 3) & ~3;
-        c.left = x0 - tlx; c.top = y0 - tly; c.rw = rw; c.rh = rh; c.tlx = tlx; c.tly = tly;
-        if (!chip_windows(c, nb, owned_bbox ? owned_bbox + 4 * k : nullptr, striped ? nlo.data() : nullptr, striped ? nhi.data() : nullptr)) continue;      // nothing of it reaches the stripe
-        par.push_back(c); geo.push_back({k, tlx, tly});
-    }
-    const int nc = (int)par.size();
-    // batches of up to 32 chips whose levels >= 1 (10 bytes per pixel, a third of the region) fit 2 GB; host chips are staged per batch
-    constexpr int MAXB = 32;
-    const size_t tmp_budget_px = ((size_t)2 << 30) / 10;
-    auto levels_px = [&](const ChipP& c) { size_t px = 0; for (int l = 1; l <= nb; l++) px += (size_t)(c.rw >> l) * (c.rh >> l); return px; };
-    struct Batch { int b0, b1, maxw, maxh; size_t px, cbytes, mbytes; };
-    std::vector<Batch> batches;
-    size_t max_px = 0, max_cb = 0, max_mb = 0;
-    for (int b0 = 0; b0 < nc;) {
-        Batch bt = {b0, b0, 0, 0, 0, 0, 0};
-        while (bt.b1 < nc && bt.b1 - b0 < MAXB) {
-            ChipP& c = par[bt.b1];
-            const size_t p = nb > 0 ? levels_px(c) : (size_t)c.rw * c.rh;
-            if (bt.b1 > b0 && bt.px + p > tmp_budget_px) break;
-            c.tmp = bt.px; bt.px += p;
-            if (!on_device) { bt.cbytes += ((size_t)c.cws * c.ch + 15) & ~(size_t)15; bt.mbytes += ((size_t)c.mws * c.ch + 15) & ~(size_t)15; }
-            bt.maxw = c.rw > bt.maxw ? c.rw : bt.maxw; bt.maxh = c.rh > bt.maxh ? c.rh : bt.maxh;
-            bt.b1++;
-        }
-        max_px = bt.px > max_px ? bt.px : max_px; max_cb = bt.cbytes > max_cb ? bt.cbytes : max_cb; max_mb = bt.mbytes > max_mb ? bt.mbytes : max_mb;
-        batches.push_back(bt);
-        b0 = bt.b1;
-    }
-    // every buffer is sized once, up front: the work below is then pure stream-ordered copies and launches (no allocation, no
-    // synchronisation between chips or batches)
-    MI_HIP(glap.reserve(max_px * 3 * sizeof(short) + 16));
-    MI_HIP(gwgt.reserve(max_px * sizeof(float) + 16));
-    MI_HIP(dpar.reserve((size_t)(nc > 0 ? nc : 1) * sizeof(ChipP)));
-    if (!on_device) { MI_HIP(dchip.reserve(max_cb + 16)); MI_HIP(dmask.reserve(max_mb + 16)); }
-    if (deferred_pixels) {
-        std::vector<int> ids((size_t)(nc > 0 ? nc : 1)), wins((size_t)4 * (nc > 0 ? nc : 1));
-        for (int i = 0; i < nc; i++) {
-            int x0 = 0, y0 = 0, x1 = par[i].cw - 1, y1 = par[i].ch - 1;
-            if (nb >= 1 && nb <= MAX_BANDS) chip_pixel_window(par[i], x0, y0, x1, y1);
-            ids[i] = geo[i].k; wins[4 * i] = x0; wins[4 * i + 1] = y0; wins[4 * i + 2] = x1; wins[4 * i + 3] = y1;
-        }
-        const int rc = mi_chip_pixels_prepare(ctx, nc, ids.data(), wins.data());
-        if (rc != MI355_OK) return rc;
-    }
-    if (on_device && nb > 0 && nc > 0) {
-        MI_HIP(hipMemcpyAsync(dpar.as<ChipP>(), par.data(), (size_t)nc * sizeof(ChipP), hipMemcpyHostToDevice, st));   // one copy, not one per batch
-        MI_HIP(hipStreamSynchronize(st));      // `par` is a local and the device-canvas path returns without another wait: the copy must have read it (the stream holds little here: the stage before ended with a wait)
-    }
-    // the canvas pyramids start from zero (after the wait above, so that the host does not sit through them)
-    MI_HIP(hipMemsetAsync(dlap.p, 0, loff[nb + 1] * 3 * sizeof(short), st));
-    MI_HIP(hipMemsetAsync(dwgt.p, 0, loff[nb + 1] * sizeof(float), st));
-    for (const Batch& bt : batches) {
-        const int b0 = bt.b0, b1 = bt.b1, B = b1 - b0, maxw = bt.maxw, maxh = bt.maxh;
-        if (!on_device) {
-            size_t co = 0, mo = 0;
-            for (int i = b0; i < b1; i++) {
-                const size_t cb = (size_t)par[i].cws * par[i].ch, mb = (size_t)par[i].mws * par[i].ch;
-                MI_HIP(hipMemcpyAsync(dchip.as<uint8_t>() + co, par[i].chip, cb, hipMemcpyHostToDevice, st));
-                MI_HIP(hipMemcpyAsync(dmask.as<uint8_t>() + mo, par[i].mask, mb, hipMemcpyHostToDevice, st));
-                par[i].chip = dchip.as<uint8_t>() + co; par[i].mask = dmask.as<uint8_t>() + mo;
-                co += (cb + 15) & ~(size_t)15; mo += (mb + 15) & ~(size_t)15;
-            }
-        }
-        if (deferred_pixels) { const int rc = mi_chip_pixels_launch(ctx, b0, B); if (rc != MI355_OK) return rc; }      // the batch's chip pixels, one launch
-        short* g = glap.as<short>();
-        float* wp = gwgt.as<float>();
-        if (nb == 0) {
-            // no pyramid: level 0 is the only level; it is materialised and accumulated (the path of bands = 0)
-            for (int i = b0; i < b1; i++) {
-                const ChipP& c = par[i];
-                hipLaunchKernelGGL(blend_prep_kernel, grid2(c.rw, c.rh), dim3(256), 0, st, c.chip, c.cws, c.mask, c.mws, c.cw, c.ch, c.left, c.top, c.rw, c.rh, g + c.tmp * 3, wp + c.tmp);
-                hipLaunchKernelGGL(blend_accumulate_kernel, grid2(c.rw, c.rh), dim3(256), 0, st, g + c.tmp * 3, wp + c.tmp, c.rw, c.rh, geo[i].tlx, geo[i].tly,
-                                   vlap(0), vwgt(0), Wp);
-            }
-            MI_HIP(hipGetLastError());
-            continue;
-        }
-        // the chips' parameters of this batch (the slot of the previous batch may still be read: one slot per batch, sized once)
-        const ChipP* d_par = dpar.as<ChipP>() + b0;
-        if (!on_device) MI_HIP(hipMemcpyAsync(dpar.as<ChipP>() + b0, par.data() + b0, (size_t)B * sizeof(ChipP), hipMemcpyHostToDevice, st));      // (device chips: all of them at once, above)
-        // REDUCE chains of the whole batch: independent of one another and of the canvas
-        // (grids: the largest active window of the batch at that level, in threads of two outputs)
+    // The launches that take a whole batch.  REDUCE chains: independent of one another and of the canvas (grids: the largest active window
+    // of the batch at that level, in threads of two outputs).  Level 0 of the whole batch at once when the masks partition the canvas.
+    void batch_launches(const bp::Batch& bt) {
+        const unsigned B = (unsigned)(bt.b1 - bt.b0);
         auto red_grid = [&](int l1) {
             int tw = 1, th = 1;
-            for (int i = b0; i < b1; i++) {
+            for (int i = bt.b0; i < bt.b1; i++) {
                 const Win wn = l1 <= MAX_BANDS ? par[i].cwin[l1] : Win{0, 0, (par[i].rw >> l1) - 1, (par[i].rh >> l1) - 1};
                 const int t = (wn.x1 - (wn.x0 & ~1)) / 2 + 1, hh = wn.y1 - wn.y0 + 1;
                 tw = t > tw ? t : tw; th = hh > th ? hh : th;
             }
-            return dim3((unsigned)((tw + 255) / 256), (unsigned)th, (unsigned)B);
+            return dim3((unsigned)((tw + 255) / 256), (unsigned)th, B);
         };
-        (void)maxw; (void)maxh;
-        hipLaunchKernelGGL(pyr_down0_batch_kernel, red_grid(1), dim3(256), 0, st, d_par, g, wp);
+        hipLaunchKernelGGL(pyr_down0_batch_kernel, red_grid(1), dim3(256), 0, st, d_par + bt.b0, g, wp);
+        for (int l = 1; l < p.nb; l++)
+            hipLaunchKernelGGL(pyr_down_pair_batch_kernel, red_grid(l + 1), dim3(256), 0, st, d_par + bt.b0, l, g, wp);
+        if (!lap0_batched) return;
+        int tw = 1, th = 1;
+        for (int i = bt.b0; i < bt.b1; i++) { const Win t = par[i].twin[0]; tw = t.x1 - t.x0 + 1 > tw ? t.x1 - t.x0 + 1 : tw; th = t.y1 - t.y0 + 1 > th ? t.y1 - t.y0 + 1 : th; }
+        hipLaunchKernelGGL(blend_lap0_accumulate_batch_kernel, dim3((unsigned)((tw + 255) / 256), (unsigned)th, B), dim3(256), 0, st, d_par + bt.b0, g, vlap(0), vwgt(0), p.Wp);
+    }
+
+    // More than MAX_BANDS levels: level by level, whole levels (the windows hold MAX_BANDS).  That takes a canvas side above 65 536 with
+    // band > 16 and about 170 GB of pyramids: no test reaches this arm, it is kept as it was.
+    void accumulate_chip_by_level(const bp::ChipP& c, const std::vector<size_t>& roff) {
+        const int nb = p.nb, Wp = p.Wp, tlx = c.tlx, tly = c.tly, rw = c.rw, rh = c.rh;
         for (int l = 1; l < nb; l++)
-            hipLaunchKernelGGL(pyr_down_pair_batch_kernel, red_grid(l + 1), dim3(256), 0, st, d_par, l, g, wp);
-        // level 0 of the whole batch at once when the masks partition the canvas (owned_bbox: they are this device's FindMasksByDistMap masks)
-        const bool lap0_batched = owned_bbox != nullptr && nb <= MAX_BANDS;
-        if (lap0_batched) {
-            int tw = 1, th = 1;
-            for (int i = b0; i < b1; i++) { const Win t = par[i].twin[0]; tw = t.x1 - t.x0 + 1 > tw ? t.x1 - t.x0 + 1 : tw; th = t.y1 - t.y0 + 1 > th ? t.y1 - t.y0 + 1 : th; }
-            hipLaunchKernelGGL(blend_lap0_accumulate_batch_kernel, dim3((unsigned)((tw + 255) / 256), (unsigned)th, (unsigned)B), dim3(256), 0, st, d_par, g, vlap(0), vwgt(0), Wp);
-        }
-        // accumulation, chip after chip in chip order: Laplacian level l = Gaussian l - EXPAND(Gaussian l + 1), accumulated as it is formed
-        for (int i = b0; i < b1; i++) {
-            const ChipP& c = par[i];
-            const int tlx = geo[i].tlx, tly = geo[i].tly, rw = c.rw, rh = c.rh;
-            std::vector<size_t> roff(nb + 2, 0);                      // levels >= 1 behind c.tmp
-            roff[1] = c.tmp;
-            for (int l = 1; l < nb; l++) roff[l + 1] = roff[l] + (size_t)(rw >> l) * (rh >> l);
-            if (!lap0_batched && c.twin[0].y1 >= c.twin[0].y0)
-                hipLaunchKernelGGL(blend_lap0_accumulate_kernel, grid2(c.twin[0].x1 - c.twin[0].x0 + 1, c.twin[0].y1 - c.twin[0].y0 + 1), dim3(256), 0, st, c, g + roff[1] * 3, tlx, tly,
-                                   vlap(0), vwgt(0), Wp);
-            if (nb > MAX_BANDS) {                                             // (band > 16 on a canvas that allows it:) level by level
-                for (int l = 1; l < nb; l++)
-                    hipLaunchKernelGGL(blend_lap_accumulate_kernel, grid2(rw >> (l + 1), rh >> (l + 1)), dim3(256), 0, st, g + roff[l + 1] * 3, rw >> (l + 1), rh >> (l + 1),
-                                       g + roff[l] * 3, wp + roff[l], tlx >> l, tly >> l, vlap(l), vwgt(l), Wp >> l);
-                hipLaunchKernelGGL(blend_accumulate_kernel, grid2(rw >> nb, rh >> nb), dim3(256), 0, st, g + roff[nb] * 3, wp + roff[nb], rw >> nb, rh >> nb, tlx >> nb, tly >> nb,
-                                   vlap(nb), vwgt(nb), Wp >> nb);
-                continue;
-            }
-            LapLevels L; memset(&L, 0, sizeof(L));
-            int grows = 0, maxw = 0;                                           // (an empty window -- a stripe -- has y1 = y0 - 1: no rows)
-            for (int l = 1; l < nb; l++) {                                     // Laplacian level l: one thread per pixel of level l + 1
-                const int i = L.n++;
-                L.row0[i] = grows; L.w[i] = rw >> (l + 1); L.h[i] = rh >> (l + 1); L.ox[i] = tlx >> l; L.oy[i] = tly >> l; L.DW[i] = Wp >> l;
-                L.fine[i] = roff[l]; L.coarse[i] = roff[l + 1]; L.dst[i] = voff[l];
-                const Win t = c.twin[l];
-                L.x0[i] = t.x0; L.y0[i] = t.y0; L.x1[i] = t.x1;
-                grows += t.y1 - t.y0 + 1; maxw = t.x1 - t.x0 + 1 > maxw ? t.x1 - t.x0 + 1 : maxw;
-            }
-            {
-                const int i = L.n++;
-                L.row0[i] = grows; L.w[i] = rw >> nb; L.h[i] = rh >> nb; L.ox[i] = tlx >> nb; L.oy[i] = tly >> nb; L.DW[i] = Wp >> nb;
-                L.fine[i] = roff[nb]; L.coarse[i] = 0; L.dst[i] = voff[nb];
-                const Win t = c.twin[nb];
-                L.x0[i] = t.x0; L.y0[i] = t.y0; L.x1[i] = t.x1;
-                grows += t.y1 - t.y0 + 1; maxw = t.x1 - t.x0 + 1 > maxw ? t.x1 - t.x0 + 1 : maxw;
-            }
-            L.row0[L.n] = grows;
-            if (grows > 0 && maxw > 0) hipLaunchKernelGGL(blend_lap_levels_kernel, grid2(maxw, grows), dim3(256), 0, st, L, g, wp, dlap.as<short>(), dwgt.as<float>());
-        }
-        MI_HIP(hipGetLastError());
+            hipLaunchKernelGGL(blend_lap_accumulate_kernel, grid2(rw >> (l + 1), rh >> (l + 1)), dim3(256), 0, st, g + roff[l + 1] * 3, rw >> (l + 1), rh >> (l + 1),
+                               g + roff[l] * 3, wp + roff[l], tlx >> l, tly >> l, vlap(l), vwgt(l), Wp >> l);
+        hipLaunchKernelGGL(blend_accumulate_kernel, grid2(rw >> nb, rh >> nb), dim3(256), 0, st, g + roff[nb] * 3, wp + roff[nb], rw >> nb, rh >> nb, tlx >> nb, tly >> nb,
+                           vlap(nb), vwgt(nb), Wp >> nb);
     }
-    for (int l = 0; l <= nb; l++) {
-        const size_t cnt = (size_t)(Wp >> l) * (size_t)(nhi[l] - nlo[l] + 1);      // the level's stored rows are contiguous from loff[l]
-        hipLaunchKernelGGL(blend_normalize_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dlap.as<short>() + loff[l] * 3, dwgt.as<float>() + loff[l], cnt);
+
+    // One chip into the canvas pyramids: Laplacian level l = Gaussian l - EXPAND(Gaussian l + 1), accumulated as it is formed.  Level 0 on its
+    // own unless the batch took it; the levels 1 .. nb as one launch.
+    void accumulate_chip(const bp::ChipP& c) {
+        const int nb = p.nb;
+        std::vector<size_t> roff(nb + 2, 0);                      // levels >= 1 behind c.tmp
+        roff[1] = c.tmp;
+        for (int l = 1; l < nb; l++) roff[l + 1] = roff[l] + (size_t)(c.rw >> l) * (c.rh >> l);
+        if (!lap0_batched && c.twin[0].y1 >= c.twin[0].y0)
+            hipLaunchKernelGGL(blend_lap0_accumulate_kernel, grid2(c.twin[0].x1 - c.twin[0].x0 + 1, c.twin[0].y1 - c.twin[0].y0 + 1), dim3(256), 0, st, ChipP{c}, g + roff[1] * 3, c.tlx, c.tly,
+                               vlap(0), vwgt(0), p.Wp);
+        if (nb > MAX_BANDS) return accumulate_chip_by_level(c, roff);
+        LapLevels L; memset(&L, 0, sizeof(L));
+        int grows = 0, maxw = 0;                                           // (an empty window -- a stripe -- has y1 = y0 - 1: no rows)
+        for (int l = 1; l <= nb; l++) {
+            // Laplacian level l < nb: one thread per pixel of level l + 1; the top level: one per pixel, no coarser level
+            const int i = L.n++, tl = l < nb ? l + 1 : nb;
+            L.row0[i] = grows; L.w[i] = c.rw >> tl; L.h[i] = c.rh >> tl; L.ox[i] = c.tlx >> l; L.oy[i] = c.tly >> l; L.DW[i] = p.Wp >> l;
+            L.fine[i] = roff[l]; L.coarse[i] = l < nb ? roff[l + 1] : 0; L.dst[i] = p.voff[l];
+            const Win t = c.twin[l];
+            L.x0[i] = t.x0; L.y0[i] = t.y0; L.x1[i] = t.x1;
+            grows += t.y1 - t.y0 + 1; maxw = t.x1 - t.x0 + 1 > maxw ? t.x1 - t.x0 + 1 : maxw;
+        }
+        L.row0[L.n] = grows;
+        if (grows > 0 && maxw > 0) hipLaunchKernelGGL(blend_lap_levels_kernel, grid2(maxw, grows), dim3(256), 0, st, L, g, wp, dl, dw);
     }
-    for (int l = nb - 1; l >= 0; l--)       // collapse: rows nlo[l] .. nhi[l] of level l from the rows of level l + 1 they read (all stored: stripe_levels)
-        hipLaunchKernelGGL((pyr_up16_combine_kernel<false>), grid2(Wp >> l, nhi[l] - nlo[l] + 1), dim3(256), 0, st, vlap(l + 1), Wp >> (l + 1), Hp >> (l + 1), vlap(l), nlo[l]);
-    const int ows = d_user ? user_ws : (W * 3 + 3) & ~3;
-    if (d_user) {
-        MI_HIP(hipMemsetAsync(d_user, 0, (size_t)ows * rows, st));
-        hipLaunchKernelGGL(blend_finalize_kernel, grid2(W, rows), dim3(256), 0, st, vlap(0), vwgt(0), Wp, W, d_user, ows, row0);
+
+    // the canvas pyramids to the canvas: normalise every level, collapse from the top
+    void normalise_and_collapse() {
+        for (int l = 0; l <= p.nb; l++) {
+            const size_t cnt = p.level_px(l);
+            hipLaunchKernelGGL(blend_normalize_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dl + p.loff[l] * 3, dw + p.loff[l], cnt);
+        }
+        for (int l = p.nb - 1; l >= 0; l--)       // collapse: rows nlo[l] .. nhi[l] of level l from the rows of level l + 1 they read (all stored: stripe_levels)
+            hipLaunchKernelGGL((pyr_up16_combine_kernel<false>), grid2(p.Wp >> l, p.nhi[l] - p.nlo[l] + 1), dim3(256), 0, st, vlap(l + 1), p.Wp >> (l + 1), p.Hp >> (l + 1), vlap(l), p.nlo[l]);
+    }
+
+    // level 0 as bytes: into the caller's device rows, or through "blend_out" into a malloc'd host canvas (never a stripe: vlap(0) is dl there)
+    int write_out(const BlendOut& out) {
+        const int W = p.W, row0 = p.striped ? p.row0 : 0, rows = p.striped ? p.rows : p.H;
+        const int ows = out.d_rows ? out.ws : (W * 3 + 3) & ~3;
+        uint8_t* dst = out.d_rows;
+        if (!dst) { DevBuf& dout = ctx->buf("blend_out"); MI_HIP(dout.reserve((size_t)ows * rows)); dst = dout.as<uint8_t>(); }
+        MI_HIP(hipMemsetAsync(dst, 0, (size_t)ows * rows, st));
+        hipLaunchKernelGGL(blend_finalize_kernel, grid2(W, rows), dim3(256), 0, st, vlap(0), vwgt(0), p.Wp, W, dst, ows, row0);
         MI_HIP(hipGetLastError());
-        if (ow) *ow = W;
-        if (oh) *oh = rows;
-        if (ows_out) *ows_out = ows;
+        if (!out.d_rows) {
+            uint8_t* host = (uint8_t*)malloc((size_t)ows * rows);
+            if (!host) return MI355_ERR_NOMEM;
+            hipError_t e = hipMemcpyAsync(host, dst, (size_t)ows * rows, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { free(host); ctx->set_error(std::string("multiband_blend: ") + hipGetErrorString(e)); return MI355_ERR_DEVICE; }
+            *out.host = host;
+        }
+        if (out.ow) *out.ow = W;
+        if (out.oh) *out.oh = rows;
+        if (out.ows) *out.ows = ows;
         return MI355_OK;
     }
-    DevBuf& dout = ctx->buf("blend_out");
-    MI_HIP(dout.reserve((size_t)ows * H));
-    MI_HIP(hipMemsetAsync(dout.p, 0, (size_t)ows * H, st));
-    hipLaunchKernelGGL(blend_finalize_kernel, grid2(W, H), dim3(256), 0, st, dlap.as<short>(), dwgt.as<float>(), Wp, W, dout.as<uint8_t>(), ows);
-    MI_HIP(hipGetLastError());
-    uint8_t* host = (uint8_t*)malloc((size_t)ows * H);
-    if (!host) return MI355_ERR_NOMEM;
-    hipError_t e = hipMemcpyAsync(host, dout.p, (size_t)ows * H, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { free(host); ctx->set_error(std::string("multiband_blend: ") + hipGetErrorString(e)); return MI355_ERR_DEVICE; }
-    *out = host;
-    if (ow) *ow = W;
-    if (oh) *oh = H;
-    if (ows_out) *ows_out = ows;
-    return MI355_OK;
+};
+
+// chips / masks / info / n: the direct form's host arrays (set == NULL)
+int blend_core(mi355_ctx* ctx, chips::ChipSet* set, const uint8_t* const* chips, const uint8_t* const* masks, const mi355_chip_info* info, int n,
+               const bp::Plan& p, const BlendOut& out) {
+    const int nb = p.nb;
+    const int* owned = set && !set->owned.empty() ? set->owned.data() : nullptr;
+    std::vector<const uint8_t*> dc, dm;                          // the set's chips and masks as pointers
+    if (set) {
+        n = set->n(); info = set->info.data();
+        dc.resize(n > 0 ? n : 1); dm.resize(n > 0 ? n : 1);
+        for (int v = 0; v < n; v++) { dc[v] = ctx->buf("chip_imgs").as<uint8_t>() + set->chip_off[v]; dm[v] = ctx->buf("chip_masks").as<uint8_t>() + set->mask_off[v]; }
+        chips = dc.data(); masks = dm.data();
+    }
+    if (n < 0 || (n > 0 && (!chips || !masks || !info)) || p.W <= 0 || p.H <= 0 || p.band < 0 || (!out.host && !out.d_rows)) { ctx->set_error("multiband_blend: bad arguments"); return MI355_ERR_ARG; }
+    if (p.striped && (p.row0 < 0 || p.rows < 1 || p.row0 + p.rows > p.H || !owned || !out.d_rows)) { ctx->set_error("multiband_blend: bad stripe"); return MI355_ERR_ARG; }
+    const hipStream_t st = ctx->stream;
+    DevBuf& dlap = ctx->buf("blend_dst_lap");
+    DevBuf& dwgt = ctx->buf("blend_dst_w");
+    MI_HIP(dlap.reserve(p.loff[nb + 1] * 3 * sizeof(short)));
+    MI_HIP(dwgt.reserve(p.loff[nb + 1] * sizeof(float)));
+    DevBuf& glap = ctx->buf("blend_src_lap");
+    DevBuf& gwgt = ctx->buf("blend_src_w");
+    DevBuf& dpar = ctx->buf("blend_chip_params");
+    bp::Feed feed;
+    if (!bp::feed_regions(p, chips, masks, info, n, owned, feed)) { ctx->set_error("multiband_blend: chip outside the canvas"); return MI355_ERR_ARG; }
+    const int nc = (int)feed.par.size();
+    const bp::Batches batches = bp::make_batches(feed.par, nb, !set);
+    // every buffer is sized once, up front: the work below is then pure stream-ordered copies and launches (no allocation, no
+    // synchronisation between chips or batches)
+    MI_HIP(glap.reserve(batches.max_px * 3 * sizeof(short) + 16));
+    MI_HIP(gwgt.reserve(batches.max_px * sizeof(float) + 16));
+    MI_HIP(dpar.reserve((size_t)(nc > 0 ? nc : 1) * sizeof(ChipP)));
+    if (!set) { MI_HIP(ctx->buf("blend_chip").reserve(batches.max_cb + 16)); MI_HIP(ctx->buf("blend_mask").reserve(batches.max_mb + 16)); }
+    if (set) {
+        // the chips hold no pixels yet: each chip's are made inside the part of the chip its active windows read (chip_pixel_window); here
+        // the windows of all chips go to the device, the launches follow batch by batch
+        std::vector<int> wins((size_t)4 * (nc > 0 ? nc : 1));
+        for (int i = 0; i < nc; i++) {
+            int x0 = 0, y0 = 0, x1 = feed.par[i].cw - 1, y1 = feed.par[i].ch - 1;
+            if (nb >= 1 && nb <= MAX_BANDS) bp::chip_pixel_window(feed.par[i], x0, y0, x1, y1);
+            wins[4 * i] = x0; wins[4 * i + 1] = y0; wins[4 * i + 2] = x1; wins[4 * i + 3] = y1;
+        }
+        const int rc = mi_chip_pixels_prepare(ctx, *set, nc, feed.chip.data(), wins.data());
+        if (rc != MI355_OK) return rc;
+    }
+    Blender b{ctx, p, set, st, std::move(feed.par), glap.as<short>(), gwgt.as<float>(), dlap.as<short>(), dwgt.as<float>(), dpar.as<ChipP>(),
+              owned != nullptr && nb <= MAX_BANDS};      // level 0 batched: the masks are this device's FindMasksByDistMap masks
+    if (set && nb > 0 && nc > 0) {
+        MI_HIP(hipMemcpyAsync(dpar.p, b.par.data(), (size_t)nc * sizeof(ChipP), hipMemcpyHostToDevice, st));   // one copy, not one per batch
+        MI_HIP(hipStreamSynchronize(st));      // `par` is a local and the device-canvas path returns without another wait: the copy must have read it (the stream holds little here: the stage before ended with a wait)
+    }
+    // the canvas pyramids start from zero (after the wait above, so that the host does not sit through them)
+    MI_HIP(hipMemsetAsync(dlap.p, 0, p.loff[nb + 1] * 3 * sizeof(short), st));
+    MI_HIP(hipMemsetAsync(dwgt.p, 0, p.loff[nb + 1] * sizeof(float), st));
+    for (const bp::Batch& bt : batches.v) {
+        if (!set) { const int rc = b.stage_batch(bt); if (rc != MI355_OK) return rc; }
+        if (set) { const int rc = mi_chip_pixels_launch(ctx, *set, bt.b0, bt.b1 - bt.b0); if (rc != MI355_OK) return rc; }      // the batch's chip pixels, one launch
+        if (nb == 0) b.accumulate_flat(bt);
+        else {
+            // the chips' parameters of this batch (the slot of the previous batch may still be read: one slot per batch, sized once)
+            if (!set) MI_HIP(hipMemcpyAsync(dpar.as<ChipP>() + bt.b0, b.par.data() + bt.b0, (size_t)(bt.b1 - bt.b0) * sizeof(ChipP), hipMemcpyHostToDevice, st));      // (device chips: all of them at once, above)
+            b.batch_launches(bt);
+            for (int i = bt.b0; i < bt.b1; i++) b.accumulate_chip(b.par[i]);      // chip after chip, in chip order
+        }
+        MI_HIP(hipGetLastError());
+    }
+    b.normalise_and_collapse();
+    return b.write_out(out);
 }
+
+}  // namespace
 
 int mi_multiband_blend(mi355_ctx* ctx, const uint8_t* const* chips, const uint8_t* const* masks, const mi355_chip_info* info, int n,
                        int W, int H, int band, uint8_t** out, int* ow, int* oh, int* ows_out) {
-    return blend_core(ctx, chips, masks, 0, info, n, W, H, band, out, ow, oh, ows_out);
+    return blend_core(ctx, nullptr, chips, masks, info, n, bp::make_plan(W, H, band), BlendOut{nullptr, 0, out, ow, oh, ows_out});
 }
 
 // The whole of LaplacianPyramidBlending (MosaicImage.cpp:2205-2510) without leaving the device between its stages: chips
 // and masks (mi_chips_and_masks_dev) feed the blender straight from HBM; only the finished canvas goes back to the host.
 int mi_mosaic_blended(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                       const uint8_t* keep, int band, uint8_t** out, int* ow, int* oh, int* ows_out) {
-    std::vector<size_t> chip_off, mask_off;
-    int nv = 0, cw = 0, ch = 0;
-    mi355_chip_info* ci = nullptr;
-    std::vector<int> bbox;
-    int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, 1, &nv, &ci, chip_off, mask_off, &cw, &ch, 0, &bbox, 1);
-    if (rc != MI355_OK) { free(ci); return rc; }
-    std::vector<const uint8_t*> dc(nv > 0 ? nv : 1), dm(nv > 0 ? nv : 1);
-    for (int v = 0; v < nv; v++) { dc[v] = ctx->buf("chip_imgs").as<uint8_t>() + chip_off[v]; dm[v] = ctx->buf("chip_masks").as<uint8_t>() + mask_off[v]; }
-    rc = blend_core(ctx, dc.data(), dm.data(), 1, ci, nv, cw, ch, band, out, ow, oh, ows_out, nullptr, 0, (int)bbox.size() == 4 * nv && nv > 0 ? bbox.data() : nullptr, 1);
-    free(ci);
-    return rc;
+    chips::ChipSet set;
+    const int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, chips::Request{chips::Request::BLEND_HOST}, set);
+    if (rc != MI355_OK) return rc;
+    return blend_core(ctx, &set, nullptr, nullptr, nullptr, 0, bp::make_plan(set.W, set.H, band), BlendOut{nullptr, 0, out, ow, oh, ows_out});
 }
 
 // The same with the survey resident in HBM: device frames in, device canvas out (C5: frames + chips + masks + distance maps + both
@@ -900,37 +723,16 @@ int mi_mosaic_blended_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
     if (lw != cw || lh != ch || cws < 3 * cw || (cws & 3)) { ctx->set_error("mosaic_blended_dev: canvas geometry does not match mi355_blend_layout"); return MI355_ERR_ARG; }
     if (rows < 0) { row0 = 0; rows = ch; }
     if (row0 < 0 || rows < 1 || row0 + rows > ch) { ctx->set_error("mosaic_blended_dev: bad stripe"); return MI355_ERR_ARG; }
-    int nb = (int)std::ceil(std::log((double)(cw > ch ? cw : ch)) / std::log(2.0));
-    if (nb > band) nb = band;
-    if (nb < 0) nb = 0;
-    bool striped = !(row0 == 0 && rows == ch);
-    if (striped && (nb < 1 || nb > MAX_BANDS)) striped = false;      // (no pyramid, or more levels than the windows hold:) the whole canvas is formed and the stripe copied out
+    const bp::Plan p = bp::make_plan(cw, ch, band, row0, rows);
     int mr0 = 0, mr1 = ch - 1;
-    if (striped) {
-        const int al = 1 << nb, Hp = (ch + al - 1) / al * al;
-        std::vector<int> nlo, nhi;
-        stripe_levels(row0, rows, nb, Hp, nlo, nhi);
-        stripe_mask_rows(nlo, nhi, ch, mr0, mr1);
-    }
-    std::vector<size_t> chip_off, mask_off;
-    int nv = 0, gw = 0, gh = 0;
-    mi355_chip_info* ci = nullptr;
-    std::vector<int> bbox;
-    int rc = mi_chips_and_masks_dev(ctx, d_imgs, w, h, ws, n, h9s, keep, 1, &nv, &ci, chip_off, mask_off, &gw, &gh, 1, &bbox, 1, mr0, mr1, cover_only);
-    if (rc != MI355_OK) { free(ci); return rc; }
-    if (cover_only) return MI355_OK;                     // mi355_mosaic_stripe_cover: the frames whose chips reach the stripe (+ the pyramids' reach) are marked, nothing was enqueued
-    std::vector<const uint8_t*> dc(nv > 0 ? nv : 1), dm(nv > 0 ? nv : 1);
-    for (int v = 0; v < nv; v++) { dc[v] = ctx->buf("chip_imgs").as<uint8_t>() + chip_off[v]; dm[v] = ctx->buf("chip_masks").as<uint8_t>() + mask_off[v]; }
-    const int* bb = (int)bbox.size() == 4 * nv && nv > 0 ? bbox.data() : nullptr;
-    if (striped || (row0 == 0 && rows == ch)) {
-        rc = blend_core(ctx, dc.data(), dm.data(), 1, ci, nv, gw, gh, band, nullptr, nullptr, nullptr, nullptr, d_canvas, cws, bb, 1, row0, striped ? rows : -1);
-    } else {
-        DevBuf& full = ctx->buf("blend_full_canvas");
-        hipError_t e = full.reserve((size_t)cws * ch);
-        if (e != hipSuccess) { free(ci); ctx->set_error(std::string("mosaic_blended_dev: ") + hipGetErrorString(e)); return MI355_ERR_NOMEM; }
-        rc = blend_core(ctx, dc.data(), dm.data(), 1, ci, nv, gw, gh, band, nullptr, nullptr, nullptr, nullptr, full.as<uint8_t>(), cws, bb, 1);
-        if (rc == MI355_OK && hipMemcpyAsync(d_canvas, full.as<uint8_t>() + (size_t)row0 * cws, (size_t)rows * cws, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = MI355_ERR_DEVICE;
-    }
-    free(ci);
+    if (p.striped) bp::stripe_mask_rows(p.nlo, p.nhi, ch, mr0, mr1);
+    chips::ChipSet set;
+    int rc = mi_chips_and_masks_dev(ctx, d_imgs, w, h, ws, n, h9s, keep, chips::Request{chips::Request::BLEND_DEVICE, 1, mr0, mr1, cover_only}, set);
+    if (rc != MI355_OK || cover_only) return rc;         // cover_only (mi355_mosaic_stripe_cover): the frames whose chips reach the stripe (+ the pyramids' reach) are marked, nothing was enqueued
+    DevBuf& full = ctx->buf("blend_full_canvas");      // copy_out: the whole canvas goes here, the rows asked for are copied out
+    const hipError_t e = p.copy_out ? full.reserve((size_t)cws * ch) : hipSuccess;
+    if (e != hipSuccess) { ctx->set_error(std::string("mosaic_blended_dev: ") + hipGetErrorString(e)); return MI355_ERR_NOMEM; }
+    rc = blend_core(ctx, &set, nullptr, nullptr, nullptr, 0, p, BlendOut{p.copy_out ? full.as<uint8_t>() : d_canvas, cws, nullptr, nullptr, nullptr, nullptr});
+    if (rc == MI355_OK && p.copy_out && hipMemcpyAsync(d_canvas, full.as<uint8_t>() + (size_t)row0 * cws, (size_t)rows * cws, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = MI355_ERR_DEVICE;
     return rc;
 }

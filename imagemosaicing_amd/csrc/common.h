@@ -169,8 +169,6 @@ struct mi355_ctx {
     void set_error(const std::string& s) { err = s; }
     DevBuf& buf(const std::string& name) { return ws[name]; }
     HostBuf& hbuf(const std::string& name) { return hws[name]; }
-    std::vector<int> deferred_dims;                    // per prepared entry: launch extent (groups of 4 columns, rows)
-    std::vector<unsigned char> deferred_warps;         // warp.hip: the chips' warp arguments when mi_chips_and_masks_dev was asked to leave the pixels to mi_chip_pixels_prepare / _launch
     // profiling brackets
     void prof_begin(const char* cls, double alg_bytes, hipStream_t st);
     void prof_end(const char* cls, hipStream_t st);
@@ -204,14 +202,7 @@ int mi_mosaic_overview_dev(mi355_ctx*, const uint8_t* d_rows, int cw, int ch, in
                            uint8_t* const* d_levels, uint16_t* const* d_covers, int row0, int rows, int only_level = 0);      // overview.hip; only_level = l: d_levels / d_covers entries other than l - 1 may be NULL (the preview)
 int mi_sift_flush(mi355_ctx*);                               // enqueues every partly filled batch (no wait)
 int mi_sift_flush_if_parked(mi355_ctx*, hipEvent_t ev);   // launches the batch still holding a parked frame with this event
-int mi_chips_and_masks_dev(mi355_ctx*, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
-                           const float* h9s, const uint8_t* keep, int find_masks, int* n_chips, mi355_chip_info** chips,
-                           std::vector<size_t>& chip_off, std::vector<size_t>& mask_off, int* canvas_w, int* canvas_h, int imgs_on_device = 0,
-                           std::vector<int>* owned_bbox = nullptr, int defer_pixels = 0, int row_lo = 0, int row_hi = 0x7fffffff, uint8_t* cover_only = nullptr);      // row_lo .. row_hi: a stripe of the canvas (see warp.hip); find_masks: per chip {min col, min row, max col, max row} of its non-zero mask bytes (max < min: none)
-// defer_pixels: the chips' validity masks (and ownership) are made at once, their PIXELS only where asked for afterwards, chip by chip
-// (the blender needs them inside a chip's active window only); columns / rows inclusive, clipped to the chip
-int mi_chip_pixels_prepare(mi355_ctx*, int n, const int* chips, const int* win4);      // entry e = chip chips[e] inside win4[4e..]: arguments to the device
-int mi_chip_pixels_launch(mi355_ctx*, int first, int count);                          // one launch for entries first .. first + count - 1
+// (the chip stage behind the blended calls -- mi_chips_and_masks_dev, mi_chip_pixels_prepare / _launch -- and its chip set: chips.h)
 int mi_mosaic_blended(mi355_ctx*, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                       const uint8_t* keep, int band, uint8_t** out, int* ow, int* oh, int* ows);
 int mi_mosaic_blended_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,

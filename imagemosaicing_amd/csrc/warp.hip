@@ -19,19 +19,14 @@
 #include "common.h"
 #include "hmath.h"
 #include "mosaic_frame.h"
-#include <memory>
+#include "chips.h"
 
 namespace {
 
-struct WarpArgs {
-    const uint8_t* src; int w, h, ws;          // source image
-    uint8_t* dst; int dws;                      // destination (canvas / chip / tight image), row stride
-    uint8_t* mask; int mws;                     // chip validity mask (CHIP mode) or nullptr
-    int x_beg, x_end, y_beg, y_end;             // inclusive destination range to visit
-    float inv[9];                               // inverse homography (destination -> source)
-    float dx, dy;                               // mode 0: xs = (float)xD - dx
-    float sx, sy; int x0, y0;                   // mode 1 (chips): ((float)xD - dx) - sx + (float)x0
-};
+// The fields live in chips.h, where the one-call blend's chip set holds the chips' arguments.  The kernels keep a parameter type of this
+// name in this namespace: it is part of their names, "(anonymous namespace)::warp_chips_kernel<1>((anonymous namespace)::WarpArgs const*)", which profiles/ quote.
+struct WarpArgs : chips::WarpArgs {};
+static_assert(sizeof(WarpArgs) == sizeof(chips::WarpArgs), "the device arrays are filled from chips::WarpArgs");
 
 // PART (chips only): 0 = pixels and validity mask, 1 = the validity mask alone (no source read), 2 = the pixels alone (the mask bytes
 // hold the ownership by then and stay as they are)
@@ -634,7 +629,7 @@ __global__ __launch_bounds__(256) void owner_kernel(const ChipDev* chips, const 
 
 // Per chip the box of its mask's non-zero bytes, i.e. of the pixels the chip OWNS after owner_kernel: {min column, min row} in
 // bbox_min[2k..] (start 0x7f7f7f7f), {max column, max row} in bbox_max[2k..] (start -1).  The blender works only where a chip's weights can
-// be non-zero (blend.hip chip_windows).  One launch for all chips, a workgroup per 256 x 64 mask block (one 32-bit load per lane and row);
+// be non-zero (blend_plan.cpp chip_windows).  One launch for all chips, a workgroup per 256 x 64 mask block (one 32-bit load per lane and row);
 // only the workgroups that meet a non-zero byte -- a chip owns a few percent of its area in a dense survey -- end with atomics.
 // (Tracked inside owner_kernel instead, every wave of a cell moved the maximum row: 12 000 atomics per address, 7 -> 18 ms per canvas.)
 __global__ __launch_bounds__(256) void mask_bbox_kernel(const ChipDev* chips, uint8_t* const* masks, int* bbox_min, int* bbox_max, int row_lo, int row_hi) {
@@ -686,21 +681,19 @@ __global__ __launch_bounds__(256) void mask_bbox_kernel(const ChipDev* chips, ui
 
 }  // namespace
 
-// Device stage of the chips: layout on the host, warps / distance maps / ownership on the device.  The chips and masks
-// stay in ctx buffers "chip_imgs" / "chip_masks" at chip_off[v] / mask_off[v]; *chips_out is malloc'd.
-// row_lo .. row_hi (canvas rows, inclusive; the default is the whole canvas): a STRIPE of the canvas -- only the chips that reach these rows
-// (widened to whole groups of 16) get storage, validity masks, a maximum distance, and ownership is decided for these rows only; the owned
-// boxes are the boxes inside the stripe, and the chips outside it report an empty box.  What is decided is what the whole canvas gives
-// there: ownership is per canvas pixel among the chips that cover it, and a chip's maximum distance is taken over the whole chip.
-int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
-                           const float* h9s, const uint8_t* keep, int find_masks, int* n_chips, mi355_chip_info** chips_out,
-                           std::vector<size_t>& chip_off, std::vector<size_t>& mask_off, int* cw_out, int* ch_out, int imgs_on_device,
-                           std::vector<int>* owned_bbox, int defer_pixels, int row_lo, int row_hi, uint8_t* cover_only) {
-    if (!imgs || !w || !h || !ws || !h9s || n <= 0 || !n_chips || !chips_out) return MI355_ERR_ARG;
-    // ---- layout, MosaicImage.cpp:2233-2343 (host, same float ops) ----
+// ---- the stages of mi_chips_and_masks_dev -----------------------------------------------------------------------------------------------
+namespace {
+
+// The canvas of the chips' layout, MosaicImage.cpp:2233-2292 (host, same float ops): the corner box of every frame that gives a chip, the
+// canvas that holds them all and its origin.  mi_blend_layout answers from the same function, so the two cannot drift apart.
+struct CanvasLayout {
+    float dGx, dGy; int W, H;
+    std::vector<int> kept;                       // the frames that give a chip, ascending
+    std::vector<float> bx0, by0, bx1, by1;       // per frame: its corner box
+};
+void canvas_layout(const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, CanvasLayout& L) {
     float maxX = 0.0f, maxY = 0.0f, minX = 0.0f, minY = 0.0f;                     // :2234 (canvas always contains the origin)
-    std::vector<float> bx0(n), by0(n), bx1(n), by1(n);
-    std::vector<int> kept;
+    L.bx0.assign(n, 0.0f); L.by0.assign(n, 0.0f); L.bx1.assign(n, 0.0f); L.by1.assign(n, 0.0f);
     for (int k = 0; k < n; k++) {
         const float* m = h9s + 9 * k;
         if ((keep && !keep[k]) || m[8] == 0.0f) continue;
@@ -710,138 +703,135 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
         if (bMinX < minX) minX = bMinX;
         if (bMaxY > maxY) maxY = bMaxY;
         if (bMinY < minY) minY = bMinY;
-        bx0[k] = bMinX; by0[k] = bMinY; bx1[k] = bMaxX; by1[k] = bMaxY;
-        kept.push_back(k);
+        L.bx0[k] = bMinX; L.by0[k] = bMinY; L.bx1[k] = bMaxX; L.by1[k] = bMaxY;
+        L.kept.push_back(k);
     }
-    const float dGx = -minX, dGy = -minY;
-    const int newW = (int)(maxX - minX + 1.5f), newH = (int)(maxY - minY + 1.5f);
-    const int nv = (int)kept.size();
-    // the stripe in whole groups of owner_kernel's 16 rows
-    const bool striped = row_lo > 0 || row_hi < newH - 1;
-    if (striped && (!find_masks || !defer_pixels || !owned_bbox)) { ctx->set_error("chips: a row window needs the one-call blend's form"); return MI355_ERR_ARG; }
-    const int row_beg = (row_lo < 0 ? 0 : row_lo) & ~(4 * OWN_ROWS - 1);
-    int row_end = row_hi >= newH - 1 ? newH : ((row_hi + 4 * OWN_ROWS) & ~(4 * OWN_ROWS - 1));      // exclusive
-    if (row_end > newH) row_end = newH;
-    // released on every failure path below; handed to the caller only on success
-    std::unique_ptr<mi355_chip_info, void (*)(void*)> ci_hold((mi355_chip_info*)calloc((size_t)(nv > 0 ? nv : 1), sizeof(mi355_chip_info)), free);
-    mi355_chip_info* ci = ci_hold.get();
-    if (!ci) return MI355_ERR_NOMEM;
-    std::vector<ChipDev> cd(nv);
-    std::vector<int> av;                                     // the chips that reach the stripe, ascending (= the reference's order)
-    size_t map_total = 0, chip_total = 0, mask_total = 0;
-    chip_off.assign(nv, 0); mask_off.assign(nv, 0);
-    for (int v = 0; v < nv; v++) {
-        const int k = kept[v];
-        const float* m = h9s + 9 * k;
-        const float bX = bx0[k] + dGx, bY = by0[k] + dGy, eX = bx1[k] + dGx, eY = by1[k] + dGy;     // :2314-2317
-        const int begX = (int)bX, begY = (int)bY, endX = (int)(eX + 0.5f), endY = (int)(eY + 0.5f);
-        const float sx = (float)begX - bX, sy = (float)begY - bY;
-        mi355_chip_info& c = ci[v];
-        c.x0 = begX; c.y0 = begY; c.w = endX - begX + 1; c.h = endY - begY + 1; c.img = k; c.sx = sx; c.sy = sy;
-        const float ox[4] = {0.0f, (float)(w[k] - 1), (float)(w[k] - 1), 0.0f};
-        const float oy[4] = {0.0f, 0.0f, (float)(h[k] - 1), (float)(h[k] - 1)};
-        for (int i = 0; i < 4; i++) {
-            float tx, ty;
-            hm::apply_recip9(m, ox[i], oy[i], tx, ty);                                               // :2334
-            c.quad[2 * i] = ((tx + dGx) + sx) - (float)begX;
-            c.quad[2 * i + 1] = ((ty + dGy) + sy) - (float)begY;
+    L.dGx = -minX; L.dGy = -minY;
+    L.W = (int)(maxX - minX + 1.5f); L.H = (int)(maxY - minY + 1.5f);
+}
+
+// one call of the chip stage: what its stages share
+struct ChipStage {
+    mi355_ctx* ctx; const uint8_t* const* imgs; const int* w; const int* h; const int* ws; const float* h9s; const chips::Request& req; chips::ChipSet& set;
+    CanvasLayout lay;
+    bool striped; int row_beg, row_end;          // the stripe in whole groups of owner_kernel's 16 rows (row_end exclusive)
+    std::vector<int> av;                         // the chips that reach the stripe, ascending (= the reference's order)
+    size_t chip_total = 0, mask_total = 0;
+    int mw = 1, mh = 1;                          // the largest chip among them: the grid of the launches that take all chips at once
+
+    // the chips' rectangles, sub-pixel shifts and quads (MosaicImage.cpp:2314-2343), and where the chips that reach the stripe are stored
+    int rectangles() {
+        const int nv = (int)lay.kept.size();
+        const float dGx = lay.dGx, dGy = lay.dGy;
+        set.W = lay.W; set.H = lay.H;
+        set.info.assign(nv, mi355_chip_info{});
+        set.chip_off.assign(nv, 0); set.mask_off.assign(nv, 0);
+        for (int v = 0; v < nv; v++) {
+            const int k = lay.kept[v];
+            const float* m = h9s + 9 * k;
+            const float bX = lay.bx0[k] + dGx, bY = lay.by0[k] + dGy, eX = lay.bx1[k] + dGx, eY = lay.by1[k] + dGy;     // :2314-2317
+            const int begX = (int)bX, begY = (int)bY, endX = (int)(eX + 0.5f), endY = (int)(eY + 0.5f);
+            const float sx = (float)begX - bX, sy = (float)begY - bY;
+            mi355_chip_info& c = set.info[v];
+            c.x0 = begX; c.y0 = begY; c.w = endX - begX + 1; c.h = endY - begY + 1; c.img = k; c.sx = sx; c.sy = sy;
+            const float ox[4] = {0.0f, (float)(w[k] - 1), (float)(w[k] - 1), 0.0f};
+            const float oy[4] = {0.0f, 0.0f, (float)(h[k] - 1), (float)(h[k] - 1)};
+            for (int i = 0; i < 4; i++) {
+                float tx, ty;
+                hm::apply_recip9(m, ox[i], oy[i], tx, ty);                                               // :2334
+                c.quad[2 * i] = ((tx + dGx) + sx) - (float)begX;
+                c.quad[2 * i + 1] = ((ty + dGy) + sy) - (float)begY;
+            }
+            if (c.w <= 0 || c.h <= 0) { ctx->set_error("chips: empty chip"); return MI355_ERR_FAILED; }
+            if (striped && (c.y0 + c.h - 1 < row_beg || c.y0 >= row_end)) continue;                      // does not reach the stripe
+            set.chip_off[v] = chip_total; set.mask_off[v] = mask_total;
+            chip_total += (size_t)((c.w * 3 + 3) & ~3) * c.h; mask_total += (size_t)((c.w + 3) & ~3) * c.h;
+            av.push_back(v);
+            mw = std::max(mw, c.w); mh = std::max(mh, c.h);
         }
-        if (c.w <= 0 || c.h <= 0) { ctx->set_error("chips: empty chip"); return MI355_ERR_FAILED; }
-        const int cws = (c.w * 3 + 3) & ~3, mws = (c.w + 3) & ~3;
-        cd[v] = ChipDev{c.x0, c.y0, c.w, c.h, mws, 0};
-        if (striped && (c.y0 + c.h - 1 < row_beg || c.y0 >= row_end)) continue;                      // does not reach the stripe
-        chip_off[v] = chip_total; mask_off[v] = mask_total;
-        chip_total += (size_t)cws * c.h; mask_total += (size_t)mws * c.h;
-        cd[v].map_off = map_total;
-        map_total += (size_t)mws * c.h;
-        av.push_back(v);
-    }
-    if (cover_only) {                                        // the images whose chips this call would form: nothing else is done
-        for (int v : av) cover_only[kept[v]] = 1;
-        *n_chips = nv; *chips_out = nullptr;
-        if (cw_out) *cw_out = newW;
-        if (ch_out) *ch_out = newH;
         return MI355_OK;
     }
-    const int na = (int)av.size();
-    DevBuf& dchips = ctx->buf("chip_imgs");
-    DevBuf& dmasks = ctx->buf("chip_masks");
-    DevBuf& dsrc = ctx->buf("warp_src");
-    DevBuf& dmeta = ctx->buf("chip_meta");
-    MI_HIP(dchips.reserve(chip_total + 16));
-    MI_HIP(dmasks.reserve(mask_total + 16));
-    // defer_pixels (the one-call blend): every mask byte of a chip's columns is written by the validity pass, the pixels later and only
-    // inside the chip's active window (mi_chip_pixels_prepare / _launch); row padding is never read there, so nothing is cleared
-    if (!defer_pixels) {
-        MI_HIP(hipMemsetAsync(dchips.p, 0, chip_total, ctx->stream));
-        MI_HIP(hipMemsetAsync(dmasks.p, 0, mask_total, ctx->stream));
+
+    // Every kept source is staged in HBM up front (frames stay resident: 288 GB), so uploads and warps of consecutive chips overlap on the
+    // stream instead of synchronising per chip.  The chips' warp arguments: launched at once (the public call), or kept in the set.
+    int sources_and_warps() {
+        const bool on_device = req.on_device(), defer = req.one_call();
+        uint8_t* dchips = ctx->buf("chip_imgs").as<uint8_t>();
+        uint8_t* dmasks = ctx->buf("chip_masks").as<uint8_t>();
+        DevBuf& dsrc = ctx->buf("warp_src");
+        if (defer) set.warps.assign((size_t)set.n(), chips::WarpArgs{});
+        std::vector<size_t> src_off(set.n(), 0);
+        size_t src_total = 0;
+        for (int v : av) {
+            const int k = lay.kept[v];
+            if (!imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) { ctx->set_error("chips: bad image geometry"); return MI355_ERR_ARG; }
+            src_off[v] = src_total; src_total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255;
+        }
+        if (!on_device) MI_HIP(dsrc.reserve(src_total + 16));
+        for (int v : av) {
+            const int k = lay.kept[v];
+            const mi355_chip_info& c = set.info[v];
+            WarpArgs a;
+            memset(&a, 0, sizeof(a));
+            if (mi_inverse_matrix_host(h9s + 9 * k, 3, a.inv, 1e-12f) != 1) { ctx->set_error("chips: homography not invertible"); return MI355_ERR_SINGULAR; }  // :2348
+            const size_t src_bytes = (size_t)ws[k] * h[k];
+            if (!on_device) MI_HIP(hipMemcpyAsync(dsrc.as<uint8_t>() + src_off[v], imgs[k], src_bytes, hipMemcpyHostToDevice, ctx->stream));
+            a.src = on_device ? imgs[k] : dsrc.as<uint8_t>() + src_off[v]; a.w = w[k]; a.h = h[k]; a.ws = ws[k];
+            a.dst = dchips + set.chip_off[v]; a.dws = (c.w * 3 + 3) & ~3;
+            a.mask = dmasks + set.mask_off[v]; a.mws = (c.w + 3) & ~3;
+            a.x_beg = 0; a.x_end = c.w - 1; a.y_beg = 0; a.y_end = c.h - 1;
+            a.dx = lay.dGx; a.dy = lay.dGy; a.sx = c.sx; a.sy = c.sy; a.x0 = c.x0; a.y0 = c.y0;
+            if (defer) set.warps[v] = a;
+            else launch_warp<3, true>(ctx, a);
+        }
+        return MI355_OK;
     }
-    if (defer_pixels) ctx->deferred_warps.assign(sizeof(WarpArgs) * (size_t)nv, 0);
-    // every kept source is staged in HBM up front (frames stay resident: 288 GB), so uploads and warps of consecutive chips
-    // overlap on the stream instead of synchronising per chip
-    std::vector<size_t> src_off(nv, 0);
-    size_t src_total = 0;
-    for (int v : av) {
-        const int k = kept[v];
-        if (!imgs[k] || w[k] < 2 || h[k] < 2 || ws[k] < 3 * w[k]) { ctx->set_error("chips: bad image geometry"); return MI355_ERR_ARG; }
-        src_off[v] = src_total; src_total += ((size_t)ws[k] * h[k] + 255) & ~(size_t)255;
-    }
-    if (!imgs_on_device) MI_HIP(dsrc.reserve(src_total + 16));
-    std::vector<WarpArgs> wargs((size_t)(na > 0 ? na : 1));
-    for (int q = 0; q < na; q++) {
-        const int v = av[q], k = kept[v];
-        const mi355_chip_info& c = ci[v];
-        WarpArgs a;
-        memset(&a, 0, sizeof(a));
-        if (mi_inverse_matrix_host(h9s + 9 * k, 3, a.inv, 1e-12f) != 1) { ctx->set_error("chips: homography not invertible"); return MI355_ERR_SINGULAR; }  // :2348
-        const size_t src_bytes = (size_t)ws[k] * h[k];
-        if (!imgs_on_device) MI_HIP(hipMemcpyAsync(dsrc.as<uint8_t>() + src_off[v], imgs[k], src_bytes, hipMemcpyHostToDevice, ctx->stream));
-        a.src = imgs_on_device ? imgs[k] : dsrc.as<uint8_t>() + src_off[v]; a.w = w[k]; a.h = h[k]; a.ws = ws[k];
-        a.dst = dchips.as<uint8_t>() + chip_off[v]; a.dws = (c.w * 3 + 3) & ~3;
-        a.mask = dmasks.as<uint8_t>() + mask_off[v]; a.mws = cd[v].mws;
-        a.x_beg = 0; a.x_end = c.w - 1; a.y_beg = 0; a.y_end = c.h - 1;
-        a.dx = dGx; a.dy = dGy; a.sx = c.sx; a.sy = c.sy; a.x0 = c.x0; a.y0 = c.y0;
-        if (defer_pixels) { memcpy(ctx->deferred_warps.data() + sizeof(WarpArgs) * (size_t)v, &a, sizeof(a)); wargs[q] = a; }
-        else launch_warp<3, true>(ctx, a);
-    }
-    if (defer_pixels && na > 0) {                       // validity masks of all chips: one launch
+
+    // validity masks of all chips whose pixels are deferred: one launch
+    int validity_launch() {
+        const int na = (int)av.size();
+        if (na <= 0) return MI355_OK;
+        std::vector<chips::WarpArgs> wargs((size_t)na);
+        for (int q = 0; q < na; q++) wargs[q] = set.warps[av[q]];
         DevBuf& dwa = ctx->buf("chip_warp_args");
         MI_HIP(dwa.reserve(sizeof(WarpArgs) * (size_t)na));
         MI_HIP(hipMemcpyAsync(dwa.p, wargs.data(), sizeof(WarpArgs) * (size_t)na, hipMemcpyHostToDevice, ctx->stream));
         MI_HIP(hipStreamSynchronize(ctx->stream));      // `wargs` is a local: the copy must have read it before it goes
-        int mw = 1, mh = 1;
-        for (int v : av) { if (ci[v].w > mw) mw = ci[v].w; if (ci[v].h > mh) mh = ci[v].h; }
         ProfScope ps(ctx, "warp", (double)mask_total);
         for (int v0 = 0; v0 < na; v0 += 65535)
             hipLaunchKernelGGL((warp_chips_kernel<1>), dim3(((mw + 3) / 4 + 63) / 64, (mh + 3) / 4, na - v0 < 65535 ? na - v0 : 65535), dim3(64, 4), 0, ctx->stream,
                                dwa.as<WarpArgs>() + v0);
+        return MI355_OK;
     }
-    // validity masks are final here unless the distance-map ownership is requested
-    if (find_masks && na > 0) {
+
+    // FindMasksByDistMap for the chips that reach the stripe: per chip its maximum distance, per canvas pixel its owner, and (the one-call
+    // form) per chip the box of what it owns
+    int ownership() {
+        const int na = (int)av.size(), newW = set.W, newH = set.H;
+        const bool boxes = req.one_call();
+        const mi355_chip_info* ci = set.info.data();
+        uint8_t* dmasks = ctx->buf("chip_masks").as<uint8_t>();
+        DevBuf& dmeta = ctx->buf("chip_meta");
         // chip lists per 256 x 256 canvas block (host: the chips' rectangles are known), ascending chip index inside a block; entries are
-        // positions in `av`
+        // positions in `av`.  One walk over a chip's blocks serves the count and the fill.
         const int bx_n = (newW + OWN_BLK - 1) / OWN_BLK, by_n = (newH + OWN_BLK - 1) / OWN_BLK;
-        std::vector<int> loff((size_t)bx_n * by_n + 1, 0);
-        for (int q = 0; q < na; q++) {
+        auto each_block = [&](int q, auto&& f) {
             const int v = av[q];
             const int bx0 = std::max(0, ci[v].x0 / OWN_BLK), bx1 = std::min(bx_n - 1, (ci[v].x0 + ci[v].w - 1) / OWN_BLK);
             const int by0 = std::max(0, ci[v].y0 / OWN_BLK), by1 = std::min(by_n - 1, (ci[v].y0 + ci[v].h - 1) / OWN_BLK);
-            for (int by = by0; by <= by1; by++) for (int bx = bx0; bx <= bx1; bx++) loff[(size_t)by * bx_n + bx + 1]++;
-        }
+            for (int by = by0; by <= by1; by++) for (int bx = bx0; bx <= bx1; bx++) f((size_t)by * bx_n + bx);
+        };
+        std::vector<int> loff((size_t)bx_n * by_n + 1, 0);
+        for (int q = 0; q < na; q++) each_block(q, [&](size_t b) { loff[b + 1]++; });
         for (size_t q = 1; q < loff.size(); q++) loff[q] += loff[q - 1];
         std::vector<int> lst((size_t)loff.back() > 0 ? loff.back() : 1), fill(loff.begin(), loff.end() - 1);
-        for (int q = 0; q < na; q++) {
-            const int v = av[q];
-            const int bx0 = std::max(0, ci[v].x0 / OWN_BLK), bx1 = std::min(bx_n - 1, (ci[v].x0 + ci[v].w - 1) / OWN_BLK);
-            const int by0 = std::max(0, ci[v].y0 / OWN_BLK), by1 = std::min(by_n - 1, (ci[v].y0 + ci[v].h - 1) / OWN_BLK);
-            for (int by = by0; by <= by1; by++) for (int bx = bx0; bx <= bx1; bx++) lst[fill[(size_t)by * bx_n + bx]++] = q;
-        }
+        for (int q = 0; q < na; q++) each_block(q, [&](size_t b) { lst[fill[b]++] = q; });
         std::vector<LineSet> lines(na);
         std::vector<ChipDev> cda(na);
         for (int q = 0; q < na; q++) {
-            const int v = av[q];
-            cda[q] = cd[v];
-            const float* qd = ci[v].quad;
+            const mi355_chip_info& c = ci[av[q]];
+            cda[q] = ChipDev{c.x0, c.y0, c.w, c.h, (c.w + 3) & ~3, set.mask_off[av[q]]};
+            const float* qd = c.quad;
             LineSet& L = lines[q];
             line_of_2_points(L.A[0], L.B[0], L.C[0], qd[0], qd[1], qd[2], qd[3]);
             line_of_2_points(L.A[1], L.B[1], L.C[1], qd[2], qd[3], qd[4], qd[5]);
@@ -865,18 +855,16 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
         // descriptors, mask pointers, the maxima (zero), the edge lines, the block lists, the owned boxes' start values
         std::vector<uint8_t> blob(meta_bytes, 0);
         memcpy(blob.data() + o_cd, cda.data(), sizeof(ChipDev) * na);
-        for (int q = 0; q < na; q++) { uint8_t* mp = dmasks.as<uint8_t>() + mask_off[av[q]]; memcpy(blob.data() + o_mp + sizeof(uint8_t*) * q, &mp, sizeof(mp)); }
+        for (int q = 0; q < na; q++) { uint8_t* mp = dmasks + set.mask_off[av[q]]; memcpy(blob.data() + o_mp + sizeof(uint8_t*) * q, &mp, sizeof(mp)); }
         memcpy(blob.data() + o_ln, lines.data(), sizeof(LineSet) * na);
         memcpy(blob.data() + o_lo, loff.data(), sizeof(int) * loff.size());
         memcpy(blob.data() + o_ls, lst.data(), sizeof(int) * lst.size());
         memset(blob.data() + o_bb, 0x7f, sizeof(int) * 2 * na);
         memset(blob.data() + o_bb + sizeof(int) * 2 * na, 0xff, sizeof(int) * 2 * na);
         MI_HIP(hipMemcpyAsync(mb, blob.data(), meta_bytes, hipMemcpyHostToDevice, ctx->stream));
-        int* d_bbmin = owned_bbox ? reinterpret_cast<int*>(mb + o_bb) : nullptr;      // [2 na] minima, then [2 na] maxima
-        int* d_bbmax = owned_bbox ? d_bbmin + 2 * na : nullptr;
+        int* d_bbmin = boxes ? reinterpret_cast<int*>(mb + o_bb) : nullptr;      // [2 na] minima, then [2 na] maxima
+        int* d_bbmax = boxes ? d_bbmin + 2 * na : nullptr;
         dim3 block(64, 4);
-        int mw = 1, mh = 1;
-        for (int v : av) { if (ci[v].w > mw) mw = ci[v].w; if (ci[v].h > mh) mh = ci[v].h; }
         {
             ProfScope ps(ctx, "distmap", (double)chip_total / 3.0);
             for (int v0 = 0; v0 < na; v0 += 65535)      // gridDim.z limit
@@ -888,47 +876,83 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
             ProfScope ps(ctx, "owner", (double)newW * (row_end - row_beg));
             hipLaunchKernelGGL(owner_kernel, grid, block, 0, ctx->stream, d_cd, d_lines, d_max, d_loff, d_list, bx_n, newW, row_end, d_mptr, row_beg);
         }
-        if (owned_bbox) {
+        if (boxes) {
             ProfScope ps(ctx, "distmap", (double)chip_total / 3.0);
             for (int v0 = 0; v0 < na; v0 += 65535)
                 hipLaunchKernelGGL(mask_bbox_kernel, dim3((mw + 255) / 256, (mh + 63) / 64, na - v0 < 65535 ? na - v0 : 65535), block, 0, ctx->stream,
                                    d_cd + v0, d_mptr + v0, d_bbmin + 2 * v0, d_bbmax + 2 * v0, row_beg, row_end - 1);
         }
         std::vector<int> bb;
-        if (owned_bbox) { bb.resize((size_t)4 * na); MI_HIP(hipMemcpyAsync(bb.data(), d_bbmin, sizeof(int) * 4 * na, hipMemcpyDeviceToHost, ctx->stream)); }
+        if (boxes) { bb.resize((size_t)4 * na); MI_HIP(hipMemcpyAsync(bb.data(), d_bbmin, sizeof(int) * 4 * na, hipMemcpyDeviceToHost, ctx->stream)); }
         MI_HIP(hipStreamSynchronize(ctx->stream));        // the host vectors above were sources of asynchronous copies
-        if (owned_bbox) {
-            owned_bbox->assign((size_t)4 * nv, 0);
-            for (int v = 0; v < nv; v++) { int* o = owned_bbox->data() + 4 * v; o[0] = 0; o[1] = 0; o[2] = -1; o[3] = -1; }      // chips outside the stripe: nothing owned
-            for (int q = 0; q < na; q++) { int* o = owned_bbox->data() + 4 * av[q]; o[0] = bb[2 * q]; o[1] = bb[2 * q + 1]; o[2] = bb[2 * na + 2 * q]; o[3] = bb[2 * na + 2 * q + 1]; }
-        }
-    } else if (owned_bbox && find_masks) {
-        owned_bbox->assign((size_t)4 * nv, 0);
-        for (int v = 0; v < nv; v++) { int* o = owned_bbox->data() + 4 * v; o[2] = -1; o[3] = -1; }
+        if (boxes)
+            for (int q = 0; q < na; q++) { int* o = set.owned.data() + 4 * av[q]; o[0] = bb[2 * q]; o[1] = bb[2 * q + 1]; o[2] = bb[2 * na + 2 * q]; o[3] = bb[2 * na + 2 * q + 1]; }      // (the chips outside the stripe keep their empty box)
+        return MI355_OK;
     }
+};
+
+}  // namespace
+
+// Device stage of the chips: layout on the host, warps / distance maps / ownership on the device.  The chips and masks
+// stay in ctx buffers "chip_imgs" / "chip_masks" at set.chip_off[v] / set.mask_off[v].
+// req.row_lo .. req.row_hi (canvas rows, inclusive; the whole canvas in two of the three forms): a STRIPE of the canvas -- only the chips that
+// reach these rows (widened to whole groups of 16) get storage, validity masks, a maximum distance, and ownership is decided for these rows
+// only; the owned boxes are the boxes inside the stripe, and the chips outside it report an empty box.  What is decided is what the whole
+// canvas gives there: ownership is per canvas pixel among the chips that cover it, and a chip's maximum distance is taken over the whole chip.
+int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                           const uint8_t* keep, const chips::Request& req, chips::ChipSet& set) {
+    if (!imgs || !w || !h || !ws || !h9s || n <= 0) return MI355_ERR_ARG;
+    set = chips::ChipSet{};
+    ChipStage s{ctx, imgs, w, h, ws, h9s, req, set};
+    canvas_layout(w, h, n, h9s, keep, s.lay);
+    const int newH = s.lay.H;
+    s.striped = req.row_lo > 0 || req.row_hi < newH - 1;
+    if (s.striped && req.form != chips::Request::BLEND_DEVICE) { ctx->set_error("chips: a row window needs the one-call blend's form"); return MI355_ERR_ARG; }
+    s.row_beg = (req.row_lo < 0 ? 0 : req.row_lo) & ~(4 * OWN_ROWS - 1);
+    s.row_end = req.row_hi >= newH - 1 ? newH : ((req.row_hi + 4 * OWN_ROWS) & ~(4 * OWN_ROWS - 1));
+    if (s.row_end > newH) s.row_end = newH;
+    int rc = s.rectangles();
+    if (rc != MI355_OK) return rc;
+    if (req.cover_only) {                                    // the images whose chips this call would form: nothing else is done
+        for (int v : s.av) req.cover_only[s.lay.kept[v]] = 1;
+        return MI355_OK;
+    }
+    MI_HIP(ctx->buf("chip_imgs").reserve(s.chip_total + 16));
+    MI_HIP(ctx->buf("chip_masks").reserve(s.mask_total + 16));
+    // deferred pixels (the one-call blend): every mask byte of a chip's columns is written by the validity pass, the pixels later and only
+    // inside the chip's active window (mi_chip_pixels_prepare / _launch); row padding is never read there, so nothing is cleared
+    if (!req.one_call()) {
+        MI_HIP(hipMemsetAsync(ctx->buf("chip_imgs").p, 0, s.chip_total, ctx->stream));
+        MI_HIP(hipMemsetAsync(ctx->buf("chip_masks").p, 0, s.mask_total, ctx->stream));
+    }
+    rc = s.sources_and_warps();
+    if (rc == MI355_OK && req.one_call()) {
+        rc = s.validity_launch();
+        set.owned.assign((size_t)4 * set.n(), 0);            // per chip an empty box, until ownership() finds what it owns
+        for (int v = 0; v < set.n(); v++) { set.owned[4 * v + 2] = -1; set.owned[4 * v + 3] = -1; }
+    }
+    // validity masks are final here unless the distance-map ownership is requested
+    if (rc == MI355_OK && req.find_masks && !s.av.empty()) rc = s.ownership();
+    if (rc != MI355_OK) return rc;
     MI_HIP(hipGetLastError());
-    *n_chips = nv; *chips_out = ci_hold.release();
-    if (cw_out) *cw_out = newW;
-    if (ch_out) *ch_out = newH;
     return MI355_OK;
 }
 
 // deferred chips: entry e of the list = chip chips[e] restricted to columns / rows win[4e .. 4e+3] (inclusive, clipped to the chip).  The
 // arguments of all entries go to the device in one copy; mi_chip_pixels_launch then renders a run of entries with one launch.
-int mi_chip_pixels_prepare(mi355_ctx* ctx, int n, const int* chips, const int* win) {
-    std::vector<WarpArgs> arr((size_t)(n > 0 ? n : 1));
-    ctx->deferred_dims.assign((size_t)2 * (n > 0 ? n : 0), 0);
+int mi_chip_pixels_prepare(mi355_ctx* ctx, chips::ChipSet& set, int n, const int* chips, const int* win) {
+    std::vector<chips::WarpArgs> arr((size_t)(n > 0 ? n : 1));
+    set.dims.assign((size_t)2 * (n > 0 ? n : 0), 0);
     for (int e = 0; e < n; e++) {
         const int chip = chips[e];
-        if (chip < 0 || sizeof(WarpArgs) * ((size_t)chip + 1) > ctx->deferred_warps.size()) { ctx->set_error("chip_pixels: no such deferred chip"); return MI355_ERR_ARG; }
-        WarpArgs a;
-        memcpy(&a, ctx->deferred_warps.data() + sizeof(WarpArgs) * (size_t)chip, sizeof(a));
+        if (chip < 0 || (size_t)chip >= set.warps.size()) { ctx->set_error("chip_pixels: no such deferred chip"); return MI355_ERR_ARG; }
+        chips::WarpArgs a = set.warps[chip];
         const int* w4 = win + 4 * e;
         a.x_beg = w4[0] > a.x_beg ? w4[0] : a.x_beg; a.y_beg = w4[1] > a.y_beg ? w4[1] : a.y_beg;
         a.x_end = w4[2] < a.x_end ? w4[2] : a.x_end; a.y_end = w4[3] < a.y_end ? w4[3] : a.y_end;
         arr[e] = a;
-        ctx->deferred_dims[2 * e] = a.x_end < a.x_beg ? 0 : (a.x_end - (a.x_beg & ~3)) / 4 + 1;      // groups of 4 columns
-        ctx->deferred_dims[2 * e + 1] = a.y_end < a.y_beg ? 0 : a.y_end - a.y_beg + 1;
+        set.dims[2 * e] = a.x_end < a.x_beg ? 0 : (a.x_end - (a.x_beg & ~3)) / 4 + 1;      // groups of 4 columns
+        set.dims[2 * e + 1] = a.y_end < a.y_beg ? 0 : a.y_end - a.y_beg + 1;
     }
     if (n <= 0) return MI355_OK;
     DevBuf& d = ctx->buf("chip_warp_windows");
@@ -936,11 +960,11 @@ int mi_chip_pixels_prepare(mi355_ctx* ctx, int n, const int* chips, const int* w
     MI_HIP(hipMemcpy(d.p, arr.data(), sizeof(WarpArgs) * (size_t)n, hipMemcpyHostToDevice));      // `arr` is a local: the copy must have read it on return
     return MI355_OK;
 }
-int mi_chip_pixels_launch(mi355_ctx* ctx, int first, int count) {
+int mi_chip_pixels_launch(mi355_ctx* ctx, const chips::ChipSet& set, int first, int count) {
     if (count <= 0) return MI355_OK;
-    if (first < 0 || (size_t)2 * (first + count) > ctx->deferred_dims.size()) { ctx->set_error("chip_pixels: bad range"); return MI355_ERR_ARG; }
+    if (first < 0 || (size_t)2 * (first + count) > set.dims.size()) { ctx->set_error("chip_pixels: bad range"); return MI355_ERR_ARG; }
     int gw = 0, gh = 0;
-    for (int e = first; e < first + count; e++) { gw = ctx->deferred_dims[2 * e] > gw ? ctx->deferred_dims[2 * e] : gw; gh = ctx->deferred_dims[2 * e + 1] > gh ? ctx->deferred_dims[2 * e + 1] : gh; }
+    for (int e = first; e < first + count; e++) { gw = set.dims[2 * e] > gw ? set.dims[2 * e] : gw; gh = set.dims[2 * e + 1] > gh ? set.dims[2 * e + 1] : gh; }
     if (gw == 0 || gh == 0) return MI355_OK;
     ProfScope ps(ctx, "warp", 0.0);
     hipLaunchKernelGGL((warp_chips_kernel<2>), dim3((gw + 63) / 64, (gh + 3) / 4, count), dim3(64, 4), 0, ctx->stream, ctx->buf("chip_warp_windows").as<WarpArgs>() + first);
@@ -948,45 +972,41 @@ int mi_chip_pixels_launch(mi355_ctx* ctx, int first, int count) {
     return MI355_OK;
 }
 
-// canvas size of the chips' layout alone (MosaicImage.cpp:2233-2292): the same float operations as the head of mi_chips_and_masks_dev
+// canvas size of the chips' layout alone
 int mi_blend_layout(const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, int* cw, int* ch) {
     if (!w || !h || !h9s || n <= 0 || !cw || !ch) return MI355_ERR_ARG;
-    float maxX = 0.0f, maxY = 0.0f, minX = 0.0f, minY = 0.0f;
-    for (int k = 0; k < n; k++) {
-        const float* m = h9s + 9 * k;
-        if ((keep && !keep[k]) || m[8] == 0.0f) continue;
-        float bMinX = big(), bMinY = big(), bMaxX = -big(), bMaxY = -big();
-        corner_bbox(m, w[k], h[k], bMinX, bMinY, bMaxX, bMaxY);
-        if (bMaxX > maxX) maxX = bMaxX;
-        if (bMinX < minX) minX = bMinX;
-        if (bMaxY > maxY) maxY = bMaxY;
-        if (bMinY < minY) minY = bMinY;
-    }
-    *cw = (int)(maxX - minX + 1.5f); *ch = (int)(maxY - minY + 1.5f);
+    CanvasLayout L;
+    canvas_layout(w, h, n, h9s, keep, L);
+    *cw = L.W; *ch = L.H;
     return MI355_OK;
 }
 
+// the C ABI's form of the chip set: malloc'd arrays, the chips and masks copied to the host
 int mi_chips_and_masks(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
                        const float* h9s, const uint8_t* keep, int find_masks, int* n_chips, mi355_chip_info** chips_out,
                        uint8_t*** chip_imgs, uint8_t*** masks_out, int* cw_out, int* ch_out) {
-    if (!chip_imgs || !masks_out) return MI355_ERR_ARG;
-    std::vector<size_t> chip_off, mask_off;
-    int nv = 0;
-    mi355_chip_info* ci = nullptr;
-    int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, find_masks, &nv, &ci, chip_off, mask_off, cw_out, ch_out);
+    if (!chip_imgs || !masks_out || !n_chips || !chips_out) return MI355_ERR_ARG;
+    chips::ChipSet set;
+    int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, chips::Request{chips::Request::PUBLIC, find_masks}, set);
     if (rc != MI355_OK) return rc;                     // nothing was handed out
+    if (cw_out) *cw_out = set.W;
+    if (ch_out) *ch_out = set.H;
+    const int nv = set.n();
     // host results: owned here until the last copy has landed, then handed to the caller
     struct HostArrays {
-        mi355_chip_info* ci; uint8_t** a = nullptr; uint8_t** b = nullptr; int n;
+        mi355_chip_info* ci = nullptr; uint8_t** a = nullptr; uint8_t** b = nullptr; int n;
         ~HostArrays() {
             if (a) for (int v = 0; v < n; v++) free(a[v]);
             if (b) for (int v = 0; v < n; v++) free(b[v]);
             free(a); free(b); free(ci);
         }
-    } hold{ci, nullptr, nullptr, nv};
+    } hold{nullptr, nullptr, nullptr, nv};
+    hold.ci = (mi355_chip_info*)calloc((size_t)(nv > 0 ? nv : 1), sizeof(mi355_chip_info));
     hold.a = (uint8_t**)calloc((size_t)(nv > 0 ? nv : 1), sizeof(uint8_t*));
     hold.b = (uint8_t**)calloc((size_t)(nv > 0 ? nv : 1), sizeof(uint8_t*));
-    if (!hold.a || !hold.b) return MI355_ERR_NOMEM;
+    if (!hold.ci || !hold.a || !hold.b) return MI355_ERR_NOMEM;
+    if (nv > 0) memcpy(hold.ci, set.info.data(), sizeof(mi355_chip_info) * (size_t)nv);
+    const mi355_chip_info* ci = hold.ci;
     DevBuf& dchips = ctx->buf("chip_imgs");
     DevBuf& dmasks = ctx->buf("chip_masks");
     for (int v = 0; v < nv; v++) {
@@ -994,8 +1014,8 @@ int mi_chips_and_masks(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w,
         hold.a[v] = (uint8_t*)malloc(cb);
         hold.b[v] = (uint8_t*)malloc(mb);
         if (!hold.a[v] || !hold.b[v]) return MI355_ERR_NOMEM;
-        MI_HIP(hipMemcpyAsync(hold.a[v], dchips.as<uint8_t>() + chip_off[v], cb, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipMemcpyAsync(hold.b[v], dmasks.as<uint8_t>() + mask_off[v], mb, hipMemcpyDeviceToHost, ctx->stream));
+        MI_HIP(hipMemcpyAsync(hold.a[v], dchips.as<uint8_t>() + set.chip_off[v], cb, hipMemcpyDeviceToHost, ctx->stream));
+        MI_HIP(hipMemcpyAsync(hold.b[v], dmasks.as<uint8_t>() + set.mask_off[v], mb, hipMemcpyDeviceToHost, ctx->stream));
     }
     MI_HIP(hipStreamSynchronize(ctx->stream));
     *n_chips = nv; *chips_out = hold.ci; *chip_imgs = hold.a; *masks_out = hold.b;

@@ -185,7 +185,7 @@ def test_gpu_blend_vs_oracle(oracle):
 @pytest.mark.gpu
 def test_gpu_blend_active_windows_dense_survey(oracle):
     """mi355_mosaic_blended works only inside each chip's active windows (the cell of the mosaic the chip owns + the reach of the REDUCE
-    filter per level; blend.hip chip_windows) and leaves out chips that own nothing.  A dense pile of small frames -- heavy overlap, cells of
+    filter per level; blend_plan.cpp chip_windows) and leaves out chips that own nothing.  A dense pile of small frames -- heavy overlap, cells of
     a few dozen pixels, chips that own nothing at all, odd window origins -- must give the bytes of the full computation (the oracle works
     on whole regions), for several pyramid depths."""
     import imagemosaicing_amd as im

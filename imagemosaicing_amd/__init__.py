@@ -16,6 +16,7 @@ from .capi import (  # noqa: F401
     BlockGainParams, BLOCK_GAIN_STATS, block_gain_params, solve_block_gains,
     FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params,
     Camera, UndistortParams, undistort_params, undistort_fit, undistort_map,
+    PAIR_NORMAL_BLOCK, ProjectiveParams, ProjectiveReport, projective_params, pair_normal_blocks_host, global_projective_refine, global_projective_refine_results,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

@@ -85,6 +85,23 @@ assert GAIN_PAIR_STATS.itemsize == 64
 # mi355_block_gain_stats: the statistics of one (cell_a, cell_b) of listed pair `pair` (an index into the pair list)
 BLOCK_GAIN_STATS = np.dtype([("pair", "<i4"), ("cell_a", "<i4"), ("cell_b", "<i4"), ("reserved", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)),
                              ("sum_b", "<i8", (3,))])
+PAIR_NORMAL_BLOCK = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("_pad", "<i4"), ("cost", "<f8"), ("g", "<f8", (16,)), ("N", "<f8", (136,))])
+
+
+class ProjectiveParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("reserved", C.c_int32), ("prior", C.c_double), ("lambda0", C.c_double), ("lambda_up", C.c_double),
+                ("lambda_down", C.c_double), ("min_rel_decrease", C.c_double)]
+
+
+class ProjectiveReport(C.Structure):
+    _fields_ = [("trials", C.c_int32), ("accepted", C.c_int32), ("n_free", C.c_int32), ("n_pairs_used", C.c_int32), ("n_points", C.c_int64),
+                ("cost0", C.c_double), ("cost_data", C.c_double), ("cost_prior", C.c_double), ("lambda_", C.c_double)]
+
+    def as_dict(self):
+        return {n.rstrip("_"): getattr(self, n) for n, _ in self._fields_}
+
+
+assert PAIR_NORMAL_BLOCK.itemsize == 1240 and C.sizeof(ProjectiveParams) == 48 and C.sizeof(ProjectiveReport) == 56
 assert BLOCK_GAIN_STATS.itemsize == 72 and C.sizeof(BlockGainParams) == 32
 assert C.sizeof(Camera) == 72 and C.sizeof(UndistortParams) == 48
 
@@ -464,6 +481,22 @@ class Context:
     def PairMomentsDev(self, d_results, n, d_out):
         """one PAIR_MOMENTS record per pair record, device to device (ctx stream)"""
         self._chk(self.L.mi355_pair_moments_dev(self._h, C.c_void_p(int(d_results)), int(n), C.c_void_p(int(d_out))))
+
+    def PairNormalBlocksDev(self, d_results, n, h8, part, d_out):
+        """one PAIR_NORMAL_BLOCK per pair record at the parameters h8 (n_images x 8 doubles, host) and flags part (n_images bytes, host:
+        0 no part, 1 takes part, 2 fixed), device to device (ctx stream)"""
+        h8 = np.ascontiguousarray(h8, np.float64).reshape(-1, 8)
+        part = np.ascontiguousarray(part, np.uint8)
+        assert len(h8) == len(part)
+        self._chk(self.L.mi355_pair_normal_blocks_dev(self._h, C.c_void_p(int(d_results)), int(n), _p(h8), _p(part), len(part), C.c_void_p(int(d_out))))
+
+    def GlobalProjectiveRefineDev(self, d_results, n_pairs, w, h, start, fixed=None, label=None, params=None):
+        """mi355_global_projective_refine_dev: the projective refinement of `start` on device records; returns (transforms, report dict)"""
+        a = _projective_args(w, h, start, fixed, label)
+        out, rep = np.zeros(len(a[2]), IMAGE_TRANSFORM), ProjectiveReport()
+        self._chk(self.L.mi355_global_projective_refine_dev(self._h, C.c_void_p(int(d_results) or None), int(n_pairs), len(a[2]), _p(a[0]), _p(a[1]), _p(a[3]), _p(a[4]), _p(a[2]),
+                                                            C.byref(params) if params is not None else None, _p(out), C.byref(rep)))
+        return out, rep.as_dict()
 
     def AllGatherMoments(self, d_local, n_local, copy=True):
         """this rank's accepted pairs -> their second moments -> every rank's host (rank-major PAIR_MOMENTS array; pinned memory of the
@@ -1356,6 +1389,60 @@ def pair_moments_host(results):
     if rc != 0:
         raise Mi355Error(rc, "pair_moments_host")
     return out
+
+
+def projective_params(**kw):
+    """mi355_default_projective_params, with fields overridden by keyword"""
+    p = ProjectiveParams()
+    load_library().mi355_default_projective_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _projective_args(w, h, start, fixed, label):
+    st = np.ascontiguousarray(start, IMAGE_TRANSFORM)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+    w, h, fixed, label = i32(w), i32(h), i32(fixed), i32(label)
+    for a in (w, h, fixed, label):
+        assert a is None or len(a) == len(st)
+    return w, h, st, fixed, label
+
+
+def pair_normal_blocks_host(results, h8, part):
+    """the normal-equation block of every record at the parameters h8 (n_images x 8) and flags part, on the host (what
+    mi355_pair_normal_blocks_dev forms on the device)"""
+    r = np.ascontiguousarray(results, PAIR_RESULT)
+    h8 = np.ascontiguousarray(h8, np.float64).reshape(-1, 8)
+    part = np.ascontiguousarray(part, np.uint8)
+    assert len(h8) == len(part)
+    out = np.zeros(len(r), PAIR_NORMAL_BLOCK)
+    L = load_library()
+    rc = L.mi355_pair_normal_blocks_host(_p(r), len(r), _p(h8), _p(part), len(part), _p(out))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return out
+
+
+def _projective_host(fn, data, w, h, start, fixed, label, params):
+    w, h, st, fixed, label = _projective_args(w, h, start, fixed, label)
+    out, rep = np.zeros(len(st), IMAGE_TRANSFORM), ProjectiveReport()
+    L = load_library()
+    rc = getattr(L, fn)(_p(data), len(data), len(st), _p(w), _p(h), _p(fixed), _p(label), _p(st), C.byref(params) if params is not None else None, _p(out), C.byref(rep))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return out, rep.as_dict()
+
+
+def global_projective_refine_results(results, w, h, start, fixed=None, label=None, params=None):
+    """the projective refinement of `start` (IMAGE_TRANSFORM per image, e.g. the affine alignment's) on host PAIR_RESULT records;
+    returns (transforms, report dict)"""
+    return _projective_host("mi355_global_projective_refine_results", np.ascontiguousarray(results, PAIR_RESULT), w, h, start, fixed, label, params)
+
+
+def global_projective_refine(match_pairs, w, h, start, fixed=None, label=None, params=None):
+    """the same on the flat MATCHPAIR list (a run of equal image indices is one pair)"""
+    return _projective_host("mi355_global_projective_refine", np.ascontiguousarray(match_pairs, MATCHPAIR), w, h, start, fixed, label, params)
 
 
 def select_connected_moments(moments, n_images):

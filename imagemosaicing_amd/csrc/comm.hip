@@ -197,6 +197,9 @@ static int compact_accepted(mi355_ctx* ctx, const mi355_pair_result* d_in, int n
     return MI355_OK;
 }
 
+// the same for the other units (projective.hip compacts its records once before its trials)
+int mi_compact_accepted(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, mi355_pair_result* d_out, int* d_n_out) { return compact_accepted(ctx, d_in, n, d_out, d_n_out); }
+
 struct mi355_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;

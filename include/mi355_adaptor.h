@@ -430,6 +430,44 @@ inline int MosaicImagesMedian(const PoseT* pImgPoses, const int nImages, const M
     return detail::render_one_pass(pImgPoses, nImages, pRectified, pMosaicResult, detail::ONE_PASS_MEDIAN);
 }
 
+// BundleAdjustmentNonlinear, MosaicWithoutPos.cpp:9750-10081, the step the driver keeps switched off (nonlinearAdjustment, :4628-4637): here
+// the damped, Jacobi-scaled projective refinement anchored to its input (include/mi355_mosaic.h, "projective refinement of the global
+// alignment"; mi355_global_projective_refine on the flat list).  Host only: no context, no device.  pImagesTransform0 is the affine result
+// (vecTransformAffineRefined); an image is fixed iff its own `fixed` member is set, as the reference's function reads it (nFixedImages is kept
+// for the signature).  The reference's signature carries no frame sizes, which the prior's control points need: pass the frames' widths and
+// heights where the caller has them (the driver does: pImgPoses[k].pImg); WITHOUT them each image's control points span the bounding box of
+// its own tie points, w = floor(max x) + 2, h = floor(max y) + 2 (at least 2) -- the region the data speaks about.  Returns 0, the reference's
+// -2 (nImages <= 1) and -3 (nPairs <= 4), else the C call's error (mi355_last_error(0)).  Unlike the reference, the input is left unchanged.
+inline int BundleAdjustmentNonlinear(MI355_NS MatchPointPairs* pMatchPairs, int nPairs, MI355_NS ImageTransform* pImagesTransform0, int nImages, int nFixedImages,
+                                     std::vector<MI355_NS ImageTransform>& vecTransformRefined, const int* pWidths = 0, const int* pHeights = 0,
+                                     const mi355_projective_params* params = 0, mi355_projective_report* report = 0) {
+    (void)nFixedImages;
+    if (nImages <= 1) return -2;
+    if (nPairs <= 4) return -3;
+    if (!pMatchPairs || !pImagesTransform0) return -1;
+    std::vector<int32_t> w((size_t)nImages, 2), h((size_t)nImages, 2), fixed((size_t)nImages, 0);
+    for (int k = 0; k < nImages; k++) fixed[k] = pImagesTransform0[k].fixed ? 1 : 0;
+    if (pWidths && pHeights) {
+        for (int k = 0; k < nImages; k++) { w[k] = pWidths[k]; h[k] = pHeights[k]; }
+    } else {
+        for (int p = 0; p < nPairs; p++) {
+            const MI355_NS MatchPointPairs& m = pMatchPairs[p];
+            const int idx[2] = {m.ptA_i, m.ptB_i};
+            const MI355_NS SfPoint* pt[2] = {&m.ptA, &m.ptB};
+            for (int s = 0; s < 2; s++) {
+                if (idx[s] < 0 || idx[s] >= nImages || !(pt[s]->x >= 0.0f && pt[s]->x < 1e9f && pt[s]->y >= 0.0f && pt[s]->y < 1e9f)) continue;
+                const int bx = (int)pt[s]->x + 2, by = (int)pt[s]->y + 2;
+                if (bx > w[idx[s]]) w[idx[s]] = bx;
+                if (by > h[idx[s]]) h[idx[s]] = by;
+            }
+        }
+    }
+    vecTransformRefined.resize((size_t)nImages);
+    return mi355_global_projective_refine(reinterpret_cast<const mi355_match_point_pairs*>(pMatchPairs), nPairs, nImages, w.data(), h.data(), fixed.data(), 0,
+                                          reinterpret_cast<const mi355_image_transform*>(pImagesTransform0), params,
+                                          reinterpret_cast<mi355_image_transform*>(vecTransformRefined.data()), report);
+}
+
 // Lens undistortion (include/mi355_mosaic.h, "lens undistortion"): src, a frame of the distorted camera `cam`, resampled into dst for the
 // pinhole camera of `params` (0: the camera's own intrinsics; mi355_undistort_fit gives the widest one without empty rim pixels).  The
 // reference has no such step: its caller, which holds host IplImages, calls this just before SiftExtraction; dst may be

@@ -657,6 +657,74 @@ int  mi355_select_connected_moments(const mi355_pair_moments* m, int n, int n_im
 int  mi355_global_affine_align_moments(const mi355_pair_moments* m, int n, int n_images, const int32_t* fixed, const int32_t* label,
                                        mi355_image_transform* out);
 
+/* ---- projective refinement of the global alignment, anchored to the affine result -----------------------------------------------------------
+ * The reference's nonlinearAdjustment (MosaicWithoutPos.cpp:4628-4637 -> BundleAdjustmentNonlinear, :9750-10081: one undamped Gauss-Newton
+ * step on 8 parameters per image, switched off there) made usable: Jacobi-scaled, damped (Levenberg-Marquardt), and held to the affine start
+ * by a prior.  All arithmetic is double; every product, sum and quotient is rounded separately, in the order written, no contraction.
+ *
+ * Taking part.  Image k takes part iff start[k].m[8] is finite and non-zero and (label == NULL or label[k] != 0); its parameters are
+ *   h[k][j] = (double)m[j] / (double)m[8], j = 0..7.  It is fixed iff (fixed ? fixed[k] != 0 : k == 0), the affine forms' rule.  A pair record
+ *   is USED iff it is accepted, 1 <= n_in <= 400, i != j, both images take part and they are not both fixed.  An image is FREE iff it takes
+ *   part, is not fixed and occurs in a used pair.
+ * Side of a point p = (x, y) (doubles of the record's floats) under parameters h:
+ *   w = (h6*x + h7*y) + 1.0;  u = (h0*x + h1*y) + h2;  v = (h3*x + h4*y) + h5;  qx = x / w, qy = y / w, q1 = 1.0 / w;  U = u / w, V = v / w;
+ *   Jx = [qx, qy, q1, 0, 0, 0, -(U*qx), -(U*qy)],  Jy = [0, 0, 0, qx, qy, q1, -(V*qx), -(V*qy)]      (:9850-9863, u*x/(w*w) as (u/w)*(x/w)).
+ * Block of a pair (i, j), inliers a[k] in image i, b[k] in image j: Rx = [Jx(a) | -Jx(b)], Ry = [Jy(a) | -Jy(b)], rx = U_b - U_a,
+ *   ry = V_b - V_a (:9891-9892); for k = 0 .. n_in - 1 in order: N[r][c] = N[r][c] + Rx[r]*Rx[c], then + Ry[r]*Ry[c] (c <= r);
+ *   g[r] = g[r] + Rx[r]*rx, then + Ry[r]*ry; cost = cost + rx*rx, then + ry*ry.  Rows 0..7 are image i's h0..h7, rows 8..15 image j's.
+ *   A record that is not used gets n_in = 0 and zeros (i, j copied).  The block entry points know the images through part[k]: 0 = takes no
+ *   part, 1 = takes part, 2 = takes part and is fixed; an accepted record with n_in > 400 or an index outside [0, n_images) gets a zero
+ *   block that KEEPS its n_in (the refine entry points answer MI355_ERR_ARG to it, like the affine forms).
+ * The block is a fixed-size POD with i, j, n_in like mi355_pair_moments, so that a later change can all-gather it between ranks (not done
+ * here: the refine entry points work on one rank's records). */
+typedef struct { int32_t i, j, n_in, _pad; double cost; double g[16]; double N[136]; } mi355_pair_normal_block;   /* 1240 B; N lower triangle, row-major: r(r+1)/2 + c */
+/* Prior.  Control points of a free frame k: c_pq = (p*(w_k-1)/2, q*(h_k-1)/2), p, q in {0, 1, 2}, q outer, p inner; targets t_pq = (U, V) of
+ *   c_pq under the start parameters; weight omega_k = (prior * n_k) / 9.0, n_k = the sum of n_in over the used pairs that contain k.  Per frame,
+ *   over the nine points in order, with the one-sided rows Jx, Jy of c_pq under the current h and rx = t.U - U, ry = t.V - V:
+ *   P[r][c] = P[r][c] + Jx[r]*Jx[c], then + Jy[r]*Jy[c]; pg[r] = pg[r] + Jx[r]*rx, then + Jy[r]*ry; pc = pc + rx*rx, then + ry*ry.  Then
+ *   N_kk[r][c] = N_kk[r][c] + omega_k*P[r][c], g_k[r] = g_k[r] + omega_k*pg[r], cost_prior = cost_prior + omega_k*pc.  Host arithmetic.
+ * System and step.  Unknowns: the free images in index order, 8 each.  Blocks are added in record order, entry by entry (a fixed image's rows
+ *   and columns are dropped, :9894-9981; cost_data = cost_data + block.cost), then the prior, frames in index order.  s_i = 1 / sqrt(N_ii)
+ *   (1 where N_ii is not positive).  Solve M y = b with M_ij = (s_i*N_ij)*s_j, M_ii = (s_i*N_ii)*s_i + lambda, b_i = s_i*g_i by the envelope
+ *   Cholesky of the affine alignment; delta_i = s_i*y_i; the trial is h' = h + delta.  A non-positive pivot is a rejected trial.
+ * Loop.  lambda = lambda0, c = data + prior cost at the start (the prior is 0 there).  While trials < max_iters and c != 0 and
+ *   lambda <= 1e16: one trial -- blocks and prior at h', c' = data' + prior'; if c' is finite and c' < c: h = h', the trial's system becomes the
+ *   system, lambda = lambda / lambda_down, rel = (c - c') / c, c = c', stop if rel < min_rel_decrease; else lambda = lambda * lambda_up.
+ *   A non-finite cost at the start is MI355_ERR_FAILED.
+ * Output.  Free images get m[j] = (float)h[j], m[8] = 1, fixed = 0; every other image is the input copied bit for bit.  No free image or no
+ *   used pair: output = input, MI355_OK, a report of zeros.
+ * Errors (MI355_ERR_ARG, the message names the value): max_iters < 0, prior < 0, lambda0 < 0, lambda_up <= 1, lambda_down <= 1,
+ *   min_rel_decrease < 0, any of them not finite, n_images < 1, a free image with w < 2 or h < 2, NULL where a pointer is required
+ *   (w, h, start, out; fixed, label, params and report may be NULL), an accepted record with n_in > 400 or an index outside the images.
+ * Same contract as the affine solver: the same bits from call to call and for every MI355_HOST_THREADS. */
+typedef struct { int32_t max_iters, reserved; double prior, lambda0, lambda_up, lambda_down, min_rel_decrease; } mi355_projective_params;
+    /* defaults 20, 0, 0.01, 1e-3, 10, 10, 1e-6.  The prior's default comes from a prototype on synthetic planar surveys with 0.5 px of tie noise:
+     * without a prior the fit shrinks far frames (the cost lives in canvas space); at 0.01 the data rms falls to the noise level and no
+     * corner moved more than 4.3 px from the affine start (CHANGELOG) */
+typedef struct { int32_t trials, accepted, n_free, n_pairs_used; int64_t n_points; double cost0, cost_data, cost_prior, lambda; } mi355_projective_report;
+    /* rms = sqrt(cost / n_points) */
+void mi355_default_projective_params(mi355_projective_params* p);
+/* one block per pair record, on the device (a wave per record); h8: n_images x 8 doubles and part: n_images bytes, both on the HOST, uploaded
+ * per call; enqueued on the ctx stream like mi355_pair_moments_dev */
+int  mi355_pair_normal_blocks_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, const double* h8, const uint8_t* part, int n_images,
+                                  mi355_pair_normal_block* d_out);
+/* the same bits on the host */
+int  mi355_pair_normal_blocks_host(const mi355_pair_result* r, int n, const double* h8, const uint8_t* part, int n_images, mi355_pair_normal_block* out);
+/* The refinement on device records: the accepted ones are compacted once (mi355_compact_accepted_dev's path), then every trial is one launch
+ * and one copy of the blocks into pinned memory of the ctx; the sparse solve runs on the host.  Errors: mi355_last_error(ctx). */
+int  mi355_global_projective_refine_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n_pairs, int n_images, const int32_t* w, const int32_t* h,
+                                        const int32_t* fixed, const int32_t* label, const mi355_image_transform* start, const mi355_projective_params* params,
+                                        mi355_image_transform* out, mi355_projective_report* report);
+/* the same loop on host records with the host blocks: no ctx, no device; errors: mi355_last_error(NULL) */
+int  mi355_global_projective_refine_results(const mi355_pair_result* r, int n_pairs, int n_images, const int32_t* w, const int32_t* h,
+                                            const int32_t* fixed, const int32_t* label, const mi355_image_transform* start, const mi355_projective_params* params,
+                                            mi355_image_transform* out, mi355_projective_report* report);
+/* ... and on the flat correspondence list: a run of equal (ptA_i, ptB_i) is one pair, a run longer than 400 is cut into blocks of 400.  Host
+ * only.  The three forms give the same bits on the same correspondences. */
+int  mi355_global_projective_refine(const mi355_match_point_pairs* v, int n, int n_images, const int32_t* w, const int32_t* h,
+                                    const int32_t* fixed, const int32_t* label, const mi355_image_transform* start, const mi355_projective_params* params,
+                                    mi355_image_transform* out, mi355_projective_report* report);
+
 /* ---- frame ownership for the compositing phase (primary form) --------------------------------------------------------------
  * A rank uploads and holds only the frames it extracts (k mod G == rank, MosaicWithoutPos.cpp:4861).  After the (replicated) alignment
  * every rank knows every rank's canvas stripe and therefore which frames each stripe reads; a frame a stripe reads and its rank does not

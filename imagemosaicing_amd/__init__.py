@@ -17,6 +17,8 @@ from .capi import (  # noqa: F401
     FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params,
     Camera, UndistortParams, undistort_params, undistort_fit, undistort_map,
     PAIR_NORMAL_BLOCK, ProjectiveParams, ProjectiveReport, projective_params, pair_normal_blocks_host, global_projective_refine, global_projective_refine_results,
+    TieParams, tie_params, TIE_REPORT, TIE_NONE, TIE_REFINED, TIE_EDGE, TIE_FLAT, TIE_LOW, TIE_BORDER,
+    TIE_FLAG_NOT_ACCEPTED, TIE_FLAG_NO_FRAME, TIE_FLAG_BAD_RECORD, TIE_FLAG_DEMOTED,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

@@ -101,6 +101,16 @@ class ProjectiveReport(C.Structure):
         return {n.rstrip("_"): getattr(self, n) for n, _ in self._fields_}
 
 
+class TieParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("search", C.c_int32), ("drop_mask", C.c_int32), ("reserved", C.c_int32), ("min_ncc", C.c_float)]
+
+
+# mi355_tie_report: what the tie refinement says of one pair record
+TIE_REPORT = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("n_out", "<i4"), ("flags", "<i4"), ("count", "<i4", (8,)), ("_pad", "<i4"),
+                       ("ncc_q_sum", "<i8")])
+TIE_NONE, TIE_REFINED, TIE_EDGE, TIE_FLAT, TIE_LOW, TIE_BORDER = 0, 1, 2, 3, 4, 5
+TIE_FLAG_NOT_ACCEPTED, TIE_FLAG_NO_FRAME, TIE_FLAG_BAD_RECORD, TIE_FLAG_DEMOTED = 1, 2, 4, 8
+assert TIE_REPORT.itemsize == 64 and C.sizeof(TieParams) == 20
 assert PAIR_NORMAL_BLOCK.itemsize == 1240 and C.sizeof(ProjectiveParams) == 48 and C.sizeof(ProjectiveReport) == 56
 assert BLOCK_GAIN_STATS.itemsize == 72 and C.sizeof(BlockGainParams) == 32
 assert C.sizeof(Camera) == 72 and C.sizeof(UndistortParams) == 48
@@ -497,6 +507,31 @@ class Context:
         self._chk(self.L.mi355_global_projective_refine_dev(self._h, C.c_void_p(int(d_results) or None), int(n_pairs), len(a[2]), _p(a[0]), _p(a[1]), _p(a[3]), _p(a[4]), _p(a[2]),
                                                             C.byref(params) if params is not None else None, _p(out), C.byref(rep)))
         return out, rep.as_dict()
+
+    # ---- tie-point refinement (mi355_refine_ties*, csrc/tie_refine.hip) ------------------------------------------------------
+    def RefineTiesDev(self, d_in, n, d_imgs, w, h, ws, d_out, d_status=0, d_ncc2=0, d_report=0, params=None, **kw):
+        """mi355_refine_ties_dev: n device pair records d_in -> d_out (may be d_in) with every inlier's position in image i moved to the
+        correlation peak of the patch around its partner in image j.  d_imgs: device frames (0 / None: not held), w, h, ws their geometry;
+        d_status (uint8 [n, 400]), d_ncc2 (float32 [n, 400]), d_report (TIE_REPORT [n]): device buffers, 0 = not wanted.  params: TieParams
+        (tie_params()) or its keyword fields (radius, search, drop_mask, min_ncc).  Enqueued on the ctx stream."""
+        n_img, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        p = params if params is not None else tie_params(**kw)
+        self._chk(self.L.mi355_refine_ties_dev(self._h, C.c_void_p(int(d_in or 0) or None), int(n), ptrs, _p(w), _p(h), _p(ws), n_img, C.byref(p),
+                                               C.c_void_p(int(d_out or 0) or None), C.c_void_p(int(d_status or 0) or None),
+                                               C.c_void_p(int(d_ncc2 or 0) or None), C.c_void_p(int(d_report or 0) or None)))
+
+    def RefineTies(self, results, imgs, img_ids=None, geom=None, params=None, **kw):
+        """mi355_refine_ties: host PAIR_RESULT records in; image k from the kept frame of img_ids[k] (>= 0) or from the host image imgs[k]
+        (None: not held).  Returns (results, status uint8 [n, 400], ncc2 float32 [n, 400], report TIE_REPORT [n])."""
+        res = np.ascontiguousarray(results, PAIR_RESULT)
+        n = len(res)
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        p = params if params is not None else tie_params(**kw)
+        out = np.zeros(n, PAIR_RESULT)
+        status, ncc2, report = np.zeros((n, 400), np.uint8), np.zeros((n, 400), np.float32), np.zeros(n, TIE_REPORT)
+        self._chk(self.L.mi355_refine_ties(self._h, _p(res), n, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), C.byref(p), _p(out), _p(status), _p(ncc2),
+                                           _p(report)))
+        return out, status, ncc2, report
 
     def AllGatherMoments(self, d_local, n_local, copy=True):
         """this rank's accepted pairs -> their second moments -> every rank's host (rank-major PAIR_MOMENTS array; pinned memory of the
@@ -1162,6 +1197,18 @@ def undistort_params(out_fx=None, out_fy=None, out_cx=None, out_cy=None, fill=No
             setattr(p, name, float(v))
     if fill is not None:
         p.fill = int(fill)
+    return p
+
+
+def tie_params(radius=None, search=None, drop_mask=None, min_ncc=None):
+    """mi355_tie_params: the library's defaults (radius 7, search 3, drop_mask 0, min_ncc 0.7) with the given fields replaced"""
+    p = TieParams()
+    load_library().mi355_default_tie_params(C.byref(p))
+    for name, v in (("radius", radius), ("search", search), ("drop_mask", drop_mask)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if min_ncc is not None:
+        p.min_ncc = float(min_ncc)
     return p
 
 

@@ -159,6 +159,13 @@ static int render_sources(mi355_ctx* ctx, const char* who, const uint8_t* const*
     return MI355_OK;
 }
 
+// The same sources for a caller that reads frames without rendering them (tie_refine.hip): image k is wanted iff need[k] != 0.
+int mi_frame_sources(mi355_ctx* ctx, const char* who, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                     int n, const uint8_t* need, const char* staging, std::vector<const uint8_t*>& dptr) {
+    const std::vector<float> h9s((size_t)9 * (size_t)n, 1.0f);
+    return render_sources(ctx, who, imgs, img_ids, w, h, ws, n, h9s.data(), need, staging, dptr);
+}
+
 // ---- canvas download ------------------------------------------------------------------------------------------------------
 // rows of row_bytes from the device canvas (pitch src_pitch) into the caller's host rows (pitch dst_pitch); the bytes past row_bytes of
 // every destination row are left as they are.  Default: chunks of whole rows go device -> pinned on the copy stream into two halves in

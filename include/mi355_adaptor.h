@@ -207,6 +207,45 @@ inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned s
     return rc;
 }
 
+// The window form with the tie-point refinement (mi355_refine_ties, "tie-point refinement by patch correlation" in mi355_mosaic.h) between the
+// pair stage and the flattening: every accepted pair's inliers in image i are moved to the correlation peak of the patch around their
+// partners in image j, read from the frames KEPT at extraction under ids 0 .. nImages - 1 (option "keep_frames"; an id without a kept
+// frame is MI355_ERR_ARG), and ties->drop_mask may drop the ties that fail.  ties == NULL: the bytes of the window form above.
+inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned seed, const int* fixedFlags,
+                                       std::vector<MI355_NS MatchPointPairs>& vecMatchPairs, int window, const mi355_tie_params* ties) {
+    if (!ties) return GetMatchedPairsOneToAllSIFT(nImages, ransacDist, seed, fixedFlags, vecMatchPairs, window);
+    mi355_ctx* c = context();
+    if (!c) return -1;
+    int n_pairs = 0;
+    mi355_pair_schedule(nImages, window, 0, 1, NULL, 0, &n_pairs);
+    if (n_pairs == 0) return 0;
+    std::vector<int32_t> pairs((size_t)n_pairs * 2), ids((size_t)nImages);
+    std::vector<int> w((size_t)nImages), h((size_t)nImages), ws((size_t)nImages);
+    for (int k = 0; k < nImages; k++) {
+        const uint8_t* d = NULL;
+        ids[k] = k;
+        const int rc = mi355_get_frame_dev(c, k, &d, &w[k], &h[k], &ws[k]);
+        if (rc != MI355_OK) return rc;
+    }
+    mi355_pair_schedule(nImages, window, 0, 1, &pairs[0], n_pairs, &n_pairs);
+    mi355_pair_result* res = (mi355_pair_result*)std::malloc(sizeof(mi355_pair_result) * (size_t)n_pairs);
+    if (!res) return -1;
+    int rc = mi355_match_pairs(c, &pairs[0], n_pairs, ransacDist, seed, res);
+    if (rc == MI355_OK) rc = mi355_refine_ties(c, res, n_pairs, NULL, &ids[0], &w[0], &h[0], &ws[0], nImages, ties, res, NULL, NULL, NULL);
+    if (rc == MI355_OK) {
+        mi355_match_point_pairs* v = NULL; int n = 0;
+        rc = mi355_results_to_match_pairs(res, n_pairs, fixedFlags, &v, &n);
+        if (rc == MI355_OK) {
+            const size_t old = vecMatchPairs.size();
+            vecMatchPairs.resize(old + n);
+            if (n) std::memcpy(&vecMatchPairs[old], v, sizeof(mi355_match_point_pairs) * n);
+            mi355_free(v);
+        }
+    }
+    std::free(res);
+    return rc;
+}
+
 // The same with the descriptor-screened schedule (mi355_screen_pairs) in place of the window: the pairs of images 0 .. nImages - 1 that the
 // screen keeps are matched, and vecMatchPairs is filled exactly as the window form fills it.  screen NULL: mi355_default_screen_params
 // (all pairs in scope); screen->window >= 2 screens the window's pairs only.

@@ -725,6 +725,75 @@ int  mi355_global_projective_refine(const mi355_match_point_pairs* v, int n, int
                                     const int32_t* fixed, const int32_t* label, const mi355_image_transform* start, const mi355_projective_params* params,
                                     mi355_image_transform* out, mi355_projective_report* report);
 
+/* ---- tie-point refinement by patch correlation in the resident frames (opt-in; csrc/tie_refine.hip) ------------------------------------------
+ * The inlier lists of a pair record are SIFT keypoint positions; nothing checks them against the pixels again.  This is the area-based step
+ * photogrammetric pipelines put between matching and adjustment: for every inlier (a, b) of every accepted pair the position a in image i is
+ * replaced by the peak of the zero-mean normalised cross-correlation of a small gray patch around b in image j, and every tie and pair gets a
+ * photometric verdict.  Nothing calls it unless asked.  It is for MEASURED ties: on exact synthetic ties it adds its own floor (DESIGN).
+ * Definition.  Every float operation is a separate float32 operation in the order written, likewise every double operation; all correlation
+ *   sums are exact integers.  R = radius, S = search, n = (2R+1)^2.
+ * Processed records.  A record is processed iff accepted != 0, 1 <= n_in <= 400, 0 <= i, j < n_images, i != j and both frames are present
+ *   (pointer not NULL).  Any other record is copied bit for bit; its status and ncc2 entries are 0 and its report carries ONE flag, the first
+ *   that applies: 1 not accepted; 4 bad record (n_in or an index out of range, or i == j); 2 a frame is missing.
+ * Gray of a texel: (1868 B + 9617 G + 4899 R + 8192) >> 14 (SIFT's and SURF's integer expression).  The gray sample at a float position (x, y)
+ *   is hm::bilin of the four texel grays at xi = (int)x, yi = (int)y with q = x - (float)xi, p = y - (float)yi: the renders' pixel expression,
+ *   truncating cast included, an integer 0..255.  A position is inside a w x h frame iff x >= 0 && x < w-1 && y >= 0 && y < h-1, tested on the
+ *   floats before any cast (NaN is outside).
+ * One tie (a, b).  M = the record's H with M[8] replaced by 1.0f (H[8] holds Ransac2D's residual); apply_div9(M, x, y) =
+ *   ((M0 x + M1 y + M2) / (M6 x + M7 y + M8), (M3 x + M4 y + M5) / (M6 x + M7 y + M8)), sums left to right.
+ *   1 Template: (b.x - R, b.y - R) and (b.x + R, b.y + R) both inside frame j, else EDGE.  T(u, v), u, v in [-R, R], is the gray sample of
+ *     frame j at (b.x + (float)u, b.y + (float)v).
+ *   2 Window: (X0, Y0) = apply_div9(M, b.x, b.y); for u, v in [-(R+S), R+S]: (X, Y) = apply_div9(M, b.x + (float)u, b.y + (float)v),
+ *     xs = (X - X0) + a.x, ys = (Y - Y0) + a.y; every position inside frame i, else EDGE.  W(u, v) is the gray sample of frame i there.
+ *   3 St = sum T, Stt = sum T^2 (int64), vt = n Stt - St St; vt == 0: FLAT.
+ *   4 For each shift (dx, dy) in [-S, S]^2, over u, v in [-R, R]: Sw = sum W(u+dx, v+dy), Sww = sum W^2, Stw = sum T W;
+ *     vw = n Sww - Sw Sw, num = n Stw - St Sw (int64).
+ *   5 score = (num > 0 && vw > 0) ? ((double)num * (double)num) / ((double)vt * (double)vw) : 0.0        (ZNCC squared, no square root)
+ *   6 Peak: the largest score; among equal scores the smallest index (dy+S)(2S+1) + (dx+S).  peak == 0 or
+ *     peak < (double)min_ncc * (double)min_ncc: LOW.  Otherwise |dx| == S or |dy| == S: BORDER.
+ *   7 Per axis, with sm, s0, sp the scores at -1, 0, +1 around the peak: den = (sm - s0) + (sp - s0);
+ *     off = den < 0 ? (0.5 * (sm - sp)) / den : 0.0;  ex = (float)((double)dx + offx), ey likewise.
+ *   8 (X1, Y1) = apply_div9(M, b.x + ex, b.y + ey); a'.x = a.x + (X1 - X0), a'.y = a.y + (Y1 - Y0); REFINED.  Ids and b never change; a tie
+ *     that is not REFINED keeps its a.
+ * Per tie, at the ORIGINAL index k: status[rec*400 + k]; ncc2[rec*400 + k] = (float)peak (0 for EDGE and FLAT).  Entries k >= n_in are 0.
+ * Dropping.  A tie with (1 << status) in drop_mask leaves both lists; the order of the rest is kept.  The output record's n_in is the number
+ *   kept (n_out) and its list entries from n_out on are zero.  If ties were dropped (n_out < n_in) and n_out <= the ctx's min_inliers the record
+ *   becomes a not-accepted record by the existing convention: accepted = 0, ok = 0, H all zero, lists kept; report flag 8.
+ * Report: i, j, n_in (input), n_out, flags, count[s] = ties of status s, ncc_q_sum = the sum over the REFINED ties of
+ *   (int64_t)(peak * 1048576.0).  A record that is not processed reports n_out = n_in and zero counts.
+ * Errors (MI355_ERR_ARG, the message names the value): radius outside [1, 10], search outside [1, 4], min_ncc not finite or outside [0, 1],
+ *   drop_mask with bits other than 2..5, reserved != 0, n < 0, n_images < 1, a NULL array, a present frame with w or h < 2 or > 2^20 or
+ *   ws < 3 w.  params NULL = defaults.
+ * Out of scope: the multi-GPU path (a rank holds frame i of its pairs but usually not frame j: such records come back with flag 2,
+ *   unchanged) and single-channel frames (3-channel BGR only). */
+#define MI355_TIE_NONE    0   /* entry at or beyond n_in, or record not processed */
+#define MI355_TIE_REFINED 1   /* position was replaced */
+#define MI355_TIE_EDGE    2   /* a patch leaves a frame */
+#define MI355_TIE_FLAT    3   /* the template has no variance */
+#define MI355_TIE_LOW     4   /* the peak is below min_ncc */
+#define MI355_TIE_BORDER  5   /* the peak lies on the border of the search range */
+#define MI355_TIE_FLAG_NOT_ACCEPTED 1
+#define MI355_TIE_FLAG_NO_FRAME     2
+#define MI355_TIE_FLAG_BAD_RECORD   4
+#define MI355_TIE_FLAG_DEMOTED      8
+typedef struct { int32_t radius, search, drop_mask, reserved; float min_ncc; } mi355_tie_params;      /* defaults 7, 3, 0, 0, 0.7f */
+typedef struct { int32_t i, j, n_in, n_out, flags, count[8], _pad; int64_t ncc_q_sum; } mi355_tie_report;      /* 64 bytes */
+void mi355_default_tie_params(mi355_tie_params* p);
+/* device records in, device records out (d_out == d_in is allowed); d_imgs: a HOST array of n_images device pointers, the renders' convention
+ * (NULL: the frame is not held); w, h, ws: host arrays.  d_status (n x 400 bytes), d_ncc2 (n x 400 floats) and d_report (n records) may each be
+ * NULL.  One launch, a workgroup per record, enqueued on the ctx stream like mi355_pair_moments_dev; n == 0 is MI355_OK with nothing launched.
+ * Profile class "tie_refine". */
+int  mi355_refine_ties_dev(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws,
+                           int n_images, const mi355_tie_params* params, mi355_pair_result* d_out, uint8_t* d_status, float* d_ncc2,
+                           mi355_tie_report* d_report);
+/* host records in and out (out == in is allowed), complete on return.  Image k comes from the kept frame of img_ids[k] or from the host image
+ * imgs[k], by mi355_mosaic_refined_into's rule and staging; images that no processed record names are neither read nor uploaded; an image with
+ * neither source is a missing frame (flag 2).  Unlike the _dev form an accepted record that would get flag 4 makes the call fail with
+ * MI355_ERR_ARG before any launch; the message names the record. */
+int  mi355_refine_ties(mi355_ctx* ctx, const mi355_pair_result* in, int n, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                       const int* ws, int n_images, const mi355_tie_params* params, mi355_pair_result* out, uint8_t* status, float* ncc2,
+                       mi355_tie_report* report);
+
 /* ---- frame ownership for the compositing phase (primary form) --------------------------------------------------------------
  * A rank uploads and holds only the frames it extracts (k mod G == rank, MosaicWithoutPos.cpp:4861).  After the (replicated) alignment
  * every rank knows every rank's canvas stripe and therefore which frames each stripe reads; a frame a stripe reads and its rank does not

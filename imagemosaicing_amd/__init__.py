@@ -19,6 +19,7 @@ from .capi import (  # noqa: F401
     PAIR_NORMAL_BLOCK, ProjectiveParams, ProjectiveReport, projective_params, pair_normal_blocks_host, global_projective_refine, global_projective_refine_results,
     TieParams, tie_params, TIE_REPORT, TIE_NONE, TIE_REFINED, TIE_EDGE, TIE_FLAT, TIE_LOW, TIE_BORDER,
     TIE_FLAG_NOT_ACCEPTED, TIE_FLAG_NO_FRAME, TIE_FLAG_BAD_RECORD, TIE_FLAG_DEMOTED,
+    LocalWarpParams, LOCAL_WARP_REPORT, local_warp_params, local_warp_stats_len, tie_residual_stats_host, solve_local_warps,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

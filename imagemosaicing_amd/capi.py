@@ -76,6 +76,16 @@ class PreviewParams(C.Structure):
     _fields_ = [("render", C.c_int32), ("ramp", C.c_int32), ("level", C.c_int32), ("nodata", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class LocalWarpParams(C.Structure):
+    _fields_ = [("grid_x", C.c_int32), ("grid_y", C.c_int32), ("min_ties", C.c_int32), ("reserved", C.c_int32), ("max_residual", C.c_double),
+                ("max_shift", C.c_double), ("smooth", C.c_double), ("prior", C.c_double)]
+
+
+# mi355_local_warp_report: what the local registration's solve says of one frame
+LOCAL_WARP_REPORT = np.dtype([("n_ties", "<i8"), ("rej_den", "<i8"), ("rej_residual", "<i8"), ("rej_side", "<i8"), ("rms_before", "<f8"),
+                              ("rms_after", "<f8"), ("max_shift", "<f8"), ("solved", "<i4"), ("_pad", "<i4")])
+assert C.sizeof(LocalWarpParams) == 48 and LOCAL_WARP_REPORT.itemsize == 64
+
 NODATA_NONE, NODATA_ZERO, NODATA_MAP = 0, 1, 2
 
 
@@ -932,6 +942,51 @@ class Context:
                                                int(out.strides[0]), C.byref(cam), C.byref(p), C.byref(cnt)))
         return out, int(cnt.value)
 
+    # ---- local registration (mi355_tie_residual_stats_*, mi355_solve_local_warps, mi355_apply_local_warps_dev, csrc/local_warp.hip) ------
+    def TieResidualStatsDev(self, d_results, n_pairs, w, h, h9s, d_stats, params=None, **kw):
+        """mi355_tie_residual_stats_dev: the residual sums of n_pairs device pair records into the device buffer d_stats
+        (local_warp_stats_len(n, grid_x, grid_y) int64 values, cleared by the call).  w, h, h9s: the frames' sizes and frame-to-canvas
+        matrices.  params: LocalWarpParams (local_warp_params()) or its keyword fields.  Enqueued on the ctx stream."""
+        w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+        if not (len(w) == len(h) == len(h9s)):
+            raise ValueError("w, h and h9s must list the same frames")
+        p = params if params is not None else local_warp_params(**kw)
+        self._chk(self.L.mi355_tie_residual_stats_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), _p(w), _p(h), _p(h9s), len(w), C.byref(p),
+                                                      C.c_void_p(int(d_stats or 0) or None)))
+
+    def ApplyLocalWarpsDev(self, d_src, d_dst, w, h, ws_src, ws_dst, grids):
+        """mi355_apply_local_warps_dev: device frames d_src resampled by their displacement grids (float32 [n, grid_y + 1, grid_x + 1, 2],
+        source pixels) into d_dst (d_dst[k] == d_src[k] with equal pitches: in place).  Complete on return; returns n_clamped, int64 [n]:
+        the pixels of each frame whose sample position was clamped to the frame."""
+        n, sp, w, h, ws_src = self._frame_args(d_src, w, h, ws_src)
+        if len(d_dst) != n:
+            raise ValueError("d_src and d_dst must list the same frames")
+        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        ws_dst = np.ascontiguousarray(ws_dst, np.int32)
+        g = np.ascontiguousarray(grids, np.float32)
+        if g.ndim != 4 or g.shape[0] != n or g.shape[3] != 2:
+            raise ValueError("grids must be [n, grid_y + 1, grid_x + 1, 2]")
+        out = np.zeros(n, np.int64)
+        self._chk(self.L.mi355_apply_local_warps_dev(self._h, sp, dp, _p(w), _p(h), _p(ws_src), _p(ws_dst), n, int(g.shape[2]) - 1, int(g.shape[1]) - 1, _p(g),
+                                                     _p(out)))
+        return out
+
+    def LocalRegisterDev(self, d_results, n_pairs, d_imgs, w, h, ws, h9s, params=None, **kw):
+        """mi355_local_register_dev: residual statistics of the device pair records, the per-frame solve and the apply in place on the
+        device frames.  Returns (grids float32 [n, grid_y + 1, grid_x + 1, 2], report LOCAL_WARP_REPORT [n])."""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+        if len(h9s) != n:
+            raise ValueError("h9s must list the same frames")
+        p = params if params is not None else local_warp_params(**kw)
+        ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
+        grids = np.zeros((n, p.grid_y + 1, p.grid_x + 1, 2) if ok else (n, 1, 1, 2), np.float32)
+        rep = np.zeros(n, LOCAL_WARP_REPORT)
+        self._chk(self.L.mi355_local_register_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), ptrs, _p(w), _p(h), _p(ws), n, _p(h9s),
+                                                  C.byref(p), _p(grids), _p(rep)))
+        return grids, rep
+
     # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
@@ -1210,6 +1265,57 @@ def tie_params(radius=None, search=None, drop_mask=None, min_ncc=None):
     if min_ncc is not None:
         p.min_ncc = float(min_ncc)
     return p
+
+
+def local_warp_params(grid_x=None, grid_y=None, min_ties=None, max_residual=None, max_shift=None, smooth=None, prior=None):
+    """mi355_local_warp_params: the library's defaults (mi355_default_local_warp_params) with the given fields replaced"""
+    p = LocalWarpParams()
+    load_library().mi355_default_local_warp_params(C.byref(p))
+    for name, v in (("grid_x", grid_x), ("grid_y", grid_y), ("min_ties", min_ties)):
+        if v is not None:
+            setattr(p, name, int(v))
+    for name, v in (("max_residual", max_residual), ("max_shift", max_shift), ("smooth", smooth), ("prior", prior)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+def local_warp_stats_len(n, grid_x, grid_y):
+    """int64 values of the statistics of n frames: MI355_LOCAL_WARP_STATS_STRIDE per frame and a tail of 8"""
+    return int(n) * (7 * (int(grid_x) + 1) * (int(grid_y) + 1) + 8) + 8
+
+
+def tie_residual_stats_host(results, w, h, h9s, params=None, **kw):
+    """mi355_tie_residual_stats_host (host only): the residual sums of host PAIR_RESULT records, int64 [local_warp_stats_len(...)]"""
+    L = load_library()
+    res = np.ascontiguousarray(results, PAIR_RESULT)
+    w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
+    h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+    if not (len(w) == len(h) == len(h9s)):
+        raise ValueError("w, h and h9s must list the same frames")
+    p = params if params is not None else local_warp_params(**kw)
+    ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
+    st = np.zeros(local_warp_stats_len(len(w), p.grid_x, p.grid_y) if ok else 8, np.int64)
+    rc = L.mi355_tie_residual_stats_host(_p(res), len(res), _p(w), _p(h), _p(h9s), len(w), C.byref(p), _p(st))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return st
+
+
+def solve_local_warps(stats, n, params=None, **kw):
+    """mi355_solve_local_warps (host only): (grids float32 [n, grid_y + 1, grid_x + 1, 2], report LOCAL_WARP_REPORT [n]) from the sums"""
+    L = load_library()
+    p = params if params is not None else local_warp_params(**kw)
+    ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
+    st = np.ascontiguousarray(stats, np.int64)
+    if ok and st.size != local_warp_stats_len(n, p.grid_x, p.grid_y):
+        raise ValueError("stats must hold local_warp_stats_len(n, grid_x, grid_y) values")
+    grids = np.zeros((n, p.grid_y + 1, p.grid_x + 1, 2) if ok else (n, 1, 1, 2), np.float32)
+    rep = np.zeros(n, LOCAL_WARP_REPORT)
+    rc = L.mi355_solve_local_warps(_p(st), int(n), C.byref(p), _p(grids), _p(rep))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return grids, rep
 
 
 def undistort_fit(cam, w, h):

@@ -16,20 +16,16 @@
 //   Its floor is HBM: 3 w h bytes read and 3 w h written per frame.
 #include "common.h"
 #include "lens.h"
+#include "frame_pass.h"
 #include "mosaic_frame.h"
-#include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int UD_NT = 256, UD_PX = 4, UD_ROWS = 8;      // lanes, adjacent pixels per lane, rows per lane
-constexpr int UD_BW = UD_NT * UD_PX;                    // output columns of a workgroup
-constexpr int UD_MAX_DIM = 1 << 20, UD_MAX_FRAMES = 65535;
-constexpr size_t UD_SCRATCH_BYTES = (size_t)512 << 20;  // in-place frames per group: as many as this holds, at least one
-constexpr int UD_MAX_BLOCKS = 1 << 30;                  // workgroups per launch
-
-struct UdFrame { const uint8_t* src; uint8_t* dst; int w, h, ws_src, ws_dst; int first_block, bx_n, k, _pad; };
-static_assert(sizeof(UdFrame) == 48, "undistort record layout");
+// the workgroup shape and the frame record are the shared host path's (frame_pass.h)
+constexpr int UD_NT = FP_NT, UD_PX = FP_PX, UD_ROWS = FP_ROWS, UD_BW = FP_BW;
+constexpr int UD_MAX_FRAMES = FP_MAX_FRAMES;
+using UdFrame = PassFrame;
 
 __global__ __launch_bounds__(UD_NT) void undistort_kernel(const UdFrame* frames, int nf, lens::Consts c, unsigned fill, unsigned long long* n_outside) {
     // the record of this workgroup's frame: the last one with first_block <= blockIdx.x (first_block ascends); the same in every lane
@@ -98,11 +94,7 @@ bool check_camera(const mi355_camera* cam, std::string& err) {
     return true;
 }
 
-bool check_size(int w, int h, std::string& err) {
-    if (w < 2 || w > UD_MAX_DIM) { err = "w=" + std::to_string(w) + " outside [2, 2^20]"; return false; }
-    if (h < 2 || h > UD_MAX_DIM) { err = "h=" + std::to_string(h) + " outside [2, 2^20]"; return false; }
-    return true;
-}
+bool check_size(int w, int h, std::string& err) { return fp_check_size(w, h, err); }
 
 // The constants of a call from a checked camera and the parameters (NULL: defaults), and the fill byte; the parameters' own checks.
 bool lens_consts(const mi355_camera& cam, const mi355_undistort_params* p, lens::Consts& c, int& fill, std::string& err) {
@@ -141,37 +133,6 @@ bool border_inside(const lens::Consts& c, int w, int h) {
     return true;
 }
 
-// One or more launches over a frame list (first_block, bx_n are filled in here; a launch takes at most UD_MAX_BLOCKS workgroups), complete
-// on return: the list is the caller's local.
-int launch_frames(mi355_ctx* ctx, std::vector<UdFrame>& fr, const lens::Consts& c, int fill, unsigned long long* d_outside) {
-    DevBuf& dfr = ctx->buf("undistort_frames");
-    for (size_t i0 = 0; i0 < fr.size();) {
-        int blocks = 0;
-        double bytes = 0.0;
-        size_t i1 = i0;
-        for (; i1 < fr.size(); i1++) {
-            UdFrame& f = fr[i1];
-            f.bx_n = (f.w + UD_BW - 1) / UD_BW;
-            const int nb = f.bx_n * ((f.h + UD_ROWS - 1) / UD_ROWS);            // at most 2^10 * 2^17
-            if (i1 > i0 && blocks > UD_MAX_BLOCKS - nb) break;
-            f.first_block = blocks;
-            blocks += nb;
-            bytes += 6.0 * (double)f.w * f.h;
-        }
-        const size_t nf = i1 - i0;
-        MI_HIP(dfr.reserve(sizeof(UdFrame) * nf));
-        MI_HIP(hipMemcpyAsync(dfr.p, fr.data() + i0, sizeof(UdFrame) * nf, hipMemcpyHostToDevice, ctx->stream));
-        {
-            ProfScope ps(ctx, "undistort", bytes);
-            hipLaunchKernelGGL(undistort_kernel, dim3((unsigned)blocks), dim3(UD_NT), 0, ctx->stream, dfr.as<UdFrame>(), (int)nf, c, (unsigned)fill, d_outside);
-            MI_HIP(hipGetLastError());
-        }
-        MI_HIP(hipStreamSynchronize(ctx->stream));                  // the table is rewritten by the next launch
-        i0 = i1;
-    }
-    return MI355_OK;
-}
-
 int undistort_frames(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws_src, const int* ws_dst,
                      int n, const mi355_camera* cam, const mi355_undistort_params* p, int64_t* n_outside) {
     const std::string who = "undistort_frames: ";
@@ -180,88 +141,13 @@ int undistort_frames(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const
     lens::Consts c; int fill;
     if (!check_camera(cam, err) || !lens_consts(*cam, p, c, fill, err)) { ctx->set_error(who + err); return MI355_ERR_ARG; }
     if (n == 0) return MI355_OK;
-    if (!d_src || !d_dst || !w || !h || !ws_src || !ws_dst) {
-        ctx->set_error(who + (!d_src ? "d_src" : !d_dst ? "d_dst" : !w ? "w" : !h ? "h" : !ws_src ? "ws_src" : "ws_dst") + " is NULL");
-        return MI355_ERR_ARG;
-    }
-    // a destination range may meet no other range of the call; a frame in place (same pointer, same pitch) is one range
-    struct Span { uintptr_t lo, hi; int k; bool dst; };
-    std::vector<Span> spans;
-    std::vector<char> in_place((size_t)n, 0);
-    for (int k = 0; k < n; k++) {
-        const std::string fk = who + "frame " + std::to_string(k) + ": ";
-        if (!d_src[k]) { ctx->set_error(fk + "d_src is NULL"); return MI355_ERR_ARG; }
-        if (!d_dst[k]) { ctx->set_error(fk + "d_dst is NULL"); return MI355_ERR_ARG; }
-        if (!check_size(w[k], h[k], err)) { ctx->set_error(fk + err); return MI355_ERR_ARG; }
-        if (ws_src[k] < 3 * w[k]) { ctx->set_error(fk + "ws_src=" + std::to_string(ws_src[k]) + " < 3 w=" + std::to_string(3 * w[k])); return MI355_ERR_ARG; }
-        if (ws_dst[k] < 3 * w[k]) { ctx->set_error(fk + "ws_dst=" + std::to_string(ws_dst[k]) + " < 3 w=" + std::to_string(3 * w[k])); return MI355_ERR_ARG; }
-        in_place[k] = d_dst[k] == d_src[k] && ws_dst[k] == ws_src[k];
-        const size_t sb = (size_t)ws_src[k] * (size_t)(h[k] - 1) + 3 * (size_t)w[k], db = (size_t)ws_dst[k] * (size_t)(h[k] - 1) + 3 * (size_t)w[k];
-        if (!in_place[k]) spans.push_back({(uintptr_t)d_src[k], (uintptr_t)d_src[k] + sb, k, false});
-        spans.push_back({(uintptr_t)d_dst[k], (uintptr_t)d_dst[k] + db, k, true});
-    }
-    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
-    {
-        uintptr_t hi_dst = 0, hi_src = 0;                           // the furthest end of the destination / source ranges that start earlier
-        int k_dst = -1, k_src = -1;
-        for (const Span& s : spans) {
-            if (hi_dst > s.lo) {
-                ctx->set_error(who + "d_dst of frame " + std::to_string(k_dst) + " overlaps " + (s.dst ? "d_dst" : "d_src") + " of frame " + std::to_string(s.k));
-                return MI355_ERR_ARG;
-            }
-            if (s.dst && hi_src > s.lo) {
-                ctx->set_error(who + "d_dst of frame " + std::to_string(s.k) + " overlaps d_src of frame " + std::to_string(k_src) + " without being in place");
-                return MI355_ERR_ARG;
-            }
-            if (s.dst) { if (s.hi > hi_dst) { hi_dst = s.hi; k_dst = s.k; } }
-            else if (s.hi > hi_src) { hi_src = s.hi; k_src = s.k; }
-        }
-    }
-    DevBuf& dout = ctx->buf("undistort_outside");
-    MI_HIP(dout.reserve(sizeof(unsigned long long) * (size_t)n));
-    MI_HIP(hipMemsetAsync(dout.p, 0, sizeof(unsigned long long) * (size_t)n, ctx->stream));
-    unsigned long long* d_outside = dout.as<unsigned long long>();
-    auto record = [&](int k, uint8_t* dst, int dst_pitch) {
-        UdFrame f;
-        f.src = d_src[k]; f.dst = dst; f.w = w[k]; f.h = h[k]; f.ws_src = ws_src[k]; f.ws_dst = dst_pitch; f.first_block = 0; f.bx_n = 0; f.k = k; f._pad = 0;
-        return f;
-    };
-    std::vector<UdFrame> fr;
-    for (int k = 0; k < n; k++)
-        if (!in_place[k]) fr.push_back(record(k, d_dst[k], ws_dst[k]));
-    if (!fr.empty()) { const int rc = launch_frames(ctx, fr, c, fill, d_outside); if (rc != MI355_OK) return rc; }
-    // in place: through the scratch buffer (rows of 3w bytes rounded up to 4, frames 256 bytes apart), group by group
-    auto scratch_bytes = [&](int k) { return ((((size_t)3 * w[k] + 3) & ~(size_t)3) * (size_t)h[k] + 255) & ~(size_t)255; };
-    for (int k0 = 0; k0 < n;) {
-        if (!in_place[k0]) { k0++; continue; }
-        size_t total = 0;
-        int k1 = k0;
-        fr.clear();
-        std::vector<size_t> off;
-        for (; k1 < n; k1++) {
-            if (!in_place[k1]) continue;
-            const size_t sb = scratch_bytes(k1);
-            if (!fr.empty() && total + sb > UD_SCRATCH_BYTES) break;
-            off.push_back(total);
-            fr.push_back(record(k1, nullptr, (3 * w[k1] + 3) & ~3));
-            total += sb;
-        }
-        DevBuf& ds = ctx->buf("undistort_scratch");
-        MI_HIP(ds.reserve(total));
-        for (size_t i = 0; i < fr.size(); i++) fr[i].dst = ds.as<uint8_t>() + off[i];
-        { const int rc = launch_frames(ctx, fr, c, fill, d_outside); if (rc != MI355_OK) return rc; }
-        for (const UdFrame& f : fr)
-            MI_HIP(hipMemcpy2DAsync(d_dst[f.k], (size_t)ws_dst[f.k], f.dst, (size_t)f.ws_dst, 3 * (size_t)f.w, (size_t)f.h, hipMemcpyDeviceToDevice, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));                  // the scratch is refilled by the next group
-        k0 = k1;
-    }
-    if (n_outside) {
-        std::vector<unsigned long long> cnt((size_t)n);
-        MI_HIP(hipMemcpyAsync(cnt.data(), dout.p, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < n; k++) n_outside[k] = (int64_t)cnt[k];
-    }
-    return MI355_OK;
+    unsigned long long* d_outside = nullptr;
+    return fp_run_frames(ctx, who, "undistort", d_src, d_dst, w, h, ws_src, ws_dst, n, n_outside,
+                         [&]() { d_outside = ctx->buf("undistort_outside").as<unsigned long long>(); return MI355_OK; },
+                         [&](const UdFrame* table, int nf, int blocks, double bytes) {
+                             ProfScope ps(ctx, "undistort", bytes);
+                             hipLaunchKernelGGL(undistort_kernel, dim3((unsigned)blocks), dim3(UD_NT), 0, ctx->stream, table, nf, c, (unsigned)fill, d_outside);
+                         });
 }
 
 }  // namespace

@@ -526,6 +526,46 @@ inline int UndistortImage(const MI355_NS IplImage* src, MI355_NS IplImage* dst, 
     return rc;
 }
 
+// Local registration (include/mi355_mosaic.h, "local registration"): what the aligned ties still disagree by on the canvas -- relief, residual
+// lens error, rolling shutter -- becomes a smooth, bounded displacement grid per frame, and the frames KEPT at extraction under ids
+// 0 .. nImages - 1 (option "keep_frames"; an id without a kept frame is MI355_ERR_ARG) are resampled by it in place, so that every render that
+// reads the kept frames (MI355_ADAPTOR_KEEP_FRAMES) shows the corrected pixels.  The reference has no such step: its caller puts it between
+// the global alignment and the render.  pMatchPairs is the list of the SIFT or SURF front-end (a run of equal (ptA_i, ptB_i) is one pair, a
+// run longer than 400 is cut into blocks of 400, the flat alignment forms' rule), pRectified the alignment's result.  params 0: the defaults;
+// grids (nImages x (grid_y+1) x (grid_x+1) x 2 floats) and report (nImages records) may be 0.  0 on success, -1 for bad arguments, else the
+// C call's error.  The caller's host images are not changed.
+inline int LocalRegistration(const MI355_NS MatchPointPairs* pMatchPairs, int nPairs, const MI355_NS ImageTransform* pRectified, int nImages,
+                             const mi355_local_warp_params* params = 0, float* grids = 0, mi355_local_warp_report* report = 0) {
+    if (!pRectified || nImages < 1 || nPairs < 0 || (nPairs > 0 && !pMatchPairs)) return -1;
+    mi355_ctx* c = context();
+    if (!c) return -1;
+    std::vector<uint8_t*> frames((size_t)nImages);
+    std::vector<int> w((size_t)nImages), h((size_t)nImages), ws((size_t)nImages);
+    std::vector<float> h9((size_t)9 * nImages);
+    for (int k = 0; k < nImages; k++) {
+        const uint8_t* d = NULL;
+        const int rc = mi355_get_frame_dev(c, k, &d, &w[k], &h[k], &ws[k]);
+        if (rc != MI355_OK) return rc;
+        frames[k] = const_cast<uint8_t*>(d);                             // the kept frame itself: the step is in place
+        std::memcpy(&h9[(size_t)9 * k], pRectified[k].h.m, 9 * sizeof(float));
+    }
+    std::vector<mi355_pair_result> rec;
+    for (int p = 0; p < nPairs; p++) {
+        const MI355_NS MatchPointPairs& m = pMatchPairs[p];
+        if (rec.empty() || rec.back().i != m.ptA_i || rec.back().j != m.ptB_i || rec.back().n_in == MI355_MAX_SELECTED) {
+            mi355_pair_result r;
+            std::memset(&r, 0, sizeof(r));
+            r.i = m.ptA_i; r.j = m.ptB_i; r.ok = 1; r.accepted = 1;
+            rec.push_back(r);
+        }
+        mi355_pair_result& r = rec.back();
+        r.a[r.n_in].x = m.ptA.x; r.a[r.n_in].y = m.ptA.y; r.a[r.n_in].id = m.ptA.id;
+        r.b[r.n_in].x = m.ptB.x; r.b[r.n_in].y = m.ptB.y; r.b[r.n_in].id = m.ptB.id;
+        r.n_in++; r.n_selected = r.n_in;
+    }
+    return mi355_local_register_results(c, rec.empty() ? NULL : &rec[0], (int)rec.size(), &frames[0], &w[0], &h[0], &ws[0], nImages, &h9[0], params, grids, report);
+}
+
 // A reduced-size mosaic (include/mi355_mosaic.h, "overview levels" / the preview): level `level` in 1..7 -- 1 / 2^level of the size -- of the
 // render `render` (0 MosaicImagesRefined's, 1 MosaicImagesWeighted's, 2 MosaicImagesSeamline's canvas), averaged over the pixels the survey
 // covers only, so that the empty surround does not darken the edge.  The survey is rendered in stripes on the device and only the small image

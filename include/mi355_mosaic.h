@@ -1036,6 +1036,125 @@ int  mi355_undistort_frames_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uin
 int  mi355_undistort_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, uint8_t* dst, int dst_ws, const mi355_camera* cam,
                            const mi355_undistort_params* p, int64_t* n_outside);
 
+/* ---- local registration (opt-in; csrc/local_warp.hip) --------------------------------------------------------------------------------
+ * What is left after the alignment is what no homography explains: relief and buildings (parallax), residual lens error, rolling shutter.
+ * The ties of the accepted pair records measure it: after the alignment their disagreement on the canvas is a sampled displacement field of
+ * each frame against its neighbours.  This section turns those residuals into a smooth, bounded displacement grid per frame (statistics, a
+ * small regularised solve per frame, as block gain) and resamples the frames by it in front of any render (as undistortion): the renders,
+ * the gain passes and the preview see ordinary frames.  Nothing calls it unless asked.
+ * Arithmetic.  Every integer expression is the one written; every float and every double operation is rounded separately, in the order
+ *   written, no contraction.  (int)v truncates; floor is the mathematical floor.
+ * Grid.  1 <= grid_x, grid_y <= 16, and a frame that takes part needs grid_x <= w-1 and grid_y <= h-1.  NX = grid_x + 1, NY = grid_y + 1,
+ *   NN = NX * NY nodes per frame; node (u, v), 0 <= u <= grid_x, 0 <= v <= grid_y, has the index v * NX + u and lies at the frame position
+ *   (u (w-1) / grid_x, v (h-1) / grid_y).  A grid holds per node the displacement (Dx, Dy) in source pixels: the corrected frame's pixel at a
+ *   position reads the source frame at position + D.
+ *
+ * Stage 1: residual statistics.
+ * Taking part.  Frame k takes part iff h9s[9k + 8] != 0 and its double inverse is finite.  With a..i = (double)h9[0..8]:
+ *     A0 = e*i - f*h;  A1 = c*h - b*i;  A2 = b*f - c*e;  A3 = f*g - d*i;  A4 = a*i - c*g;  A5 = c*d - a*f;
+ *     A6 = d*h - e*g;  A7 = b*g - a*h;  A8 = a*e - b*d;  det = (a*A0 + b*A3) + c*A6;  I[q] = A[q] / det, q = 0..8;
+ *   the inverse is finite iff all nine I[q] are.  Formed on the host, once per call.
+ * Processed records.  Tie refinement's rule: accepted != 0, 1 <= n_in <= 400, 0 <= i, j < n, i != j; and both frames take part.  Any other
+ *   record contributes nothing and counts towards n_skipped.
+ * Map.  P(M, x, y), M nine doubles: den = (M6*x + M7*y) + M8;  X = ((M0*x + M1*y) + M2) / den;  Y = ((M3*x + M4*y) + M5) / den
+ *   (apply_div9's two divisions and left-to-right sums).
+ * One tie (a in frame i, b in frame j; coordinates are the doubles of the record's floats), H_k = the doubles of h9s[9k ..]:
+ *   1 ci = P(H_i, a), cj = P(H_j, b).  A den that is not finite or <= 0 rejects the tie: REJ_DEN.
+ *   2 rx = cj.x - ci.x, ry = cj.y - ci.y.  rx*rx + ry*ry > max_residual*max_residual rejects the tie: REJ_RESIDUAL (an outlier of the
+ *     alignment, not relief).
+ *   3 mx = ci.x + 0.5*rx, my = ci.y + 0.5*ry.
+ *   4 For each side (k, p) in ((i, a), (j, b)): q = P(I_k, m);  dx = p.x - q.x, dy = p.y - q.y.  The side is kept iff
+ *     q.x >= 0 && q.x <= (double)(w_k-1) && q.y >= 0 && q.y <= (double)(h_k-1) && fabs(dx) <= max_shift && fabs(dy) <= max_shift (NaN fails);
+ *     else REJ_SIDE.  A kept side says: the corrected frame k reads, at q, the source pixel p.
+ *   REJ_DEN and REJ_RESIDUAL count once in frame i and once in frame j; REJ_SIDE counts in the side's frame.
+ * Quantisation of a kept side in frame k:
+ *     sx = (q.x * (double)grid_x) / (double)(w-1);  cx = min((int)sx, grid_x-1);  fx = (int)floor((sx - (double)cx) * 256.0 + 0.5)  (0..256);
+ *     sy, cy, fy likewise from q.y, grid_y, h;  dqx = (int)floor(dx * 256.0 + 0.5), dqy likewise  (Q8).
+ *   The side's four nodes and Q16 weights: (cx, cy): (256-fx)(256-fy);  (cx+1, cy): fx (256-fy);  (cx, cy+1): (256-fx) fy;  (cx+1, cy+1): fx fy.
+ *   They sum to 65536.
+ * Sums per frame, all int64_t, in a block of MI355_LOCAL_WARP_STATS_STRIDE(grid_x, grid_y) = 7 NN + 8 values:
+ *     [0, 5 NN)        S[t][node], t = 0..4: the sum of weight(node) * weight(neighbour t of node) over the kept sides, neighbour 0 = the node itself,
+ *                      1 = E (u+1, v), 2 = S (u, v+1), 3 = SE (u+1, v+1), 4 = SW (u-1, v+1): the symmetric 9-point stencil;
+ *     [5 NN, 6 NN)     bx[node] = sum of weight * dqx;      [6 NN, 7 NN)   by[node] = sum of weight * dqy;
+ *     7 NN + 0 .. 7    n_ties (kept sides), sum of dqx dqx + dqy dqy, REJ_DEN, REJ_RESIDUAL, REJ_SIDE, 0, 0, 0.
+ *   The n blocks are followed by one tail of 8 values: n_skipped, then zeros: n * stride + 8 values in all.  The sums are exact: they do not
+ *   depend on record order, launch geometry or the entry point that formed them.
+ * Stage 2: solve (host only, no ctx).  Per frame with n_ties >= max(min_ties, 1), in double, unknowns = the nodes, one system, two
+ *   right-hand sides:  A = S / 2^32 + smooth * L + prior * I,  L the Laplacian of the 4-neighbour node lattice (degree on the diagonal, -1
+ *   per lattice edge);  rhs = bx / 2^24 and by / 2^24 (source pixels).  Banded Cholesky (envelope_chol.h, half bandwidth NX + 1) in a fixed
+ *   single-threaded order per frame, threads across frames only: the same bits for every call and thread count; within 1e-9 relative
+ *   (infinity norm) of the exact solution for prior >= 1e-6 of A's largest diagonal entry.  The solution, clamped to [-max_shift, max_shift]
+ *   and cast to float, is grids[n][NY][NX][2] (x then y).  Every other frame gets exact zeros.
+ *   Report per frame, from the sums and the unclamped solution g alone: n_ties and the reject counts; rms_before =
+ *   sqrt((sum dq^2 / 65536) / n_ties); rms_after = sqrt(max(0, dd - 2 g.b + g^T S g) / n_ties) with dd, b, S scaled as above (the fit's
+ *   residual at the ties, both components); max_shift = the largest |grid value| after the clamp; solved = 1 iff the frame was solved.
+ * Stage 3: apply.  Node values nq = (int)floor((double)g * 256.0 + 0.5) per component (Q8, |nq| <= 16384).  Pixel (x, y) of a w x h frame:
+ *     num = x * grid_x;  i0 = min(num / (w-1), grid_x-1);  fx = ((num - i0 (w-1)) * 256) / (w-1)      (integer division; 0..256)
+ *     j0, fy likewise from y, grid_y, h-1;
+ *     Dx = (256-fy) ((256-fx) nq[j0][i0].x + fx nq[j0][i0+1].x) + fy ((256-fx) nq[j0+1][i0].x + fx nq[j0+1][i0+1].x)   (int32, Q24, below 2^31)
+ *     Dy likewise;  then in f32:  xs = (float)x + (float)Dx * 0x1p-24f;  ys = (float)y + (float)Dy * 0x1p-24f;
+ *     xs = xs < 0 ? 0 : xs > (float)(w-1) ? (float)(w-1) : xs, ys likewise (edge replication); a pixel with either coordinate changed by
+ *     that counts towards the frame's n_clamped;
+ *     xi = min((int)xs, w-2), yi = min((int)ys, h-2), q = xs - (float)xi, p = ys - (float)yi; the sample is undistortion's (its "Sample").
+ *   Consequences: an all-zero grid returns the source byte for byte, last row and column included, n_clamped = 0.  A frame's bytes depend
+ *   only on its own pixels, its size and its grid: not on pitches, its position in the call or the other frames.  In-place output equals
+ *   out-of-place output.  Bytes [0, 3w) of each destination row are written, the row padding is not.
+ * Errors (MI355_ERR_ARG before any launch, the message names the value, the ctx stays usable): grid_x or grid_y outside 1..16, or
+ *   grid_x > w-1 or grid_y > h-1 on a frame that takes part (apply: on any frame); max_residual, max_shift, smooth or prior not finite;
+ *   max_residual <= 0, max_shift outside (0, 64], smooth < 0, prior <= 0, min_ties < 0; reserved != 0; a NULL array; w or h outside 2..2^20;
+ *   ws < 3w; n < 0 or n > 65535; n_pairs < 0; a grid value that is not finite or outside [-64, 64]; a negative sum in the solve's input; and,
+ *   in the apply, mi355_undistort_frames_dev's overlap rules.
+ * Out of scope: the multi-GPU path (the sums are integers and would add across ranks; no collective is added); single-channel frames;
+ *   iterating the step; moving keypoints or ties into the warped frames (the caller has the grids for that). */
+#define MI355_LOCAL_WARP_STATS_STRIDE(grid_x, grid_y) (7 * ((grid_x) + 1) * ((grid_y) + 1) + 8)
+typedef struct {
+    int32_t grid_x, grid_y;     /* cells per frame, 1..16 each */
+    int32_t min_ties;           /* a frame with fewer kept sides keeps a zero grid */
+    int32_t reserved;
+    double max_residual;        /* canvas pixels: ties that disagree by more are outliers of the alignment */
+    double max_shift;           /* source pixels: bound of a side's displacement and of the grid values, (0, 64] */
+    double smooth;              /* weight of the lattice Laplacian */
+    double prior;               /* weight of the pull towards zero, > 0 */
+} mi355_local_warp_params;
+typedef struct {
+    int64_t n_ties, rej_den, rej_residual, rej_side;
+    double rms_before, rms_after, max_shift;      /* source pixels */
+    int32_t solved, _pad;
+} mi355_local_warp_report;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_local_warp_params) == 48, "mi355_local_warp_params is 48 bytes");
+static_assert(sizeof(mi355_local_warp_report) == 64, "mi355_local_warp_report is 64 bytes");
+#else
+_Static_assert(sizeof(mi355_local_warp_params) == 48, "mi355_local_warp_params is 48 bytes");
+_Static_assert(sizeof(mi355_local_warp_report) == 64, "mi355_local_warp_report is 64 bytes");
+#endif
+/* grid 8 x 6, min_ties 8, max_residual 8, max_shift 8, smooth 2, prior 0.25 (DESIGN: the sweep behind them) */
+void mi355_default_local_warp_params(mi355_local_warp_params* p);
+/* the sums of device records into d_stats (DEVICE, n * stride + 8 int64_t, cleared by the call): one launch over the records, a workgroup per
+ * record, enqueued on the ctx stream like mi355_pair_moments_dev.  w, h, h9s: host arrays, read before the call returns.  Of p only grid_x,
+ * grid_y, max_residual and max_shift are used (NULL: defaults).  Profile class "tie_residuals". */
+int  mi355_tie_residual_stats_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n_pairs, const int* w, const int* h, const float* h9s, int n,
+                                  const mi355_local_warp_params* p, int64_t* d_stats);
+/* the same bits from host records (no ctx, no device; errors: mi355_last_error(NULL)) */
+int  mi355_tie_residual_stats_host(const mi355_pair_result* results, int n_pairs, const int* w, const int* h, const float* h9s, int n,
+                                   const mi355_local_warp_params* p, int64_t* stats);
+/* stage 2 (host only, no ctx): stats as above -> grids (n x NY x NX x 2 floats) and report (n records; may be NULL) */
+int  mi355_solve_local_warps(const int64_t* stats, int n, const mi355_local_warp_params* p, float* grids, mi355_local_warp_report* report);
+/* stage 3: d_dst[k] = frame d_src[k] resampled by grids[k], for every k: frames of any mix of sizes, one launch, complete on return.
+ * grids: HOST, n x NY x NX x 2.  n_clamped: HOST, n values, may be NULL.  In place (d_dst[k] == d_src[k], equal pitches), the scratch
+ * groups, the overlap checks and n = 0 are mi355_undistort_frames_dev's, rule for rule.  Profile class "local_warp". */
+int  mi355_apply_local_warps_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uint8_t* const* d_dst, const int* w, const int* h, const int* ws_src,
+                                 const int* ws_dst, int n, int grid_x, int grid_y, const float* grids, int64_t* n_clamped);
+/* stages 1 to 3 in place on d_imgs (frames that take no part are not touched and may be NULL); grids_out (HOST, n x NY x NX x 2) and
+ * report_out (HOST, n records) may be NULL.  p NULL: defaults.  Complete on return. */
+int  mi355_local_register_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n_pairs, uint8_t* const* d_imgs, const int* w, const int* h,
+                              const int* ws, int n, const float* h9s, const mi355_local_warp_params* p, float* grids_out,
+                              mi355_local_warp_report* report_out);
+/* the same from HOST records (uploaded by the call): for callers that hold the pair stage's records on the host, as the adaptor does */
+int  mi355_local_register_results(mi355_ctx* ctx, const mi355_pair_result* results, int n_pairs, uint8_t* const* d_imgs, const int* w, const int* h,
+                                  const int* ws, int n, const float* h9s, const mi355_local_warp_params* p, float* grids_out,
+                                  mi355_local_warp_report* report_out);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

@@ -60,7 +60,6 @@ extern "C" int mi355_create(mi355_ctx** out, const mi355_params* params, int dev
     if (e != hipSuccess) { g_create_error = hipGetErrorString(e); delete c; return MI355_ERR_DEVICE; }
     c->stream = c->own_stream;
     if (const char* e = getenv("MI355_BLUR_STREAM")) c->blur_stream = atoi(e) ? 1 : 0;
-    if (const char* e = getenv("MI355_CASCADE")) { const int v = atoi(e); c->cascade = v < 0 ? 0 : (v > 3 ? 3 : v); }
     if (getenv("MI355_SERIAL_HEAVY")) c->serial_heavy = 1;
     {
         struct { const char* n; int* p; } knobs[] = {{"MI355_RANSAC_SPLIT", &c->ransac_split}};
@@ -408,7 +407,6 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
         ctx->keepall_max = value;
         return MI355_OK;
     }
-    if (std::string(name) == "keepall_order") { ctx->keepall_order = value == 1 ? 1 : 0; return MI355_OK; }
     if (std::string(name) == "big_subpairs_max") { ctx->big_sub_max = value < 1 ? 1 : value; return MI355_OK; }
     {
         struct { const char* n; int* p; } knobs[] = {{"ransac_split", &ctx->ransac_split}, {"strict_frames", &ctx->strict_frames}};
@@ -429,7 +427,7 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
     if (std::string(name) == "download_mode") { ctx->download_mode = value < 0 || value > 2 ? 0 : value; return MI355_OK; }
     if (std::string(name) == "sift_flush") return mi_sift_flush(ctx);      // close the batch that is collecting frames now (no wait): the caller shapes the batches of a short survey
     if (std::string(name) == "blur_stream") { ctx->blur_stream = value ? 1 : 0; return MI355_OK; }
-    if (std::string(name) == "sift_cascade") { ctx->cascade = value < 0 ? 0 : (value > 3 ? 3 : value); return MI355_OK; }
+    if (std::string(name) == "sift_cascade" || std::string(name) == "keepall_order") return MI355_OK;      // accepted and ignored: the kernels they chose between are gone
     if (std::string(name) == "serial_heavy") {
         int rc = mi_resolve_features(ctx);
         if (rc != MI355_OK) return rc;

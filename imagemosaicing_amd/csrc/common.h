@@ -148,7 +148,6 @@ struct mi355_ctx {
     int download_mode = 0;                            // option "download_mode" (measurement): 0 pinned double buffer, 1 hipMemcpy2DAsync into dst, 2 hipHostRegister(dst) + 2D copy
     hipStream_t dl_stream = nullptr;                   // copy stream of those downloads
     hipEvent_t dl_ev[3] = {nullptr, nullptr, nullptr}; // [0], [1]: the pinned halves filled; [2]: the render finished on ctx->stream
-    int cascade = 3;                                   // octaves >= 2000 px wide: 3 (default) = the first three levels ({gray | L0} -> L0/L1 L2) in one pass (pyr_chain), the rest per level; 2 = also L3..L5 in one pass; 1 = all six in one pass (pyr_cascade); 0 = every level on its own. Same bits; option "sift_cascade"
     int blur_stream = 1;                               // big pyramid levels through blur_stream (0: tile kernel only); option "blur_stream"
     int sift_nslots = 3;                               // batch work areas in flight, each on its own stream (option "sift_slots", env MI355_SIFT_SLOTS)
     int xstream_min_w = 1500, xstream_min_frames = 4;  // extrema_stream for octaves at least this wide (and 3/4 as high) in batches of at least so many frames
@@ -162,7 +161,6 @@ struct mi355_ctx {
     mi355_comm* comm = nullptr;                        // RCCL communicator (mi355_comm_init), comm.hip
     SurfState* surf = nullptr;                         // SURF variant of the path (surf.hip)
     int keepall_max = MI355_SIFT_KEEPALL_MAX;          // option "keepall_max": keypoints per keep-all frame (multiple of 2048 in [32768, 262144]); every check of a frame's or pair's keypoint count uses it
-    int keepall_order = 0;                             // option "keepall_order" (measurement): 0 tile sort + binary search (sift.hip), 1 the brute-force rank count
     int big_sub_max = 65536;                           // option "big_subpairs_max" (debug): sub-pairs of <= 2048 x 2048 per large-pair run of the matcher (bounds the nn workspaces: 12 B x 2048 each)
     int last_counts[8] = {0};                          // SIFT counters of the last frame: candidates, refined, keypoints, selected, overflow
 

@@ -7,26 +7,28 @@
 // |DoG| > 20, Cramer's rule for the 3x3 fit.  This file implements that definition, independently, for the GPU, and the parity
 // tests compare keypoints and descriptors bit for bit with the oracle.
 //
-// Host side: frames collect into batches (SiftWork, sift_run_batch at the end of this file); every launch below covers all frames
-// of a batch.  Kernels:
-//   blur16_stream<R,BGR>  separable Gaussian of one level (>= 512 columns): a wave walks down a strip of 256 columns, rows arrive
+// Host side (end of this file): frames collect into batches (SiftWork); sift_plan.{h,cpp} decides a batch's layout and its pyramid and
+// extrema launches, sift_run_batch enqueues them, and every launch covers all frames of the batch.  Kernels:
+//   blur16_stream<R,BGR,DS,W>  separable Gaussian of one level (>= 512 columns): a wave walks down a strip of 256 columns, rows arrive
 //                         once from HBM (8 bytes per lane: four 16-bit samples), the row-filtered rows of the last 2R+1 steps live in
 //                         registers (the column pass needs its taps centre first, then symmetric pairs: a gather, not a scatter),
 //                         no workgroup barrier; BGR = true forms gray x 48 of the caller's frame on the fly (base level, no gray
-//                         image is ever stored); level 3 also writes the decimated base of the next octave
+//                         image is ever stored); DS = true (level 3) also writes the decimated base of the next octave
 //   blur16_tile<R,BGR>    the same filter for small levels: 64x32 tile + halo in LDS, row pass then column pass
 //   downsample16          next octave seed = every second pixel of level 3 (when the blur did not write it on the way out)
 //   extrema_stream / extrema_kernel   DoG never materialised in HBM: the 6 Gaussian levels are read once, 26-neighbour
 //                         test on the 5 DoG planes (registers / LDS), candidates leave with their 3x3x3 neighbourhood
-//   refine                one lane per candidate: quadratic fit, contrast / edge tests, duplicate claim bitmap
-//   resp_threshold        response threshold above which nfeatures + 256 refined points lie (radix select)
+//   refine                one lane per candidate: quadratic fit, contrast / edge tests, duplicate claim bitmap, response histogram
+//   select_unclaim        response threshold above which nfeatures + 256 refined points lie; takes the claim bits back
 //   orient                one wave per refined point above the threshold: 36-bin histogram in order-free fixed point,
 //                         smoothing + peaks via lane shuffles
 //   topk                  one workgroup per frame: radix select of the nfeatures-th response, bitonic sort of the
 //                         survivors by the total order (response desc, octave, layer, row, col, bin)
+//   keepall_live / _reset / _sort_tiles / _place   nfeatures <= 0: selection and top-k replaced by "every point, in generation order"
 //   describe              one workgroup per keypoint: trilinear contributions quantised to 2^-10 and added with
 //                         64-bit LDS atomics (order-free by definition), normalise / clip / renormalise -> u8
 #include "common.h"
+#include "sift_plan.h"
 #include <memory>
 #include "detmath.h"
 #include <cmath>
@@ -34,12 +36,13 @@
 
 namespace {
 
-constexpr int N_LAYERS = 3, N_LEVELS = 6, IMG_BORDER = 5, MAX_INTERP = 5, ORI_BINS = 36, MAX_OCT = 16;
+using namespace sift_plan;                     // the constants the host plan shares with the kernels (N_LEVELS, MAX_R, EW, XSW, ...)
+constexpr int MAX_INTERP = 5, ORI_BINS = 36;
 constexpr int FIXPT_SCALE = 48;                 // SIFT_FIXPT_SCALE of the reference's OpenCV build: pyramid samples are gray x 48 in 16 bits
 constexpr float DOG_THRESHOLD_P1 = 21.0f;       // |DoG| > floor(0.5 * 0.01 / 3 * 255 * 48) = 20, on integers: |DoG| >= 21
 constexpr float HIST_Q = 1024.0f;               // order-free histogram accumulation: contributions quantised to 2^-10 (oracle_sift.c)
-constexpr int MAX_R = 16;
 constexpr int SIFT_BATCH_MAX = MI355_SIFT_BATCH_MAX;
+static_assert(SIFT_BATCH_MAX == BATCH_MAX, "sift_plan.h: BATCH_MAX");
 typedef int16_t lvl_t;                          // one pyramid sample
 
 __host__ __device__ __forceinline__ int reflect101(int p, int n) {
@@ -104,7 +107,6 @@ struct Blur16Args {
     int nb;                                  // frames in the launch
 };
 
-constexpr int T16W = 64, T16H = 32;
 template <int R, bool BGR>
 __global__ __launch_bounds__(256) void blur16_tile(Blur16Args a) {
     constexpr int ROWS = T16H + 2 * R, COLS = T16W + 2 * R, PIN = COLS | 1, PMID = T16W + 4;
@@ -267,19 +269,10 @@ __global__ __launch_bounds__(256) void downsample16(const lvl_t* src, int sw, lv
 // ---------- K3: DoG extrema -------------------------------------------------------------------------------------
 struct OctaveDev { lvl_t* lv[N_LEVELS]; int w, h; };
 
-#ifndef EXT_EH
-#define EXT_EH 16
-#endif
-constexpr int EW = 64, EH = EXT_EH, ECAP = 128;
-#ifndef REG_SHIFT_V
-#define REG_SHIFT_V 0
-#endif
-constexpr int REG_SHIFT = REG_SHIFT_V;      // 2^REG_SHIFT consecutive tiles append to the same region: refine_kernel then walks spatially coherent runs
-constexpr int NREG = 64, REG_STRIDE = 32;   // candidate list split into 64 regions, one counter per 128-byte line:
-                                            // a single counter caps at ~1e8 returning atomics/s (one per tile = 0.5 ms)
+constexpr int ECAP = 128;
+constexpr int REG_STRIDE = 32;              // one counter of the NREG candidate regions per 128-byte line
 // batched launches: frame f = blockIdx.y (z for refine) works on its own copy of every buffer, a fixed stride apart
 struct BatchStride { size_t pyr, claimed, cand, refined, kps, cube, sel, mins; };   // elements of the respective type (sel: selected keypoints per frame; mins: keep-all's start-key table)
-constexpr size_t CNT_STRIDE = 64, CCNT_STRIDE = (size_t)64 * 32, SEL_STRIDE = 2048;
 struct FrameOuts { mi355_keypoint* kp[SIFT_BATCH_MAX]; uint8_t* d8[SIFT_BATCH_MAX]; };
 
 // ---------- K3b: sub-pixel refinement ---------------------------------------------------------------------------
@@ -513,15 +506,6 @@ __global__ __launch_bounds__(256) void extrema_kernel(OctaveDev oc, int octave, 
 // together with its 3x3x3 DoG neighbourhood, taken from the registers of the lane and of its two neighbours; the list
 // goes to global memory when it is full and at the end of the segment.
 constexpr int XCAP = 512;                       // candidate records buffered per wave (4 KB); the list is emptied when half full, between runs of the row loop
-#ifndef MI355_XD
-#define MI355_XD 2
-#endif
-constexpr int XD = MI355_XD;                           // rows in flight per wave
-#ifndef MI355_XWAVES
-#define MI355_XWAVES 3
-#endif
-constexpr int XWAVES = MI355_XWAVES;                       // waves per SIMD the streamed test is compiled for (the launcher sizes its grid to whole rounds of them)
-constexpr int XSW = 248;                        // columns a wave is responsible for: lanes 1..62; lanes 0 and 63 carry the neighbours' columns
 // The DoG values are 16-bit integers and stay PACKED, two columns per register, from the level rows to the test: v_pk_sub_i16 forms
 // them straight from the loaded level words (no unpacking), v_pk_max_i16 / v_pk_min_i16 take the extremes of two columns at a time and
 // the 16-bit compares read either half (SDWA).  Half the registers of the float form of round 3 (4 waves per SIMD instead of 2) and
@@ -1306,39 +1290,10 @@ __device__ __forceinline__ bool keepall_fits(unsigned N, unsigned kp_cap, unsign
     return false;
 }
 
-// (measurement, option "keepall_order" = 1) the rank by brute force: every workgroup walks all keys of its frame in tiles through LDS, O(N^2)
-__global__ __launch_bounds__(256) void keepall_output_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, unsigned kmax, FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, BatchStride bs) {
-    const size_t fr = blockIdx.y;
-    kps += fr * bs.kps; kp_count += fr * CNT_STRIDE; out_sel += fr * bs.sel; out_n += fr * CNT_STRIDE; overflow += fr * CNT_STRIDE;
-    mi355_keypoint* out_kp = outs.kp[0];
-#pragma unroll
-    for (int q = 1; q < SIFT_BATCH_MAX; q++) if ((int)fr == q) out_kp = outs.kp[q];
-    unsigned N = *kp_count;
-    if (!keepall_fits(N, kp_cap, kmax, out_n, overflow, blockIdx.x == 0 && threadIdx.x == 0)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *out_n = (int)N;
-    __shared__ unsigned long long s_key[1024];
-    const unsigned i = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x * 256 >= N) return;
-    KpRec mine;
-    unsigned long long mk = ~0ull;
-    if (i < N) { mine = kps[i]; mk = keepall_key(mine); }
-    unsigned rank = 0;
-    for (unsigned t0 = 0; t0 < N; t0 += 1024) {
-        __syncthreads();
-        for (unsigned q = threadIdx.x; q < 1024; q += 256) s_key[q] = t0 + q < N ? keepall_key(kps[t0 + q]) : ~0ull;
-        __syncthreads();
-        const unsigned cntq = N - t0 < 1024 ? N - t0 : 1024;
-        for (unsigned q = 0; q < cntq; q++) rank += s_key[q] < mk ? 1u : 0u;
-    }
-    if (i >= N) return;
-    keepall_emit(mine, out_kp, out_sel, rank);
-}
-
 // The rank in O(N log N), two launches.  Phase A (keepall_sort_tiles_kernel): every workgroup sorts a tile of KA_TILE keys (key << 18 | index)
 // in LDS, bitonic, and writes it to the frame's scratch area padded with all-ones.  A frame of one tile is done there: the sorted position is
 // the output position.  Phase B (keepall_place_kernel, frames of more than one tile): a keypoint's position = the sum over the tiles of the
 // number of keys there below its own (lower_bound, 13 probes of a KA_TILE-sized tile; in its own tile that is its place in the tile).
-constexpr int KA_TILE = 4096;
 
 __global__ __launch_bounds__(1024) void keepall_sort_tiles_kernel(const KpRec* kps, const unsigned* kp_count, unsigned kp_cap, unsigned kmax, unsigned long long* sorted,
                                                                   size_t sorted_stride, FrameOuts outs, SelRec* out_sel, BatchStride bs) {
@@ -1549,112 +1504,73 @@ __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* s
 }
 
 // ---------- host ---------------------------------------------------------------------------------------------------
-int gauss_kernel_host(double sigma, float* k) {
-    const int ksize = ((int)lrint(sigma * 8.0 + 1.0)) | 1;
-    const int r = ksize / 2;
-    // cv::getGaussianKernel(ksize, sigma, CV_32F): each exp() rounded to float, the floats summed in double, taps (float)(tap / sum)
-    double sum = 0.0;
-    const double scale2x = -0.5 / (sigma * sigma);
-    for (int i = 0; i < ksize; i++) { const double x = (double)i - (double)(ksize - 1) * 0.5; k[i] = (float)std::exp(scale2x * x * x); sum += (double)k[i]; }
-    sum = 1.0 / sum;
-    for (int i = 0; i < ksize; i++) k[i] = (float)((double)k[i] * sum);
-    return r;
-}
-
-// does this level go through blur16_stream?  (8-byte aligned rows, last strip wider than the largest radius, enough strips x frames to fill the chip;
-// the decimated copy needs an even height: the even rows of every segment are then the even rows of the image)
-inline bool blur_streams(const Blur16Args& a, bool bgr, int R, int stream_mode) {
-    const bool has_r = bgr ? R == 6 : (R == 5 || R == 6 || R == 8 || R == 10 || R == 13);
-    bool ok = stream_mode && has_r && (a.w & 3) == 0 && ((a.w & 255) == 0 || (a.w & 255) > MAX_R) && a.w >= 512 && a.h >= 64;
-    if (bgr) { for (int f = 0; f < a.nb; f++) ok = ok && ((uintptr_t)a.bgr[f] & 3) == 0 && (a.bgr_ws[f] & 3) == 0 && a.bgr_ws[f] >= 3 * a.w; }
-    else ok = ok && ((uintptr_t)a.src & 7) == 0;
-    if (a.ds) ok = ok && R == 8 && (a.h & 1) == 0;
-    return ok && ((uintptr_t)a.dst & 7) == 0 && (a.fstride & 3) == 0;
-}
-inline void stream_grid(int w, int h, int& L, int& nstrip, int& nseg, int nb = 1, int waves = 2) {
-    static const int units_env = [] { const char* e = getenv("MI355_STREAM_UNITS"); return e ? atoi(e) : 0; }();
-    const int units_target = units_env ? units_env : 1024 * waves;
-    static const int stream_minl = [] { const char* e = getenv("MI355_STREAM_MINL"); return e ? atoi(e) : 64; }();
-    nstrip = (w + 255) / 256;
-    nseg = (units_target + nstrip * nb - 1) / (nstrip * nb);
-    L = (h + nseg - 1) / nseg;
-    if (L < stream_minl) L = stream_minl;
-    L = (L + 1) & ~1;
-    nseg = (h + L - 1) / L;
-}
+// the blur kernel of a launch, among those this library carries (sift_plan routes a level to a streamed one only where one exists)
+struct BlurFn { void (*stream)(Blur16Args, int, int, int); void (*tile)(Blur16Args); };
 template <bool BGR>
-bool launch_blur(hipStream_t st, int R, const Blur16Args& a_in, int stream_mode, bool* streamed = nullptr) {
-    Blur16Args a = a_in;
-    const int nb = a.nb > 1 ? a.nb : 1;
-    if (streamed) *streamed = false;
-    if (blur_streams(a, BGR, R, stream_mode)) {
-        // barrier-free streaming kernel over the whole chip: W waves per SIMD (W x 1024 waves, one round), segments of >= 64 rows, all frames of
-        // a batch in one launch.  The register ring of the row results (4 x (2R + 2) registers) decides W: R <= 8 fits 128 registers, R = 10 / 13 168
-        static const int w4 = [] { const char* e = getenv("MI355_STREAM_W4"); return e ? atoi(e) : 8; }();
-        const int waves = (R <= w4 && R <= 8) ? 4 : 3;      // (grids sized for one wave per SIMD fewer, to leave registers to the other batches' keypoint kernels, measured the same: profiles/r05_pipeline_layouts.txt)
-        double ksum = 0.0;
-        for (int t = 0; t <= 2 * R; t++) ksum += std::fabs((double)a.k[t]);
-        if (ksum < 2.6) {                            // the kernel's rounding assumes results in [0, 32767]: samples <= 255 * 48, taps positive and normalised
-            for (int t = 0; t <= R; t++) { a.kp[2 * t] = a.k[t]; a.kp[2 * t + 1] = t ? a.k[t - 1] : 0.0f; }
-            int L, nstrip, nseg;
-            stream_grid(a.w, a.h, L, nstrip, nseg, nb, waves);
-            const int units = nstrip * nseg * nb;
-            const dim3 grid((units + 3) / 4), block(256);
-            if (streamed) *streamed = true;
-#define LAUNCH(RR, DS, WW) hipLaunchKernelGGL((blur16_stream<RR, BGR, DS, WW>), grid, block, 0, st, a, L, nstrip, nseg); return true
-            if constexpr (BGR) { if (waves == 4) { LAUNCH(6, false, 4); } else { LAUNCH(6, false, 3); } }
-            else {
-                switch (R) {
-                    case 5: if (waves == 4) { LAUNCH(5, false, 4); } else { LAUNCH(5, false, 3); }
-                    case 6: if (waves == 4) { LAUNCH(6, false, 4); } else { LAUNCH(6, false, 3); }
-                    case 8: if (a.ds) { if (waves == 4) { LAUNCH(8, true, 4); } else { LAUNCH(8, true, 3); } }
-                            else { if (waves == 4) { LAUNCH(8, false, 4); } else { LAUNCH(8, false, 3); } }
-                    case 10: LAUNCH(10, false, 3);
-                    case 13: LAUNCH(13, false, 3);
-                    default: break;
-                }
-            }
-#undef LAUNCH
+BlurFn blur_kernel(const Launch& L) {
+    const bool w4 = L.waves == 4;
+    if (L.kind == BLUR_STREAM) {
+        if constexpr (BGR) return {w4 ? blur16_stream<6, true, false, 4> : blur16_stream<6, true, false, 3>, nullptr};
+        else switch (L.radius) {
+            case 5: return {w4 ? blur16_stream<5, false, false, 4> : blur16_stream<5, false, false, 3>, nullptr};
+            case 6: return {w4 ? blur16_stream<6, false, false, 4> : blur16_stream<6, false, false, 3>, nullptr};
+            case 8: if (L.ds) return {w4 ? blur16_stream<8, false, true, 4> : blur16_stream<8, false, true, 3>, nullptr};
+                    return {w4 ? blur16_stream<8, false, false, 4> : blur16_stream<8, false, false, 3>, nullptr};
+            case 10: return {blur16_stream<10, false, false, 3>, nullptr};
+            case 13: return {blur16_stream<13, false, false, 3>, nullptr};
         }
     }
-    const dim3 grid(a.tiles_x * a.tiles_y, nb), block(256);
-    switch (R) {
-#define CASE(RR) case RR: hipLaunchKernelGGL((blur16_tile<RR, BGR>), grid, block, 0, st, a); return true;
+    switch (L.radius) {
+#define CASE(RR) case RR: return {nullptr, blur16_tile<RR, BGR>};
         CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
 #undef CASE
-        default: return false;
     }
+    return {nullptr, nullptr};
 }
 
-}  // namespace
-
-// One batch work area: room for `nb` frames (every per-frame buffer nb times, a fixed stride apart) and one stream.
-// Frames handed to mi_sift_extract_dev() collect in `pend`; a full batch (or a flush) is enqueued as
-//   phase 1  per frame : the chip-filling kernels of the big octaves (base level, blur_stream, extrema)
-//   phase 2  per octave: the small octaves of ALL frames of the batch in one launch each (grid dimension = frame)
-//   phase 3  per stage : refine / threshold / orientation / top-k / descriptors of ALL frames in one launch each
-// so that the latency-bound launches (30 tiny blurs, single-workgroup selections) are paid once per batch instead of
-// once per frame, on ONE in-order stream -- no reliance on how the runtime maps streams to hardware queues.
-struct SiftWork {
-    int w = 0, h = 0;                        // input frame size the buffers are sized for
-    int nb = 0;                              // frames the buffers hold
-    int n_oct = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;               // recorded after the last launch of the latest batch
+// the device buffers of a batch work area: every per-frame buffer nb times, a stride of the layout apart
+struct SiftBufs {
     DevBuf pyr;                              // all Gaussian levels
     DevBuf claimed;                          // duplicate claim bitmaps
     DevBuf cand, refined, kps, kresp, sel, counters, rhist, ccnt;
     DevBuf olist;                            // per frame: indices of the refined points at or above the response threshold
-    DevBuf mins; bool keepall = false;       // keep-all (nfeatures <= 0): smallest start key per refined location, all ones between batches
-    int kmax = 0;                            // keep-all: the ctx's ceiling (option "keepall_max") the batch was sized for; bs.sel = kmax
-    DevBuf ksort; size_t ksort_stride = 0;   // keep-all: per frame, its keys sorted tile by tile (keepall_sort_tiles_kernel)
-    DevBuf cube; unsigned cube_cap = 0;       // 3x3x3 DoG neighbourhoods of the first cube_cap candidates of every region (128 B each)
+    DevBuf mins;                             // keep-all (nfeatures <= 0): smallest start key per refined location, all ones between batches
+    DevBuf ksort;                            // keep-all: per frame, its keys sorted tile by tile (keepall_sort_tiles_kernel)
+    DevBuf cube;                             // 3x3x3 DoG neighbourhoods of the first cube_cap candidates of every region (128 B each)
+    hipError_t reserve(const Layout& l, int nb, hipStream_t st) {
+        const Strides& bs = l.bs;
+        const struct { DevBuf* b; size_t bytes; } want[] = {
+            {&pyr, bs.pyr * sizeof(lvl_t)}, {&claimed, bs.claimed * sizeof(unsigned)}, {&cand, bs.cand * sizeof(unsigned long long)},
+            {&refined, bs.refined * sizeof(Refined)}, {&kps, bs.kps * sizeof(KpRec)}, {&kresp, bs.kps * sizeof(unsigned)}, {&sel, bs.sel * sizeof(SelRec)},
+            {&mins, bs.mins * sizeof(unsigned)}, {&ksort, l.ksort_stride * sizeof(unsigned long long)}, {&counters, CNT_STRIDE * sizeof(unsigned)},
+            {&rhist, bs.refined * sizeof(unsigned)}, {&olist, bs.refined * sizeof(unsigned)}, {&ccnt, CCNT_STRIDE * sizeof(unsigned)}, {&cube, bs.cube * sizeof(float)}};
+        for (const auto& w : want) {
+            if (!w.bytes) { w.b->release(); continue; }      // mins, ksort without keep-all
+            if (const hipError_t e = w.b->reserve((size_t)nb * w.bytes); e != hipSuccess) return e;
+        }
+        // the claim bits are kept zero between batches (select_unclaim_kernel takes them back), the start keys all ones (keepall_reset_kernel)
+        if (const hipError_t e = hipMemsetAsync(claimed.p, 0, (size_t)nb * bs.claimed * sizeof(unsigned), st); e != hipSuccess) return e;
+        return l.keepall ? hipMemsetAsync(mins.p, 0xff, (size_t)nb * bs.mins * sizeof(unsigned), st) : hipSuccess;
+    }
+    void release() { for (DevBuf* b : {&pyr, &claimed, &cand, &refined, &kps, &kresp, &sel, &counters, &rhist, &ccnt, &olist, &mins, &ksort, &cube}) b->release(); }
+};
+
+}  // namespace
+
+// One batch work area: room for `nb` frames and one stream.  Frames handed to mi_sift_extract_dev() collect in `pend`; a full batch
+// (or a flush) is enqueued by sift_run_batch() on that ONE in-order stream -- no reliance on how the runtime maps streams to hardware
+// queues -- and every launch covers all frames of the batch (the frame is a grid dimension, or a factor of a streamed kernel's
+// units): the pyramid octave by octave as sift_plan::pyramid_launches lists it (a base blur or a downsample, five blurs, one
+// extrema test), then refine, selection, orientation, top-k and descriptors once each.  The latency-bound launches (30 tiny blurs,
+// single-workgroup selections) are thus paid once per batch instead of once per frame.
+struct SiftWork {
+    Layout lay;                              // of the frames the buffers are sized for (lay.w == 0: none yet)
+    int nb = 0;                              // frames the buffers hold
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;               // recorded after the last launch of the latest batch
+    SiftBufs b;
     PyrDev P;                                // pointers of frame 0
     BatchStride bs;
-    unsigned cand_cap = 0, ref_cap = 0, kp_cap = 0;
-    float kern[N_LEVELS][2 * MAX_R + 1];
-    int radius[N_LEVELS];
-    float kern0[2 * MAX_R + 1]; int radius0 = 0;
     struct Pend { int img_id; const uint8_t* d_bgr; int ws; hipEvent_t ev; };   // ev: recorded once the batch is enqueued (optional)
     std::vector<Pend> pend;
 };
@@ -1667,7 +1583,7 @@ void mi_sift_release(mi355_ctx* ctx) {
         if (!s) continue;
         if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
         if (s->done) (void)hipEventDestroy(s->done);
-        s->pyr.release(); s->claimed.release(); s->cand.release(); s->refined.release(); s->kps.release(); s->kresp.release(); s->sel.release(); s->counters.release(); s->rhist.release(); s->ccnt.release(); s->cube.release(); s->olist.release(); s->mins.release(); s->ksort.release();
+        s->b.release();
         delete s;
     }
     ctx->sift_slots.clear();
@@ -1758,87 +1674,28 @@ static int* pinned_slot(mi355_ctx* ctx) {
     return ctx->pinned_chunks[chunk] + off * 8;
 }
 
-static inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
-
-static int sift_prepare(mi355_ctx* ctx, SiftWork* s, int w, int h, int nb, bool keepall, int kmax) {
-    if (s->w == w && s->h == h && s->nb == nb && s->keepall == keepall && s->kmax == kmax) return MI355_OK;
+// sizes the work area for nb frames of the layout (nothing to do while the key and nb stay) and points P at frame 0
+static int sift_prepare(mi355_ctx* ctx, SiftWork* s, const Layout& lay, int nb) {
+    if (s->lay.same_key(lay) && s->nb == nb) return MI355_OK;
     MI_HIP(hipStreamSynchronize(s->stream));
-    if (s->radius0 == 0) {
-        // Gaussian kernels (double math on the host, like the oracle): sigma_i = sqrt((s k^i)^2 - (s k^(i-1))^2)
-        const double sigma = 1.6, k = std::pow(2.0, 1.0 / N_LAYERS);
-        for (int i = 1; i < N_LEVELS; i++) {
-            const double sp = std::pow(k, (double)(i - 1)) * sigma, st = sp * k;
-            s->radius[i] = gauss_kernel_host(std::sqrt(st * st - sp * sp), s->kern[i]);
-        }
-        // base level: createInitialImage(image, false, sigma) blurs with sqrtf(max(sigma^2 - 0.5^2, 0.01f)), computed in float
-        const float sd = std::sqrt(std::max((float)sigma * (float)sigma - 0.25f, 0.01f));
-        s->radius0 = gauss_kernel_host((double)sd, s->kern0);
-    }
-    // octave 0 is the image itself (no doubling in the reference's OpenCV build); nOctaves = cvRound(log2(min(w, h)) - 2)
-    int nOct = (int)lrint(std::log((double)(w < h ? w : h)) / std::log(2.0) - 2.0);
-    if (nOct > MAX_OCT) nOct = MAX_OCT;
-    size_t fl = 0, cl = 0;
-    int no = 0;
-    for (int o = 0; o < nOct; o++) {
-        const int ow = w >> o, oh = h >> o;
-        if (ow < 2 * IMG_BORDER + 2 || oh < 2 * IMG_BORDER + 2) break;          // no keypoint can exist in smaller octaves
-        fl += up64((size_t)ow * oh) * N_LEVELS;                     // every level starts on a 128-byte boundary
-        cl += (((size_t)ow * oh * 4 + 31) / 32 + 63) & ~(size_t)63;
-        no = o + 1;
-    }
-    if (no == 0) { ctx->set_error("sift: image too small"); return MI355_ERR_ARG; }
-    // capacities.  Candidates are DoG extrema with |DoG| > 20: a plateau of equal values is the worst case (every pixel a tied
-    // extremum); 3 layers x sum_o px0 / 4^o <= 4 px0 is provisioned.  Refined points / keypoints must survive the contrast test.
-    const size_t px0 = (size_t)w * h;
-    if (4 * px0 + 1024 > 0xfffffff0ull) { ctx->set_error("sift: image too large"); return MI355_ERR_ARG; }
-    s->cand_cap = (unsigned)((4 * px0 + 1024 + NREG - 1) / NREG + ((size_t)MAX_OCT * 3 * EW * EH << REG_SHIFT) + 1024);   // + one full run of tiles per octave
-    s->ref_cap = (unsigned)(px0 / 8 + 65536);
-    s->kp_cap = (unsigned)(px0 / 8 + 65536);
-    s->cube_cap = (unsigned)(px0 / 4 / NREG + 4096);
-    if (s->cube_cap > s->cand_cap) s->cube_cap = s->cand_cap;
-    s->bs.cube = (size_t)s->cube_cap * NREG * 32;
-    s->bs.pyr = fl; s->bs.claimed = cl; s->bs.cand = (size_t)s->cand_cap * NREG; s->bs.refined = s->ref_cap; s->bs.kps = s->kp_cap;
-    s->bs.sel = keepall ? (size_t)kmax : SEL_STRIDE;
-    s->ksort_stride = keepall ? (size_t)((kmax + KA_TILE - 1) / KA_TILE) * KA_TILE : 0;
-    size_t ml = 0;                                              // keep-all: one word per claim bit (4 per pixel of every octave)
-    if (keepall) for (int o = 0; o < no; o++) ml += (size_t)(w >> o) * (h >> o) * 4;
-    s->bs.mins = ml;
-    const size_t B = (size_t)nb;
-    MI_HIP(s->pyr.reserve(B * fl * sizeof(lvl_t)));
-    MI_HIP(s->claimed.reserve(B * cl * sizeof(unsigned)));
-    MI_HIP(hipMemsetAsync(s->claimed.p, 0, B * cl * sizeof(unsigned), s->stream));      // kept zero between batches (select_unclaim_kernel takes the bits back)
-    MI_HIP(s->cand.reserve(B * s->bs.cand * sizeof(unsigned long long)));
-    MI_HIP(s->refined.reserve(B * s->bs.refined * sizeof(Refined)));
-    MI_HIP(s->kps.reserve(B * s->bs.kps * sizeof(KpRec)));
-    MI_HIP(s->kresp.reserve(B * s->bs.kps * sizeof(unsigned)));
-    MI_HIP(s->sel.reserve(B * s->bs.sel * sizeof(SelRec)));
-    if (keepall) { MI_HIP(s->mins.reserve(B * ml * sizeof(unsigned))); MI_HIP(hipMemsetAsync(s->mins.p, 0xff, B * ml * sizeof(unsigned), s->stream)); }      // kept all ones between batches by keepall_reset_kernel
-    else s->mins.release();
-    if (keepall) MI_HIP(s->ksort.reserve(B * s->ksort_stride * sizeof(unsigned long long)));
-    else s->ksort.release();
-    MI_HIP(s->counters.reserve(B * CNT_STRIDE * sizeof(unsigned)));
-    MI_HIP(s->rhist.reserve(B * s->bs.refined * sizeof(unsigned)));
-    MI_HIP(s->olist.reserve(B * s->bs.refined * sizeof(unsigned)));      // |response| bits of the refined points (SoA next to `refined`)
-    MI_HIP(s->ccnt.reserve(B * CCNT_STRIDE * sizeof(unsigned)));
-    MI_HIP(s->cube.reserve(B * s->bs.cube * sizeof(float)));
+    MI_HIP(s->b.reserve(lay, nb, s->stream));
+    // with the layout's offsets and strides (multiples of 64 elements) every level, bitmap and frame copy then starts on a 128-byte boundary
+    if ((((uintptr_t)s->b.pyr.p) | ((uintptr_t)s->b.claimed.p)) & 127) { ctx->set_error("sift: work area is not 128-byte aligned"); return MI355_ERR_FAILED; }
     memset(&s->P, 0, sizeof(s->P));
-    size_t fo = 0, co = 0, mo = 0;
-    for (int o = 0; o < no; o++) {
-        const int ow = w >> o, oh = h >> o;
-        s->P.oc[o].w = ow; s->P.oc[o].h = oh;
-        for (int i = 0; i < N_LEVELS; i++) { s->P.oc[o].lv[i] = s->pyr.as<lvl_t>() + fo; fo += up64((size_t)ow * oh); }
-        s->P.claimed[o] = s->claimed.as<unsigned>() + co;
-        co += (((size_t)ow * oh * 4 + 31) / 32 + 63) & ~(size_t)63;
-        s->P.mins[o] = keepall ? s->mins.as<unsigned>() + mo : nullptr;
-        mo += (size_t)ow * oh * 4;
+    for (int o = 0; o < lay.n_oct; o++) {
+        const Octave& oc = lay.oc[o];
+        s->P.oc[o].w = oc.w; s->P.oc[o].h = oc.h;
+        for (int i = 0; i < N_LEVELS; i++) s->P.oc[o].lv[i] = s->b.pyr.as<lvl_t>() + oc.lv[i];
+        s->P.claimed[o] = s->b.claimed.as<unsigned>() + oc.claimed;
+        s->P.mins[o] = lay.keepall ? s->b.mins.as<unsigned>() + oc.mins : nullptr;
     }
-    s->P.n_oct = no; s->n_oct = no;
-    s->w = w; s->h = h; s->nb = nb; s->keepall = keepall; s->kmax = kmax;
+    s->P.n_oct = lay.n_oct;
+    s->bs = BatchStride{lay.bs.pyr, lay.bs.claimed, lay.bs.cand, lay.bs.refined, lay.bs.kps, lay.bs.cube, lay.bs.sel, lay.bs.mins};
+    s->lay = lay; s->nb = nb;
     return MI355_OK;
 }
 
-
-// Accepts one frame: it joins the current batch, which is enqueued once it holds ctx->sift_batch frames (or on a
+// Accepts one frame: it joins the current batch, which is enqueued once it holds its sift_plan::batch_frames frames (or on a
 // flush: any call that needs features, mi355_synchronize, or n_kp != NULL).  The frame memory must stay valid and
 // unchanged until then.  Returns without waiting; the keypoint count is adopted later by mi_resolve_features().
 int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w, int h, int ws, int* n_kp) {
@@ -1847,8 +1704,9 @@ int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w,
     const bool keepall = ctx->p.nfeatures <= 0;
     const int kmax = keepall ? ctx->keepall_max : 0;
     if (keepall && (w > 16384 || h > 16384)) { ctx->set_error("sift: keep-all frames are at most 16384 x 16384"); return MI355_ERR_ARG; }
-    if ((size_t)w >= (1u << 20) || (size_t)h >= (1u << 20)) { ctx->set_error("sift: image too large"); return MI355_ERR_ARG; }
-    if (w < 16 || h < 16) { ctx->set_error("sift: image too small"); return MI355_ERR_ARG; }
+    std::string refused;
+    const Layout lay = make_layout(w, h, keepall, kmax, refused);
+    if (!refused.empty()) { ctx->set_error(refused); return MI355_ERR_ARG; }
     if (ctx->sift_slots.empty()) {
         ctx->sift_slots.resize(SIFT_SLOTS_MAX, nullptr);
         MI_HIP(hipEventCreateWithFlags(&ctx->sift_in_ev, hipEventDisableTiming));
@@ -1862,20 +1720,10 @@ int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w,
     }
     SiftWork* s = ctx->sift_slots[slot];
     int rc = MI355_OK;
-    int nb = ctx->sift_batch < 1 ? 1 : (ctx->sift_batch > SIFT_BATCH_MAX ? SIFT_BATCH_MAX : ctx->sift_batch);
-    {
-        // A frame's work area is ~60 bytes per pixel (pyramid 16, worst-case candidate list 32, neighbourhood records 8, the rest 4): keep
-        // slots x batch x that under 60 % of the device memory by shortening the batch for very large frames
-        static size_t total_mem = [] { size_t fr = 0, tot = 0; return hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : (size_t)0; }();
-        const double per_frame = 60.0 * (double)w * (double)h;
-        if (total_mem) {
-            const int fit = (int)(0.6 * (double)total_mem / ((keepall ? 1.4 : 1.0) * per_frame) / (double)SIFT_SLOTS);      // keep-all: + 21 B per pixel of start keys
-            if (fit < nb) nb = fit < 1 ? 1 : fit;
-        }
-        if (keepall && nb > 8) nb = 8;
-    }
-    if (!s->pend.empty() && (s->w != w || s->h != h || s->nb != nb || s->keepall != keepall || s->kmax != kmax)) { rc = sift_run_batch(ctx, s); if (rc != MI355_OK) return rc; }   // size or ceiling change: close the batch
-    rc = sift_prepare(ctx, s, w, h, nb, keepall, kmax);
+    static const size_t total_mem = [] { size_t fr = 0, tot = 0; return hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : (size_t)0; }();
+    const int nb = batch_frames(w, h, keepall, ctx->sift_batch, SIFT_SLOTS, total_mem);
+    if (!s->pend.empty() && !(s->lay.same_key(lay) && s->nb == nb)) { rc = sift_run_batch(ctx, s); if (rc != MI355_OK) return rc; }   // size or ceiling change: close the batch
+    rc = sift_prepare(ctx, s, lay, nb);
     if (rc != MI355_OK) return rc;
     auto fit = ctx->feats.find(img_id);
     if (fit != ctx->feats.end() && fit->second.pending) { rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }   // same id re-extracted while in flight
@@ -1902,17 +1750,151 @@ int mi_sift_extract_dev(mi355_ctx* ctx, int img_id, const uint8_t* d_bgr, int w,
     return MI355_OK;
 }
 
+// one batch on its way to the device: what the steps of sift_run_batch share
+struct BatchRun {
+    mi355_ctx* ctx; SiftWork* s; hipStream_t st;
+    std::vector<SiftWork::Pend> pend;        // the batch's n frames
+    std::vector<Features*> fs;
+    int n;
+    unsigned* cnt;                           // per frame: [0] candidates [1] refined [2] keypoints [3] n_sel [4] overflow [8,9] ctrl
+    FrameOuts outs;
+    int enqueue_pyramid();
+    void enqueue_keypoints();
+    int publish_batch();
+};
+
+// the pyramid and the extrema test, octave by octave: sift_plan decides the launches, this fills in the pointers
+int BatchRun::enqueue_pyramid() {
+    const PyramidTaps& taps = pyramid_taps();
+    Routes routes = {ctx->blur_stream, ctx->xstream_min_w, ctx->xstream_min_frames, true};
+    for (const SiftWork::Pend& p : pend) routes.base_frames_aligned = routes.base_frames_aligned && ((uintptr_t)p.d_bgr & 3) == 0 && (p.ws & 3) == 0 && p.ws >= 3 * s->lay.w;
+    for (const Launch& L : pyramid_launches(s->lay, n, routes)) {
+        const OctaveDev& oc = s->P.oc[L.octave];
+        const dim3 grid(L.gx, L.gy, L.gz), block(256);
+        switch (L.kind) {
+            case BLUR_STREAM: case BLUR_TILE: {
+                const bool base = L.level == 0;       // straight from the caller's frames: gray x 48 formed on the fly
+                const Taps& t = base ? taps.base : taps.lv[L.level];
+                Blur16Args a; memset(&a, 0, sizeof(a));
+                a.w = oc.w; a.h = oc.h; a.tiles_x = (oc.w + T16W - 1) / T16W; a.tiles_y = (oc.h + T16H - 1) / T16H;
+                a.fstride = s->bs.pyr; a.nb = n;
+                if (base) for (int k = 0; k < n; k++) { a.bgr[k] = pend[k].d_bgr; a.bgr_ws[k] = pend[k].ws; }
+                else a.src = oc.lv[L.level - 1];
+                a.dst = oc.lv[L.level];
+                if (L.ds) a.ds = s->P.oc[L.octave + 1].lv[0];
+                memcpy(a.k, t.k, sizeof(float) * (2 * t.r + 1));
+                const BlurFn k = base ? blur_kernel<true>(L) : blur_kernel<false>(L);
+                if (!k.stream && !k.tile) { ctx->set_error("sift: unsupported kernel radius"); return MI355_ERR_FAILED; }
+                ProfScope ps(ctx, k.stream ? "gauss_stream" : "gauss", L.bytes, st);
+                if (k.stream) {
+                    for (int i = 0; i <= t.r; i++) { a.kp[2 * i] = a.k[i]; a.kp[2 * i + 1] = i ? a.k[i - 1] : 0.0f; }
+                    hipLaunchKernelGGL(k.stream, grid, block, 0, st, a, L.L, L.nstrip, L.nseg);
+                } else hipLaunchKernelGGL(k.tile, grid, block, 0, st, a);
+                break;
+            }
+            case DOWNSAMPLE: {
+                const OctaveDev& pv = s->P.oc[L.octave - 1];
+                ProfScope ps(ctx, "downsample", L.bytes, st);
+                hipLaunchKernelGGL(downsample16, grid, block, 0, st, pv.lv[N_LAYERS], pv.w, oc.lv[0], oc.w, oc.h, s->bs.pyr);
+                break;
+            }
+            case EXTREMA_STREAM: case EXTREMA_TILE: {
+                ProfScope ps(ctx, "extrema", L.bytes, st);
+                const SiftBufs& d = s->b;
+                if (L.kind == EXTREMA_STREAM) hipLaunchKernelGGL(extrema_stream, grid, block, 0, st, oc, L.octave, d.cand.as<unsigned long long>(), d.ccnt.as<unsigned>(), s->lay.cand_cap, cnt + 4, s->bs,
+                                                                 d.cube.as<float>(), s->lay.cube_cap, L.L, L.nstrip, L.nseg, n, L.xsw);
+                else hipLaunchKernelGGL(extrema_kernel, grid, block, 0, st, oc, L.octave, d.cand.as<unsigned long long>(), d.ccnt.as<unsigned>(), s->lay.cand_cap, cnt + 4, s->bs, d.cube.as<float>(), s->lay.cube_cap);
+                break;
+            }
+        }
+    }
+    return MI355_OK;
+}
+
+// the keypoint stages of all n frames, one launch each
+void BatchRun::enqueue_keypoints() {
+    const SiftBufs& d = s->b;
+    const Layout& lay = s->lay;
+    const BatchStride bs = s->bs;
+    const unsigned kmax = (unsigned)lay.kmax;
+    {
+        ProfScope ps(ctx, "refine", 0.0, st);
+        hipLaunchKernelGGL(refine_kernel, dim3(REFINE_GX, NREG, n), dim3(256), 0, st, s->P, d.cand.as<unsigned long long>(), d.ccnt.as<unsigned>(), lay.cand_cap, cnt + 0,
+                           ctx->p.contrast_threshold, ctx->p.edge_threshold, 1.6f, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, d.rhist.as<unsigned>(), bs, d.cube.as<float>(), lay.cube_cap);
+    }
+    {
+        // keep-all: every refined point that holds its location's smallest start key is oriented; top-k: those above the response threshold of nfeatures + 256
+        ProfScope ps(ctx, "kp_select", 0.0, st);
+        if (lay.keepall) {
+            hipLaunchKernelGGL(keepall_live_kernel, dim3(256, n), dim3(256), 0, st, s->P, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, cnt + 8, d.olist.as<unsigned>(), bs);
+            hipLaunchKernelGGL(keepall_reset_kernel, dim3(256, n), dim3(256), 0, st, s->P, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, bs);
+        } else {
+            hipLaunchKernelGGL(select_unclaim_kernel, dim3(1 + UNCLAIM_WGS, n), dim3(1024), 0, st, s->P, d.refined.as<Refined>(), bs, d.rhist.as<unsigned>(), cnt + 1, lay.ref_cap,
+                               (unsigned)ctx->p.nfeatures + 256u, cnt + 8, bs.refined, d.olist.as<unsigned>());
+        }
+    }
+    // top-k: pass 1 (everything below the response threshold) exits at once unless top-k asked for it; keep-all: one pass, the keypoints leave in generation order
+    for (int pass = 0; pass < (lay.keepall ? 1 : 2); pass++) {
+        {
+            ProfScope ps(ctx, "orient", 0.0, st);
+            hipLaunchKernelGGL(orient_kernel, dim3(ctx->num_cu * 4, n), dim3(256), 0, st, s->P, d.refined.as<Refined>(), cnt + 1, lay.ref_cap,
+                               d.kps.as<KpRec>(), d.kresp.as<unsigned>(), cnt + 2, lay.kp_cap, cnt + 8, pass, bs, d.olist.as<unsigned>());
+        }
+        ProfScope ps(ctx, "topk", 0.0, st);
+        if (lay.keepall) {
+            hipLaunchKernelGGL(keepall_sort_tiles_kernel, dim3((kmax + KA_TILE - 1) / KA_TILE, n), dim3(1024), 0, st, d.kps.as<KpRec>(), cnt + 2, lay.kp_cap, kmax,
+                               d.ksort.as<unsigned long long>(), lay.ksort_stride, outs, d.sel.as<SelRec>(), bs);
+            hipLaunchKernelGGL(keepall_place_kernel, dim3((kmax + 255) / 256, n), dim3(256), 0, st, d.kps.as<KpRec>(), cnt + 2, lay.kp_cap, kmax,
+                               d.ksort.as<const unsigned long long>(), lay.ksort_stride, outs, d.sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
+        } else {
+            hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), 0, st, d.kps.as<KpRec>(), d.kresp.as<unsigned>(), cnt + 2, lay.kp_cap, ctx->p.nfeatures,
+                               outs, d.sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), cnt + 8, pass, bs);
+        }
+    }
+    ProfScope ps(ctx, "describe", 0.0, st);
+    hipLaunchKernelGGL(describe_kernel, dim3(((int)bs.sel + 3) / 4, n), dim3(256), 0, st, s->P, d.sel.as<SelRec>(), reinterpret_cast<const int*>(cnt + 3), outs, bs);
+}
+
+// hands the batch's results over: the matcher's operands, the counters into pinned slots, and the events that say so
+int BatchRun::publish_batch() {
+    const Layout& lay = s->lay;
+    // the matcher's operands of all n frames in one launch, their counters in one strided copy (n launches + n copies of ~5 us each kept
+    // the batch's stream, and a pipeline slot, busy for 0.3 ms per batch of 32)
+    { int rc = mi_finish_features_batch(ctx, fs.data(), n, reinterpret_cast<const int*>(cnt + 3), (int)CNT_STRIDE, st, lay.keepall ? lay.kmax : 2048); if (rc != MI355_OK) return rc; }
+    if (ctx->pinned_used % PINNED_CHUNK + (size_t)n > PINNED_CHUNK) ctx->pinned_used += PINNED_CHUNK - ctx->pinned_used % PINNED_CHUNK;   // n slots in one chunk
+    int* h0 = nullptr;
+    for (int k = 0; k < n; k++) {
+        int* hc = pinned_slot(ctx);
+        if (!hc) { ctx->set_error("sift: pinned alloc failed"); return MI355_ERR_NOMEM; }
+        if (k == 0) h0 = hc;
+        Features& f = *fs[k];
+        f.h_cnt = hc; f.pending = true; f.n = 0;
+        f.caps[0] = 0xffffffffu; f.caps[1] = lay.ref_cap; f.caps[2] = lay.kp_cap;      // candidate overflow is flagged by the kernel (cnt[4])
+        f.kp_limit = lay.keepall ? lay.kmax : 0;
+    }
+    MI_HIP(hipMemcpy2DAsync(h0, 8 * sizeof(int), cnt, CNT_STRIDE * sizeof(unsigned), 8 * sizeof(unsigned), (size_t)n, hipMemcpyDeviceToHost, st));
+    MI_HIP(hipEventRecord(s->done, st));
+    // the batch's own event: mi_resolve_features_of() waits for it, not for the streams
+    if (ctx->batch_events_used >= ctx->batch_events.size()) {
+        hipEvent_t e = nullptr;
+        MI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->batch_events.push_back(e);
+    }
+    hipEvent_t e = ctx->batch_events[ctx->batch_events_used++];
+    MI_HIP(hipEventRecord(e, st));
+    for (int k = 0; k < n; k++) fs[k]->ready = e;
+    for (int k = 0; k < n; k++) if (pend[k].ev) MI_HIP(hipEventRecord(pend[k].ev, st));
+    return MI355_OK;
+}
+
 static int sift_run_batch(mi355_ctx* ctx, SiftWork* s) {
-    std::vector<SiftWork::Pend> pend;
-    pend.swap(s->pend);
-    const int n = (int)pend.size();
+    BatchRun b = {};
+    b.ctx = ctx; b.s = s;
+    b.pend.swap(s->pend);
+    const int n = b.n = (int)b.pend.size();
     if (n == 0) return MI355_OK;
     ctx->sift_next = (ctx->sift_next + 1) % SIFT_SLOTS;     // the next batch collects in the next work area
-    const hipStream_t st = s->stream;
-    const hipStream_t tt = st;                        // (the keypoint stages; on a stream of their own, at a lower queue priority or on CUs of their own they only lose: profiles/r05_pipeline_layouts.txt)
-    const int w = s->w, h = s->h;
-    const int nf = ctx->p.nfeatures;
-    const BatchStride bs = s->bs;
+    const hipStream_t st = b.st = s->stream;
     // the frames were produced on the caller's stream
     MI_HIP(hipEventRecord(ctx->sift_in_ev, ctx->stream));
     MI_HIP(hipStreamWaitEvent(st, ctx->sift_in_ev, 0));
@@ -1920,173 +1902,22 @@ static int sift_run_batch(mi355_ctx* ctx, SiftWork* s) {
     // after a wait takes the end of the stream's last command as its time, which would put the waiting into the first bracket
     const bool serial_heavy = ctx->serial_heavy != 0;
     if (serial_heavy && ctx->heavy_ev_valid) MI_HIP(hipStreamWaitEvent(st, ctx->heavy_ev, 0));
-    unsigned* cnt = s->counters.as<unsigned>();      // per frame: [0] candidates [1] refined [2] keypoints [3] n_sel [4] overflow [8,9] ctrl
-    MI_HIP(hipMemsetAsync(cnt, 0, (size_t)n * CNT_STRIDE * sizeof(unsigned), st));
-    MI_HIP(hipMemsetAsync(s->ccnt.p, 0, (size_t)n * CCNT_STRIDE * sizeof(unsigned), st));
-    FrameOuts outs;
-    memset(&outs, 0, sizeof(outs));
-    std::vector<Features*> fs(n);
+    b.cnt = s->b.counters.as<unsigned>();
+    MI_HIP(hipMemsetAsync(b.cnt, 0, (size_t)n * CNT_STRIDE * sizeof(unsigned), st));
+    MI_HIP(hipMemsetAsync(s->b.ccnt.p, 0, (size_t)n * CCNT_STRIDE * sizeof(unsigned), st));
     for (int k = 0; k < n; k++) {
-        fs[k] = &ctx->feats[pend[k].img_id];
-        outs.kp[k] = fs[k]->kp.as<mi355_keypoint>(); outs.d8[k] = fs[k]->d8.as<uint8_t>();
+        Features* f = &ctx->feats[b.pend[k].img_id];
+        b.fs.push_back(f);
+        b.outs.kp[k] = f->kp.as<mi355_keypoint>(); b.outs.d8[k] = f->d8.as<uint8_t>();
     }
-    auto blur_args = [&](const OctaveDev& oc) {
-        Blur16Args a; memset(&a, 0, sizeof(a));
-        a.w = oc.w; a.h = oc.h; a.tiles_x = (oc.w + T16W - 1) / T16W; a.tiles_y = (oc.h + T16H - 1) / T16H;
-        a.fstride = bs.pyr; a.nb = n;
-        return a;
-    };
-    // ---- phases 1+2: the pyramid, octave by octave, every launch covering all n frames of the batch ----
-    bool ds_fused = false;
-    for (int o = 0; o < s->n_oct; o++) {
-        const OctaveDev& oc = s->P.oc[o];
-        const double level_bytes = (double)oc.w * oc.h * sizeof(lvl_t) * n;
-        if (o == 0) {
-            // base level straight from the caller's frames: gray x 48 formed on the fly, blurred with sqrt(1.6^2 - 0.5^2)
-            Blur16Args a = blur_args(oc);
-            for (int k = 0; k < n; k++) { a.bgr[k] = pend[k].d_bgr; a.bgr_ws[k] = pend[k].ws; }
-            a.dst = oc.lv[0];
-            memcpy(a.k, s->kern0, sizeof(float) * (2 * s->radius0 + 1));
-            const bool streams = blur_streams(a, true, s->radius0, ctx->blur_stream);
-            ProfScope ps(ctx, streams ? "gauss_stream" : "gauss", level_bytes + (double)w * h * 3.0 * n, st);      // read the u8 frames, write level 0
-            if (!launch_blur<true>(st, s->radius0, a, ctx->blur_stream)) { ctx->set_error("sift: unsupported kernel radius"); return MI355_ERR_FAILED; }
-        } else if (!ds_fused) {
-            const OctaveDev& pv = s->P.oc[o - 1];
-            ProfScope ps(ctx, "downsample", level_bytes * 2.0, st);
-            hipLaunchKernelGGL(downsample16, dim3((oc.w + 63) / 64, (oc.h + 3) / 4, n), dim3(256), 0, st, pv.lv[N_LAYERS], pv.w, oc.lv[0], oc.w, oc.h, bs.pyr);
-        }
-        ds_fused = false;
-        for (int i = 1; i < N_LEVELS; i++) {
-            Blur16Args a = blur_args(oc);
-            a.src = oc.lv[i - 1]; a.dst = oc.lv[i];
-            memcpy(a.k, s->kern[i], sizeof(float) * (2 * s->radius[i] + 1));
-            // the level that seeds the next octave writes its decimation on the way out (saves re-reading it)
-            if (i == N_LAYERS && o + 1 < s->n_oct && (oc.w & 3) == 0 && (s->P.oc[o + 1].w == (oc.w >> 1)) && (s->P.oc[o + 1].h == (oc.h >> 1))) {
-                a.ds = s->P.oc[o + 1].lv[0]; ds_fused = true;
-                if (!blur_streams(a, false, s->radius[i], ctx->blur_stream)) {         // (odd height, unusual radius:) rather stream without the copy
-                    Blur16Args b = a; b.ds = nullptr;
-                    if (blur_streams(b, false, s->radius[i], ctx->blur_stream)) { a.ds = nullptr; ds_fused = false; }
-                }
-            }
-            const bool streams = blur_streams(a, false, s->radius[i], ctx->blur_stream);
-            ProfScope ps(ctx, streams ? "gauss_stream" : "gauss", level_bytes * 2.0, st);   // one read + one write of the level
-            if (!launch_blur<false>(st, s->radius[i], a, ctx->blur_stream)) { ctx->set_error("sift: unsupported kernel radius"); return MI355_ERR_FAILED; }
-        }
-        {
-            ProfScope ps(ctx, "extrema", level_bytes * 6.0, st);
-            // the streamed test pays off on the big octaves of a full batch; smaller launches do not keep enough rows in flight and stay with the tiled kernel
-            const bool xs = ctx->blur_stream && (oc.w & 3) == 0 && oc.w >= ctx->xstream_min_w && oc.h >= ctx->xstream_min_w * 3 / 4 && n >= ctx->xstream_min_frames;
-            if (xs) {
-                // no row halo to amortise here (3 + XD rows to prime a segment): many short segments balance the wave slots
-                const int nstrip = (oc.w + XSW - 1) / XSW;
-                const int xsw = ((oc.w + nstrip - 1) / nstrip + 3) & ~3;      // equal strips (<= 248 columns) instead of a nearly empty last one
-                // whole rounds of the 1024 x XWAVES wave slots: the largest k <= 2 whose segments stay >= 64 rows
-                int nseg = 1, L = oc.h;
-                for (int k = 2; k >= 1; k--) {
-                    const int ns = (1024 * XWAVES * k) / (nstrip * n);
-                    if (ns < 1) continue;
-                    const int l = (oc.h + ns - 1) / ns;
-                    if (l >= 64 || k == 1) { L = l < 64 ? 64 : l; break; }
-                }
-                nseg = (oc.h + L - 1) / L;
-                hipLaunchKernelGGL(extrema_stream, dim3((nstrip * nseg * n + 3) / 4), dim3(256), 0, st,
-                                   oc, o, s->cand.as<unsigned long long>(), s->ccnt.as<unsigned>(), s->cand_cap, cnt + 4, bs, s->cube.as<float>(), s->cube_cap, L, nstrip, nseg, n, xsw);
-            } else {
-                hipLaunchKernelGGL(extrema_kernel, dim3(((oc.w + EW - 1) / EW) * ((oc.h + EH - 1) / EH), n), dim3(256), 0, st,
-                                   oc, o, s->cand.as<unsigned long long>(), s->ccnt.as<unsigned>(), s->cand_cap, cnt + 4, bs, s->cube.as<float>(), s->cube_cap);
-            }
-        }
-    }
+    { const int rc = b.enqueue_pyramid(); if (rc != MI355_OK) return rc; }
     if (serial_heavy) {
         if (!ctx->heavy_ev) MI_HIP(hipEventCreateWithFlags(&ctx->heavy_ev, hipEventDisableTiming));
         MI_HIP(hipEventRecord(ctx->heavy_ev, st)); ctx->heavy_ev_valid = true;
     }
-    // ---- phase 3: keypoint stages of all n frames ----
-    {
-        ProfScope ps(ctx, "refine", 0.0, tt);
-        static const int refine_gx = [] { const char* e = getenv("MI355_REFINE_GX"); return e ? atoi(e) : 2; }();      // workgroups per candidate region: 32 x 64 regions x frames of mostly empty workgroups cost more to dispatch than the fits
-        hipLaunchKernelGGL(refine_kernel, dim3(refine_gx, NREG, n), dim3(256), 0, tt, s->P, s->cand.as<unsigned long long>(), s->ccnt.as<unsigned>(), s->cand_cap, cnt + 0,
-                           ctx->p.contrast_threshold, ctx->p.edge_threshold, 1.6f, s->refined.as<Refined>(), cnt + 1, s->ref_cap, s->rhist.as<unsigned>(), bs, s->cube.as<float>(), s->cube_cap);
-    }
-    if (s->keepall) {
-        // keep-all: every refined point that holds its location's smallest start key is oriented; the keypoints leave in generation order
-        {
-            ProfScope ps(ctx, "kp_select", 0.0, tt);
-            hipLaunchKernelGGL(keepall_live_kernel, dim3(256, n), dim3(256), 0, tt, s->P, s->refined.as<Refined>(), cnt + 1, s->ref_cap, cnt + 8, s->olist.as<unsigned>(), bs);
-            hipLaunchKernelGGL(keepall_reset_kernel, dim3(256, n), dim3(256), 0, tt, s->P, s->refined.as<Refined>(), cnt + 1, s->ref_cap, bs);
-        }
-        {
-            ProfScope ps(ctx, "orient", 0.0, tt);
-            hipLaunchKernelGGL(orient_kernel, dim3(ctx->num_cu * 4, n), dim3(256), 0, tt, s->P, s->refined.as<Refined>(), cnt + 1, s->ref_cap,
-                               s->kps.as<KpRec>(), s->kresp.as<unsigned>(), cnt + 2, s->kp_cap, cnt + 8, 0, bs, s->olist.as<unsigned>());
-        }
-        {
-            ProfScope ps(ctx, "topk", 0.0, tt);
-            const unsigned kmax = (unsigned)s->kmax;
-            if (ctx->keepall_order == 1) {
-                hipLaunchKernelGGL(keepall_output_kernel, dim3((kmax + 255) / 256, n), dim3(256), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax, outs, s->sel.as<SelRec>(),
-                                   reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
-            } else {
-                hipLaunchKernelGGL(keepall_sort_tiles_kernel, dim3((kmax + KA_TILE - 1) / KA_TILE, n), dim3(1024), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax,
-                                   s->ksort.as<unsigned long long>(), s->ksort_stride, outs, s->sel.as<SelRec>(), bs);
-                hipLaunchKernelGGL(keepall_place_kernel, dim3((kmax + 255) / 256, n), dim3(256), 0, tt, s->kps.as<KpRec>(), cnt + 2, s->kp_cap, kmax,
-                                   s->ksort.as<const unsigned long long>(), s->ksort_stride, outs, s->sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
-            }
-        }
-    } else {
-    {
-        ProfScope ps(ctx, "kp_select", 0.0, tt);
-        hipLaunchKernelGGL(select_unclaim_kernel, dim3(1 + UNCLAIM_WGS, n), dim3(1024), 0, tt, s->P, s->refined.as<Refined>(), bs, s->rhist.as<unsigned>(), cnt + 1, s->ref_cap, (unsigned)nf + 256u, cnt + 8,
-                           bs.refined, s->olist.as<unsigned>());
-    }
-    for (int pass = 0; pass < 2; pass++) {       // pass 1 (everything below the response threshold) exits at once unless top-k asked for it
-        {
-            ProfScope ps(ctx, "orient", 0.0, tt);
-            hipLaunchKernelGGL(orient_kernel, dim3(ctx->num_cu * 4, n), dim3(256), 0, tt, s->P, s->refined.as<Refined>(), cnt + 1, s->ref_cap,
-                               s->kps.as<KpRec>(), s->kresp.as<unsigned>(), cnt + 2, s->kp_cap, cnt + 8, pass, bs, s->olist.as<unsigned>());
-        }
-        {
-            ProfScope ps(ctx, "topk", 0.0, tt);
-            hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), 0, tt, s->kps.as<KpRec>(), s->kresp.as<unsigned>(), cnt + 2, s->kp_cap, nf,
-                               outs, s->sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), cnt + 8, pass, bs);
-        }
-    }
-    }
-    {
-        ProfScope ps(ctx, "describe", 0.0, tt);
-        hipLaunchKernelGGL(describe_kernel, dim3(((int)bs.sel + 3) / 4, n), dim3(256), 0, tt, s->P, s->sel.as<SelRec>(), reinterpret_cast<const int*>(cnt + 3), outs, bs);
-    }
+    b.enqueue_keypoints();
     MI_HIP(hipGetLastError());
-    // the matcher's operands of all n frames in one launch, their counters in one strided copy (n launches + n copies of ~5 us each kept
-    // the batch's stream, and a pipeline slot, busy for 0.3 ms per batch of 32)
-    { int rc = mi_finish_features_batch(ctx, fs.data(), n, reinterpret_cast<const int*>(cnt + 3), (int)CNT_STRIDE, tt, s->keepall ? s->kmax : 2048); if (rc != MI355_OK) return rc; }
-    {
-        if (ctx->pinned_used % PINNED_CHUNK + (size_t)n > PINNED_CHUNK) ctx->pinned_used += PINNED_CHUNK - ctx->pinned_used % PINNED_CHUNK;   // n slots in one chunk
-        int* h0 = nullptr;
-        for (int k = 0; k < n; k++) {
-            int* hc = pinned_slot(ctx);
-            if (!hc) { ctx->set_error("sift: pinned alloc failed"); return MI355_ERR_NOMEM; }
-            if (k == 0) h0 = hc;
-            Features& f = *fs[k];
-            f.h_cnt = hc; f.pending = true; f.n = 0;
-            f.caps[0] = 0xffffffffu; f.caps[1] = s->ref_cap; f.caps[2] = s->kp_cap;      // candidate overflow is flagged by the kernel (cnt[4])
-            f.kp_limit = s->keepall ? s->kmax : 0;
-        }
-        MI_HIP(hipMemcpy2DAsync(h0, 8 * sizeof(int), cnt, CNT_STRIDE * sizeof(unsigned), 8 * sizeof(unsigned), (size_t)n, hipMemcpyDeviceToHost, tt));
-    }
-    MI_HIP(hipEventRecord(s->done, tt));
-    {                                                       // the batch's own event: mi_resolve_features_of() waits for it, not for the streams
-        if (ctx->batch_events_used >= ctx->batch_events.size()) {
-            hipEvent_t e = nullptr;
-            MI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->batch_events.push_back(e);
-        }
-        hipEvent_t e = ctx->batch_events[ctx->batch_events_used++];
-        MI_HIP(hipEventRecord(e, tt));
-        for (int k = 0; k < n; k++) fs[k]->ready = e;
-    }
-    for (int k = 0; k < n; k++) if (pend[k].ev) MI_HIP(hipEventRecord(pend[k].ev, tt));
-    return MI355_OK;
+    return b.publish_batch();
 }
 
 // a frame parked with event `ev` still waits for its batch to fill: enqueue that batch now (the event gets recorded)

@@ -99,20 +99,20 @@ const char* mi355_last_error(mi355_ctx* ctx);          /* ctx may be NULL: last 
 /* Run on a caller-provided hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = ctx-owned stream. */
 int  mi355_set_stream(mi355_ctx* ctx, void* hip_stream);
 int  mi355_synchronize(mi355_ctx* ctx);
-/* Tunables: "sift_batch" = frames per detect+describe batch (1..8, default 8): frames handed to mi355_sift_extract_dev
- * collect until the batch is full (or until a call needs their features) and are then enqueued together, the small
- * pyramid octaves and the keypoint stages of all frames of the batch in one launch each; "sift_slots" = batch work areas
- * that may be in flight at once, each on its own stream (1..4, default 3; a work area holds sift_batch pyramids and
- * candidate lists, 3.2 GB per frame at 4000x3000); "blur_stream" = 1 (default) runs pyramid levels of >= 2048x1536
- * through the barrier-free streaming Gaussian, 0 forces the tiled kernels everywhere (same bits either way);
- * "xstream_min_w" (3000) / "xstream_min_frames" (4): octaves at least that wide, in batches of at least that many frames,
- * take the streamed extrema kernel instead of the tiled one (same candidates either way); "serial_heavy" = 1 (measurement only,
- * default 0): the pyramid + extrema phase of a batch waits for the previous batch's, so that the chip-filling kernels of different
- * batches never overlap and their event-bracketed durations are exclusive (the whole job loses ~10 %); "sift_cascade" (0..3,
- * default 3): how octaves of at least 2000 x 1500 compute their Gaussian levels -- 0: every level with its own launch; 3: the
- * first three levels in one pass, handed from wave to wave through LDS and written to HBM once, the other levels on their own
- * (+4 % end to end); 2: the other three in a second such pass; 1: all six in one pass.  The same bits in every mode (2 and 1 are
- * VALU-issue-bound and no faster end to end on MI355X); "profile_every:<class>" = n (measurement only, default 1): with
+/* Tunables: "sift_batch" = frames per detect+describe batch (1..32, default 16): frames handed to mi355_sift_extract_dev
+ * collect until the batch is full (or until a call needs their features) and are then enqueued together, every pyramid
+ * level and every keypoint stage of all frames of the batch in one launch each; batches of very large frames are shortened
+ * so that the work areas stay under 60 % of the device memory, keep-all batches (nfeatures <= 0) hold at most 8;
+ * "sift_slots" = batch work areas that may be in flight at once, each on its own stream (1..4, default 3; a work area
+ * holds the pyramids and candidate lists of one batch); "blur_stream" = 1 (default) runs pyramid levels of at least 512
+ * columns and 64 rows whose width is a multiple of 4 (with a last 256-column strip that is full or wider than 16) through the barrier-free streaming Gaussian and lets big octaves
+ * take the streamed extrema kernel, 0 forces the tiled kernels everywhere (same bits either way);
+ * "xstream_min_w" (>= 256, default 1500) / "xstream_min_frames" (>= 1, default 4): octaves at least that wide and 3/4 as
+ * high, in batches of at least that many frames, take the streamed extrema kernel instead of the tiled one (same candidates
+ * either way); "serial_heavy" = 1 (measurement only, default 0): the pyramid + extrema phase of a batch waits for the previous
+ * batch's, so that the chip-filling kernels of different batches never overlap and their event-bracketed durations are
+ * exclusive (the whole job loses ~10 %); "sift_cascade" and "keepall_order" are accepted and ignored (the kernels they chose
+ * between are gone); "profile_every:<class>" = n (measurement only, default 1): with
  * mi355_profile_enable only every n-th launch of that kernel class is bracketed by events (the average duration is then a sample);
  * "keep_frames" = 1 (default 0): host-frame extractions keep their HBM copy (see mi355_get_frame_dev); "download_chunk_mb" (default 64):
  * bytes per chunk, in MB, of the _into calls' canvas download; "download_threads" (1..16, default 4): host threads that copy a downloaded
@@ -123,8 +123,7 @@ int  mi355_synchronize(mi355_ctx* ctx);
  * more rows; resolves pending extractions first; any other value, or one below the keypoint count of a resident image (named in the
  * error), returns MI355_ERR_ARG and leaves the ceiling as it was.  Every rank of a multi-GPU run sets the same value: a rank whose ceiling
  * is below a frame it receives fails its install (MI355_ERR_ARG, its features unchanged) while the other ranks return normally;
- * "keepall_order" (measurement only, default 0): 1 orders keep-all keypoints by the brute-force rank count instead of the tile sort (the
- * same bytes); "big_subpairs_max" (debug, default 65536): sub-pairs of <= 2048 x 2048 per run of the matcher's large-pair path (the same
+ * "big_subpairs_max" (debug, default 65536): sub-pairs of <= 2048 x 2048 per run of the matcher's large-pair path (the same
  * results at any value >= 1). */
 int  mi355_set_option(mi355_ctx* ctx, const char* name, int value);
 void mi355_free(void* p);                               /* frees host buffers returned by this library */

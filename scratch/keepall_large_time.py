@@ -1,6 +1,6 @@
 """Keep-all SIFT (nfeatures = 0) on the 4000x3000 survey frames and on the reference's 1000x750 frames, on one MI355X: the keypoint counts
-(mi355_last_sift_counters), the per-frame times of the keep-all stages (event brackets: kp_select, orient, topk = the ordering, describe),
-the tile-sort ordering against the brute-force rank count (option "keepall_order" = 1), the describe grid's empty workgroups (the same
+(mi355_last_sift_counters), the per-frame times of the keep-all stages (event brackets: kp_select, orient, topk = the tile-sort ordering, describe), the describe
+grid's empty workgroups (the same
 2 900-keypoint frame under keepall_max 32768 and 262144) and one 80 000-class pair through the matcher ("match", "select" brackets).
 
     python scratch/keepall_large_time.py [--frames 4] [--reps 3] [--out profiles/keepall_large_time.json]
@@ -31,9 +31,8 @@ def keepall_ctx(im, kmax):
     return ctx
 
 
-def stage_times(ctx, extract, n_frames, reps, order):
+def stage_times(ctx, extract, n_frames, reps):
     """ms per frame of every bracketed class, median over reps of one batch of n_frames"""
-    ctx.set_option("keepall_order", order)
     extract()                                         # warm-up (work areas)
     ctx.synchronize()
     per = {c: [] for c in CLASSES}
@@ -76,7 +75,7 @@ def main():
         out["default_ctx"] = {"error": str(e)}
     out["default_ctx"]["counters"] = ctx.last_sift_counters()
     ctx.close()
-    # 2. the survey frames under the largest ceiling: counts, stage times, sort against brute force (same bytes)
+    # 2. the survey frames under the largest ceiling: counts, stage times
     ctx = keepall_ctx(im, 262144)
     counts = []
     for k in range(a.frames):
@@ -90,13 +89,7 @@ def main():
             ctx.SiftExtractDev(k, fr[k].data_ptr(), w, h, ws)
         ctx.set_option("sift_flush", 1)
 
-    feats = {}
-    for order, name in ((0, "sort"), (1, "brute_force")):
-        out[f"survey_stage_ms_{name}"] = stage_times(ctx, survey, a.frames, a.reps, order)
-        feats[name] = [ctx.GetFeatures(k, max_kp=262144) for k in range(a.frames)]
-    out["survey_sort_equals_brute_force"] = all(np.array_equal(x[0].view(np.uint8), y[0].view(np.uint8)) and np.array_equal(x[1], y[1])
-                                                for x, y in zip(feats["sort"], feats["brute_force"]))
-    ctx.set_option("keepall_order", 0)
+    out["survey_stage_ms_sort"] = stage_times(ctx, survey, a.frames, a.reps)
     # 3. one 80 000-class pair (two overlapping survey frames) through the matcher
     ctx.MatchPairs([(0, 1)], 2.5, 3)                  # warm-up
     ctx.profile_enable(True)
@@ -111,7 +104,7 @@ def main():
     ctx.close()
     del fr
     torch.cuda.empty_cache()
-    # 4. the reference's frames (about 2 900 keypoints): sort against brute force, and the describe grid at two ceilings
+    # 4. the reference's frames (about 2 900 keypoints): the describe grid at two ceilings
     gold = os.path.join(ROOT, "tests", "golden")
     names = ["DSC%05d.JPG" % k for k in range(4, 4 + a.frames)]
     imgs = [np.ascontiguousarray(np.array(Image.open(os.path.join(gold, n)).convert("RGB"))[:, :, ::-1]) for n in names]
@@ -124,10 +117,7 @@ def main():
                 ctx.SiftExtractDev(k, d.data_ptr(), d.shape[1], d.shape[0], d.stride(0))
             ctx.set_option("sift_flush", 1)
 
-        for order, name in ((0, "sort"), (1, "brute_force")):
-            if kmax != 32768 and order == 1:
-                continue
-            out[f"reference_stage_ms_{name}_keepall_max_{kmax}"] = stage_times(ctx, ref, a.frames, a.reps, order)
+        out[f"reference_stage_ms_sort_keepall_max_{kmax}"] = stage_times(ctx, ref, a.frames, a.reps)
         out.setdefault("reference_keypoints", [len(ctx.GetFeatures(k, max_kp=kmax)[0]) for k in range(a.frames)])
         ctx.close()
     s = json.dumps(out, indent=1)

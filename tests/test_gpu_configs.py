@@ -62,7 +62,7 @@ def test_c3_default_route_12mp():
     from tests import oracle_lib as ol
     from tests.synth_survey import render_frames, host_image
     orc = ol.load_oracle_fast()
-    ctx = im.Context(0)                     # library defaults: sift_batch 16, sift_slots 3, xstream_min_w 3000, xstream_min_frames 4
+    ctx = im.Context(0)                     # library defaults: sift_batch 16, sift_slots 3, xstream_min_w 1500, xstream_min_frames 4
     w, h, F = 4000, 3000, 20
     frames, A, gains, ws = render_frames(ctx, torch, F, w, h)
     for k in range(F):

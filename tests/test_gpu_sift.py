@@ -156,6 +156,40 @@ def test_sift_streamed_extrema(ctx, oracle):
     c.close()
 
 
+def test_sift_launch_routes_follow_the_plan(ctx):
+    """launches per profile class of one device batch of four frames (csrc/sift_plan.cpp decides them; a wrong route gives the same
+    features more slowly).  1100x780 has seven octaves: octave 0 streams its six blurs, levels 3 of octaves 0 and 4 write the next
+    octave's base (6 / 30 / 4 / 7 launches of gauss_stream / gauss / downsample / extrema, counted on the host code the plan
+    replaced); the streamed extrema route moves inside its class; 320x240 stays on the tile kernels with every base fused
+    (0 / 26 / 0 / 5).  Features equal the single-frame extraction."""
+    import torch
+    import imagemosaicing_amd as im
+    from tests.synth_frames import terrain
+    big = [terrain(1100, 780, seed=60 + k) for k in range(4)]
+    small = [terrain(320, 240, seed=64 + k) for k in range(4)]
+    for tag, imgs, opts, want in [("1100x780", big, {}, (6, 30, 4, 7)),
+                                  ("1100x780 streamed extrema", big, {"xstream_min_w": 1000, "xstream_min_frames": 1}, (6, 30, 4, 7)),
+                                  ("320x240", small, {}, (0, 26, 0, 5))]:
+        h, w = imgs[0].shape[:2]
+        c = im.Context(0)
+        c.set_option("sift_batch", 4)
+        for name, value in opts.items():
+            c.set_option(name, value)
+        c.profile_enable(True)
+        dev = [torch.from_numpy(np.ascontiguousarray(i)).cuda() for i in imgs]
+        torch.cuda.synchronize()
+        c.profile_reset()
+        for k, d in enumerate(dev):
+            c.SiftExtractDev(k, d.data_ptr(), w, h, 3 * w)
+        feats = [c.GetFeatures(k) for k in range(4)]
+        got = tuple(int(c.profile_get(cls)[1]) for cls in ("gauss_stream", "gauss", "downsample", "extrema"))
+        c.close()
+        assert got == want, (tag, got, want)
+        for k, img in enumerate(imgs):
+            kp, desc = ctx.SiftExtract(600 + k, img)
+            assert len(kp) > 100 and np.array_equal(kp.view(np.uint8), feats[k][0].view(np.uint8)) and np.array_equal(desc, feats[k][1]), (tag, k)
+
+
 def test_sift_host_frames_deferred(ctx):
     """mi355_sift_extract with nothing asked back: host frames go through the staging ring and join batches; the source
     array is overwritten right after each call; more frames than the ring holds"""

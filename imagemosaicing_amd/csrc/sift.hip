@@ -17,7 +17,8 @@
 //   blur16_tile<R,BGR>    the same filter for small levels: 64x32 tile + halo in LDS, row pass then column pass
 //   downsample16          next octave seed = every second pixel of level 3 (when the blur did not write it on the way out)
 //   extrema_stream / extrema_kernel   DoG never materialised in HBM: the 6 Gaussian levels are read once, 26-neighbour
-//                         test on the 5 DoG planes (registers / LDS), candidates leave with their 3x3x3 neighbourhood
+//                         test on the 5 DoG planes (extrema_stream: row extremes in registers, the raw rows in a wave-private
+//                         LDS ring; extrema_kernel: LDS tiles), candidates leave with their 3x3x3 neighbourhood
 //   refine                one lane per candidate: quadratic fit, contrast / edge tests, duplicate claim bitmap, response histogram
 //   select_unclaim        response threshold above which nfeatures + 256 refined points lie; takes the claim bits back
 //   orient                one wave per refined point above the threshold: 36-bin histogram in order-free fixed point,
@@ -500,12 +501,18 @@ __global__ __launch_bounds__(256) void extrema_kernel(OctaveDev oc, int octave, 
 
 // ---- extrema_stream: the same test, streamed -------------------------------------------------------------------
 // One WAVE owns a strip of 256 columns (4 per lane) and walks down its rows: every row of the six levels is read once
-// (XD rows are in flight while the current one is processed), the five DoG planes of three consecutive rows live in
-// registers, the neighbours' columns come through DPP wave shifts, and nothing waits on a workgroup barrier.  The hot
-// loop issues no memory operation besides those row loads: a candidate (rare) is parked in a wave-private LDS list
-// together with its 3x3x3 DoG neighbourhood, taken from the registers of the lane and of its two neighbours; the list
-// goes to global memory when it is full and at the end of the segment.
-constexpr int XCAP = 512;                       // candidate records buffered per wave (4 KB); the list is emptied when half full, between runs of the row loop
+// (XD rows are in flight while the current one is processed), the 3-wide extremes of the five DoG planes of three
+// consecutive rows live in registers, the neighbours' columns come through DPP wave shifts, and nothing waits on a
+// workgroup barrier.  The raw DoG rows of the window also sit in a wave-private LDS ring (plane, row mod 3, column).
+// The hot loop issues no GLOBAL memory operation besides those row loads: a candidate (rare) is parked in a wave-private
+// LDS list together with its 3x3x3 DoG neighbourhood, read from the ring; the list and the neighbourhoods go to global
+// memory when the list is half full and at the end of the segment.
+constexpr int XCAP = 144;                       // candidate records buffered per wave (8 bytes each)
+constexpr int XNB_CAP = 64;                     // the first XNB_CAP of them also have their neighbourhood parked; the list is emptied when XNB_CAP / 2 are in it, between runs of the row loop
+constexpr int XRING_DW = 5 * 3 * 128;           // the ring: 5 planes x 3 rows x 256 columns of 16 bits = 7680 B per wave
+constexpr int XNB_DW = 18;                      // a parked neighbourhood: 3 planes x 3 rows x the two packed dwords (4 columns) that hold columns c-1 .. c+1
+constexpr int XLDS_BYTES = 4 * (XRING_DW * 4 + XCAP * 8 + XNB_CAP * XNB_DW * 4);
+static_assert(XWAVES * XLDS_BYTES <= 160 * 1024 && XLDS_BYTES <= 53 * 1024, "extrema_stream: ring + list must leave room for XWAVES workgroups per CU");
 // The DoG values are 16-bit integers and stay PACKED, two columns per register, from the level rows to the test: v_pk_sub_i16 forms
 // them straight from the loaded level words (no unpacking), v_pk_max_i16 / v_pk_min_i16 take the extremes of two columns at a time and
 // the 16-bit compares read either half (SDWA).  Half the registers of the float form of round 3 (4 waves per SIMD instead of 2) and
@@ -650,15 +657,29 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
 #pragma unroll
         for (int p = 0; p < 5; p++) { d.m[p][0] = as_s2(q.m[p + 1].x) - as_s2(q.m[p].x); d.m[p][1] = as_s2(q.m[p + 1].y) - as_s2(q.m[p].y); }
     };
-    // Candidates are rare per lane but not per wave (a 12 MP frame has ~2 per wave-row): a hit only appends its 8-byte record to a
-    // wave-private LDS list (slots from a ballot, the list length is wave-uniform and lives in a scalar); the list goes to the region's
-    // candidate list behind one region-counter atomic per flush.  The 3x3x3 DoG neighbourhoods refine starts from are gathered by
-    // refine_kernel itself, one lane per candidate: gathered here (round 3), every flush stalled its wave for the round trip of
-    // 36 scattered loads of rows that had long left the L2 -- a third of this kernel's time (73 -> 49 us per 12 MP frame without).
+    // Candidates are rare per lane but not per wave (a 12 MP frame has ~2 per wave-row): a hit appends its 8-byte record and its 3x3x3
+    // DoG neighbourhood to a wave-private LDS list (slots from a ballot, the list length is wave-uniform and lives in a scalar); the
+    // list goes to the region's candidate list and cube buffer behind one region-counter atomic per flush, in extrema_kernel's format.
+    // The neighbourhood comes from LDS, not from memory: gathered with global loads at flush time (round 3), every flush stalled its
+    // wave for the round trip of 36 scattered loads of rows that had long left the L2 -- a third of this kernel's time.
+    // The ring: dword d of a (plane, row) holds columns 2d, 2d+1 of the wave's 256 (lane l: dwords 2l, 2l+1) and lives at
+    // [d * 15 + plane * 3 + row slot], so that the 18 dwords of a neighbourhood are 9 two-dword reads off one address.  The LDS
+    // operations of a wave execute in order: a row written by all lanes is readable by any of them without a barrier.
+    __shared__ unsigned s_ring[4][XRING_DW];
     __shared__ unsigned long long s_rec[4][XCAP];
+    __shared__ uint2 s_nb[4][XNB_CAP][XNB_DW / 2];
+    static_assert(sizeof(s_ring) + sizeof(s_rec) + sizeof(s_nb) == XLDS_BYTES, "XLDS_BYTES");
+    auto ring_put = [&](const XDog& d, int slot) {
+        unsigned* q = &s_ring[wave][lane * 30 + slot];
+#pragma unroll
+        for (int p = 0; p < 5; p++) { q[p * 3] = as_u(d.m[p][0]); q[p * 3 + 15] = as_u(d.m[p][1]); }
+    };
     int nq = 0;                                      // wave-uniform
     auto wave_sync = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    auto flush = [&]() {
+    // flush<CUBES>: the row loop's candidates leave with bit 63 set and their cube (those that found room in s_nb, and where the region's
+    // cube buffer has room), the slow loop's without: refine_kernel gathers those itself
+    auto flush = [&](auto cubes) {
+        constexpr bool CUBES = decltype(cubes)::value;
         if (nq == 0) return;
         wave_sync();
         unsigned base = 0;
@@ -667,15 +688,32 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
         for (int idx = lane; idx < nq; idx += 64) {
             const unsigned g = base + (unsigned)idx;
             if (g >= cap) { *overflow = 1; continue; }
-            cand[(size_t)reg * cap + g] = s_rec[wave][idx];                                             // bit 63 clear: refine_kernel gathers the neighbourhood itself
+            const unsigned long long rec = s_rec[wave][idx];
+            const bool has = CUBES && idx < XNB_CAP && g < cube_cap;
+            cand[(size_t)reg * cap + g] = rec | (has ? (1ull << 63) : 0ull);
+            if (has) {
+                // the four columns of the parked dwords start at c - 1 (c even: sh = 16 drops column c - 2) or at c - 1 exactly (c odd)
+                const int sh = (rec & 1ull) ? 0 : 16;
+                float* cb = cube + (size_t)reg * 32 * cube_cap + g;                                     // [element][candidate]: coalesced across the lanes
+#pragma nounroll                                                                                        // (rolled: 27 store addresses at once would spill the row loop's window)
+                for (int i = 0; i < XNB_DW / 2; i++, cb += (size_t)3 * cube_cap) {                      // i = plane * 3 + row: elements 3i .. 3i + 2
+                    const uint2 wv = s_nb[wave][idx][i];
+                    const unsigned long long ww = (((unsigned long long)wv.y << 32) | wv.x) >> sh;
+                    cb[0] = (float)(int)(short)(ww & 0xffffu);
+                    cb[cube_cap] = (float)(int)(short)((ww >> 16) & 0xffffu);
+                    cb[(size_t)2 * cube_cap] = (float)(int)(short)((ww >> 32) & 0xffffu);
+                }
+            }
         }
         wave_sync();
         nq = 0;
     };
-    // emit<IN_LOOP>: the row loop's form never touches global memory (false = the list is full, nothing of this row was kept); the slow
-    // loop's form empties the list on the spot
-    auto emit = [&](unsigned hit, int rc, auto in_loop) -> bool {
-        constexpr bool IN_LOOP = decltype(in_loop)::value;
+    // emit<SB>: SB >= 0 is the row loop's form, SB the ring slot of the centre row: it never touches global memory (false = the list is
+    // full, nothing of this row was kept); a run of rows denser than XNB_CAP / 2 candidates parks the excess as bare records, which
+    // costs those candidates their cube and nothing else.  SB < 0 is the slow loop's form: no neighbourhood, and it empties the list on the spot
+    auto emit = [&](unsigned hit, int rc, auto sbc) -> bool {
+        constexpr int SB = decltype(sbc)::value;
+        constexpr bool IN_LOOP = SB >= 0;
         const int nq0 = nq;
         while (__builtin_amdgcn_ballot_w64(hit != 0)) {
             const bool mine = hit != 0;
@@ -685,54 +723,71 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
             const int add = __builtin_popcountll(m);
             if (nq + add > XCAP) {
                 if constexpr (IN_LOOP) { nq = nq0; return false; }
-                else flush();
+                else flush(std::false_type{});
             }
+            if constexpr (IN_LOOP) wave_sync();                                                         // the ring rows written by the other lanes
             if (mine) {
-                const int layer = bb / 4 + 1, c = xm + (bb & 3);
-                s_rec[wave][nq + __builtin_popcountll(m & ((1ull << lane) - 1ull))] =
-                    ((unsigned long long)octave << 48) | ((unsigned long long)layer << 40) | ((unsigned long long)rc << 20) | (unsigned long long)c;
+                const int layer = bb / 4 + 1, k = bb & 3, c = xm + k;
+                const int slot = nq + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+                s_rec[wave][slot] = ((unsigned long long)octave << 48) | ((unsigned long long)layer << 40) | ((unsigned long long)rc << 20) | (unsigned long long)c;
+                if (IN_LOOP && slot < XNB_CAP) {
+                    // columns c-1 .. c+1 = 4 * lane + k - 1 .. + 1 of the wave's 256 lie in dwords d0, d0 + 1 (lanes 1 .. 62 only: 1 <= d0 <= 125)
+                    const unsigned* q = &s_ring[wave][(2 * lane + ((k + 1) >> 1) - 1) * 15 + (layer - 1) * 3];
+                    uint2* nbp = s_nb[wave][slot];
+                    uint2 v[XNB_DW / 2];                                                                // every read before the first write: the reads stay in flight together
+#pragma unroll
+                    for (int pl = 0; pl < 3; pl++)
+#pragma unroll
+                        for (int dr = 0; dr < 3; dr++) {
+                            const int o = pl * 3 + (SB + dr + 2) % 3;                                   // dr = 0: the row above the centre
+                            v[pl * 3 + dr] = make_uint2(q[o], q[o + 15]);
+                        }
+#pragma unroll
+                    for (int i = 0; i < XNB_DW / 2; i++) nbp[i] = v[i];
+                }
             }
             nq += add;
         }
         return true;
     };
-    // rows t-1 and t as row extremes, rows t+1 .. t+XD in flight
+    // rows t-1 and t as row extremes (ring slots 0 and 1), rows t+1 .. t+XD in flight
     XH win[3];
     XCen cen[3];
     XRow nxt[XD];
-    {
+    auto prime = [&](int t) {
         XRow q; XDog dq;
-        load_row(y0 - 1, q); to_dog(q, dq); xrow_extremes(dq, win[0], cen[0]);
-        load_row(y0, q); to_dog(q, dq); xrow_extremes(dq, win[1], cen[1]);
+        load_row(y0 + t - 1, q); to_dog(q, dq); ring_put(dq, 0); xrow_extremes(dq, win[0], cen[0]);
+        load_row(y0 + t, q); to_dog(q, dq); ring_put(dq, 1); xrow_extremes(dq, win[1], cen[1]);
 #pragma unroll
-        for (int d = 0; d < XD; d++) load_row(y0 + 1 + d, nxt[d]);
-    }
-    // The row loop holds NO memory operation besides its row loads: the candidate list is emptied between runs of the loop, never
+        for (int d = 0; d < XD; d++) load_row(y0 + t + 1 + d, nxt[d]);
+    };
+    prime(0);
+    // The row loop holds NO global memory operation besides its row loads: the candidate list is emptied between runs of the loop, never
     // inside (a store or the returning atomic of flush() anywhere in the loop body made the compiler wait for ALL outstanding loads at
-    // the top of every row, the prefetched rows included: 73 -> 55 us per 12 MP frame).  A run ends when the list is half full; a
-    // group of rows that would overflow it (> 256 extrema in 6 rows of 248 columns: noise, not photographs) sends the wave into the
-    // plain loop below for the rest of its segment.
+    // the top of every row, the prefetched rows included: 73 -> 55 us per 12 MP frame).  A run ends when XNB_CAP / 2 candidates are
+    // parked; a group of rows that would overflow the records (> XCAP - XNB_CAP / 2 extrema in 6 rows of 248 columns: noise, not
+    // photographs) sends the wave into the plain loop below for the rest of its segment.
     int tb = 0, t_slow = -1;
     for (bool done = false; !done;) {
         for (;;) {
             if (tb >= lact) { done = true; break; }
-            if (nq > XCAP / 2) break;
+            if (nq > XNB_CAP / 2) break;
             auto step = [&](auto jc) -> bool {
                 constexpr int j = decltype(jc)::value;
                 const int tt = tb + j;
                 if (tt >= lact) return false;
                 const int rc = y0 + tt;
                 XH& A = win[j % 3]; XH& B = win[(j + 1) % 3]; XH& Cc = win[(j + 2) % 3];
-                { XDog dq; to_dog(nxt[j % XD], dq); xrow_extremes(dq, Cc, cen[(j + 2) % 3]); }
+                { XDog dq; to_dog(nxt[j % XD], dq); ring_put(dq, (j + 2) % 3); xrow_extremes(dq, Cc, cen[(j + 2) % 3]); }
                 load_row(rc + 1 + XD, nxt[j % XD]);           // the bottom row of XD steps ahead, in flight meanwhile
                 const unsigned hit = xtest_rows(A, B, Cc, cen[(j + 1) % 3], xm, clo, chi, rc >= IMG_BORDER && rc < oc.h - IMG_BORDER);
-                if (!emit(hit, rc, std::true_type{})) { t_slow = tt; return false; }
+                if (!emit(hit, rc, std::integral_constant<int, (j + 1) % 3>{})) { t_slow = tt; return false; }
                 return true;
             };
             if (!static_rows<0, 3 * XD>(step)) { done = true; break; }
             tb += 3 * XD;
         }
-        flush();
+        flush(std::true_type{});
     }
     if (t_slow >= 0) {
         for (int tt = t_slow; tt < lact; tt++) {
@@ -741,9 +796,9 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
             load_row(rc - 1, q); to_dog(q, A);
             load_row(rc, q); to_dog(q, B);
             load_row(rc + 1, q); to_dog(q, Cc);
-            emit(xtest_row(A, B, Cc, xm, clo, chi, rc >= IMG_BORDER && rc < oc.h - IMG_BORDER), rc, std::false_type{});
+            emit(xtest_row(A, B, Cc, xm, clo, chi, rc >= IMG_BORDER && rc < oc.h - IMG_BORDER), rc, std::integral_constant<int, -1>{});
         }
-        flush();
+        flush(std::false_type{});
     }
 }
 

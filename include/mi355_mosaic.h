@@ -255,6 +255,9 @@ int  mi355_mosaic_feathered(mi355_ctx* ctx, const uint8_t* const* imgs, const in
  * mi355_mosaic_seamline_cover: need[k] = 1 exactly for the frames that own at least one pixel of the rows -- the ownership walk with nothing
  *   sampled; what a rank must hold to render the stripe (feeds mi355_exchange_frames with MI355_EXCHANGE_NEED_IS_LOCAL, as
  *   MI355_COVER_REFINED_EXACT does for the refined render).  mi355_mosaic_stripe_cover is unchanged.
+ *   A frame the render skips -- h9[8] == 0, or no inverse (a homography of rank 2, say) -- follows the refined render's rule here as in the
+ *   render: it owns no pixel, so need[k] = 0 and d_imgs[k] may be NULL, while the corners of a frame with h9[8] != 0 still count for the
+ *   layout (mi355_mosaic_layout).  The same holds for mi355_mosaic_median_cover and for the feathered render's box cover.
  * Errors: as the feathered twins (argument checks, n <= 1 -> MI355_ERR_FAILED in the host forms, n > 65535, canvas geometry, ramp < 0, frame
  *   geometry); params NULL = defaults. */
 typedef struct { int32_t ramp; int32_t reserved[3]; } mi355_seamline_params;   /* ramp as in mi355_feather_params */

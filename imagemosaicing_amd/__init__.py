@@ -17,6 +17,8 @@ from .capi import (  # noqa: F401
     FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params,
     Camera, UndistortParams, undistort_params, undistort_fit, undistort_map,
     PAIR_NORMAL_BLOCK, ProjectiveParams, ProjectiveReport, projective_params, pair_normal_blocks_host, global_projective_refine, global_projective_refine_results,
+    PAIR_CALIB_BLOCK, CalibParams, CalibReport, calib_params, pair_calib_blocks_host, calibrate_lens, calibrate_lens_results, match_pairs_to_results,
+    CALIB_K1, CALIB_K2, CALIB_P1, CALIB_P2, CALIB_K3,
     TieParams, tie_params, TIE_REPORT, TIE_NONE, TIE_REFINED, TIE_EDGE, TIE_FLAT, TIE_LOW, TIE_BORDER,
     TIE_FLAG_NOT_ACCEPTED, TIE_FLAG_NO_FRAME, TIE_FLAG_BAD_RECORD, TIE_FLAG_DEMOTED,
     LocalWarpParams, LOCAL_WARP_REPORT, local_warp_params, local_warp_stats_len, tie_residual_stats_host, solve_local_warps,

@@ -111,6 +111,27 @@ class ProjectiveReport(C.Structure):
         return {n.rstrip("_"): getattr(self, n) for n, _ in self._fields_}
 
 
+# mi355_pair_calib_block: the normal-equation block of one pair record for the lens self-calibration (8 state values | k1 k2 p1 p2 k3)
+PAIR_CALIB_BLOCK = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("n_bad", "<i4"), ("cost", "<f8"), ("g", "<f8", (13,)), ("N", "<f8", (91,))])
+CALIB_K1, CALIB_K2, CALIB_P1, CALIB_P2, CALIB_K3 = 1, 2, 4, 8, 16
+
+
+class CalibParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("mask", C.c_int32), ("min_ties", C.c_int32), ("reserved", C.c_int32), ("lambda0", C.c_double),
+                ("lambda_up", C.c_double), ("lambda_down", C.c_double), ("min_rel_decrease", C.c_double)]
+
+
+class CalibReport(C.Structure):
+    _fields_ = [("trials", C.c_int32), ("accepted", C.c_int32), ("n_pairs_used", C.c_int32), ("n_unused_records", C.c_int32), ("n_points", C.c_int64),
+                ("cost0", C.c_double), ("cost", C.c_double), ("lambda_", C.c_double)]
+
+    def as_dict(self):
+        return {n.rstrip("_"): getattr(self, n) for n, _ in self._fields_}
+
+
+assert PAIR_CALIB_BLOCK.itemsize == 856 and C.sizeof(CalibParams) == 48 and C.sizeof(CalibReport) == 48
+
+
 class TieParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("search", C.c_int32), ("drop_mask", C.c_int32), ("reserved", C.c_int32), ("min_ncc", C.c_float)]
 
@@ -516,6 +537,24 @@ class Context:
         out, rep = np.zeros(len(a[2]), IMAGE_TRANSFORM), ProjectiveReport()
         self._chk(self.L.mi355_global_projective_refine_dev(self._h, C.c_void_p(int(d_results) or None), int(n_pairs), len(a[2]), _p(a[0]), _p(a[1]), _p(a[3]), _p(a[4]), _p(a[2]),
                                                             C.byref(params) if params is not None else None, _p(out), C.byref(rep)))
+        return out, rep.as_dict()
+
+    # ---- lens self-calibration (mi355_pair_calib_blocks_dev, mi355_calibrate_lens_dev; csrc/calib.hip) --------------------------
+    def PairCalibBlocksDev(self, d_results, n, h8, cam, d_out, min_ties=16):
+        """one PAIR_CALIB_BLOCK per pair record at the camera `cam` (Camera: its coefficients are theta) and the states h8 (n x 8 doubles,
+        one row per record, host), device to device (ctx stream)"""
+        h8 = None if h8 is None else np.ascontiguousarray(h8, np.float64).reshape(-1, 8)
+        assert h8 is None or len(h8) >= int(n)
+        self._chk(self.L.mi355_pair_calib_blocks_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), _p(h8), C.byref(cam) if cam is not None else None,
+                                                     int(min_ties), C.c_void_p(int(d_out or 0) or None)))
+
+    def CalibrateLensDev(self, d_results, n_pairs, start, params=None, **kw):
+        """mi355_calibrate_lens_dev: the Brown-Conrady coefficients of the camera `start` (Camera; its intrinsics are held fixed) from device
+        pair records of the original frames; returns (Camera, report dict)"""
+        p = params if params is not None else calib_params(**kw)
+        out, rep = Camera(), CalibReport()
+        self._chk(self.L.mi355_calibrate_lens_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), C.byref(start) if start is not None else None, C.byref(p),
+                                                  C.byref(out), C.byref(rep)))
         return out, rep.as_dict()
 
     # ---- tie-point refinement (mi355_refine_ties*, csrc/tie_refine.hip) ------------------------------------------------------
@@ -1596,6 +1635,67 @@ def global_projective_refine_results(results, w, h, start, fixed=None, label=Non
 def global_projective_refine(match_pairs, w, h, start, fixed=None, label=None, params=None):
     """the same on the flat MATCHPAIR list (a run of equal image indices is one pair)"""
     return _projective_host("mi355_global_projective_refine", np.ascontiguousarray(match_pairs, MATCHPAIR), w, h, start, fixed, label, params)
+
+
+def calib_params(**kw):
+    """mi355_default_calib_params (20 trials, mask k1 | k2, min_ties 16, lambda 1e-3, up and down 10, min_rel_decrease 1e-6), with fields
+    overridden by keyword"""
+    p = CalibParams()
+    load_library().mi355_default_calib_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def pair_calib_blocks_host(results, h8, cam, min_ties=16):
+    """the calibration's normal-equation block of every record at the camera `cam` and the states h8 (one row of 8 per record), on the host
+    (what mi355_pair_calib_blocks_dev forms on the device)"""
+    r = np.ascontiguousarray(results, PAIR_RESULT)
+    h8 = np.ascontiguousarray(h8, np.float64).reshape(-1, 8)
+    assert len(h8) == len(r)
+    out = np.zeros(len(r), PAIR_CALIB_BLOCK)
+    L = load_library()
+    rc = L.mi355_pair_calib_blocks_host(_p(r), len(r), _p(h8), C.byref(cam) if cam is not None else None, int(min_ties), _p(out))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return out
+
+
+def _calibrate_host(fn, data, start, params, kw):
+    p = params if params is not None else calib_params(**kw)
+    out, rep = Camera(), CalibReport()
+    L = load_library()
+    rc = getattr(L, fn)(_p(data), len(data), C.byref(start) if start is not None else None, C.byref(p), C.byref(out), C.byref(rep))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return out, rep.as_dict()
+
+
+def calibrate_lens_results(results, start, params=None, **kw):
+    """mi355_calibrate_lens_results: the Brown-Conrady coefficients of the camera `start` (Camera; its intrinsics are held fixed, its
+    coefficients are the start) from host PAIR_RESULT records of the original frames; params: CalibParams or its keyword fields.
+    Returns (Camera, report dict)"""
+    return _calibrate_host("mi355_calibrate_lens_results", np.ascontiguousarray(results, PAIR_RESULT), start, params, kw)
+
+
+def calibrate_lens(match_pairs, start, params=None, **kw):
+    """the same on the flat MATCHPAIR list (a run of equal image indices is one pair; its start homography is fitted to its own ties)"""
+    return _calibrate_host("mi355_calibrate_lens", np.ascontiguousarray(match_pairs, MATCHPAIR), start, params, kw)
+
+
+def match_pairs_to_results(match_pairs):
+    """mi355_match_pairs_to_results: the flat MATCHPAIR list as accepted PAIR_RESULT records (runs cut at 400), each with the least-squares
+    homography of its own ties as H"""
+    v = np.ascontiguousarray(match_pairs, MATCHPAIR)
+    L = load_library()
+    n = C.c_int(0)
+    rc = L.mi355_match_pairs_to_results(_p(v), len(v), None, 0, C.byref(n))
+    out = np.zeros(n.value, PAIR_RESULT)
+    if rc == 0 and n.value:
+        rc = L.mi355_match_pairs_to_results(_p(v), len(v), _p(out), n.value, C.byref(n))
+    if rc != 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return out
 
 
 def select_connected_moments(moments, n_images):

@@ -526,6 +526,18 @@ inline int UndistortImage(const MI355_NS IplImage* src, MI355_NS IplImage* dst, 
     return rc;
 }
 
+// Lens self-calibration (include/mi355_mosaic.h, "lens self-calibration"): the Brown-Conrady coefficients of the camera from the match list
+// of the ORIGINAL frames (the SIFT or SURF front-end's vecMatchPairs; a run of equal (ptA_i, ptB_i) is one pair, cut at 400).  `start` gives
+// fx, fy, cx, cy, which are held fixed, and the coefficients to start from (usually 0); `out` is `start` with the free coefficients (params->mask,
+// default k1 | k2) replaced.  The reference has no such step; its caller puts it between the front-end and UndistortImage, and runs the
+// front-end again on the undistorted frames.  Host only: no context, no device.  0 on success, -1 for bad arguments, else
+// the C call's error (mi355_last_error(0)).
+inline int CalibrateLens(const MI355_NS MatchPointPairs* pMatchPairs, int nPairs, const mi355_camera& start, mi355_camera& out,
+                         const mi355_calib_params* params = 0, mi355_calib_report* report = 0) {
+    if (nPairs < 0 || (nPairs > 0 && !pMatchPairs)) return -1;
+    return mi355_calibrate_lens(reinterpret_cast<const mi355_match_point_pairs*>(pMatchPairs), nPairs, &start, params, &out, report);
+}
+
 // Local registration (include/mi355_mosaic.h, "local registration"): what the aligned ties still disagree by on the canvas -- relief, residual
 // lens error, rolling shutter -- becomes a smooth, bounded displacement grid per frame, and the frames KEPT at extraction under ids
 // 0 .. nImages - 1 (option "keep_frames"; an id without a kept frame is MI355_ERR_ARG) are resampled by it in place, so that every render that

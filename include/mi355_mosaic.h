@@ -1038,6 +1038,111 @@ int  mi355_undistort_frames_dev(mi355_ctx* ctx, const uint8_t* const* d_src, uin
 int  mi355_undistort_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, uint8_t* dst, int dst_ws, const mi355_camera* cam,
                            const mi355_undistort_params* p, int64_t* n_outside);
 
+/* ---- lens self-calibration: Brown-Conrady coefficients from the ties (opt-in; csrc/calib.hip, csrc/calib_solve.cpp, csrc/calib.h) ------------
+ * The undistortion above needs a mi355_camera.  This stage estimates its coefficients from the pair stage's own records of the ORIGINAL
+ * (distorted) frames: a lens error is the part of the ties' disagreement that no per-pair homography explains, the same in every frame.
+ * The order of use is pair stage on the original frames -> calibrate -> undistort -> extract and match again.  Nothing calls it unless asked.
+ * All arithmetic is double; every product, sum and quotient is rounded separately, in the order written, no contraction.
+ *
+ * One camera per call.  fx, fy, cx, cy of the start camera are HELD FIXED: planar ties under free pair homographies do not determine them (a
+ *   change of the intrinsics is absorbed by the homographies).  theta = (k1, k2, p1, p2, k3) starts at the start camera's values, usually 0;
+ *   `mask` selects the free entries (MI355_CALIB_K1 ... _K3, bits 0..4), the default is k1 | k2.
+ * Point undistortion U_theta(xo, yo) of an observed pixel:  xd = (xo - cx) / fx, yd = (yo - cy) / fy;  x = xd, y = yd;  then
+ *   MI355_CALIB_STEPS (16) times, with lens::distort's terms in double
+ *     xx = x*x; yy = y*y; xy = x*y; r2 = xx + yy; a1 = xy + xy;  t = r2*k3; t = k2 + t; t = r2*t; t = k1 + t; t = r2*t;  rad = 1.0 + t;
+ *     tx = (p1*a1) + (p2*(r2 + (xx + xx)));   ty = (p1*(r2 + (yy + yy))) + (p2*a1);
+ *   the step  inv = 1.0 / rad;  xn = (xd - tx)*inv;  yn = (yd - ty)*inv;  dx = xn - x;  dy = yn - y;  x = xn;  y = yn   (one division).
+ *   At the last (x, y), with the terms formed once more:  dr = r2*k3; dr = 3.0*dr; dr = (k2 + k2) + dr; dr = r2*dr; dr = k1 + dr;  d2 = dr + dr;
+ *     a11 = (rad + d2*xx) + ((p1*(y + y)) + (p2*(6.0*x)));  a12 = (d2*xy) + ((p1*(x + x)) + (p2*(y + y)));
+ *     a22 = (rad + d2*yy) + ((p1*(6.0*y)) + (p2*(x + x)));  idet = 1.0 / (a11*a22 - a12*a12)          (dD/d(x, y), symmetric)
+ *     r4 = r2*r2; r6 = r4*r2;  dD/dtheta: ex = [x*r2, x*r4, a1, r2 + (xx + xx), x*r6],  ey = [y*r2, y*r4, r2 + (yy + yy), a1, y*r6];
+ *     gx[m] = -((a22*ex[m] - a12*ey[m])*idet),  gy[m] = -((a11*ey[m] - a12*ex[m])*idet)       (dU/dtheta by implicit differentiation).
+ *   The point is GOOD iff x, y and idet are finite and |dx|, |dy| <= MI355_CALIB_TOL (1e-7, normalised units: 5e-5 px at f = 520).
+ *   Both constants were chosen on tests/calib_ref.py (tests/test_calib_ref.py keeps the sweep): at 640 x 480, f = 520, every camera whose
+ *   distort map moves a frame corner by a tenth of the half-diagonal (39.9 px) through k1 of either sign, p1, p2 of either sign or outward
+ *   (positive) k2, k3, alone or mixed, is good at every pixel of the frame (the slowest, k3 alone, needs 15 steps, inward k1 13); inward k2
+ *   and k3 fold the frame over sooner: good at every pixel only up to 0.06 and 0.04 of the half-diagonal, NOT at the tenth.
+ * One tie (a in image i, b in image j) of a record with state h (8 doubles, h8 = 1; normalised coordinates, image j -> image i):
+ *   (ua, va) = U(a), (ub, vb) = U(b);  w = (h6*ub + h7*vb) + 1.0;  u = (h0*ub + h1*vb) + h2;  v = (h3*ub + h4*vb) + h5;  q1 = 1.0 / w;
+ *   qx = ub*q1; qy = vb*q1; px = u*q1; py = v*q1.  The residual is in pixels: r = (fx (ua - px), fy (va - py)).  The rows hold the residual's
+ *   Jacobian and the NEGATED residual (so that g below is minus half the cost's gradient, the step's right-hand side, as in the projective block):
+ *     X[0..7] = [-(fx*qx), -(fx*qy), -(fx*q1), 0, 0, 0, fx*(px*qx), fx*(px*qy)],   Y[0..7] = [0, 0, 0, -(fy*qx), -(fy*qy), -(fy*q1), fy*(py*qx), fy*(py*qy)];
+ *     dxu = (h0 - px*h6)*q1; dxv = (h1 - px*h7)*q1; dyu = (h3 - py*h6)*q1; dyv = (h4 - py*h7)*q1;
+ *     X[8 + m] = fx*(gx_a[m] - (dxu*gx_b[m] + dxv*gy_b[m])),   Y[8 + m] = fy*(gy_a[m] - (dyu*gx_b[m] + dyv*gy_b[m])),   m = k1, k2, p1, p2, k3;
+ *     X[13] = fx*(px - ua),   Y[13] = fy*(py - va).
+ *   A tie is good iff both its points are good and px, py are finite.
+ * Block of a record: over its good ties k = 0 .. n_in - 1 in index order, S[r][c] = S[r][c] + X[r]*X[c], then + Y[r]*Y[c] (c <= r <= 13): N is
+ *   rows 0..12 (lower triangle, r(r+1)/2 + c), g row 13, cost S[13][13].  Bad ties add nothing and are counted in n_bad.  The block always
+ *   covers all five coefficients; the mask is the host loop's business.
+ * Used records.  A record is USED iff it is accepted, min_ties <= n_in <= 400 (default 16), i != j, i, j >= 0 and its eight state values are
+ *   finite.  A used record's block carries the record's n_in; any other record gets a zero block with n_in = 0 (i, j copied).  The START STATE
+ *   of a record is K^-1 M K scaled to its last entry: M = the record's H as doubles with M[8] = 1 (H[8] carries Ransac2D's residual),
+ *   T[r] = [M[r][0]*fx, M[r][1]*fy, (M[r][0]*cx + M[r][1]*cy) + M[r][2]],  G[0][c] = (T[0][c] - cx*T[2][c]) / fx,  G[1][c] = (T[1][c] - cy*T[2][c]) / fy,
+ *   G[2][c] = T[2][c],  h[k] = G[k] / G[8].  If any of the eight is not finite the record is unused, and counted.
+ * Loop (host; Levenberg-Marquardt with Marquardt's diagonal).  Unknowns: theta's free entries and eight per used record.  lambda = lambda0,
+ *   c = the sum of the used blocks' costs in record order.  While trials < max_iters and c != 0 and lambda <= 1e16, one trial: per used record,
+ *   A = its N's 8 x 8 part with A_rr = A_rr + lambda*A_rr, factored A = L L^T (Cholesky, row by row, each entry's products subtracted in column
+ *   order); W = L^-1 B for B = N's rows of the free coefficients against h; z = L^-1 g_h; its contribution S_mn = C_mn - sum_r W_rm W_rn,
+ *   s_m = g_m - sum_r W_rm z_r (r ascending), C its N's free-coefficient part.  The contributions and the diagonals C_mm are summed in record order;
+ *   S_mm = S_mm + lambda*(sum C_mm); S dtheta = s by Cholesky; per record dh = L^-T (z - W dtheta).  theta' = theta + dtheta, h' = h + dh, blocks
+ *   at (theta', h'), c' = their cost.  The trial FAILS (lambda = lambda*lambda_up) when a pivot is not positive, theta' is not finite, any used
+ *   record has a bad tie or is no longer used, or c' is not finite or not below c; else theta, h, c = the trial's, lambda = lambda / lambda_down,
+ *   and the loop stops if (c - c') / c < min_rel_decrease.  Bad ties at the start camera are MI355_ERR_FAILED, the message naming the record
+ *   and the tie; so is a start cost that is not finite.  The per-record work may run on MI355_HOST_THREADS threads: the sums are taken in
+ *   record order afterwards, so the bits are the same for every thread count.
+ * Output: the start camera with the free coefficients replaced; the report; rms = sqrt(cost / n_points) in pixels.  n_unused_records counts
+ *   the ACCEPTED records that are not used.  No used record: the start camera, a zero report, MI355_OK.
+ * Errors (MI355_ERR_ARG before any launch, the message names the value, the ctx stays usable): a camera value that is not finite; fx or
+ *   fy <= 0; mask 0 or with bits above 4; min_ties below 8 or above 400; max_iters < 0; lambda0 < 0; lambda_up or lambda_down <= 1;
+ *   min_rel_decrease < 0; any of them not finite; NULL where a pointer is required (params and report may be NULL); n < 0.
+ * Out of scope: estimating fx, fy, cx, cy; other lens models; a different camera per frame; robust weighting or re-gating of the ties between
+ *   trials (the records are RANSAC inliers); priors on the coefficients -- on 16 frames with 60 ties a pair and 0.5 px of tie noise, freeing
+ *   p1 and p2 left the data rms unchanged and moved the distort map by 4-10 px: the tangential component is close to what a homography
+ *   absorbs, so leave it fixed unless the ties are many and clean --; moving the ties into the undistorted frames (extract again); the
+ *   multi-GPU path (the rank that holds the gathered records runs the host form). */
+#define MI355_CALIB_K1 1
+#define MI355_CALIB_K2 2
+#define MI355_CALIB_P1 4
+#define MI355_CALIB_P2 8
+#define MI355_CALIB_K3 16
+#define MI355_CALIB_STEPS 16
+#define MI355_CALIB_TOL 1e-7
+typedef struct { int32_t i, j, n_in, n_bad; double cost; double g[13]; double N[91]; } mi355_pair_calib_block;   /* 856 B; N lower triangle, row-major: r(r+1)/2 + c */
+typedef struct { int32_t max_iters, mask, min_ties, reserved; double lambda0, lambda_up, lambda_down, min_rel_decrease; } mi355_calib_params;
+    /* defaults 20, k1 | k2, 16, 0, 1e-3, 10, 10, 1e-6 */
+typedef struct { int32_t trials, accepted, n_pairs_used, n_unused_records; int64_t n_points; double cost0, cost, lambda; } mi355_calib_report;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_pair_calib_block) == 856 && sizeof(mi355_calib_params) == 48 && sizeof(mi355_calib_report) == 48, "calibration records");
+#else
+_Static_assert(sizeof(mi355_pair_calib_block) == 856 && sizeof(mi355_calib_params) == 48 && sizeof(mi355_calib_report) == 48, "calibration records");
+#endif
+void mi355_default_calib_params(mi355_calib_params* p);
+/* one block per pair record on the device (a wave per record), at the camera `cam` (all nine values: the coefficients are theta) and the
+ * states h8: n x 8 doubles, one row per RECORD, on the HOST, uploaded per call; enqueued on the ctx stream like mi355_pair_normal_blocks_dev */
+int  mi355_pair_calib_blocks_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, const double* h8, const mi355_camera* cam, int min_ties,
+                                 mi355_pair_calib_block* d_out);
+/* the same bits on the host (no ctx; errors: mi355_last_error(NULL)) */
+int  mi355_pair_calib_blocks_host(const mi355_pair_result* r, int n, const double* h8, const mi355_camera* cam, int min_ties, mi355_pair_calib_block* out);
+/* The calibration on device records: the accepted ones are compacted once (mi355_compact_accepted_dev's path) and their 64-byte heads copied
+ * for the start states; then every trial is one launch and one copy of the blocks into pinned memory of the ctx; the solve runs on the host.
+ * Profile class "calibrate".  n_pairs = 0 or no used record launches nothing more.  Errors: mi355_last_error(ctx). */
+int  mi355_calibrate_lens_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n_pairs, const mi355_camera* start, const mi355_calib_params* params,
+                              mi355_camera* out, mi355_calib_report* report);
+/* the same loop on host records with the host blocks: no ctx, no device; errors: mi355_last_error(NULL) */
+int  mi355_calibrate_lens_results(const mi355_pair_result* r, int n_pairs, const mi355_camera* start, const mi355_calib_params* params, mi355_camera* out,
+                                  mi355_calib_report* report);
+/* The flat correspondence list as accepted pair records: a run of equal (ptA_i, ptB_i) is one record, a run longer than 400 is cut into
+ * records of 400 (the projective form's rule).  The list carries no homography, so each record's H is the least-squares homography of its own
+ * ties (image j -> image i, H[8] = 1): both sides shifted to their mean and scaled by s = 1 / sqrt((sxx + syy) / n) of the shifted points, the
+ * eight unknowns of  (h0 x + h1 y + h2) - x'(h6 x + h7 y) = x',  (h3 x + h4 y + h5) - y'(h6 x + h7 y) = y'  from the normal equations by
+ * Cholesky, mapped back and scaled to its last entry; all sums in tie order.  A run it cannot fit gets an H of NaN (such a record is unused
+ * by the calibration).  *n_out = the number of records; out may be NULL to ask for the count; cap < the count is MI355_ERR_ARG.  Host only. */
+int  mi355_match_pairs_to_results(const mi355_match_point_pairs* v, int n, mi355_pair_result* out, int cap, int* n_out);
+/* ... and the calibration on the flat list: mi355_calibrate_lens_results on mi355_match_pairs_to_results' records.  Host only.  The three
+ * forms give the same bits on the same correspondences and homographies. */
+int  mi355_calibrate_lens(const mi355_match_point_pairs* v, int n, const mi355_camera* start, const mi355_calib_params* params, mi355_camera* out,
+                          mi355_calib_report* report);
+
 /* ---- local registration (opt-in; csrc/local_warp.hip) --------------------------------------------------------------------------------
  * What is left after the alignment is what no homography explains: relief and buildings (parallax), residual lens error, rolling shutter.
  * The ties of the accepted pair records measure it: after the alignment their disagreement on the canvas is a sampled displacement field of

@@ -2,26 +2,15 @@
 // (include/mi355_mosaic.h, "lens self-calibration"), written once for both compilers, and the loop's interface to whoever forms the blocks.
 // Every operation is a separately rounded double operation in the header's order (the build's -ffp-contract=off is part of the contract).
 #pragma once
-#include "../../include/mi355_mosaic.h"
-#include <string>
-#include <vector>
-
-#ifdef __HIP__
-#define MI_CAL_HD __host__ __device__
-#else
-#define MI_CAL_HD
-#endif
+#include "tie_blocks.h"
 
 constexpr int MI_CAL_ROW = 14;                   // a tie's row [d rx / d (h0..h7, k1, k2, p1, p2, k3) | -rx] (and the same of ry)
-constexpr int MI_CAL_SUMS = 105;                 // the lower triangle of X X^T + Y Y^T: 91 of N, 13 of g (row 13, columns 0..12), the cost (13, 13)
-
-MI_CAL_HD inline bool mi_cal_finite(double v) { return __builtin_isfinite(v); }
 
 // one side of a tie: the undistorted point U_theta(xo, yo) in normalised coordinates, dU/dtheta, and whether the point is good
 struct CalSide { double x, y, gx[5], gy[5]; bool good; };
 
 // lens::distort's terms at (x, y), in double
-MI_CAL_HD inline void mi_cal_terms(const mi355_camera& c, double x, double y, double& xx, double& yy, double& xy, double& r2, double& a1, double& rad,
+MI_TIE_HD inline void mi_cal_terms(const mi355_camera& c, double x, double y, double& xx, double& yy, double& xy, double& r2, double& a1, double& rad,
                                    double& tx, double& ty) {
     xx = x * x; yy = y * y; xy = x * y; r2 = xx + yy; a1 = xy + xy;
     double t = r2 * c.k3;
@@ -31,7 +20,7 @@ MI_CAL_HD inline void mi_cal_terms(const mi355_camera& c, double x, double y, do
     ty = (c.p1 * (r2 + (yy + yy))) + (c.p2 * a1);
 }
 
-MI_CAL_HD inline void mi_cal_undistort(const mi355_camera& c, double xo, double yo, CalSide& s) {
+MI_TIE_HD inline void mi_cal_undistort(const mi355_camera& c, double xo, double yo, CalSide& s) {
     const double xd = (xo - c.cx) / c.fx, yd = (yo - c.cy) / c.fy;
     double x = xd, y = yd, dx = 0.0, dy = 0.0, xx, yy, xy, r2, a1, rad, tx, ty;
     for (int it = 0; it < MI355_CALIB_STEPS; it++) {
@@ -58,13 +47,13 @@ MI_CAL_HD inline void mi_cal_undistort(const mi355_camera& c, double xo, double 
         s.gy[m] = -((a11 * ey[m] - a12 * ex[m]) * idet);
     }
     s.x = x; s.y = y;
-    s.good = mi_cal_finite(x) && mi_cal_finite(y) && mi_cal_finite(idet) && (dx < 0.0 ? -dx : dx) <= MI355_CALIB_TOL && (dy < 0.0 ? -dy : dy) <= MI355_CALIB_TOL;
+    s.good = mi_finite(x) && mi_finite(y) && mi_finite(idet) && (dx < 0.0 ? -dx : dx) <= MI355_CALIB_TOL && (dy < 0.0 ? -dy : dy) <= MI355_CALIB_TOL;
 }
 
 // image j's side through the state h: columns 0..7 of the two rows, the projected point, and dU_b/dtheta chained through the homography
 struct CalChain { double X[8], Y[8], px, py, cx[5], cy[5]; bool good; };
 
-MI_CAL_HD inline void mi_cal_chain(const mi355_camera& c, const double* h, const CalSide& b, CalChain& o) {
+MI_TIE_HD inline void mi_cal_chain(const mi355_camera& c, const double* h, const CalSide& b, CalChain& o) {
     const double w = (h[6] * b.x + h[7] * b.y) + 1.0;
     const double u = (h[0] * b.x + h[1] * b.y) + h[2];
     const double v = (h[3] * b.x + h[4] * b.y) + h[5];
@@ -79,11 +68,11 @@ MI_CAL_HD inline void mi_cal_chain(const mi355_camera& c, const double* h, const
         o.cy[m] = dyu * b.gx[m] + dyv * b.gy[m];
     }
     o.px = px; o.py = py;
-    o.good = b.good && mi_cal_finite(px) && mi_cal_finite(py);
+    o.good = b.good && mi_finite(px) && mi_finite(py);
 }
 
 // image i's side closes the rows: columns 8..12 and the negated residual (X and Y point at columns 8..13)
-MI_CAL_HD inline void mi_cal_close(const mi355_camera& c, const CalSide& a, double px, double py, const double* cx, const double* cy, double* X, double* Y) {
+MI_TIE_HD inline void mi_cal_close(const mi355_camera& c, const CalSide& a, double px, double py, const double* cx, const double* cy, double* X, double* Y) {
     for (int m = 0; m < 5; m++) {
         X[m] = c.fx * (a.gx[m] - cx[m]);
         Y[m] = c.fy * (a.gy[m] - cy[m]);
@@ -93,9 +82,9 @@ MI_CAL_HD inline void mi_cal_close(const mi355_camera& c, const CalSide& a, doub
 }
 
 // is the record used, as far as a block entry point can tell (h: the record's eight state values)
-MI_CAL_HD inline bool mi_cal_used(int accepted, int n_in, int i, int j, int min_ties, const double* h) {
+MI_TIE_HD inline bool mi_cal_used(int accepted, int n_in, int i, int j, int min_ties, const double* h) {
     if (!accepted || n_in < min_ties || n_in > MI355_MAX_SELECTED || i == j || i < 0 || j < 0) return false;
-    for (int k = 0; k < 8; k++) if (!mi_cal_finite(h[k])) return false;
+    for (int k = 0; k < 8; k++) if (!mi_finite(h[k])) return false;
     return true;
 }
 

@@ -2,72 +2,47 @@
 // block of every pair record at the current camera and states, and the entry points that run the host loop (calib_solve.cpp) on blocks
 // formed here.  Compiled with -ffp-contract=off like the host twin: the same chain of separately rounded double operations per sum
 // (calib.h), so the calibration gives the same bits from either.
-#include "common.h"
+#include "tie_blocks_dev.h"
 #include "calib.h"
-
-int mi_compact_accepted(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, mi355_pair_result* d_out, int* d_n_out);     // comm.hip
 
 namespace {
 
-constexpr int CB_CHUNK = 32;                      // ties per pass: lanes 0..31 form image i's side of one tie each, lanes 32..63 image j's
-constexpr int CB_LD = 2 * MI_CAL_ROW;             // a tie's rows in LDS: X[14] | Y[14]
 constexpr size_t CB_HEAD = 64;                    // a record's bytes in front of its tie lists: i, j, n_in, n_selected, ok, accepted, H[9], _pad
 static_assert(offsetof(mi355_pair_result, a) == CB_HEAD && offsetof(mi355_pair_result, H) == 24, "pair record head");
 
-// A wave per pair record, four per workgroup (pair_normal_blocks_kernel's launch).  The 105 sums of a block are the lower triangle of
-// X X^T + Y Y^T over the ties' 14-rows; sum s (= r(r+1)/2 + c) belongs to lane s mod 64 -- a lane owns whole sums, up to two, and walks the
-// ties in order: no atomics, no reduction across lanes.  The fixed-point undistortion (a division per step) and the 2 x 2 inverse are the
-// expensive part, so they are done once per tie and side (one side per lane, 32 ties per pass); image j's lane chains its side through the
-// state and hands the projected point and the chained derivatives to image i's lane by __shfl; the rows pass through LDS.  A bad tie's
-// rows are zeros, which leave every sum's bits as they are (a sum starts at +0.0 and can never become -0.0).  Every wave of the workgroup
-// makes the same number of passes (the largest of the four records'), so the barriers are reached by all.
-// cam9: fx, fy, cx, cy, k1, k2, p1, p2, k3; h8: n x 8, one state per record.
-__global__ __launch_bounds__(256) void pair_calib_blocks_kernel(const mi355_pair_result* in, int n, const double* h8, const double* cam9, int min_ties,
-                                                                mi355_pair_calib_block* out) {
-    __shared__ double rows[4][CB_CHUNK][CB_LD];
-    const int wv = threadIdx.x >> 6, t = threadIdx.x & 63, p = blockIdx.x * 4 + wv;
+// The rows of tie_blocks_kernel for the calibration: the 14-rows of calib.h.  The fixed-point undistortion (a division per step) and the
+// 2 x 2 inverse are the expensive part, so they are done once per tie and side; image j's lane chains its side through the state and hands
+// the projected point and the chained derivatives to image i's lane by __shfl.  A bad tie's rows are zeros, which leave every sum's bits
+// as they are (a sum starts at +0.0 and can never become -0.0).
+// Args: cam9 = fx, fy, cx, cy, k1, k2, p1, p2, k3; h8: n x 8, one state per record.
+struct CalibFormer {
+    static constexpr int ROW = MI_CAL_ROW;
+    using Block = mi355_pair_calib_block;
+    struct Args { const double* h8; const double* cam9; int min_ties; };
+    Args a;
     mi355_camera cam;
-    cam.fx = cam9[0]; cam.fy = cam9[1]; cam.cx = cam9[2]; cam.cy = cam9[3]; cam.k1 = cam9[4]; cam.k2 = cam9[5]; cam.p1 = cam9[6]; cam.p2 = cam9[7]; cam.k3 = cam9[8];
-    int cnt = 0, pi = 0, pj = 0;
+    const mi355_pair_result* e = nullptr;
+    int pi = 0, pj = 0, n_bad = 0;
     double h[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (p < n) {
-        const mi355_pair_result& e = in[p];
-        pi = e.i; pj = e.j;
-        for (int k = 0; k < 8; k++) h[k] = h8[(size_t)8 * p + k];
-        if (mi_cal_used(e.accepted, e.n_in, pi, pj, min_ties, h)) cnt = e.n_in;
+    __device__ __forceinline__ CalibFormer(const Args& a_) : a(a_) {
+        const double* c = a.cam9;
+        cam.fx = c[0]; cam.fy = c[1]; cam.cx = c[2]; cam.cy = c[3]; cam.k1 = c[4]; cam.k2 = c[5]; cam.p1 = c[6]; cam.p2 = c[7]; cam.k3 = c[8];
     }
-    int cmax = 0;                                  // the workgroup's largest count, found by every lane alike
-    for (int q = 0; q < 4; q++) {
-        const int pq = blockIdx.x * 4 + q;
-        if (pq >= n) continue;
-        const mi355_pair_result& e = in[pq];
-        if (mi_cal_used(e.accepted, e.n_in, e.i, e.j, min_ties, h8 + (size_t)8 * pq) && e.n_in > cmax) cmax = e.n_in;
+    __device__ __forceinline__ static int count(const Args& a, const mi355_pair_result* in, int p, int n) {
+        return p < n && mi_cal_used(in[p].accepted, in[p].n_in, in[p].i, in[p].j, a.min_ties, a.h8 + (size_t)8 * p) ? in[p].n_in : 0;
     }
-    // this lane's sums: s = t and t + 64 (the second only below 105) -> (r, c) of the 14 x 14 lower triangle
-    int sr[2], sc[2];
-    for (int q = 0; q < 2; q++) {
-        int s = t + 64 * q;
-        if (s >= MI_CAL_SUMS) s = 0;
-        int r = 0;
-        while ((r + 1) * (r + 2) / 2 <= s) r++;
-        sr[q] = r; sc[q] = s - r * (r + 1) / 2;
+    __device__ __forceinline__ int open(const mi355_pair_result* in, int p, int n) {
+        e = in + p;
+        if (p >= n) return 0;
+        pi = e->i; pj = e->j;
+        for (int k = 0; k < 8; k++) h[k] = a.h8[(size_t)8 * p + k];
+        return mi_cal_used(e->accepted, e->n_in, pi, pj, a.min_ties, h) ? e->n_in : 0;
     }
-    double acc[2] = {0.0, 0.0};
-    int n_bad = 0;
-    const int side = t >> 5, kq = t & 31;
-    for (int k0 = 0; k0 < cmax; k0 += CB_CHUNK) {
-        const int k = k0 + kq;
-        const bool live = k < cnt;
-        CalSide sd;
-        sd.x = 0.0; sd.y = 0.0; sd.good = false;
-        for (int m = 0; m < 5; m++) { sd.gx[m] = 0.0; sd.gy[m] = 0.0; }
-        CalChain ch;
-        ch.px = 0.0; ch.py = 0.0; ch.good = false;
-        for (int m = 0; m < 5; m++) { ch.cx[m] = 0.0; ch.cy[m] = 0.0; }
-        for (int c = 0; c < 8; c++) { ch.X[c] = 0.0; ch.Y[c] = 0.0; }
+    __device__ __forceinline__ void form(bool live, int side, int kq, int k, double* X) {
+        CalSide sd = {};                           // zeros and not good: what a lane that is not live hands over
+        CalChain ch = {};
         if (live) {
-            const mi355_pair_result& e = in[p];
-            const mi355_sfpoint pt = side ? e.b[k] : e.a[k];
+            const mi355_sfpoint pt = side ? e->b[k] : e->a[k];
             mi_cal_undistort(cam, (double)pt.x, (double)pt.y, sd);
             if (side) mi_cal_chain(cam, h, sd, ch);
         }
@@ -78,8 +53,7 @@ __global__ __launch_bounds__(256) void pair_calib_blocks_kernel(const mi355_pair
         const int good_b = __shfl((int)ch.good, kq + 32), good_a = __shfl((int)sd.good, kq);
         const bool good = good_a && good_b;
         if (live) {
-            double* X = rows[wv][kq];
-            double* Y = X + MI_CAL_ROW;
+            double* Y = X + ROW;
             if (side) {
                 for (int c = 0; c < 8; c++) { X[c] = good ? ch.X[c] : 0.0; Y[c] = good ? ch.Y[c] : 0.0; }
             } else {
@@ -89,45 +63,20 @@ __global__ __launch_bounds__(256) void pair_calib_blocks_kernel(const mi355_pair
             }
         }
         n_bad += __popcll(__ballot(live && side == 0 && !good));
-        __syncthreads();
-        const int m = cnt - k0 < CB_CHUNK ? cnt - k0 : CB_CHUNK;
-        for (int kk = 0; kk < m; kk++) {
-            const double* X = rows[wv][kk];
-            const double* Y = X + MI_CAL_ROW;
-            for (int q = 0; q < 2; q++) {
-                double v = acc[q];
-                v = v + X[sr[q]] * X[sc[q]];
-                v = v + Y[sr[q]] * Y[sc[q]];
-                acc[q] = v;
-            }
-        }
-        __syncthreads();
     }
-    if (p >= n) return;
-    mi355_pair_calib_block& o = out[p];
-    if (t == 0) { o.i = pi; o.j = pj; o.n_in = cnt; o.n_bad = n_bad; }
-    for (int q = 0; q < 2; q++) {
-        const int s = t + 64 * q;
-        if (s >= MI_CAL_SUMS) break;
-        if (s < 91) o.N[s] = acc[q]; else if (s < 104) o.g[s - 91] = acc[q]; else o.cost = acc[q];
-    }
-}
+    __device__ __forceinline__ void head(Block& o, int cnt) const { o.i = pi; o.j = pj; o.n_in = cnt; o.n_bad = n_bad; }
+};
 
-// caller holds the ctx lock: states and camera to the device (through pinned memory: the caller's arrays may be gone before the copy runs), one launch
+// caller holds the ctx lock: states and camera to the device, one launch
 int launch_blocks(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, const double* h8, const mi355_camera& cam, int min_ties, mi355_pair_calib_block* d_out) {
-    const size_t hb = sizeof(double) * 8 * (size_t)n, total = hb + sizeof(double) * 9;
-    HostBuf& stage = ctx->hbuf("calib_params_host");
-    DevBuf& dpar = ctx->buf("calib_params");
-    MI_HIP(stage.reserve(total));
-    MI_HIP(dpar.reserve(total));
-    MI_HIP(hipStreamSynchronize(ctx->stream));            // the previous call's upload has left the staging area
-    memcpy(stage.p, h8, hb);
+    const size_t hb = sizeof(double) * 8 * (size_t)n;
     const double c9[9] = {cam.fx, cam.fy, cam.cx, cam.cy, cam.k1, cam.k2, cam.p1, cam.p2, cam.k3};
-    memcpy(stage.as<uint8_t>() + hb, c9, sizeof(c9));
-    MI_HIP(hipMemcpyAsync(dpar.p, stage.p, total, hipMemcpyHostToDevice, ctx->stream));
+    uint8_t* dpar = nullptr;
+    { const int rc = mi_upload_params(ctx, "calib", h8, hb, c9, sizeof(c9), &dpar); if (rc != MI355_OK) return rc; }
     {
         ProfScope ps(ctx, "calibrate", (double)n * (sizeof(mi355_pair_result) + sizeof(mi355_pair_calib_block)));
-        hipLaunchKernelGGL(pair_calib_blocks_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_results, n, dpar.as<double>(), dpar.as<double>() + (size_t)8 * n, min_ties, d_out);
+        hipLaunchKernelGGL(tie_blocks_kernel<CalibFormer>, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_results, n,
+                           CalibFormer::Args{reinterpret_cast<const double*>(dpar), reinterpret_cast<const double*>(dpar + hb), min_ties}, d_out);
     }
     MI_HIP(hipGetLastError());
     return MI355_OK;
@@ -139,49 +88,34 @@ struct DevSource : CalibSource {
     const mi355_pair_result* d_rec;
     int n;
     int count() override { return n; }
-    int fail(std::string& err, int rc) { err = ctx->err; return rc; }
-    int heads(CalibHead* out, std::string& err) override {
-        HostBuf& hh = ctx->hbuf("calib_heads_host");
-        const int rc = copy_heads(hh);
-        if (rc != MI355_OK) return fail(err, rc);
-        for (int p = 0; p < n; p++) {
-            const uint8_t* e = hh.as<uint8_t>() + CB_HEAD * (size_t)p;
-            memcpy(&out[p].i, e, sizeof(int32_t) * 3);              // i, j, n_in lead the record
-            memcpy(out[p].H, e + offsetof(mi355_pair_result, H), sizeof(float) * 9);
-        }
-        return MI355_OK;
+    template <class F> int guarded(std::string& err, F&& f) {            // a device error's message lives in the ctx: hand it to the loop
+        const int rc = f();
+        if (rc != MI355_OK) err = ctx->err;
+        return rc;
     }
-    int copy_heads(HostBuf& hh) {
-        MI_HIP(hh.reserve(CB_HEAD * (size_t)n));
-        MI_HIP(hipMemcpy2DAsync(hh.p, CB_HEAD, d_rec, sizeof(mi355_pair_result), CB_HEAD, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        return MI355_OK;
+    int heads(CalibHead* out, std::string& err) override {
+        return guarded(err, [&]() -> int {
+            HostBuf& hh = ctx->hbuf("calib_heads_host");
+            MI_HIP(hh.reserve(CB_HEAD * (size_t)n));
+            MI_HIP(hipMemcpy2DAsync(hh.p, CB_HEAD, d_rec, sizeof(mi355_pair_result), CB_HEAD, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+            MI_HIP(hipStreamSynchronize(ctx->stream));
+            for (int p = 0; p < n; p++) {
+                const uint8_t* e = hh.as<uint8_t>() + CB_HEAD * (size_t)p;
+                memcpy(&out[p].i, e, sizeof(int32_t) * 3);              // i, j, n_in lead the record
+                memcpy(out[p].H, e + offsetof(mi355_pair_result, H), sizeof(float) * 9);
+            }
+            return MI355_OK;
+        });
     }
     int blocks(const double* h8, const mi355_camera& cam, int min_ties, const mi355_pair_calib_block** out, std::string& err) override {
-        const int rc = run(h8, cam, min_ties);
-        if (rc != MI355_OK) return fail(err, rc);
-        *out = ctx->hbuf("calib_blocks_host").as<mi355_pair_calib_block>();
-        return MI355_OK;
-    }
-    int run(const double* h8, const mi355_camera& cam, int min_ties) {
-        DevBuf& dblk = ctx->buf("calib_blocks");
-        HostBuf& hblk = ctx->hbuf("calib_blocks_host");
-        const size_t bytes = sizeof(mi355_pair_calib_block) * (size_t)n;
-        MI_HIP(dblk.reserve(bytes));
-        MI_HIP(hblk.reserve(bytes));
-        { const int rc = launch_blocks(ctx, d_rec, n, h8, cam, min_ties, dblk.as<mi355_pair_calib_block>()); if (rc != MI355_OK) return rc; }
-        MI_HIP(hipMemcpyAsync(hblk.p, dblk.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        return MI355_OK;
+        return guarded(err, [&] { return mi_blocks_round_trip(ctx, "calib", n, nullptr, [&](mi355_pair_calib_block* d) { return launch_blocks(ctx, d_rec, n, h8, cam, min_ties, d); }, out); });
     }
     int record(int p, mi355_pair_result* out, std::string& err) override {
-        const int rc = fetch(p, out);
-        return rc == MI355_OK ? rc : fail(err, rc);
-    }
-    int fetch(int p, mi355_pair_result* out) {
-        MI_HIP(hipMemcpyAsync(out, d_rec + p, sizeof(mi355_pair_result), hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-        return MI355_OK;
+        return guarded(err, [&]() -> int {
+            MI_HIP(hipMemcpyAsync(out, d_rec + p, sizeof(mi355_pair_result), hipMemcpyDeviceToHost, ctx->stream));
+            MI_HIP(hipStreamSynchronize(ctx->stream));
+            return MI355_OK;
+        });
     }
 };
 
@@ -206,19 +140,9 @@ extern "C" int mi355_calibrate_lens_dev(mi355_ctx* ctx, const mi355_pair_result*
     }
     { const int rc = mi_calib_check("calibrate_lens_dev", start, params, err); if (rc != MI355_OK) { ctx->set_error(err); return rc; } }
     if (!out) { ctx->set_error("calibrate_lens_dev: NULL out"); return MI355_ERR_ARG; }
-    // the accepted records to the front, once: the trials' launches and copies then walk those alone
-    int n_acc = 0;
-    DevBuf& dcomp = ctx->buf("calib_compact");
-    if (n_pairs > 0) {
-        DevBuf& dcnt = ctx->buf("ag_res_counts");
-        MI_HIP(dcnt.reserve(sizeof(int) * 64));
-        MI_HIP(dcomp.reserve(sizeof(mi355_pair_result) * (size_t)n_pairs));
-        { const int rc = mi_compact_accepted(ctx, d_results, n_pairs, dcomp.as<mi355_pair_result>(), dcnt.as<int>()); if (rc != MI355_OK) return rc; }
-        MI_HIP(hipMemcpyAsync(&n_acc, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        MI_HIP(hipStreamSynchronize(ctx->stream));
-    }
     DevSource src;
-    src.ctx = ctx; src.d_rec = dcomp.as<mi355_pair_result>(); src.n = n_acc;
+    src.ctx = ctx;
+    { const int rc = mi_compact_for_loop(ctx, "calib", d_results, n_pairs, &src.d_rec, &src.n); if (rc != MI355_OK) return rc; }
     const int rc = mi_calibrate_lens(src, start, params, out, report, err);
     if (rc != MI355_OK) ctx->set_error(err);
     return rc;

@@ -3,7 +3,6 @@
 // eliminates every record's eight unknowns into the system of the free coefficients.  Host-only code, no device work; calib.hip hands the
 // loop its blocks through calib.h.
 #include "calib.h"
-#include "envelope_chol.h"
 #include "host_error.h"
 #include <cmath>
 #include <cstdint>
@@ -18,8 +17,7 @@ void block_host(const mi355_pair_result& e, const double* h, const mi355_camera&
     o.i = e.i; o.j = e.j;
     if (!mi_cal_used(e.accepted, e.n_in, e.i, e.j, min_ties, h)) return;
     o.n_in = e.n_in;
-    double S[MI_CAL_SUMS];
-    for (int s = 0; s < MI_CAL_SUMS; s++) S[s] = 0.0;
+    double S[MI_CAL_ROW * (MI_CAL_ROW + 1) / 2] = {};
     for (int k = 0; k < e.n_in; k++) {
         CalSide a, b;
         CalChain ch;
@@ -30,21 +28,12 @@ void block_host(const mi355_pair_result& e, const double* h, const mi355_camera&
         double X[MI_CAL_ROW], Y[MI_CAL_ROW];
         for (int c = 0; c < 8; c++) { X[c] = ch.X[c]; Y[c] = ch.Y[c]; }
         mi_cal_close(cam, a, ch.px, ch.py, ch.cx, ch.cy, X + 8, Y + 8);
-        int s = 0;
-        for (int r = 0; r < MI_CAL_ROW; r++)
-            for (int c = 0; c <= r; c++, s++) {
-                double v = S[s];
-                v = v + X[r] * X[c];
-                v = v + Y[r] * Y[c];
-                S[s] = v;
-            }
+        mi_tri_add<MI_CAL_ROW>(S, X, Y);
     }
-    memcpy(o.N, S, sizeof(double) * 91);
-    memcpy(o.g, S + 91, sizeof(double) * 13);
-    o.cost = S[104];
+    mi_tri_split<MI_CAL_ROW>(S, o);
 }
 
-// the loop's records on the host: a thread owns whole records, so every sum keeps its order
+// the loop's records on the host (blocks: tie_blocks.h, threads from 4000 ties on)
 struct HostSource : CalibSource {
     std::vector<const mi355_pair_result*> recs;
     std::vector<mi355_pair_calib_block> blk;
@@ -55,11 +44,8 @@ struct HostSource : CalibSource {
     }
     int blocks(const double* h8, const mi355_camera& cam, int min_ties, const mi355_pair_calib_block** out, std::string&) override {
         blk.resize(recs.size());
-        size_t nties = 0;
-        for (const mi355_pair_result* r : recs) nties += (size_t)(r->n_in > 0 && r->n_in <= MI355_MAX_SELECTED ? r->n_in : 0);
-        parallel_chunks(recs.size(), nties > 4000 ? (host_threads() < 8 ? host_threads() : 8) : 1, [&](size_t lo, size_t hi) {
-            for (size_t p = lo; p < hi; p++) block_host(*recs[p], h8 + 8 * p, cam, min_ties, blk[p]);
-        });
+        mi_host_blocks(recs.size(), 4000, [&](size_t p) { return (size_t)(recs[p]->n_in > 0 && recs[p]->n_in <= MI355_MAX_SELECTED ? recs[p]->n_in : 0); },
+                       [&](size_t p) { block_host(*recs[p], h8 + 8 * p, cam, min_ties, blk[p]); });
         *out = blk.data();
         return MI355_OK;
     }
@@ -115,8 +101,6 @@ void eliminate(const mi355_pair_calib_block& b, double lambda, const int* fr, in
     }
 }
 
-bool finite_d(double v) { return std::isfinite(v); }
-
 void start_state(const float* H, const mi355_camera& c, double* h) {
     double M[9], T[9], G[9];
     for (int k = 0; k < 9; k++) M[k] = (double)H[k];
@@ -132,7 +116,7 @@ void start_state(const float* H, const mi355_camera& c, double* h) {
         G[6 + k] = T[6 + k];
     }
     bool ok = true;
-    for (int k = 0; k < 8; k++) { h[k] = G[k] / G[8]; ok = ok && finite_d(h[k]); }
+    for (int k = 0; k < 8; k++) { h[k] = G[k] / G[8]; ok = ok && mi_finite(h[k]); }
     if (!ok) for (int k = 0; k < 8; k++) h[k] = std::numeric_limits<double>::quiet_NaN();
 }
 
@@ -148,7 +132,7 @@ void fit_h(const mi355_match_point_pairs* v, int n, float* H) {
         va = va + (ax * ax + ay * ay); vb = vb + (bx * bx + by * by);
     }
     const double sa = 1.0 / std::sqrt(va / (double)n), sb = 1.0 / std::sqrt(vb / (double)n);
-    if (!finite_d(sa) || !finite_d(sb)) return;
+    if (!mi_finite(sa) || !mi_finite(sb)) return;
     double N[64], g[8];
     for (int k = 0; k < 64; k++) N[k] = 0.0;
     for (int k = 0; k < 8; k++) g[k] = 0.0;
@@ -174,15 +158,13 @@ void fit_h(const mi355_match_point_pairs* v, int n, float* H) {
     }
     for (int c = 0; c < 3; c++) { Q[c] = P[c] / sa + m[0] * P[6 + c]; Q[3 + c] = P[3 + c] / sa + m[1] * P[6 + c]; Q[6 + c] = P[6 + c]; }
     float out[9];
-    for (int k = 0; k < 9; k++) { const double q = Q[k] / Q[8]; if (!finite_d(q)) return; out[k] = (float)q; }
+    for (int k = 0; k < 9; k++) { const double q = Q[k] / Q[8]; if (!mi_finite(q)) return; out[k] = (float)q; }
     memcpy(H, out, sizeof(out));
 }
 
 int flat_runs(const mi355_match_point_pairs* v, int n, mi355_pair_result* out) {      // out NULL: count only
     int cnt = 0;
-    for (int p = 0; p < n;) {
-        int q = p;
-        while (q < n && q - p < MI355_MAX_SELECTED && v[q].ptA_i == v[p].ptA_i && v[q].ptB_i == v[p].ptB_i) q++;
+    mi_flat_runs(v, n, MI355_MAX_SELECTED, [&](int p, int q) {
         if (out) {
             mi355_pair_result& r = out[cnt];
             memset(&r, 0, sizeof(r));
@@ -191,8 +173,7 @@ int flat_runs(const mi355_match_point_pairs* v, int n, mi355_pair_result* out) {
             fit_h(v + p, q - p, r.H);
         }
         cnt++;
-        p = q;
-    }
+    });
     return cnt;
 }
 
@@ -209,7 +190,7 @@ static int check_camera(const char* who, const mi355_camera* cam, std::string& e
     const double v[9] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2, cam->k3};
     static const char* const name[9] = {"fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3"};
     for (int k = 0; k < 9; k++)
-        if (!finite_d(v[k])) { err = std::string(who) + ": camera " + name[k] + " = " + std::to_string(v[k]) + " (finite)"; return MI355_ERR_ARG; }
+        if (!mi_finite(v[k])) { err = std::string(who) + ": camera " + name[k] + " = " + std::to_string(v[k]) + " (finite)"; return MI355_ERR_ARG; }
     for (int k = 0; k < 2; k++)
         if (v[k] <= 0.0) { err = std::string(who) + ": camera " + name[k] + " = " + std::to_string(v[k]) + " (above 0)"; return MI355_ERR_ARG; }
     return MI355_OK;
@@ -221,18 +202,11 @@ static int check_min_ties(const char* who, int min_ties, std::string& err) {
 
 int mi_calib_check(const char* who, const mi355_camera* cam, const mi355_calib_params* pp, std::string& err) {
     { const int rc = check_camera(who, cam, err); if (rc != MI355_OK) return rc; }
-    if (pp) {
-        const mi355_calib_params& p = *pp;
-        auto bad = [&](const char* name, double v, const char* rule) { err = std::string(who) + ": " + name + " = " + std::to_string(v) + " (" + rule + ")"; return MI355_ERR_ARG; };
-        if (p.mask <= 0 || p.mask > 31) { err = std::string(who) + ": mask = " + std::to_string(p.mask) + " (1 .. 31: bits 0..4 = k1, k2, p1, p2, k3)"; return MI355_ERR_ARG; }
-        { const int rc = check_min_ties(who, p.min_ties, err); if (rc != MI355_OK) return rc; }
-        if (p.max_iters < 0) { err = std::string(who) + ": max_iters = " + std::to_string(p.max_iters) + " (not negative)"; return MI355_ERR_ARG; }
-        if (!finite_d(p.lambda0) || p.lambda0 < 0.0) return bad("lambda0", p.lambda0, "finite, not negative");
-        if (!finite_d(p.lambda_up) || p.lambda_up <= 1.0) return bad("lambda_up", p.lambda_up, "finite, above 1");
-        if (!finite_d(p.lambda_down) || p.lambda_down <= 1.0) return bad("lambda_down", p.lambda_down, "finite, above 1");
-        if (!finite_d(p.min_rel_decrease) || p.min_rel_decrease < 0.0) return bad("min_rel_decrease", p.min_rel_decrease, "finite, not negative");
-    }
-    return MI355_OK;
+    if (!pp) return MI355_OK;
+    const mi355_calib_params& p = *pp;
+    if (p.mask <= 0 || p.mask > 31) { err = std::string(who) + ": mask = " + std::to_string(p.mask) + " (1 .. 31: bits 0..4 = k1, k2, p1, p2, k3)"; return MI355_ERR_ARG; }
+    { const int rc = check_min_ties(who, p.min_ties, err); if (rc != MI355_OK) return rc; }
+    return mi_lm_check(who, mi_lm_schedule(p), err);
 }
 
 int mi_calib_check_blocks(const char* who, int n, const void* records, const double* h8, const mi355_camera* cam, int min_ties, const void* out, std::string& err) {
@@ -294,72 +268,61 @@ int mi_calibrate_lens(CalibSource& src, const mi355_camera* start, const mi355_c
     std::vector<mi355_pair_calib_block> cur(nu);
     double c = 0.0;
     for (size_t o = 0; o < nu; o++) { cur[o] = blk[used[o]]; c = c + cur[o].cost; }
-    if (!finite_d(c)) { err = "calibrate_lens: the cost at the start is not finite"; return MI355_ERR_FAILED; }
+    if (!mi_finite(c)) { err = "calibrate_lens: the cost at the start is not finite"; return MI355_ERR_FAILED; }
     rep.n_pairs_used = (int)nu; rep.n_unused_records = n - (int)nu; rep.n_points = n_points; rep.cost0 = c;
 
-    double lambda = P.lambda0;
     std::vector<RecWork> work(nu);
     const int threads = nu >= 256 ? (host_threads() < 8 ? host_threads() : 8) : 1;
-    while (rep.trials < P.max_iters && c != 0.0 && lambda <= 1e16) {
-        rep.trials++;
+    LmState lm;
+    double tt[5];
+    const mi355_pair_calib_block* tb = nullptr;
+    // a trial: every record's eight unknowns eliminated into the system of the free coefficients, the back-substitution, the blocks there
+    auto try_step = [&](double lambda, double, double& c2, int& rc) {
         parallel_chunks(nu, threads, [&](size_t lo, size_t hi) { for (size_t o = lo; o < hi; o++) eliminate(cur[o], lambda, fr, np, work[o]); });
-        bool ok = true;
         double S[25], s[5], Cd[5];
         for (int k = 0; k < 25; k++) S[k] = 0.0;
-        for (int k = 0; k < 5; k++) { s[k] = 0.0; Cd[k] = 0.0; }
-        for (size_t o = 0; o < nu && ok; o++) {
+        for (int k = 0; k < 5; k++) { s[k] = 0.0; Cd[k] = 0.0; tt[k] = th[k]; }
+        for (size_t o = 0; o < nu; o++) {
             const RecWork& w = work[o];
-            if (!w.ok) { ok = false; break; }
+            if (!w.ok) return false;
             for (int m = 0; m < np; m++) {
                 for (int q = 0; q <= m; q++) S[m * 5 + q] = S[m * 5 + q] + w.S[m][q];
                 s[m] = s[m] + w.s[m];
                 Cd[m] = Cd[m] + w.Cd[m];
             }
         }
-        double tt[5] = {th[0], th[1], th[2], th[3], th[4]};
-        if (ok) {
-            for (int m = 0; m < np; m++) S[m * 5 + m] = S[m * 5 + m] + lambda * Cd[m];
-            ok = chol(S, np, 5);
-        }
-        if (ok) {
-            solve_lower(S, np, 5, s);
-            solve_upper(S, np, 5, s);
-            for (int m = 0; m < np; m++) { tt[fr[m]] = th[fr[m]] + s[m]; ok = ok && finite_d(tt[fr[m]]); }
-        }
-        double c2 = 0.0;
-        const mi355_pair_calib_block* tb = nullptr;
-        if (ok) {
-            ht = hc;
-            parallel_chunks(nu, threads, [&](size_t lo, size_t hi) {
-                for (size_t o = lo; o < hi; o++) {
-                    const RecWork& w = work[o];
-                    double y[8];
-                    for (int r = 0; r < 8; r++) { double v = w.z[r]; for (int m = 0; m < np; m++) v = v - w.W[m][r] * s[m]; y[r] = v; }
-                    solve_upper(w.L, 8, 8, y);
-                    double* h = ht.data() + (size_t)8 * used[o];
-                    for (int r = 0; r < 8; r++) h[r] = h[r] + y[r];
-                }
-            });
-            { const int rc = src.blocks(ht.data(), camera_of(tt), P.min_ties, &tb, err); if (rc != MI355_OK) return rc; }
-            for (size_t o = 0; o < nu; o++) {
-                const mi355_pair_calib_block& b = tb[used[o]];
-                if (b.n_in != cur[o].n_in || b.n_bad != 0) { ok = false; break; }
-                c2 = c2 + b.cost;
+        for (int m = 0; m < np; m++) S[m * 5 + m] = S[m * 5 + m] + lambda * Cd[m];
+        if (!chol(S, np, 5)) return false;
+        solve_lower(S, np, 5, s);
+        solve_upper(S, np, 5, s);
+        for (int m = 0; m < np; m++) { tt[fr[m]] = th[fr[m]] + s[m]; if (!mi_finite(tt[fr[m]])) return false; }
+        ht = hc;
+        parallel_chunks(nu, threads, [&](size_t lo, size_t hi) {
+            for (size_t o = lo; o < hi; o++) {
+                const RecWork& w = work[o];
+                double y[8];
+                for (int r = 0; r < 8; r++) { double v = w.z[r]; for (int m = 0; m < np; m++) v = v - w.W[m][r] * s[m]; y[r] = v; }
+                solve_upper(w.L, 8, 8, y);
+                double* h = ht.data() + (size_t)8 * used[o];
+                for (int r = 0; r < 8; r++) h[r] = h[r] + y[r];
             }
-            ok = ok && finite_d(c2) && c2 < c;
+        });
+        rc = src.blocks(ht.data(), camera_of(tt), P.min_ties, &tb, err);
+        if (rc != MI355_OK) return false;
+        for (size_t o = 0; o < nu; o++) {
+            const mi355_pair_calib_block& b = tb[used[o]];
+            if (b.n_in != cur[o].n_in || b.n_bad != 0) return false;
+            c2 = c2 + b.cost;
         }
-        if (ok) {
-            rep.accepted++;
-            hc.swap(ht);
-            for (int k = 0; k < 5; k++) th[k] = tt[k];
-            for (size_t o = 0; o < nu; o++) cur[o] = tb[used[o]];
-            lambda = lambda / P.lambda_down;
-            const double rel = (c - c2) / c;
-            c = c2;
-            if (rel < P.min_rel_decrease) break;
-        } else lambda = lambda * P.lambda_up;
-    }
-    rep.cost = c; rep.lambda = lambda;
+        return true;
+    };
+    auto accept = [&] {
+        hc.swap(ht);
+        for (int k = 0; k < 5; k++) th[k] = tt[k];
+        for (size_t o = 0; o < nu; o++) cur[o] = tb[used[o]];
+    };
+    { const int rc = mi_lm_run(mi_lm_schedule(P), c, lm, try_step, accept); if (rc != MI355_OK) return rc; }
+    rep.trials = lm.trials; rep.accepted = lm.accepted; rep.cost = lm.c; rep.lambda = lm.lambda;
     *out = camera_of(th);
     if (report) *report = rep;
     return MI355_OK;

@@ -231,6 +231,7 @@ void mi_comm_release(mi355_ctx*);
 void mi_surf_release(mi355_ctx*);
 int  mi_kept_frame_slot(mi355_ctx*, int img_id, int w, int h, int ws, const char* who, uint8_t** d_frame);   // frames.hip: the kept buffer of img_id, ready for a new frame
 void mi_frames_release(mi355_ctx*);
+int mi_compact_accepted(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, mi355_pair_result* d_out, int* d_n_out);     // comm.hip
 
 // host helpers
 #include "host_error.h"

@@ -19,7 +19,7 @@
 #include <thread>
 #include <chrono>
 #include <vector>
-#include "envelope_chol.h"
+#include "tie_blocks.h"
 
 static_assert(sizeof(mi355_match_point_pairs) == 40, "MatchPointPairs must be 40 bytes (matchPairs.match record)");
 static_assert(sizeof(mi355_keypoint) == 28, "cv::KeyPoint must be 28 bytes (keypoint_%d.key record)");
@@ -398,12 +398,7 @@ extern "C" int mi355_global_affine_align(const mi355_match_point_pairs* v, int n
                                          mi355_image_transform* out) {
     if (n < 0 || n_images <= 0 || (n > 0 && !v) || !out) return MI355_ERR_ARG;
     std::vector<PairGroup> groups;                      // the records of one image pair are consecutive (mi355_results_to_match_pairs)
-    for (int p = 0; p < n;) {
-        int q = p;
-        while (q < n && v[q].ptA_i == v[p].ptA_i && v[q].ptB_i == v[p].ptB_i) q++;
-        groups.push_back(PairGroup{v[p].ptA_i, v[p].ptB_i, (size_t)p, q - p});
-        p = q;
-    }
+    mi_flat_runs(v, n, 0, [&](int p, int q) { groups.push_back(PairGroup{v[p].ptA_i, v[p].ptB_i, (size_t)p, q - p}); });          // whole runs: no cap
     return align_core(groups, [v](size_t k, float& xa, float& ya, float& xb, float& yb) { xa = v[k].ptA.x; ya = v[k].ptA.y; xb = v[k].ptB.x; yb = v[k].ptB.y; },
                       n_images, fixed, out);
 }

@@ -1,21 +1,13 @@
 // csrc/projective.h -- what the projective refinement's host loop (projective_solve.cpp) and its device half (projective.hip) share: the
 // arithmetic of one side of a point, written once for both compilers, and the loop's interface to whoever forms the blocks.
 #pragma once
-#include "../../include/mi355_mosaic.h"
-#include <string>
-
-#ifdef __HIP__
-#define MI_PROJ_HD __host__ __device__
-#else
-#define MI_PROJ_HD
-#endif
+#include "tie_blocks.h"
 
 constexpr int MI_PROJ_ROW = 17;                  // a point's row [Rx | rx] (and [Ry | ry]): the 153 sums of a block are the lower triangle of X X^T + Y Y^T
-constexpr int MI_PROJ_SUMS = 153;                // 136 of N, 16 of g (row 16, columns 0..15), the cost (16, 16)
 
 // one side of a point under the parameters h (include/mi355_mosaic.h, "Side of a point"): the eight entries of Jx and Jy times `sign`
 // (+1 for image i's side, -1 for image j's: a negation is exact), and U, V
-MI_PROJ_HD inline void mi_proj_side(const double* h, double x, double y, double sign, double* jx, double* jy, double& U, double& V) {
+MI_TIE_HD inline void mi_proj_side(const double* h, double x, double y, double sign, double* jx, double* jy, double& U, double& V) {
     const double w = (h[6] * x + h[7] * y) + 1.0;
     const double u = (h[0] * x + h[1] * y) + h[2];
     const double v = (h[3] * x + h[4] * y) + h[5];
@@ -27,7 +19,7 @@ MI_PROJ_HD inline void mi_proj_side(const double* h, double x, double y, double 
 
 // is the record used, as far as a block entry point can tell (part: 0 no part, 1 takes part, 2 takes part and is fixed)?  *keep_n = the n_in
 // the block carries: the record's own for a used record and for a malformed accepted one, else 0
-MI_PROJ_HD inline bool mi_proj_used(int accepted, int n_in, int i, int j, const uint8_t* part, int n_images, int* keep_n) {
+MI_TIE_HD inline bool mi_proj_used(int accepted, int n_in, int i, int j, const uint8_t* part, int n_images, int* keep_n) {
     *keep_n = 0;
     if (!accepted || n_in < 1) return false;
     if (n_in > MI355_MAX_SELECTED || i < 0 || i >= n_images || j < 0 || j >= n_images) { *keep_n = n_in; return false; }

@@ -3,7 +3,6 @@
 // damped system, the prior, and the Levenberg-Marquardt loop.  Host-only code, no device work; projective.hip hands the loop its blocks
 // through projective.h.  The factorisation is the affine alignment's envelope Cholesky (envelope_chol.h), 8 rows per image, one right-hand side.
 #include "projective.h"
-#include "envelope_chol.h"
 #include "host_error.h"
 #include <cmath>
 #include <cstdint>
@@ -24,8 +23,7 @@ void block_host(const PairView& e, const double* h8, const uint8_t* part, int n_
     if (!used) return;
     const double* hi = h8 + (size_t)8 * e.i;
     const double* hj = h8 + (size_t)8 * e.j;
-    double S[MI_PROJ_SUMS];
-    for (int s = 0; s < MI_PROJ_SUMS; s++) S[s] = 0.0;
+    double S[MI_PROJ_ROW * (MI_PROJ_ROW + 1) / 2] = {};
     for (int k = 0; k < e.n_in; k++) {
         const mi355_sfpoint& pa = *reinterpret_cast<const mi355_sfpoint*>(e.a + e.stride * (size_t)k);
         const mi355_sfpoint& pb = *reinterpret_cast<const mi355_sfpoint*>(e.b + e.stride * (size_t)k);
@@ -33,37 +31,23 @@ void block_host(const PairView& e, const double* h8, const uint8_t* part, int n_
         mi_proj_side(hi, (double)pa.x, (double)pa.y, 1.0, X, Y, Ua, Va);
         mi_proj_side(hj, (double)pb.x, (double)pb.y, -1.0, X + 8, Y + 8, Ub, Vb);
         X[16] = Ub - Ua; Y[16] = Vb - Va;
-        int s = 0;
-        for (int r = 0; r < MI_PROJ_ROW; r++)
-            for (int c = 0; c <= r; c++, s++) {
-                double v = S[s];
-                v = v + X[r] * X[c];
-                v = v + Y[r] * Y[c];
-                S[s] = v;
-            }
+        mi_tri_add<MI_PROJ_ROW>(S, X, Y);
     }
-    memcpy(o.N, S, sizeof(double) * 136);
-    memcpy(o.g, S + 136, sizeof(double) * 16);
-    o.cost = S[152];
+    mi_tri_split<MI_PROJ_ROW>(S, o);
 }
 
-// blocks of a list of views on a few threads: a thread owns whole pairs, so every sum keeps its order
+// blocks of a list of views (tie_blocks.h: threads from 20000 points on)
 struct HostSource : ProjectiveSource {
     std::vector<PairView> views;
     std::vector<mi355_pair_normal_block> blk;
     int blocks(const double* h8, const uint8_t* part, int n_images, const mi355_pair_normal_block** out, int* n, std::string&) override {
         blk.resize(views.size());
-        size_t npoints = 0;
-        for (const PairView& v : views) npoints += (size_t)(v.n_in > 0 ? v.n_in : 0);
-        parallel_chunks(views.size(), npoints > 20000 ? (host_threads() < 8 ? host_threads() : 8) : 1, [&](size_t lo, size_t hi) {
-            for (size_t p = lo; p < hi; p++) block_host(views[p], h8, part, n_images, blk[p]);
-        });
+        mi_host_blocks(views.size(), 20000, [&](size_t p) { return (size_t)(views[p].n_in > 0 ? views[p].n_in : 0); },
+                       [&](size_t p) { block_host(views[p], h8, part, n_images, blk[p]); });
         *out = blk.data(); *n = (int)blk.size();
         return MI355_OK;
     }
 };
-
-bool finite_d(double v) { return std::isfinite(v); }
 
 // the system of one parameter set: the band of N (lower, envelope layout), g, the two costs
 struct System {
@@ -82,17 +66,12 @@ int mi_projective_check(int n_images, const int32_t* w, const int32_t* h, const 
                         mi355_image_transform* out, std::string& err) {
     if (n_images < 1) { err = "projective_refine: n_images = " + std::to_string(n_images) + " (at least 1)"; return MI355_ERR_ARG; }
     if (!w || !h || !start || !out) { err = std::string("projective_refine: NULL ") + (!w ? "w" : !h ? "h" : !start ? "start" : "out"); return MI355_ERR_ARG; }
-    if (pp) {
-        const mi355_projective_params& p = *pp;
-        auto bad = [&](const char* name, double v, const char* rule) { err = std::string("projective_refine: ") + name + " = " + std::to_string(v) + " (" + rule + ")"; return MI355_ERR_ARG; };
-        if (p.max_iters < 0) { err = "projective_refine: max_iters = " + std::to_string(p.max_iters) + " (not negative)"; return MI355_ERR_ARG; }
-        if (!finite_d(p.prior) || p.prior < 0.0) return bad("prior", p.prior, "finite, not negative");
-        if (!finite_d(p.lambda0) || p.lambda0 < 0.0) return bad("lambda0", p.lambda0, "finite, not negative");
-        if (!finite_d(p.lambda_up) || p.lambda_up <= 1.0) return bad("lambda_up", p.lambda_up, "finite, above 1");
-        if (!finite_d(p.lambda_down) || p.lambda_down <= 1.0) return bad("lambda_down", p.lambda_down, "finite, above 1");
-        if (!finite_d(p.min_rel_decrease) || p.min_rel_decrease < 0.0) return bad("min_rel_decrease", p.min_rel_decrease, "finite, not negative");
+    if (!pp) return MI355_OK;
+    if (pp->max_iters >= 0 && (!mi_finite(pp->prior) || pp->prior < 0.0)) {          // reported after max_iters, before the rest of the schedule
+        err = "projective_refine: prior = " + std::to_string(pp->prior) + " (finite, not negative)";
+        return MI355_ERR_ARG;
     }
-    return MI355_OK;
+    return mi_lm_check("projective_refine", mi_lm_schedule(*pp), err);
 }
 
 int mi_projective_refine(ProjectiveSource& src, int n_images, const int32_t* w, const int32_t* h, const int32_t* fixed, const int32_t* label,
@@ -208,43 +187,34 @@ int mi_projective_refine(ProjectiveSource& src, int n_images, const int32_t* w, 
     System cur, tri;
     assemble(hc.data(), blk, cur);
     double c = cur.cost_data + cur.cost_prior;
-    if (!finite_d(c)) { err = "projective_refine: the cost at the start is not finite"; return MI355_ERR_FAILED; }
+    if (!mi_finite(c)) { err = "projective_refine: the cost at the start is not finite"; return MI355_ERR_FAILED; }
     rep.n_free = nf; rep.n_pairs_used = (int)used.size(); rep.n_points = n_points; rep.cost0 = c;
-    double lambda = P.lambda0;
     std::vector<double> M((size_t)D * W), sc((size_t)D), y((size_t)D), ht(hc.size());
-    while (rep.trials < P.max_iters && c != 0.0 && lambda <= 1e16) {
-        rep.trials++;
+    LmState lm;
+    // a trial: the scaled damped system by the envelope Cholesky, the blocks at the stepped parameters, their cost
+    auto try_step = [&](double lambda, double, double& c2, int& rc) {
         for (int i = 0; i < D; i++) { const double d = at(cur.N, i, i); sc[i] = d > 0.0 ? 1.0 / std::sqrt(d) : 1.0; }
         for (int i = 0; i < D; i++) {
             for (int j = fst[i]; j < i; j++) at(M, i, j) = (sc[i] * at(cur.N, i, j)) * sc[j];
             at(M, i, i) = (sc[i] * at(cur.N, i, i)) * sc[i] + lambda;
             y[i] = sc[i] * cur.g[i];
         }
-        bool ok = envelope_cholesky(M.data(), D, bw, fst);
-        double c2 = 0.0;
-        if (ok) {
-            envelope_solve(M.data(), D, bw, fst, y.data(), nullptr);
-            ht = hc;
-            for (int o = 0; o < nf; o++) for (int r = 0; r < 8; r++) ht[(size_t)8 * freeimg[o] + r] = hc[(size_t)8 * freeimg[o] + r] + sc[8 * o + r] * y[8 * o + r];
-            const mi355_pair_normal_block* tb = nullptr;
-            int tn = 0;
-            { const int rc = src.blocks(ht.data(), part.data(), n_images, &tb, &tn, err); if (rc != MI355_OK) return rc; }
-            if (tn != nb) { err = "projective_refine: the block count changed between trials"; return MI355_ERR_FAILED; }
-            assemble(ht.data(), tb, tri);
-            c2 = tri.cost_data + tri.cost_prior;
-            ok = finite_d(c2) && c2 < c;
-        }
-        if (ok) {
-            rep.accepted++;
-            hc.swap(ht);
-            std::swap(cur, tri);
-            lambda = lambda / P.lambda_down;
-            const double rel = (c - c2) / c;
-            c = c2;
-            if (rel < P.min_rel_decrease) break;
-        } else lambda = lambda * P.lambda_up;
-    }
-    rep.cost_data = cur.cost_data; rep.cost_prior = cur.cost_prior; rep.lambda = lambda;
+        if (!envelope_cholesky(M.data(), D, bw, fst)) return false;
+        envelope_solve(M.data(), D, bw, fst, y.data(), nullptr);
+        ht = hc;
+        for (int o = 0; o < nf; o++) for (int r = 0; r < 8; r++) ht[(size_t)8 * freeimg[o] + r] = hc[(size_t)8 * freeimg[o] + r] + sc[8 * o + r] * y[8 * o + r];
+        const mi355_pair_normal_block* tb = nullptr;
+        int tn = 0;
+        rc = src.blocks(ht.data(), part.data(), n_images, &tb, &tn, err);
+        if (rc == MI355_OK && tn != nb) { err = "projective_refine: the block count changed between trials"; rc = MI355_ERR_FAILED; }
+        if (rc != MI355_OK) return false;
+        assemble(ht.data(), tb, tri);
+        c2 = tri.cost_data + tri.cost_prior;
+        return true;
+    };
+    { const int rc = mi_lm_run(mi_lm_schedule(P), c, lm, try_step, [&] { hc.swap(ht); std::swap(cur, tri); }); if (rc != MI355_OK) return rc; }
+    rep.trials = lm.trials; rep.accepted = lm.accepted;
+    rep.cost_data = cur.cost_data; rep.cost_prior = cur.cost_prior; rep.lambda = lm.lambda;
     for (int k : freeimg) {
         for (int j = 0; j < 8; j++) out[k].m[j] = (float)hc[(size_t)8 * k + j];
         out[k].m[8] = 1.0f; out[k].fixed = 0;
@@ -281,12 +251,9 @@ extern "C" int mi355_global_projective_refine(const mi355_match_point_pairs* v, 
     std::string err;
     if (n < 0 || (n > 0 && !v)) { mi_set_host_error("projective_refine: n = " + std::to_string(n) + " or a NULL list"); return MI355_ERR_ARG; }
     HostSource src;
-    for (int p = 0; p < n;) {                      // the records of one image pair are consecutive (mi355_results_to_match_pairs); at most 400 per block
-        int q = p;
-        while (q < n && q - p < MI355_MAX_SELECTED && v[q].ptA_i == v[p].ptA_i && v[q].ptB_i == v[p].ptB_i) q++;
+    mi_flat_runs(v, n, MI355_MAX_SELECTED, [&](int p, int q) {          // at most 400 per block
         src.views.push_back(PairView{v[p].ptA_i, v[p].ptB_i, q - p, 1, reinterpret_cast<const char*>(&v[p].ptA), reinterpret_cast<const char*>(&v[p].ptB), sizeof(mi355_match_point_pairs)});
-        p = q;
-    }
+    });
     const int rc = mi_projective_refine(src, n_images, w, h, fixed, label, start, params, out, report, err);
     if (rc != MI355_OK) mi_set_host_error(err);
     return rc;

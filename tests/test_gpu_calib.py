@@ -1,4 +1,4 @@
-"""GPU: the lens self-calibration's device half (csrc/calib.hip) against its host twin -- the blocks of pair_calib_blocks_kernel and the whole
+"""GPU: the lens self-calibration's device half (csrc/calib.hip) against its host twin -- the blocks of tie_blocks_kernel<CalibFormer> and the whole
 loop on device records give the same BITS as mi355_pair_calib_blocks_host and mi355_calibrate_lens_results -- and the stage end to end from
 pixels."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU: the projective refinement's device half (csrc/projective.hip) against its host twin -- the blocks of pair_normal_blocks_kernel and
+"""GPU: the projective refinement's device half (csrc/projective.hip) against its host twin -- the blocks of tie_blocks_kernel<NormalFormer> and
 the whole loop on device records give the same BITS as mi355_pair_normal_blocks_host and mi355_global_projective_refine_results."""
 import numpy as np
 import pytest

@@ -25,14 +25,13 @@ __device__ __forceinline__ float det_expf(float x) { return det_exp2f(x * 1.4426
 __device__ __forceinline__ float det_atan2deg(float y, float x) {
     const float p1 = 57.283627f, p3 = -18.667446f, p5 = 8.9140005f, p7 = -2.5397246f;
     const float ax = fabsf(x), ay = fabsf(y);
-    float a;
-    if (ax >= ay) {
-        const float c = ay / (ax + 2.220446e-16f), c2 = c * c;
-        a = fmaf(fmaf(fmaf(p7, c2, p5), c2, p3), c2, p1) * c;
-    } else {
-        const float c = ax / (ay + 2.220446e-16f), c2 = c * c;
-        a = 90.0f - fmaf(fmaf(fmaf(p7, c2, p5), c2, p3), c2, p1) * c;
-    }
+    // The oracle branches on ax >= ay and divides in the arm it takes.  Lanes of one wave disagree on the arm practically always, so a
+    // branch here runs both divisions and both polynomials for every wave; one select of the operands gives the taken arm's quotient from
+    // one division (same numerator, same denominator, same roundings; a tie takes the first form as in the oracle).
+    const bool flat = ax >= ay;
+    const float c = (flat ? ay : ax) / ((flat ? ax : ay) + 2.220446e-16f), c2 = c * c;
+    const float t = fmaf(fmaf(fmaf(p7, c2, p5), c2, p3), c2, p1) * c;
+    float a = flat ? t : 90.0f - t;
     if (x < 0.0f) a = 180.0f - a;
     if (y < 0.0f) a = 360.0f - a;
     return a;

@@ -1063,6 +1063,31 @@ __global__ __launch_bounds__(1024) void select_unclaim_kernel(PyrDev P, const Re
     if (tid == 0) ctrl[2] = s_cnt;
 }
 
+// ---------- gradient of a level sample (K4 orientations, K5 descriptors) ----------------------------------------------------------
+// Both kernels hand one keypoint to a wave, so the level a wave samples is the same for its 64 lanes: the callers pick it with
+// readfirstlane'd octave and layer, which leaves its address in scalar registers, and a lane carries the sample's byte offset in 32 bits.
+// The four loads then take scalar base + vector offset, with the +-1 column in the instruction's immediate.  (Indexed with size_t per
+// lane, the four addresses cost three 64-bit multiply-adds and six 64-bit shift-adds per sample.)
+// Why 32 bits hold the offset: make_layout() refuses a frame with 4 w h + 1024 > 0xfffffff0, so w h < 2^30, no level has more samples
+// than the frame, and a sample is 2 bytes: every byte offset inside a level is below 2^31 (the largest frame in use, 16384^2 in keep-all
+// mode, reaches 2^29).  Callers pass 1 <= r <= rows - 2 and 1 <= c <= cols - 2, so r - 1 and c - 1 do not wrap below zero.
+static_assert(sizeof(lvl_t) == 2, "level_taps forms byte offsets of 2-byte samples in 32 bits");
+// The samples right, left, above and below (r, c) as loaded, 16 bits each: nothing is computed from them here (not even the widening to
+// int), so a caller can issue the loads of one sample and consume those of another before it waits for these.
+struct LevelTaps { lvl_t e, w, n, s; };
+__device__ __forceinline__ LevelTaps level_taps(const lvl_t* lvl, int cols, int r, int c) {      // lvl, cols: wave-uniform
+    const char* b = (const char*)lvl;
+    const unsigned row = 2u * (unsigned)cols, o = 2u * ((unsigned)r * (unsigned)cols + (unsigned)c);
+    LevelTaps t;
+    t.e = *(const lvl_t*)(b + o + 2); t.w = *(const lvl_t*)(b + o - 2);
+    t.n = *(const lvl_t*)(b + (o - row)); t.s = *(const lvl_t*)(b + (o + row));
+    return t;
+}
+// dx = right - left, dy = above - below, as int differences of the int16 samples (exact for any sample values)
+__device__ __forceinline__ void level_grad(const LevelTaps& t, float& dx, float& dy) {
+    dx = (float)((int)t.e - (int)t.w); dy = (float)((int)t.n - (int)t.s);
+}
+
 constexpr int OCAP = 256;                     // emitted keypoints buffered per workgroup between flushes
 __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* ref, const unsigned* ref_count, unsigned ref_cap,
                                                      KpRec* out, unsigned* out_resp, unsigned* out_count, unsigned out_cap,
@@ -1091,8 +1116,8 @@ __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* re
         }
         if (take) {
             const Refined rr = ref[k];
-            const OctaveDev& oc = P.oc[rr.o];
-            const lvl_t* img = oc.lv[rr.layer] + foff;
+            const OctaveDev& oc = P.oc[__builtin_amdgcn_readfirstlane(rr.o)];                     // one keypoint per wave: scalar level, width and height
+            const lvl_t* img = oc.lv[__builtin_amdgcn_readfirstlane(rr.layer)] + foff;
             const int radius = (int)rintf(4.5f * rr.scl);
             const float osig = 1.5f * rr.scl;
             const float expf_scale = -1.0f / (2.0f * osig * osig);
@@ -1105,7 +1130,7 @@ __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* re
             const int per = (S + 63) / 64;
             int sc = lane * per, ic = sc / side, jc = sc - ic * side;
             for (int k0 = 0; k0 < per; k0 += 4) {
-                float dxv[4], dyv[4]; int d2v[4]; bool okv[4];
+                LevelTaps tv[4]; int d2v[4]; bool okv[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int s = k0 + u < per ? sc : S;
@@ -1115,16 +1140,14 @@ __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* re
                     const int y = rr.r + i, x = rr.c + j;
                     okv[u] = (s < S) && !(y <= 0 || y >= oc.h - 1 || x <= 0 || x >= oc.w - 1);
                     d2v[u] = i * i + j * j;
-                    dxv[u] = 0.0f; dyv[u] = 0.0f;
-                    if (okv[u]) {
-                        dxv[u] = (float)((int)img[(size_t)y * oc.w + x + 1] - (int)img[(size_t)y * oc.w + x - 1]);
-                        dyv[u] = (float)((int)img[(size_t)(y - 1) * oc.w + x] - (int)img[(size_t)(y + 1) * oc.w + x]);
-                    }
+                    tv[u] = LevelTaps{0, 0, 0, 0};
+                    if (okv[u]) tv[u] = level_taps(img, oc.w, y, x);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (!okv[u]) continue;
-                    const float dx = dxv[u], dy = dyv[u];
+                    float dx, dy;
+                    level_grad(tv[u], dx, dy);
                     const float wgt = det_expf((float)d2v[u] * expf_scale);
                     const float ang = det_atan2deg(dy, dx);
                     const float mag = sqrtf(dx * dx + dy * dy);
@@ -1132,7 +1155,9 @@ __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* re
                     if (b >= ORI_BINS) b -= ORI_BINS;
                     if (b < 0) b += ORI_BINS;
                     const float t = wgt * mag;
-                    atomicAdd(&s_hq[wv][b], (unsigned long long)(long long)(int)rintf(t * HIST_Q));      // order-free by definition; t <= sqrt(2) x 255 x 48: 32 bits hold t x 2^10
+                    // order-free by definition; 0 <= t <= sqrt(2) x 255 x 48 (a weight times a square root): 32 bits hold t x 2^10 and the
+                    // 64-bit addend's high word is zero, not a sign extension
+                    atomicAdd(&s_hq[wv][b], (unsigned long long)(unsigned)(int)rintf(t * HIST_Q));
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1425,8 +1450,9 @@ __global__ __launch_bounds__(256) void keepall_place_kernel(const KpRec* kps, co
 
 // ---------- K5: descriptors -----------------------------------------------------------------------------------------
 // One WAVE per keypoint, four keypoints per workgroup (16 frames x 2000 keypoints as 256-thread workgroups of their own were
-// dispatch- and latency-bound: each lane looped over ~20 samples with four dependent 2-byte loads each).  A lane takes four
-// samples per trip and issues their 16 gradient loads before any is consumed; the histogram lives in wave-private LDS.
+// dispatch- and latency-bound: each lane looped over ~20 samples with four dependent 2-byte loads each).  A lane tests four
+// samples of the window per round; the samples that pass are queued and consumed 64 at a time, and the four gradient loads of a
+// trip are issued one trip ahead of their use (below); the histogram lives in wave-private LDS.
 __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* sel, const int* n_sel, FrameOuts outs, BatchStride bs) {
     const size_t fr = blockIdx.y, foff = fr * bs.pyr;             // frame of the batch
     sel += fr * bs.sel; n_sel += fr * CNT_STRIDE;
@@ -1443,8 +1469,8 @@ __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* s
     float* s_dst = s_dst4[wv];
     auto wave_sync = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); };
     const SelRec k = sel[kidx];
-    const OctaveDev& oc = P.oc[k.o];
-    const lvl_t* img = oc.lv[k.layer] + foff;
+    const OctaveDev& oc = P.oc[__builtin_amdgcn_readfirstlane(k.o)];                          // one keypoint per wave: scalar level, width and height
+    const lvl_t* img = oc.lv[__builtin_amdgcn_readfirstlane(k.layer)] + foff;
     const int rows = oc.h, cols = oc.w;
     for (int i = lane; i < HB; i += 64) s_hq[i] = 0ull;
     wave_sync();
@@ -1464,15 +1490,26 @@ __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* s
     __shared__ int s_q4[4][64 * 5];
     int* s_q = s_q4[wv];
     int qn = 0;                                       // wave-uniform
-    auto heavy = [&](int packed) {
+    // One full trip of 64 queued samples stays pending: its list word and its four samples, loaded and not yet consumed.  It is accumulated
+    // when the next full trip's loads have been issued (possibly after further rounds of the cheap test, which hide its latency as well) or
+    // in the tail, so no trip waits for its own loads with nothing else to do.
+    bool pending = false;                             // wave-uniform
+    int p_word = 0;
+    LevelTaps p_taps = {0, 0, 0, 0};
+    // The expensive part in two halves, so that a trip's four loads are in flight while the trip before it is accumulated: fetch() issues
+    // the loads of a queued sample, heavy() consumes them.
+    auto fetch = [&](int packed) {
+        const int i = (int)((unsigned)packed >> 16) - 32768, j = (int)((unsigned)packed & 0xffffu) - 32768;
+        return level_taps(img, cols, py + i, px + j);
+    };
+    auto heavy = [&](int packed, const LevelTaps& taps) {
         const int i = (int)((unsigned)packed >> 16) - 32768, j = (int)((unsigned)packed & 0xffffu) - 32768;
         const float c_rot = (float)j * cos_t - (float)i * sin_t;
         const float r_rot = (float)j * sin_t + (float)i * cos_t;
         float rbin = r_rot + (float)(d / 2) - 0.5f;
         float cbin = c_rot + (float)(d / 2) - 0.5f;
-        const int r = py + i, c = px + j;
-        const float dx = (float)((int)img[(size_t)r * cols + c + 1] - (int)img[(size_t)r * cols + c - 1]);
-        const float dy = (float)((int)img[(size_t)(r - 1) * cols + c] - (int)img[(size_t)(r + 1) * cols + c]);
+        float dx, dy;
+        level_grad(taps, dx, dy);
         const float ori = det_atan2deg(dy, dx);
         const float mag = sqrtf(dx * dx + dy * dy) * det_expf((c_rot * c_rot + r_rot * r_rot) * exp_scale);
         float obin = (ori - k.angle) * bins_per_deg;
@@ -1490,8 +1527,12 @@ __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* s
         const float v_rco011 = v_rc01 * obin, v_rco010 = v_rc01 - v_rco011;
         const float v_rco001 = v_rc00 * obin, v_rco000 = v_rc00 - v_rco001;
         const int idx = ((r0 + 1) * (d + 2) + c0 + 1) * (n + 2) + o0;
-        // order-free accumulation: rint(v * 2^10) as 64-bit integers (two's complement add == unsigned add)
-#define FIXQ(v) ((unsigned long long)(long long)(int)rintf((v) * HIST_Q))     /* |v| <= sqrt(2) x 255 x 48: v x 2^10 fits 32 bits (one v_cvt_i32_f32 instead of the 64-bit conversion sequence) */
+        // order-free accumulation: rint(v * 2^10) as 64-bit integers.  v <= sqrt(2) x 255 x 48, so v x 2^10 fits 32 bits (one
+        // v_cvt_i32_f32 instead of the 64-bit conversion sequence).  And v >= 0, so the addend's high word is zero and not a sign extension:
+        // mag is a square root times det_expf (a positive polynomial times a power of two, or 0); rbin, cbin and obin are x - floor(x), in
+        // [0, 1]; a product of a >= 0 and a factor in [0, 1] rounds to at most a (a is itself a float and rounding is monotone), so each
+        // v_*1 lies in [0, a] and each v_*0 = a - v_*1 is >= 0.
+#define FIXQ(v) ((unsigned long long)(unsigned)(int)rintf((v) * HIST_Q))
         atomicAdd(&s_hq[idx], FIXQ(v_rco000)); atomicAdd(&s_hq[idx + 1], FIXQ(v_rco001));
         atomicAdd(&s_hq[idx + (n + 2)], FIXQ(v_rco010)); atomicAdd(&s_hq[idx + (n + 3)], FIXQ(v_rco011));
         atomicAdd(&s_hq[idx + (d + 2) * (n + 2)], FIXQ(v_rco100)); atomicAdd(&s_hq[idx + (d + 2) * (n + 2) + 1], FIXQ(v_rco101));
@@ -1521,11 +1562,19 @@ __global__ __launch_bounds__(256) void describe_kernel(PyrDev P, const SelRec* s
         wave_sync();
         while (qn >= 64) {
             qn -= 64;
-            heavy(s_q[qn + lane]);
+            const int word = s_q[qn + lane];
+            const LevelTaps taps = fetch(word);
+            if (pending) heavy(p_word, p_taps);
+            p_word = word; p_taps = taps; pending = true;
         }
         wave_sync();
     }
-    if (lane < qn) heavy(s_q[lane]);
+    const bool tail = lane < qn;
+    int t_word = 0;
+    LevelTaps t_taps = {0, 0, 0, 0};
+    if (tail) { t_word = s_q[lane]; t_taps = fetch(t_word); }
+    if (pending) heavy(p_word, p_taps);
+    if (tail) heavy(t_word, t_taps);
     wave_sync();
 #pragma unroll
     for (int half = 0; half < 2; half++) {

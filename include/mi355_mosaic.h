@@ -540,7 +540,12 @@ int  mi355_pair_schedule(int n_images, int window, int rank, int world, int32_t*
  *   Symmetric; a frame without keypoints scores 0 with every other.
  * Selection: position a ranks its in-scope candidates by (score descending, position ascending) and nominates the first `partners` of them
  * whose score is >= min_score (partners == 0: every candidate with score >= min_score).  A pair is kept when either side nominates it.
- * Scope: all pairs (window == 0) or the positions with |a - b| < window (mi355_pair_schedule's window).
+ * Scope: all pairs (window == 0) or the positions with |a - b| < window (mi355_pair_schedule's window); window >= n is all pairs.
+ * Edges of the definition (tests/test_gpu_screen_edges.py): top_k is any multiple of 32, a power of two or not, with the same list order;
+ * +-0 responses are equal, +infinity is the strongest, negative and denormal responses order as numbers.
+ * A score is at most top_k, so min_score > top_k nominates nothing and the schedule is empty; min_score <= 0 acts as 0.  partners above
+ * the number of candidates nominates all of them.  world > n is valid: rank r owns the rows a == r (mod world), so the ranks from n - 1
+ * on own no pair and return an empty list.  n = 0 and n = 1 give an empty schedule (and an n x n matrix of -1).
  * Limits: n <= 16384 (the n x n score matrix is 1 GB there).  MI355_ERR_ARG, with a message naming the value, for an unknown or duplicate
  * id, top_k outside {32, 64, ..., 512}, partners < 0, ratio_pct outside [1, 100], window == 1 or < 0, and a bad rank / world.
  * Results are identical across contexts and devices for the same features: every rank of a multi-GPU run computes the whole screen after

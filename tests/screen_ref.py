@@ -94,3 +94,83 @@ def select_pairs(S, partners, min_score, window=0, rank=0, world=1):
             if b in nom[a] or a in nom[b]:
                 out.append((a, b))
     return np.array(out, np.int32).reshape(-1, 2)
+
+
+# ---- the batched form: many pairs of short lists at once --------------------------------------------------------------------------------------
+PAIR_CHUNK = 1 << 22          # the device scores the flat pair list in launches of this many pairs; score_matrix_batched walks it the same way
+
+
+def pair_list(n, window=0):
+    """the in-scope pairs (a, b), a < b, in (a, b) order: the flat list the device scores (int64 arrays)"""
+    win = window if window else n
+    cnt = np.clip(np.minimum(n - 1 - np.arange(n, dtype=np.int64), win - 1), 0, None)
+    a = np.repeat(np.arange(n, dtype=np.int64), cnt)
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    b = a + 1 + (np.arange(len(a), dtype=np.int64) - off[a])
+    return a, b
+
+
+def chunk_bases(total, chunk=PAIR_CHUNK):
+    """the flat index each launch starts at"""
+    return list(range(0, total, chunk))
+
+
+def list_codes(lists):
+    """(code [n, R], DC): every distinct row gets a code, DC the exact int64 distances of the codes; the last code is the padding of a short
+    list, at distance INF from everything (so a padded row is never a neighbour and a one-row list has d2 = INF)"""
+    n = len(lists)
+    lens = np.array([len(l) for l in lists], np.int64)
+    R = max(1, int(lens.max()) if n else 1)
+    rows = np.concatenate([np.asarray(l, np.uint8).reshape(-1, 128) for l in lists] + [np.zeros((0, 128), np.uint8)])
+    uniq, inv = np.unique(rows, axis=0, return_inverse=True)
+    U = len(uniq)
+    u = uniq.astype(np.int64)
+    DC = np.full((U + 1, U + 1), INF, np.int64)
+    DC[:U, :U] = (u * u).sum(1)[:, None] + (u * u).sum(1)[None, :] - 2 * (u @ u.T)
+    code = np.full((n, R), U, np.int64)
+    code[np.arange(R)[None, :] < lens[:, None]] = np.asarray(inv).reshape(-1)
+    return code, DC
+
+
+def _nn_batched(D, ratio_pct):
+    """per pair and query row: (nn, valid and passing) over D [P, Rq, Rt]"""
+    nn = np.argmin(D, axis=2)                               # the first minimum: the lower position
+    d1 = np.take_along_axis(D, nn[:, :, None], 2)[:, :, 0]
+    d2 = np.sort(D, axis=2)[:, :, 1] if D.shape[2] >= 2 else np.full(d1.shape, INF, np.int64)
+    return nn, (d1 < INF) & passes_nd(d1, d2, ratio_pct)
+
+
+def passes_nd(d1, d2, ratio_pct):
+    if ratio_pct >= 100:
+        return np.ones(d1.shape, bool)
+    return np.int64(10000) * d1 < np.int64(ratio_pct) * np.int64(ratio_pct) * d2
+
+
+def score_pairs_batched(codes, a, b, ratio_pct=80):
+    """scores of the pairs (a[k], b[k]) from list_codes(lists); equal to score_lists(lists[a[k]], lists[b[k]], ratio_pct)"""
+    code, DC = codes
+    R = code.shape[1]
+    out = np.zeros(len(a), np.int32)
+    step = max(1, (1 << 21) // (R * R))
+    for s in range(0, len(a), step):
+        ca, cb = code[a[s:s + step]], code[b[s:s + step]]
+        D = DC[ca[:, :, None], cb[:, None, :]]
+        na, oka = _nn_batched(D, ratio_pct)
+        nb, okb = _nn_batched(D.transpose(0, 2, 1), ratio_pct)
+        back = np.take_along_axis(nb, na, 1) == np.arange(R)[None, :]
+        out[s:s + step] = np.count_nonzero(oka & back & np.take_along_axis(okb, na, 1), axis=1)
+    return out
+
+
+def score_matrix_batched(lists, ratio_pct=80, window=0, chunk=PAIR_CHUNK):
+    """score_matrix for lists of a few rows, launch by launch as the device walks the flat pair list"""
+    n = len(lists)
+    S = np.full((n, n), -1, np.int32)
+    a, b = pair_list(n, window)
+    codes = list_codes(lists)
+    for base in chunk_bases(len(a), chunk):
+        g = slice(base, min(base + chunk, len(a)))
+        s = score_pairs_batched(codes, a[g], b[g], ratio_pct)
+        S[a[g], b[g]] = s
+        S[b[g], a[g]] = s
+    return S

@@ -1,6 +1,6 @@
 """GPU: the descriptor-screened pair schedule (mi355_screen_scores_dev / mi355_screen_pairs, csrc/screen.hip).
 
-  * scores: bit for bit equal to tests/screen_ref.py on 40 synthetic 1280x960 frames (all pairs) at top_k 32 / 256 / 512 and
+  * scores: bit for bit equal to tests/screen_ref.py on 40 synthetic 1280x960 frames (all pairs) at top_k 32 / 160 / 256 / 512 and
     ratio_pct 80 / 100, with SetFeatures frames of 5 and 0 keypoints and one whose responses tie across the K boundary, and on keep-all
     frames (nfeatures <= 0, keypoints not in response order) of more than 2048 keypoints;
   * an unordered survey: the same 40 frames (a 4-row serpentine) with their ids permuted: a window of 3 over that order does not connect
@@ -60,7 +60,7 @@ def ref_lists(feats_by_id, ids, top_k):
     return [sr.top_list(feats_by_id[i][0], feats_by_id[i][1], top_k) for i in ids]
 
 
-@pytest.mark.parametrize("top_k", [32, 256, 512])
+@pytest.mark.parametrize("top_k", [32, 160, 256, 512])
 def test_scores_equal_restatement(survey, top_k):
     ctx, _, feats, extra = survey
     ids = list(range(F)) + sorted(extra)

@@ -1325,3 +1325,40 @@ extern "C" int mi355_debug_rand_stream(mi355_ctx* ctx, uint32_t seed, int32_t* o
     return MI355_OK;
 }
 
+
+// diagnostic (tests/test_gpu_ransac_edges.py): the device-built draw tables of mi_ransac_tables for n in [n_lo, n_hi] -- what a batch whose n is
+// known only on the device reads -- as uint16 [n_hi - n_lo + 1][4999][4]
+extern "C" int mi355_debug_draw_tables(mi355_ctx* ctx, uint32_t seed, int n_lo, int n_hi, uint16_t* out) {
+    if (!out || n_lo < 4 || n_hi < n_lo || n_hi > MI355_MAX_SELECTED) return MI355_ERR_ARG;
+    LOCKED_PROLOGUE
+    const size_t one = (size_t)MAX_DRAWS * 4;
+    const uint16_t* d_tables = nullptr;
+    const int rc = mi_ransac_tables(ctx, seed, &d_tables);              // (the ctx stream now waits for the slot's build)
+    if (rc != MI355_OK) return rc;
+    MI_HIP(hipMemcpyAsync(out, d_tables + one * (size_t)(n_lo - 4), one * (size_t)(n_hi - n_lo + 1) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    return MI355_OK;
+}
+
+// diagnostic (tests/test_gpu_ransac_edges.py): mi_ransac_batch on host arrays p1 / p2 [n_pairs][400] with n[pair] correspondences each, the
+// records back to the host.  host_tables != 0: the host knows every n (one host-built table per distinct n, as mi355_ransac2d); 0: n is known
+// on the device only (the seed's device-built tables of every n, as mi355_match_pairs)
+extern "C" int mi355_debug_ransac_batch(mi355_ctx* ctx, const mi355_sfpoint* p1, const mi355_sfpoint* p2, const int32_t* n, int n_pairs, float dist, int sample_times,
+                                        uint32_t seed, int min_keep, int host_tables, mi355_pair_result* out_records) {
+    if (!p1 || !p2 || !n || !out_records || n_pairs <= 0) return MI355_ERR_ARG;
+    LOCKED_PROLOGUE
+    for (int i = 0; i < n_pairs; i++)
+        if (n[i] > MI355_MAX_SELECTED) { ctx->set_error("debug_ransac_batch: more than 400 correspondences in one pair"); return MI355_ERR_ARG; }
+    DevBuf& d1 = ctx->buf("debug_rb_p1"); DevBuf& d2 = ctx->buf("debug_rb_p2"); DevBuf& dn = ctx->buf("debug_rb_n"); DevBuf& dres = ctx->buf("debug_rb_out");
+    const size_t pb = sizeof(mi355_sfpoint) * MI355_MAX_SELECTED * (size_t)n_pairs;
+    MI_HIP(d1.reserve(pb)); MI_HIP(d2.reserve(pb)); MI_HIP(dn.reserve(sizeof(int) * (size_t)n_pairs)); MI_HIP(dres.reserve(sizeof(mi355_pair_result) * (size_t)n_pairs));
+    MI_HIP(hipMemcpyAsync(d1.p, p1, pb, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(d2.p, p2, pb, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP(hipMemcpyAsync(dn.p, n, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = mi_ransac_batch(ctx, d1.as<mi355_sfpoint>(), d2.as<mi355_sfpoint>(), dn.as<int>(), host_tables ? n : nullptr, n_pairs, MI355_MAX_SELECTED, dist, sample_times,
+                                   seed, dres.as<mi355_pair_result>(), min_keep);
+    if (rc != MI355_OK) return rc;
+    MI_HIP(hipMemcpyAsync(out_records, dres.p, sizeof(mi355_pair_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    return MI355_OK;
+}

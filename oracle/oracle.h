@@ -44,6 +44,18 @@ int  orc_rand(orc_glibc_rand* g);
 /* mosaicimage.h:1729-2035; returns 1/0 like the bool */
 int  orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
                   unsigned seed, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9]);
+/* The same loop (one body, shared) with a record of its bookkeeping, for the tests that pick inputs by what the loop does on them:
+ *   took[d]      (4999 bytes) 1 when draw d took a hypothesis slot, 0 when its 4-point residual skipped it; written for d < draws
+ *   supports[t]  (5000 ints) support of slot t, t < n_slots
+ *   n_slots      slots filled (the stopper's included);  draws: draws consumed
+ *   stop_slot / stop_draw  the slot and draw at which support / n > 0.99 ended the loop, -1 if it never did
+ *   win_slot / win_support the winner (first strict maximum up to the stop), -1 / 0 when no support was ever positive
+ * keep_going != 0: the stop is recorded but the draws run on to the slot and draw limits, so that the supports behind the stop are
+ * known; winner, inliers, H and the return value are those of the loop that stops. */
+typedef struct { int32_t n_slots, draws, stop_slot, stop_draw, win_slot, win_support; } orc_ransac_trace;
+int  orc_ransac2d_trace(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
+                        unsigned seed, int keep_going, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9],
+                        orc_ransac_trace* tr, uint8_t* took, int32_t* supports);
 
 /* ---- oracle_select.c ----------------------------------------------------- */
 /* MosaicWithoutPos.cpp:4977-5028; matches = (queryIdx,trainIdx) pairs already sorted */

@@ -48,10 +48,14 @@ static void apply3(const float* M, float x, float y, float* X, float* Y)   /* ma
     *Y = (M[3] * x + M[4] * y + M[5]) / (M[6] * x + M[7] * y + 1.0f);
 }
 
-int orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
-                 unsigned seed, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9])
+/* The loop of Ransac2D, shared by orc_ransac2d and orc_ransac2d_trace (tr == NULL: no record is kept).  With keep_going the 0.99
+ * stop is noted but the loop runs on, so that the supports behind the stop are known; the winner stays the one the stop left. */
+static int ransac2d_loop(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
+                         unsigned seed, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9],
+                         int keep_going, orc_ransac_trace* tr, uint8_t* took, int32_t* supports)
 {
     *n_in = 0;
+    if (tr) { tr->n_slots = 0; tr->stop_slot = -1; tr->stop_draw = -1; tr->win_slot = -1; tr->win_support = 0; tr->draws = 0; }
     if (n <= 0) return 0;                                   /* :1739-1744 */
     float d2 = dist * dist;                                 /* :1757 */
     if (n < 4) return 0;                                    /* :1760-1761 */
@@ -61,10 +65,12 @@ int orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist
     if (sample_times < 1) return 0;
     float (*hyp)[9] = (float (*)[9])calloc((size_t)sample_times, sizeof(float[9]));
     orc_glibc_rand g; orc_srand(&g, seed);                  /* :1777 */
-    int maxSupport = 0, maxIdx = 0, real = 0;
+    int maxSupport = 0, maxIdx = 0, real = 0, stopped = 0, slots = 0, draws = 0;
     for (int t = 0; t < sample_times;) {                    /* :1785 */
         real++;
         if (real >= maxTimes) break;                        /* :1789-1792 */
+        draws = real;
+        if (took) took[real - 1] = 0;
         int s[4];
         do { for (int i = 0; i < 4; i++) s[i] = orc_rand(&g) % n; }      /* :1801-1813 */
         while (s[0] == s[1] || s[0] == s[2] || s[0] == s[3] || s[1] == s[2] || s[1] == s[3] || s[2] == s[3]);
@@ -86,12 +92,20 @@ int orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist
             float dd = dx * dx + dy * dy;
             if (dd < d2) support++;
         }
-        if (support > maxSupport) {                         /* :1905-1917 */
+        if (took) took[real - 1] = 1;
+        if (supports) supports[t] = support;
+        slots = t + 1;
+        if (!stopped && support > maxSupport) {             /* :1905-1917 */
             maxSupport = support; maxIdx = t;
-            if ((float)maxSupport * invn > 0.99f) break;
+            if ((float)maxSupport * invn > 0.99f) {
+                if (tr) { tr->stop_slot = t; tr->stop_draw = real - 1; }
+                if (!(tr && keep_going)) break;
+                stopped = 1;                                /* trace only: the loop is over, the draws go on */
+            }
         }
         t++;
     }
+    if (tr) { tr->n_slots = slots; tr->draws = draws; tr->win_slot = maxSupport > 0 ? maxIdx : -1; tr->win_support = maxSupport; }
     int cnt = 0;
     for (int i = 0; i < n; i++) {                           /* :1922-1944, true-division form */
         float bx, by; apply3(hyp[maxIdx], p2[i].x, p2[i].y, &bx, &by);
@@ -111,4 +125,17 @@ int orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist
     free(hyp);
     if (cnt < 4) return 0;                                  /* :2024-2032 */
     return 1;
+}
+
+int orc_ransac2d(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
+                 unsigned seed, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9])
+{
+    return ransac2d_loop(p1, p2, n, dist, sample_times, seed, in1, in2, n_in, H, 0, NULL, NULL, NULL);
+}
+
+int orc_ransac2d_trace(const orc_sfpoint* p1, const orc_sfpoint* p2, int n, float dist, int sample_times,
+                       unsigned seed, int keep_going, orc_sfpoint* in1, orc_sfpoint* in2, int* n_in, float H[9],
+                       orc_ransac_trace* tr, uint8_t* took, int32_t* supports)
+{
+    return ransac2d_loop(p1, p2, n, dist, sample_times, seed, in1, in2, n_in, H, keep_going, tr, took, supports);
 }

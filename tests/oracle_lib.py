@@ -17,6 +17,7 @@ KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 CHIPINFO = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("img", "<i4"),
                      ("sx", "<f4"), ("sy", "<f4"), ("quad", "<f4", (8,))])
 
+RANSAC_TRACE = np.dtype([("n_slots", "<i4"), ("draws", "<i4"), ("stop_slot", "<i4"), ("stop_draw", "<i4"), ("win_slot", "<i4"), ("win_support", "<i4")])
 SURF_STATS = np.dtype([("maxima", "<i8"), ("kept", "<i8"), ("dropped", "<i8"), ("short_ori", "<i8"), ("clamped", "<i8"), ("layer_mask", "<i4", (4,))])
 
 fp = C.POINTER(C.c_float)
@@ -84,6 +85,25 @@ class Oracle:
         ok = self.L.orc_ransac2d(_p(p1), _p(p2), n, C.c_float(dist), sample_times, C.c_uint(seed),
                                  _p(i1), _p(i2), C.byref(nin), _p(H))
         return ok, i1[:nin.value].copy(), i2[:nin.value].copy(), H
+
+    def ransac2d_trace(self, p1, p2, dist, sample_times, seed, keep_going=False):
+        """orc_ransac2d_trace: ((ok, in1, in2, H) as ransac2d, trace).  trace: dict of n_slots, draws, stop_slot, stop_draw, win_slot,
+        win_support, took (uint8 per draw consumed) and supports (int32 per slot filled); keep_going runs the draws on past the
+        0.99 stop (the result stays that of the loop that stops)."""
+        n = len(p1)
+        i1 = np.zeros(max(n, 1), SFPOINT)
+        i2 = np.zeros(max(n, 1), SFPOINT)
+        nin = C.c_int(0)
+        H = np.zeros(9, np.float32)
+        tr = np.zeros(1, RANSAC_TRACE)
+        took = np.zeros(4999, np.uint8)
+        sup = np.zeros(5000, np.int32)
+        ok = self.L.orc_ransac2d_trace(_p(p1), _p(p2), n, C.c_float(dist), int(sample_times), C.c_uint(seed), int(bool(keep_going)),
+                                       _p(i1), _p(i2), C.byref(nin), _p(H), _p(tr), _p(took), _p(sup))
+        t = {k: int(tr[0][k]) for k in RANSAC_TRACE.names}
+        t["took"] = took[:t["draws"]].copy()
+        t["supports"] = sup[:t["n_slots"]].copy()
+        return (ok, i1[:nin.value].copy(), i2[:nin.value].copy(), H), t
 
     # ---- selection / matching --------------------------------------------
     def select(self, matches, kp1, kp2, nMatch, w, h, gx=3, gy=3):

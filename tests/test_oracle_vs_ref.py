@@ -48,7 +48,7 @@ def test_ransac_degenerate_inputs(oracle, ref):
     """the degenerate correspondences of tests/test_gpu_parity.py::test_ransac2d_degenerate_inputs_vs_oracle, oracle vs the
     reference's own code"""
     import numpy as np
-    from tests.test_gpu_parity import _degenerate_case
+    from tests.ransac_patterns import _degenerate_case
     rng = np.random.default_rng(77)
     for kind in range(5):
         for m in (4, 9, 60, 250, 400):

@@ -22,6 +22,9 @@ from .capi import (  # noqa: F401
     TieParams, tie_params, TIE_REPORT, TIE_NONE, TIE_REFINED, TIE_EDGE, TIE_FLAT, TIE_LOW, TIE_BORDER,
     TIE_FLAG_NOT_ACCEPTED, TIE_FLAG_NO_FRAME, TIE_FLAG_BAD_RECORD, TIE_FLAG_DEMOTED,
     LocalWarpParams, LOCAL_WARP_REPORT, local_warp_params, local_warp_stats_len, tie_residual_stats_host, solve_local_warps,
+    VerifyParams, verify_params, PAIR_EDGE, PAIR_CYCLE, PAIR_RESIDUAL, VERIFY_REPORT, VERIFY_SUMMARY, EDGE_USABLE, EDGE_TESTABLE,
+    VERDICT_NOT_USED, VERDICT_VERIFIED, VERDICT_ADMITTED, VERDICT_BRIDGE, VERDICT_REJECTED, VERDICT_UNDECIDED, VERIFY_SUSPECT,
+    pair_edges_host, pair_cycles_host, pair_residuals_host, verify_pairs_results,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

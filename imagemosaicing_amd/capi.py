@@ -147,6 +147,24 @@ assert BLOCK_GAIN_STATS.itemsize == 72 and C.sizeof(BlockGainParams) == 32
 assert C.sizeof(Camera) == 72 and C.sizeof(UndistortParams) == 48
 
 
+# ---- pair verification (mi355_pair_edges_*, mi355_pair_cycles_*, mi355_pair_residuals_*, mi355_verify_pairs_*; csrc/verify.hip) ----
+class VerifyParams(C.Structure):
+    _fields_ = [("cycle_tol", C.c_double), ("gate_abs", C.c_double), ("gate_k", C.c_double), ("max_rounds", C.c_int32), ("bridges", C.c_int32)]
+
+
+PAIR_EDGE = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("flags", "<i4"), ("box", "<f4", (4,)), ("F", "<f8", (9,)), ("B", "<f8", (9,))])
+PAIR_CYCLE = np.dtype([("n_ok", "<i4"), ("n_bad", "<i4"), ("min_e2", "<f8")])
+PAIR_RESIDUAL = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_used", "<i4"), ("n_den", "<i4"), ("sum_r2", "<f8"), ("max_r2", "<f8")])
+VERIFY_REPORT = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("verdict", "<i4"), ("n_ok", "<i4"), ("n_bad", "<i4"), ("round", "<i4"),
+                          ("flags", "<i4"), ("min_e2", "<f8"), ("rms", "<f8"), ("max_r2", "<f8"), ("reserved", "<f8")])
+VERIFY_SUMMARY = np.dtype([("count", "<i4", (8,)), ("rounds", "<i4"), ("n_labelled", "<i4"), ("reserved", "<i4", (2,)), ("s", "<f8"), ("gate", "<f8")])
+EDGE_USABLE, EDGE_TESTABLE = 1, 2
+VERDICT_NOT_USED, VERDICT_VERIFIED, VERDICT_ADMITTED, VERDICT_BRIDGE, VERDICT_REJECTED, VERDICT_UNDECIDED = 0, 1, 2, 3, 4, 5
+VERIFY_SUSPECT = 1
+assert PAIR_EDGE.itemsize == 176 and PAIR_CYCLE.itemsize == 16 and PAIR_RESIDUAL.itemsize == 32
+assert C.sizeof(VerifyParams) == 32 and VERIFY_REPORT.itemsize == 64 and VERIFY_SUMMARY.itemsize == 64
+
+
 class Mi355Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355 error %d: %s" % (code, msg))
@@ -1026,6 +1044,41 @@ class Context:
                                                   C.byref(p), _p(grids), _p(rep)))
         return grids, rep
 
+    # ---- pair verification (mi355_pair_edges_dev, mi355_pair_cycles_dev, mi355_pair_residuals_dev, mi355_verify_pairs_dev; csrc/verify.hip) ------
+    def PairEdgesDev(self, d_results, n, n_images, d_out):
+        """mi355_pair_edges_dev: one PAIR_EDGE per device pair record, device to device (ctx stream)"""
+        self._chk(self.L.mi355_pair_edges_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), int(n_images), C.c_void_p(int(d_out or 0) or None)))
+
+    def PairCyclesDev(self, edges, n_images, cycle_tol=6.0):
+        """mi355_pair_cycles_dev: the triangle counts of host PAIR_EDGE records, formed on the device; returns PAIR_CYCLE [n]"""
+        e = np.ascontiguousarray(edges, PAIR_EDGE)
+        out = np.zeros(len(e), PAIR_CYCLE)
+        self._chk(self.L.mi355_pair_cycles_dev(self._h, _p(e), len(e), int(n_images), C.c_double(cycle_tol), _p(out)))
+        return out
+
+    def PairResidualsDev(self, d_results, n, h9s, label, d_out):
+        """mi355_pair_residuals_dev: one PAIR_RESIDUAL per device pair record under the transforms h9s (float32 [n_images, 9], host) and the
+        labels (int32 [n_images], host, or None), device to device (ctx stream)"""
+        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+        lb = None if label is None else np.ascontiguousarray(label, np.int32)
+        assert lb is None or len(lb) == len(h9s)
+        self._chk(self.L.mi355_pair_residuals_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), _p(h9s), _p(lb), len(h9s),
+                                                  C.c_void_p(int(d_out or 0) or None)))
+
+    def VerifyPairsDev(self, d_results, n_pairs, n_images, d_out, fixed=None, params=None, **kw):
+        """mi355_verify_pairs_dev: n_pairs device pair records d_results -> d_out (may be d_results) with every usable pair that is not kept
+        demoted.  Returns (label int32 [n_images], transforms IMAGE_TRANSFORM [n_images], report VERIFY_REPORT [n_pairs], summary
+        VERIFY_SUMMARY scalar).  params: VerifyParams (verify_params()) or its keyword fields."""
+        p = params if params is not None else verify_params(**kw)
+        ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
+        assert ff is None or len(ff) == int(n_images)
+        m = max(int(n_images), 1)
+        label, tr = np.zeros(m, np.int32), np.zeros(m, IMAGE_TRANSFORM)
+        rep, summ = np.zeros(max(int(n_pairs), 0), VERIFY_REPORT), np.zeros(1, VERIFY_SUMMARY)
+        self._chk(self.L.mi355_verify_pairs_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), int(n_images), _p(ff), C.byref(p),
+                                                C.c_void_p(int(d_out or 0) or None), _p(label), _p(tr), _p(rep), _p(summ)))
+        return label, tr, rep, summ[0]
+
     # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
@@ -1317,6 +1370,69 @@ def local_warp_params(grid_x=None, grid_y=None, min_ties=None, max_residual=None
         if v is not None:
             setattr(p, name, float(v))
     return p
+
+
+def verify_params(cycle_tol=None, gate_abs=None, gate_k=None, max_rounds=None, bridges=None):
+    """mi355_verify_params: the library's defaults (6.0, 3.0, 4.0, 8, 1) with the given fields replaced"""
+    p = VerifyParams()
+    load_library().mi355_default_verify_params(C.byref(p))
+    for name, v in (("cycle_tol", cycle_tol), ("gate_abs", gate_abs), ("gate_k", gate_k)):
+        if v is not None:
+            setattr(p, name, float(v))
+    for name, v in (("max_rounds", max_rounds), ("bridges", bridges)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def _host_rc(L, rc):
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+
+
+def pair_edges_host(results, n_images):
+    """mi355_pair_edges_host (host only): PAIR_EDGE [n] of host PAIR_RESULT records"""
+    L = load_library()
+    r = np.ascontiguousarray(results, PAIR_RESULT)
+    out = np.zeros(len(r), PAIR_EDGE)
+    _host_rc(L, L.mi355_pair_edges_host(_p(r), len(r), int(n_images), _p(out)))
+    return out
+
+
+def pair_cycles_host(edges, n_images, cycle_tol=6.0):
+    """mi355_pair_cycles_host (host only): PAIR_CYCLE [n] of PAIR_EDGE records"""
+    L = load_library()
+    e = np.ascontiguousarray(edges, PAIR_EDGE)
+    out = np.zeros(len(e), PAIR_CYCLE)
+    _host_rc(L, L.mi355_pair_cycles_host(_p(e), len(e), int(n_images), C.c_double(cycle_tol), _p(out)))
+    return out
+
+
+def pair_residuals_host(results, h9s, label=None):
+    """mi355_pair_residuals_host (host only): PAIR_RESIDUAL [n] of host PAIR_RESULT records under h9s (float32 [n_images, 9]) and label"""
+    L = load_library()
+    r = np.ascontiguousarray(results, PAIR_RESULT)
+    h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+    lb = None if label is None else np.ascontiguousarray(label, np.int32)
+    assert lb is None or len(lb) == len(h9s)
+    out = np.zeros(len(r), PAIR_RESIDUAL)
+    _host_rc(L, L.mi355_pair_residuals_host(_p(r), len(r), _p(h9s), _p(lb), len(h9s), _p(out)))
+    return out
+
+
+def verify_pairs_results(results, n_images, fixed=None, params=None, **kw):
+    """mi355_verify_pairs_results (host only): -> (records with the pairs that are not kept demoted, label int32 [n_images], transforms
+    IMAGE_TRANSFORM [n_images], report VERIFY_REPORT [n], summary VERIFY_SUMMARY scalar)"""
+    L = load_library()
+    r = np.ascontiguousarray(results, PAIR_RESULT)
+    p = params if params is not None else verify_params(**kw)
+    ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
+    assert ff is None or len(ff) == int(n_images)
+    m = max(int(n_images), 1)
+    out, label, tr = np.zeros(len(r), PAIR_RESULT), np.zeros(m, np.int32), np.zeros(m, IMAGE_TRANSFORM)
+    rep, summ = np.zeros(len(r), VERIFY_REPORT), np.zeros(1, VERIFY_SUMMARY)
+    _host_rc(L, L.mi355_verify_pairs_results(_p(r), len(r), int(n_images), _p(ff), C.byref(p), _p(out), _p(label), _p(tr), _p(rep), _p(summ)))
+    return out, label, tr, rep, summ[0]
 
 
 def local_warp_stats_len(n, grid_x, grid_y):

@@ -789,13 +789,18 @@ extern "C" int mi355_compact_accepted_dev(mi355_ctx* ctx, const mi355_pair_resul
     return MI355_OK;
 }
 
+// the launch for callers that hold the ctx lock (verify.hip); n > 0
+int mi_pair_moments(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, mi355_pair_moments* d_out) {
+    hipLaunchKernelGGL(pair_moments_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_results, n, d_out);
+    MI_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
 extern "C" int mi355_pair_moments_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, mi355_pair_moments* d_out) {
     LOCKED_PROLOGUE
     if (n < 0 || (n > 0 && (!d_results || !d_out))) return MI355_ERR_ARG;
     if (n == 0) return MI355_OK;
-    hipLaunchKernelGGL(pair_moments_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, d_results, n, d_out);
-    MI_HIP(hipGetLastError());
-    return MI355_OK;
+    return mi_pair_moments(ctx, d_results, n, d_out);
 }
 
 // mi355_allgather_results' protocol (counts first, a rank with bad arguments sends -1, payload padded to the largest count) on the moments of

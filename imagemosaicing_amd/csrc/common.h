@@ -232,6 +232,7 @@ void mi_surf_release(mi355_ctx*);
 int  mi_kept_frame_slot(mi355_ctx*, int img_id, int w, int h, int ws, const char* who, uint8_t** d_frame);   // frames.hip: the kept buffer of img_id, ready for a new frame
 void mi_frames_release(mi355_ctx*);
 int mi_compact_accepted(mi355_ctx* ctx, const mi355_pair_result* d_in, int n, mi355_pair_result* d_out, int* d_n_out);     // comm.hip
+int mi_pair_moments(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, mi355_pair_moments* d_out);                   // comm.hip: mi355_pair_moments_dev's launch, n > 0
 
 // host helpers
 #include "host_error.h"

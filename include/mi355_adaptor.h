@@ -246,6 +246,40 @@ inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned s
     return rc;
 }
 
+// The window form with pair verification (mi355_verify_pairs_results, "pair verification" in mi355_mosaic.h) between the pair stage and the
+// flattening: the accepted pairs whose homographies contradict their neighbours are demoted, so the list holds the kept pairs'
+// correspondences only.  The flat list carries no homographies, so there is no flat form of the verification: it runs here, on the records.
+// verify == NULL: the library's defaults.  summary (may be NULL) receives the counts per verdict.  An error of the verification (for
+// example MI355_ERR_FAILED, "no pair could be verified": mi355_last_error(NULL)) leaves vecMatchPairs as it was.
+inline int GetMatchedPairsOneToAllSIFT(int nImages, float ransacDist, unsigned seed, const int* fixedFlags,
+                                       std::vector<MI355_NS MatchPointPairs>& vecMatchPairs, int window, const mi355_verify_params* verify,
+                                       mi355_verify_summary* summary) {
+    mi355_ctx* c = context();
+    if (!c) return -1;
+    int n_pairs = 0;
+    mi355_pair_schedule(nImages, window, 0, 1, NULL, 0, &n_pairs);
+    if (n_pairs == 0) return 0;
+    std::vector<int32_t> pairs((size_t)n_pairs * 2), label((size_t)nImages);
+    std::vector<mi355_image_transform> tr((size_t)nImages);
+    mi355_pair_schedule(nImages, window, 0, 1, &pairs[0], n_pairs, &n_pairs);
+    mi355_pair_result* res = (mi355_pair_result*)std::malloc(sizeof(mi355_pair_result) * (size_t)n_pairs);
+    if (!res) return -1;
+    int rc = mi355_match_pairs(c, &pairs[0], n_pairs, ransacDist, seed, res);
+    if (rc == MI355_OK) rc = mi355_verify_pairs_results(res, n_pairs, nImages, fixedFlags, verify, res, &label[0], &tr[0], NULL, summary);
+    if (rc == MI355_OK) {
+        mi355_match_point_pairs* v = NULL; int n = 0;
+        rc = mi355_results_to_match_pairs(res, n_pairs, fixedFlags, &v, &n);
+        if (rc == MI355_OK) {
+            const size_t old = vecMatchPairs.size();
+            vecMatchPairs.resize(old + n);
+            if (n) std::memcpy(&vecMatchPairs[old], v, sizeof(mi355_match_point_pairs) * n);
+            mi355_free(v);
+        }
+    }
+    std::free(res);
+    return rc;
+}
+
 // The same with the descriptor-screened schedule (mi355_screen_pairs) in place of the window: the pairs of images 0 .. nImages - 1 that the
 // screen keeps are matched, and vecMatchPairs is filled exactly as the window form fills it.  screen NULL: mi355_default_screen_params
 // (all pairs in scope); screen->window >= 2 screens the window's pairs only.

@@ -1267,6 +1267,134 @@ int  mi355_local_register_results(mi355_ctx* ctx, const mi355_pair_result* resul
                                   const int* ws, int n, const float* h9s, const mi355_local_warp_params* p, float* grids_out,
                                   mi355_local_warp_report* report_out);
 
+/* ---- pair verification (opt-in; csrc/verify.hip, csrc/verify.h, csrc/verify_loop.cpp) -------------------------------------------------
+ * A pair is accepted when RANSAC finds more than min_inliers ties that agree with one homography.  On repetitive ground that also happens
+ * for frames that do not overlap, or that overlap and were matched one period off, and ONE such record bends the linear alignment by
+ * hundreds of pixels (DESIGN).  This stage sits between the pair stage and the alignment: it keeps the pairs whose homographies close
+ * triangles with their neighbours, aligns on them, admits the rest by their residual against that alignment, and demotes what is left.
+ * Nothing calls it unless asked; no other entry point changes its bits.
+ * Arithmetic.  All of it is double unless it says float; every operation is rounded separately, in the order written, no contraction.
+ * Map.  P(M, x, y) is local registration's: den = (M6*x + M7*y) + M8;  X = ((M0*x + M1*y) + M2) / den;  Y = ((M3*x + M4*y) + M5) / den.
+ *   A den that is not finite or <= 0 is a DEN FAILURE.
+ *
+ * Stage 1: edges, one per record (device: a wave per record; the host twin gives the same bytes).
+ *   A record is USABLE iff accepted != 0, 1 <= n_in <= 400, 0 <= i, j < n_images and i != j (tie refinement's rule).  Any other record gives
+ *   a zero edge with i, j, n_in copied and flags = 0.  For a usable record:
+ *   F[q] = (double)H[q], q = 0..7, F[8] = 1.0 (the record's H[8] is Ransac2D's max residual, not a matrix entry): F maps frame j to frame i.
+ *   B = the inverse of F by local registration's adjugate formula (A0..A8, det, I[q] = A[q] / det with a..i = F[0..8]).
+ *   box = (min x, min y, max x, max y) over b[0 .. n_in): floats, frame j coordinates, the support of F.  Minimum and maximum are those of
+ *     the total order of the float bit patterns (-0 below +0, a NaN beyond the infinity of its sign): the box does not depend on the order.
+ *   flags: bit 0 USABLE; bit 1 TESTABLE: all 18 of F and B are finite.  A NaN among them is stored as the quiet NaN 0x7ff8000000000000
+ *     (so is a NaN sum_r2 below): the sign and payload of an arithmetic NaN differ between processors, the stored bytes do not.
+ *   Two usable records of the same unordered frame pair are MI355_ERR_ARG wherever the adjacency is built (the cycle and the verify entry
+ *   points; the message names both record indexes): the check runs on the host, on the edges.
+ *
+ * Stage 2: cycles.  The host builds a CSR adjacency of the testable edges (per frame its neighbours ascending; with each neighbour the edge
+ *   index and one bit: the frame is the edge's i) and uploads it.  Device: a wave per edge, four per workgroup; the lanes stride over the
+ *   shorter of the two lists (frame i's when they are equally long), find each candidate in the other by binary search, and the counts are
+ *   reduced across the wave, no atomics.  For a testable edge e = (i, j) and every frame k adjacent to both:
+ *     M_kj = the map j -> k of the edge between j and k: its F if that edge's i is k, else its B;  M_ik = the map k -> i, likewise.
+ *     Control points: (x0, y0, x1, y1) = (double)box, xm = (x0 + x1) * 0.5, ym = (y0 + y1) * 0.5; the nine (x, y), y outer over
+ *       {y0, ym, y1}, x inner over {x0, xm, x1}.
+ *     Per point c: d = P(F_e, c);  t = P(M_kj, c);  l = P(M_ik, t.x, t.y);  e2 = (l.x - d.x)*(l.x - d.x) + (l.y - d.y)*(l.y - d.y).
+ *     A den failure in any of the three maps at any point makes the triangle BAD.  Otherwise E = the largest e2 of the nine (a NaN e2
+ *     makes E NaN); a non-finite E is BAD; OK iff E <= cycle_tol * cycle_tol.
+ *   Per edge: n_ok, n_bad, and min_e2 = the smallest E over the triangles without a den failure (+inf if there are none; a NaN E never
+ *   lowers it).  The three do not depend on order, launch geometry or entry point.  Edges that are not testable get 0, 0, +inf.
+ *
+ * Pair residuals of the records under transforms h9s (n_images x 9 floats) and label (n_images int32, may be NULL): one launch, a wave per
+ *   record.  A record is MEASURED iff it is usable, both frames have label != 0 (or label == NULL) and both h9s[9k + 8] != 0.  Per tie in
+ *   order, H_k = the doubles of h9s[9k ..]: ci = P(H_i, a), cj = P(H_j, b); a den failure counts in n_den and adds nothing; otherwise
+ *   rx = cj.x - ci.x, ry = cj.y - ci.y, r2 = rx*rx + ry*ry, sum_r2 = sum_r2 + r2, max_r2 = r2 > max_r2 ? r2 : max_r2, n_used + 1.
+ *   The sum is sequential in tie order (the lanes form the r2 values, one lane adds them).  Records that are not measured get n_used = 0 and
+ *   zeros (i, j copied).
+ *
+ * Stage 3: the loop (host only).  Parameters: cycle_tol, gate_abs, gate_k, max_rounds, bridges; defaults 6.0, 3.0, 4.0, 8, 1 (DESIGN: the
+ *   sweep behind them, for 0.5 px of tie noise).
+ *   Initial states.  Usable and n_ok >= 1 && n_ok > n_bad: KEPT, verdict VERIFIED.  Other usable records: PENDING.  The rest: NOT_USED.
+ *     A pending pair with n_ok == 0 && n_bad == 0 is UNTESTED.
+ *   Seed.  If no pair is KEPT, the untested pending pair with the largest n_in (ties: the lowest record index) becomes KEPT / BRIDGE, round 0.
+ *     If there is none: MI355_ERR_FAILED, "no pair could be verified".
+ *   A round r = 1 .. max_rounds:
+ *     1 label = mi355_select_connected_moments over the KEPT pairs' moments (every other entry with n_in = 0).
+ *     2 transforms = mi355_global_affine_align_moments on the same moments with that label and the caller's fixed.  The solver needs a
+ *       fixed frame among the labelled ones: a round without one (a seed pair far from the fixed frame) also fixes the lowest labelled
+ *       frame, for that round only.  The output pass does not: without a fixed frame among its labelled ones it is MI355_ERR_FAILED.
+ *     3 The residuals of all records under those transforms and that label.  rms_p = sqrt(sum_r2 / n_used), +inf when n_used == 0.
+ *       s = the lower median of rms_p over the KEPT measured pairs (sorted ascending, element (m - 1) / 2; 0 when there are none).
+ *       g = gate_k * s;  gate = g > gate_abs ? g : gate_abs.
+ *     4 Every PENDING measured pair becomes KEPT / ADMITTED if rms_p <= gate, else REJECTED; its round is r.
+ *     5 If step 4 changed nothing and bridges != 0: layers, without re-aligning, until a layer admits none.  A layer looks, with the labels
+ *       as they stand at its start, at every frame with label 0 that an untested pending pair joins to a labelled frame, and admits for
+ *       each such frame the one such pair with the largest n_in (ties: the lowest record index) as KEPT / BRIDGE, round r; then those
+ *       frames get label 1.  A pair that failed every triangle it is in (n_ok == 0, n_bad > 0) never bridges.
+ *     6 If steps 4 and 5 changed nothing, stop.
+ *   After the loop PENDING pairs become UNDECIDED; label and transforms are formed once more as in 1 and 2 (they are the output), and the
+ *   residuals, s and gate under them are the report's.  The output therefore equals, bit for bit, what mi355_select_connected_results and
+ *   mi355_global_affine_align_results return for the kept records alone.
+ *   Report per record: i, j, n_in, verdict, n_ok, n_bad, round (0 where no round decided it), flags, min_e2, rms (+inf unless measured
+ *   with n_used > 0), max_r2.  flags bit 0 = SUSPECT: a kept pair whose final rms exceeds the final gate; reported only.
+ *   Summary: count[v] = records of verdict v, rounds used, frames labelled, s and gate of the final pass.
+ *
+ * Stage 4: apply.  The records are copied to the output (in place is allowed); every usable pair that is not KEPT is demoted as tie
+ *   refinement demotes: ok = 0, accepted = 0, H all zero, n_in and both lists kept.  KEPT and NOT_USED records are byte-identical copies.
+ *
+ * Errors: MI355_ERR_ARG before any kernel of this section runs, the message names the value, the ctx stays usable: cycle_tol, gate_abs or
+ *   gate_k not finite or <= 0; max_rounds < 1; n_images < 1 or > 65535; n_pairs < 0; a NULL required pointer (params NULL = defaults;
+ *   fixed, report and summary may be NULL); an accepted record with n_in > 400 or an index outside the images (as the affine forms answer
+ *   it; the _dev form sees it in the moments); the duplicate pair.
+ * Limits (DESIGN): a survey with little redundancy splits instead of bending -- a wrong pair leaves its neighbours without a good
+ *   triangle; a survey without any triangle (adjacent pairs only) keeps everything as BRIDGE, and the summary says so: count[VERIFIED] = 0.
+ * Out of scope: the multi-GPU path, cycles longer than three, re-fitting homographies, tie-level gating (local registration's
+ *   max_residual does that), verification under non-affine transforms (the residual entry point takes any h9s; the loop aligns affinely),
+ *   the SURF path. */
+#define MI355_EDGE_USABLE   1
+#define MI355_EDGE_TESTABLE 2
+#define MI355_VERDICT_NOT_USED  0
+#define MI355_VERDICT_VERIFIED  1   /* kept: more of its triangles agree than disagree */
+#define MI355_VERDICT_ADMITTED  2   /* kept: its residual against the alignment of the kept pairs is inside the gate */
+#define MI355_VERDICT_BRIDGE    3   /* kept: in no triangle, and the only way to a frame (or the seed) */
+#define MI355_VERDICT_REJECTED  4   /* demoted: its residual is outside the gate */
+#define MI355_VERDICT_UNDECIDED 5   /* demoted: never measured (a frame of it stayed outside the kept pairs' component) */
+#define MI355_VERIFY_SUSPECT 1
+typedef struct { int32_t i, j, n_in, flags; float box[4]; double F[9], B[9]; } mi355_pair_edge;             /* 176 bytes */
+typedef struct { int32_t n_ok, n_bad; double min_e2; } mi355_pair_cycle;                                    /* 16 bytes */
+typedef struct { int32_t i, j, n_used, n_den; double sum_r2, max_r2; } mi355_pair_residual;                  /* 32 bytes */
+typedef struct { double cycle_tol, gate_abs, gate_k; int32_t max_rounds, bridges; } mi355_verify_params;    /* 32 bytes */
+typedef struct { int32_t i, j, n_in, verdict, n_ok, n_bad, round, flags; double min_e2, rms, max_r2, reserved; } mi355_verify_report;   /* 64 bytes */
+typedef struct { int32_t count[8]; int32_t rounds, n_labelled, reserved[2]; double s, gate; } mi355_verify_summary;                    /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(mi355_pair_edge) == 176 && sizeof(mi355_pair_cycle) == 16 && sizeof(mi355_pair_residual) == 32, "pair verification records");
+static_assert(sizeof(mi355_verify_params) == 32 && sizeof(mi355_verify_report) == 64 && sizeof(mi355_verify_summary) == 64, "pair verification records");
+#else
+_Static_assert(sizeof(mi355_pair_edge) == 176 && sizeof(mi355_pair_cycle) == 16 && sizeof(mi355_pair_residual) == 32, "pair verification records");
+_Static_assert(sizeof(mi355_verify_params) == 32 && sizeof(mi355_verify_report) == 64 && sizeof(mi355_verify_summary) == 64, "pair verification records");
+#endif
+void mi355_default_verify_params(mi355_verify_params* p);
+/* stage 1: device records -> device edges, one launch, enqueued on the ctx stream like mi355_pair_moments_dev.  Profile class "pair_edges". */
+int  mi355_pair_edges_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, int n_images, mi355_pair_edge* d_out);
+/* the same bytes on the host (no ctx; errors: mi355_last_error(NULL)) */
+int  mi355_pair_edges_host(const mi355_pair_result* r, int n, int n_images, mi355_pair_edge* out);
+/* stage 2: edges and out are HOST arrays of n entries; the adjacency is built here, the edges and the adjacency are uploaded, one launch,
+ * complete on return.  Profile class "pair_cycles". */
+int  mi355_pair_cycles_dev(mi355_ctx* ctx, const mi355_pair_edge* edges, int n, int n_images, double cycle_tol, mi355_pair_cycle* out);
+int  mi355_pair_cycles_host(const mi355_pair_edge* edges, int n, int n_images, double cycle_tol, mi355_pair_cycle* out);
+/* the residuals: device records -> device residual records; h9s and label are HOST arrays, read before the call returns; one launch on the
+ * ctx stream.  Profile class "pair_residuals". */
+int  mi355_pair_residuals_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n, const float* h9s, const int32_t* label, int n_images,
+                              mi355_pair_residual* d_out);
+int  mi355_pair_residuals_host(const mi355_pair_result* r, int n, const float* h9s, const int32_t* label, int n_images, mi355_pair_residual* out);
+/* Stages 1 to 4 on device records: the moments by mi355_pair_moments_dev's kernel, edges and cycles once, one residual launch per round
+ * and one for the report, the apply pass into d_out (n_pairs records; d_out == d_results is allowed).  label_out (n_images), transforms_out
+ * (n_images) are HOST arrays; report (n_pairs records) and summary may be NULL.  Complete on return. */
+int  mi355_verify_pairs_dev(mi355_ctx* ctx, const mi355_pair_result* d_results, int n_pairs, int n_images, const int32_t* fixed,
+                            const mi355_verify_params* params, mi355_pair_result* d_out, int32_t* label_out, mi355_image_transform* transforms_out,
+                            mi355_verify_report* report, mi355_verify_summary* summary);
+/* the same on host records with the host twins: no ctx, no device, the same bits (out == r is allowed); errors: mi355_last_error(NULL) */
+int  mi355_verify_pairs_results(const mi355_pair_result* r, int n_pairs, int n_images, const int32_t* fixed, const mi355_verify_params* params,
+                                mi355_pair_result* out, int32_t* label_out, mi355_image_transform* transforms_out, mi355_verify_report* report,
+                                mi355_verify_summary* summary);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

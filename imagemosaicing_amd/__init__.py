@@ -25,6 +25,7 @@ from .capi import (  # noqa: F401
     VerifyParams, verify_params, PAIR_EDGE, PAIR_CYCLE, PAIR_RESIDUAL, VERIFY_REPORT, VERIFY_SUMMARY, EDGE_USABLE, EDGE_TESTABLE,
     VERDICT_NOT_USED, VERDICT_VERIFIED, VERDICT_ADMITTED, VERDICT_BRIDGE, VERDICT_REJECTED, VERDICT_UNDECIDED, VERIFY_SUSPECT,
     pair_edges_host, pair_cycles_host, pair_residuals_host, verify_pairs_results,
+    GuidedParams, default_guided_params, guided_candidates, guided_candidates_count, merge_pair_results,
     PreviewParams, preview_params, overview_layout, NODATA_NONE, NODATA_ZERO, NODATA_MAP,
 )
 

@@ -165,6 +165,14 @@ assert PAIR_EDGE.itemsize == 176 and PAIR_CYCLE.itemsize == 16 and PAIR_RESIDUAL
 assert C.sizeof(VerifyParams) == 32 and VERIFY_REPORT.itemsize == 64 and VERIFY_SUMMARY.itemsize == 64
 
 
+# ---- guided matching (mi355_guided_select_dev, mi355_guided_match*, mi355_guided_candidates, mi355_merge_pair_results; csrc/guided.hip) ----
+class GuidedParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("max_dist2", C.c_int32), ("ratio", C.c_float), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(GuidedParams) == 16
+
+
 class Mi355Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355 error %d: %s" % (code, msg))
@@ -1079,6 +1087,35 @@ class Context:
                                                 C.c_void_p(int(d_out or 0) or None), _p(label), _p(tr), _p(rep), _p(summ)))
         return label, tr, rep, summ[0]
 
+    # ---- guided matching (mi355_guided_select_dev, mi355_guided_match_dev, mi355_guided_match; csrc/guided.hip) ------
+    @staticmethod
+    def _guided_args(pairs, guides, params, kw):
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        guides = np.ascontiguousarray(guides, np.float32).reshape(-1, 9)
+        assert len(pairs) == len(guides)
+        return pairs, guides, params if params is not None else default_guided_params(**kw)
+
+    def GuidedSelectDev(self, pairs, guides, d_a, d_b, d_nsel, d_dist=0, params=None, **kw):
+        """mi355_guided_select_dev: the guided selection of the pairs (int32 [n, 2], host) under the guides (float32 [n, 9], image j -> image i, host)
+        into device lists d_a, d_b (n x 400 SFPOINT), d_nsel (n int32) and d_dist (n x 400 int32, or 0); one launch on the ctx stream.
+        params: GuidedParams (default_guided_params()) or its keyword fields."""
+        pairs, guides, p = self._guided_args(pairs, guides, params, kw)
+        self._chk(self.L.mi355_guided_select_dev(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), C.c_void_p(int(d_a or 0) or None),
+                                                 C.c_void_p(int(d_b or 0) or None), C.c_void_p(int(d_nsel or 0) or None), C.c_void_p(int(d_dist or 0) or None)))
+
+    def GuidedMatchDev(self, pairs, guides, d_out, ransac_dist=2.5, seed=1, params=None, **kw):
+        """mi355_guided_match_dev: guided selection plus the pair stage's tail, n PAIR_RESULT records at the device pointer d_out"""
+        pairs, guides, p = self._guided_args(pairs, guides, params, kw)
+        self._chk(self.L.mi355_guided_match_dev(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), C.c_float(ransac_dist), C.c_uint32(seed),
+                                                C.c_void_p(int(d_out or 0) or None)))
+
+    def GuidedMatch(self, pairs, guides, ransac_dist=2.5, seed=1, params=None, **kw):
+        """mi355_guided_match: the same, returns PAIR_RESULT [n]"""
+        pairs, guides, p = self._guided_args(pairs, guides, params, kw)
+        out = np.zeros(len(pairs), PAIR_RESULT)
+        self._chk(self.L.mi355_guided_match(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), C.c_float(ransac_dist), C.c_uint32(seed), _p(out)))
+        return out
+
     # ---- overview levels and the striped preview (mi355_mosaic_overview*, mi355_mosaic_preview_into, csrc/overview.hip) ------
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
@@ -1388,6 +1425,57 @@ def verify_params(cycle_tol=None, gate_abs=None, gate_k=None, max_rounds=None, b
 def _host_rc(L, rc):
     if rc < 0:
         raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+
+
+def default_guided_params(radius=None, max_dist2=None, ratio=None, reserved=None):
+    """mi355_guided_params: the library's defaults (radius 4, max_dist2 90000, ratio 0.8) with the given fields replaced"""
+    p = GuidedParams()
+    load_library().mi355_default_guided_params(C.byref(p))
+    for name, v in (("radius", radius), ("ratio", ratio)):
+        if v is not None:
+            setattr(p, name, float(v))
+    for name, v in (("max_dist2", max_dist2), ("reserved", reserved)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def guided_candidates(w, h, transforms, have=None, min_points=0, max_pairs=None):
+    """mi355_guided_candidates (host only): the pairs (int32 [n, 2], ascending) the alignment `transforms` (float32 [n_images, 9], frame -> canvas,
+    m[8] == 0: not placed) says overlap and `have` ([m, 2]) does not cover, with their guides (float32 [n, 9], image j -> image i).
+    max_pairs=None sizes the buffers by a count-only call first; an explicit max_pairs below the count raises (the count is in the message)."""
+    L = load_library()
+    t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 9)
+    hv = np.zeros((0, 2), np.int32) if have is None else np.ascontiguousarray(have, np.int32).reshape(-1, 2)
+    n = C.c_int(0)
+    if max_pairs is None:
+        _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), None, None, 0, C.byref(n)))
+        max_pairs = n.value
+    pairs, guides = np.zeros((max(int(max_pairs), 1), 2), np.int32), np.zeros((max(int(max_pairs), 1), 9), np.float32)
+    _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), _p(pairs), _p(guides), int(max_pairs), C.byref(n)))
+    return pairs[:n.value].copy(), guides[:n.value].copy()
+
+
+def guided_candidates_count(w, h, transforms, have=None, min_points=0):
+    """mi355_guided_candidates with pairs_ij == NULL: the number of candidate pairs"""
+    L = load_library()
+    t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 9)
+    hv = np.zeros((0, 2), np.int32) if have is None else np.ascontiguousarray(have, np.int32).reshape(-1, 2)
+    n = C.c_int(0)
+    _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), None, None, 0, C.byref(n)))
+    return n.value
+
+
+def merge_pair_results(base, extra):
+    """mi355_merge_pair_results (host only): base records keep their places, an extra record of the same (i, j) replaces one with a smaller n_in,
+    the others are appended in order; returns PAIR_RESULT [n_out]"""
+    L = load_library()
+    b = np.ascontiguousarray(base, PAIR_RESULT)
+    e = np.ascontiguousarray(extra, PAIR_RESULT)
+    out = np.zeros(max(len(b) + len(e), 1), PAIR_RESULT)
+    n = C.c_int(0)
+    _host_rc(L, L.mi355_merge_pair_results(_p(b), len(b), _p(e), len(e), _p(out), C.byref(n)))
+    return out[:n.value].copy()
 
 
 def pair_edges_host(results, n_images):

@@ -217,6 +217,7 @@ int mi_ransac_batch(mi355_ctx*, const mi355_sfpoint* d_p1, const mi355_sfpoint* 
 int mi_ransac_big(mi355_ctx*, const mi355_sfpoint* p1, const mi355_sfpoint* p2, int n, float dist, int sample_times, uint32_t seed,
                   mi355_sfpoint* in1, mi355_sfpoint* in2, int* n_in, float* H, int* ok);
 int mi_match_pairs_dev(mi355_ctx*, const int32_t* pairs, int n_pairs, float dist, uint32_t seed, mi355_pair_result* d_out);
+int mi_finalize_pairs(mi355_ctx*, const int32_t* pairs_ij /*host*/, int n_pairs, const int* d_nsel, mi355_pair_result* d_out);   // match.hip: finalize_kernel on records a stage selected by itself (guided.hip); complete on return
 int mi_bf_match(mi355_ctx*, int img_i, int img_j, int sorted, mi355_dmatch* matches, int32_t* d2, int32_t* second, int maxm, int* nm);
 int mi_select_grid(mi355_ctx*, const mi355_dmatch* sorted, int n, const float* kp1, int nk1, const float* kp2, int nk2,
                    int nMatch, int width, int height, int gx, int gy, mi355_sfpoint* v1, mi355_sfpoint* v2, int* n_out);

@@ -703,6 +703,21 @@ int mi_match_pairs_dev(mi355_ctx* ctx, const int32_t* pairs, int n_pairs, float 
     return MI355_OK;
 }
 
+// finalize_kernel for a stage that selects by itself (guided.hip): the pair table holds the image ids alone, nsel is that stage's count per pair
+int mi_finalize_pairs(mi355_ctx* ctx, const int32_t* pairs_ij, int n_pairs, const int* d_nsel, mi355_pair_result* d_out) {
+    if (n_pairs <= 0) return MI355_OK;
+    std::vector<PairDesc> pd((size_t)n_pairs);
+    memset(pd.data(), 0, sizeof(PairDesc) * pd.size());
+    for (int p = 0; p < n_pairs; p++) { pd[p].img_i = pairs_ij[2 * p]; pd[p].img_j = pairs_ij[2 * p + 1]; }
+    PairWs ws(ctx);
+    MI_HIP(ws.pairs.reserve(sizeof(PairDesc) * pd.size()));
+    MI_HIP(hipMemcpyAsync(ws.pairs.p, pd.data(), sizeof(PairDesc) * pd.size(), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(finalize_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, ctx->stream, ws.pairs.as<PairDesc>(), d_nsel, n_pairs, ctx->p.min_inliers, d_out);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(ctx->stream));           // the table is this function's local
+    return MI355_OK;
+}
+
 int mi_bf_match(mi355_ctx* ctx, int img_i, int img_j, int sorted, mi355_dmatch* matches, int32_t* d2, int32_t* second, int maxm, int* nm) {
     const int32_t pr[2] = {img_i, img_j};
     std::vector<PairDesc> pd;

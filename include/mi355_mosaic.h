@@ -1395,6 +1395,71 @@ int  mi355_verify_pairs_results(const mi355_pair_result* r, int n_pairs, int n_i
                                 mi355_pair_result* out, int32_t* label_out, mi355_image_transform* transforms_out, mi355_verify_report* report,
                                 mi355_verify_summary* summary);
 
+/* ---- guided matching (opt-in; csrc/guided.hip, csrc/guided_host.cpp) ------------------------------------------------------------------------
+ * The pair stage has one way to find ties: the global 1-NN of every descriptor, the best 30 % by distance, the grid cap.  On frames that
+ * overlap by a third or less the true matches are a minority of that list.  Where the caller already knows where frame j lies in frame i -- from
+ * the pair's own H, from a chain of neighbouring H's, from the global alignment -- guided matching looks for each keypoint's partner only near
+ * its predicted position: what stitchers and SfM pipelines run after a first geometric fit.  Nothing calls it unless asked.
+ * Definition.  Every float operation is a separate float32 operation in the order written.
+ * Input per pair p: image ids (i, j) with features resident, i != j, each frame with 0 .. 2048 keypoints (keep-all frames, nfeatures <= 0 with
+ *   more than 2048 keypoints, are out of scope for this stage: such a frame is refused), and a guide G[9], row-major, mapping image-j
+ *   coordinates to image-i coordinates; G[8] is used as given (a caller who passes a record's H sets [8] = 1: H[8] holds Ransac2D's residual).
+ * For each keypoint q of frame j, with b = xy_j[q]:
+ *   1 (X, Y) = apply_div9(G, b.x, b.y) (the tie-refinement section's expression: sums left to right, two true divisions).
+ *   2 Candidates: the keypoints k of frame i with dx = a_k.x - X, dy = a_k.y - Y and dx*dx + dy*dy <= radius*radius.  A NaN on either side
+ *     fails (so does an infinite X or Y).
+ *   3 For each candidate d = the sum over the 128 dimensions of (d8_i[k][c] - d8_j[q][c])^2 as int32 (at most 8 323 200).
+ *   4 (d1, k1) = the smallest (d, k) in lexicographic order; d2 = the smallest d among the other candidates, if there are any.
+ *   5 q proposes k1 iff d1 <= max_dist2 and one of: there is no second candidate; ratio <= 0; (float)d1 < (ratio*ratio) * (float)d2
+ *     (equality fails).
+ * One-to-one: a keypoint k of frame i keeps, among the queries that proposed it, the one with the smallest (d1, q).  The result does not
+ *   depend on evaluation order.
+ * Cut and order: the surviving ties in ascending (d1, q) order; the first max_selected of them (the ctx parameter, at most 400) form the
+ *   selection lists a[t] = {xy_i[k], id k}, b[t] = {xy_j[q], id q} with count n_sel and distances d1[t].
+ * Tail: exactly the pair stage's -- Ransac2D on the lists with ransac_dist, the ctx's sample_times and the seed, the closing refinement skipped
+ *   for a pair that will not be accepted, then i, j, n_selected = n_sel, accepted = n_in > min_inliers.  A rejected record therefore follows
+ *   mi355_pair_result's convention: real n_in, the winning hypothesis's inliers, H zero, ok 0.
+ * Radius against guide precision: the radius must cover the guide's error.  A pair's own H is good to about ransac_dist; a guide chained over
+ *   many pairs drifts by several pixels per hop and finds FEWER ties at radius 4 than the pair stage did, so a guided record must never
+ *   replace a better existing one: mi355_merge_pair_results keeps the record with the larger n_in, which makes a bad guide harmless.
+ * Errors (MI355_ERR_ARG, decided on the host before any launch, the message names the value): radius not finite or outside (0, 64]; max_dist2
+ *   outside [0, 8323200]; ratio not finite or outside [0, 1]; reserved != 0; n < 0; a NULL array with n > 0; i == j; a frame without resident
+ *   features; a frame with more than 2048 keypoints; a ctx whose max_selected is outside [0, 400].  params NULL = defaults.  n == 0 returns
+ *   MI355_OK and launches nothing.
+ * Out of scope: the C++ adaptor, the multi-GPU path, the SURF path, keep-all frames. */
+typedef struct { float radius; int32_t max_dist2; float ratio; int32_t reserved; } mi355_guided_params;      /* defaults 4.0f, 90000, 0.8f, 0 */
+void mi355_default_guided_params(mi355_guided_params* p);
+/* The selection alone.  pairs_ij (n x {i, j}) and guides (n x 9) are HOST arrays, read before the call returns; d_a, d_b (n x 400 sfpoints),
+ * d_nsel (n ints) and d_dist (n x 400 int32, may be NULL) are device pointers; list entries from n_sel on are zero.  One launch, a workgroup per
+ * pair, on the ctx stream.  Frames still in flight are waited for like mi355_match_pairs does.  Profile class "guided_select". */
+int  mi355_guided_select_dev(mi355_ctx* ctx, const int32_t* pairs_ij, int n, const float* guides, const mi355_guided_params* params,
+                             mi355_sfpoint* d_a, mi355_sfpoint* d_b, int32_t* d_nsel, int32_t* d_dist);
+/* Selection plus tail: n records at d_out (device pointer), complete on return. */
+int  mi355_guided_match_dev(mi355_ctx* ctx, const int32_t* pairs_ij, int n, const float* guides, const mi355_guided_params* params,
+                            float ransac_dist, uint32_t seed, mi355_pair_result* d_out);
+/* The same into a host array of n records. */
+int  mi355_guided_match(mi355_ctx* ctx, const int32_t* pairs_ij, int n, const float* guides, const mi355_guided_params* params,
+                        float ransac_dist, uint32_t seed, mi355_pair_result* out);
+/* The pairs an alignment says overlap and no record covers (host only, no ctx; errors: mi355_last_error(NULL)).  transforms: n_images x 9,
+ * frame -> canvas, m[8] == 0: the frame is not placed.  have_ij: n_have x {i, j} pairs that need no guide, in either orientation.  Every i < j
+ * with both frames placed and (i, j) not in have is considered.  Every double operation is a separate operation in the order written:
+ *   A = adj(T_i) (A0 = t4 t8 - t5 t7, A1 = t2 t7 - t1 t8, A2 = t1 t5 - t2 t4, A3 = t5 t6 - t3 t8, A4 = t0 t8 - t2 t6, A5 = t2 t3 - t0 t5,
+ *   A6 = t3 t7 - t4 t6, A7 = t1 t6 - t0 t7, A8 = t0 t4 - t1 t3), det = t0 A0 + t1 A3 + t2 A6; P[r][c] = (A[r][0] U[0][c] + A[r][1] U[1][c] +
+ *   A[r][2] U[2][c]) / det with U = T_j, sums left to right; G[k] = (float)(P[k] / P[8]).  A pair whose det or P[8] is zero or not finite is
+ *   skipped.  Control points: the 3 x 3 grid {0, (w-1)/2, w-1} x {0, (h-1)/2, h-1} of frame j through G (the rounded floats, as doubles:
+ *   X = (g0 x + g1 y + g2) / (g6 x + g7 y + g8), Y likewise) and the same grid of frame i through adj(G) / det(G) entry by entry; the count
+ *   is the number of the 18 points that land in [0, w-1] x [0, h-1] of the other frame (NaN lands nowhere).  The pair is a candidate iff
+ *   count >= min_points (default 2; min_points <= 0 selects the default).  Output ascending (i, j): pairs_ij (max_pairs x 2) and guides
+ *   (max_pairs x 9, may be NULL).  pairs_ij == NULL: only the count is returned in *n_pairs.  max_pairs below the count: MI355_ERR_ARG,
+ *   nothing written but the count in *n_pairs. */
+int  mi355_guided_candidates(int w, int h, int n_images, const float* transforms, const int32_t* have_ij, int n_have, int min_points,
+                             int32_t* pairs_ij, float* guides, int max_pairs, int* n_pairs);
+/* base and extra record sets into out (host only; room for n_base + n_extra records; out may be base).  The base records keep their places.  An
+ * extra record whose (i, j), as written, is already in out replaces that record iff its n_in is larger (base wins ties; so does the earlier of
+ * two extra records); any other extra record is appended, in order.  *n_out: the records in out. */
+int  mi355_merge_pair_results(const mi355_pair_result* base, int n_base, const mi355_pair_result* extra, int n_extra, mi355_pair_result* out,
+                              int* n_out);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------------------- */
 /* When enabled, every launch of the named kernel class is bracketed by hipEvents on the ctx stream. */
 int  mi355_profile_enable(mi355_ctx* ctx, int on);

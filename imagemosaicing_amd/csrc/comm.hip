@@ -21,6 +21,7 @@
 // The pack / install halves are separate entry points so that a caller with its own transport (the gloo CPU tests, MPI)
 // moves the same records.
 #include "common.h"
+#include "feature_rows.h"
 #include <algorithm>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -73,34 +74,6 @@ RcclApi* rccl_api() {
         ncclResult_t r_ = (call);                                                                              \
         if (r_ != ncclSuccess) { ctx->set_error(std::string(#call) + ": " + rccl_api()->GetErrorString(r_)); return MI355_ERR_DEVICE; } \
     } while (0)
-
-static_assert(sizeof(mi355_feature_header) == 16, "feature header");
-static_assert(MI355_FEATURE_RECORD_BYTES >= 2048 * 28 + 2048 * 128 && MI355_FEATURE_RECORD_BYTES % 256 == 0, "feature record");
-
-// record layout: [0, 57344) keypoints (2048 x 28 B), [57344, 319488) descriptors u8 (2048 x 128); rows beyond n_kp are zero
-constexpr size_t REC_KP_BYTES = (size_t)2048 * sizeof(mi355_keypoint), REC_D8_OFF = REC_KP_BYTES, REC_D8_BYTES = (size_t)2048 * 128;
-
-struct PackSrc { const uint8_t* kp; const uint8_t* d8; int n; };
-
-// one workgroup column per record: 16-byte moves, zero fill beyond the frame's n keypoints
-__global__ __launch_bounds__(256) void pack_features_kernel(const PackSrc* src, uint8_t* payload) {
-    const PackSrc s = src[blockIdx.y];
-    uint4* dst = reinterpret_cast<uint4*>(payload + (size_t)blockIdx.y * MI355_FEATURE_RECORD_BYTES);
-    const size_t kp_bytes = (size_t)s.n * sizeof(mi355_keypoint), d8_bytes = (size_t)s.n * 128;
-    const size_t total16 = MI355_FEATURE_RECORD_BYTES / 16;
-    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < total16; q += (size_t)gridDim.x * 256) {
-        const size_t b = q * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (b < REC_KP_BYTES) {
-            if (b + 16 <= kp_bytes) v = *reinterpret_cast<const uint4*>(s.kp + b);
-            else if (b < kp_bytes) { uint8_t t[16] = {0}; for (size_t i = 0; b + i < kp_bytes; i++) t[i] = s.kp[b + i]; v = *reinterpret_cast<uint4*>(t); }
-        } else if (b < REC_D8_OFF + REC_D8_BYTES) {
-            const size_t o = b - REC_D8_OFF;
-            if (o + 16 <= d8_bytes) v = *reinterpret_cast<const uint4*>(s.d8 + o);      // d8_bytes is a multiple of 128
-        }
-        dst[q] = v;
-    }
-}
 
 // accepted pair records to the front, order kept (what the reference pushes to the driver, MosaicWithoutPos.cpp:5201-5227).  Three launches:
 // accepted records per block of 256, an exclusive scan of the block counts by one workgroup, the moves (every lane of a wave helps moving the
@@ -206,116 +179,17 @@ struct mi355_comm {
 };
 
 // ---- pack / install (transport-agnostic halves) ---------------------------------------------------------------------------
-extern "C" int mi355_pack_features_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_header* hdr, void* d_payload) {
-    LOCKED_PROLOGUE
-    if (n < 0 || (n > 0 && (!img_ids || !hdr || !d_payload))) return MI355_ERR_ARG;
-    if (n == 0) return MI355_OK;
-    { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
-    std::vector<PackSrc> src(n);
-    for (int k = 0; k < n; k++) {
-        auto it = ctx->feats.find(img_ids[k]);
-        if (it == ctx->feats.end()) { ctx->set_error("pack_features: no resident features for image " + std::to_string(img_ids[k])); return MI355_ERR_ARG; }
-        const Features& f = it->second;
-        if (f.n > 2048) { ctx->set_error("pack_features: more than 2048 keypoints"); return MI355_ERR_ARG; }
-        hdr[k].img_id = img_ids[k]; hdr[k].n_kp = f.n; hdr[k].w = f.w; hdr[k].h = f.h;
-        src[k] = PackSrc{f.kp.as<uint8_t>(), f.d8.as<uint8_t>(), f.n};
-    }
-    DevBuf& dsrc = ctx->buf("pack_src");
-    MI_HIP(dsrc.reserve(sizeof(PackSrc) * n));
-    MI_HIP(hipMemcpyAsync(dsrc.p, src.data(), sizeof(PackSrc) * n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(pack_features_kernel, dim3(16, n), dim3(256), 0, ctx->stream, dsrc.as<PackSrc>(), reinterpret_cast<uint8_t*>(d_payload));
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // `src` goes out of scope
-    return MI355_OK;
-}
-
-// One launch installs every received record: keypoints and descriptors move into the image's resident buffers and the matcher's
-// operands (xy, int8 rows, squared norms) are derived on the way -- the per-frame form (two copies + finish_features per frame)
-// costs ~1500 API calls per step at C4.
-struct InstallDst { const uint8_t* rec; mi355_keypoint* kp; uint8_t* d8; float2* xy; int8_t* s8; int* n8; int n, npad; };
-
-__global__ __launch_bounds__(256) void install_features_kernel(const InstallDst* tab) {
-    const InstallDst t = tab[blockIdx.y];
-    const int row = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;     // 8 lanes per descriptor row, 16 bytes each
-    if (row >= t.npad) return;
-    uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);           // padding rows: zeros after the shift
-    if (row < t.n) {
-        v = *reinterpret_cast<const uint4*>(t.rec + REC_D8_OFF + (size_t)row * 128 + part * 16);
-        *reinterpret_cast<uint4*>(t.d8 + (size_t)row * 128 + part * 16) = v;
-    }
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) { const int u = (int)((w[q] >> (8 * b)) & 0xffu) - 128; s += u * u; }
-    // the matcher's int8 operand (match.hip): u - 128 = u ^ 0x80 as a byte
-    *reinterpret_cast<uint4*>(t.s8 + (size_t)row * 128 + part * 16) = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-    if (part == 0) t.n8[row] = s;
-    if (row < t.n && part < 7) {
-        const unsigned kw = reinterpret_cast<const unsigned*>(t.rec + (size_t)row * sizeof(mi355_keypoint))[part];
-        reinterpret_cast<unsigned*>(t.kp + row)[part] = kw;
-        if (part < 2) reinterpret_cast<unsigned*>(t.xy + row)[part] = kw;               // x, y are the first two fields
-    }
-}
-
-static int install_features(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n, const int32_t* skip_ids, int n_skip) {
-    std::vector<InstallDst> tab;
-    tab.reserve(n);
-    bool resolved = false;
-    for (int k = 0; k < n; k++) {
-        const mi355_feature_header& hk = hdr[k];
-        if (hk.img_id < 0) continue;                     // padding record of a rank with fewer frames
-        bool skip = false;
-        for (int q = 0; q < n_skip; q++) if (skip_ids[q] == hk.img_id) { skip = true; break; }
-        if (skip) continue;
-        if (hk.n_kp < 0 || hk.n_kp > 2048 || hk.w <= 0 || hk.h <= 0) { ctx->set_error("install_features: bad record header"); return MI355_ERR_ARG; }
-        auto it = ctx->feats.find(hk.img_id);
-        if (it != ctx->feats.end() && it->second.pending && !resolved) { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; resolved = true; }
-        Features& f = ctx->feats[hk.img_id];
-        f.n = hk.n_kp; f.w = hk.w; f.h = hk.h; f.pending = false; f.h_cnt = nullptr;
-        f.npad = ((f.n + 255) / 256) * 256;
-        if (f.npad == 0) f.npad = 256;
-        // sized for 2048 keypoints once: no allocation in steady state when the counts change from step to step
-        MI_HIP(f.kp.reserve(sizeof(mi355_keypoint) * 2048));
-        MI_HIP(f.d8.reserve((size_t)128 * 2048));
-        MI_HIP(f.xy.reserve(sizeof(float2) * 2048));
-        MI_HIP(f.s8.reserve((size_t)128 * 2048));
-        MI_HIP(f.n8.reserve(sizeof(int) * 2048));
-        InstallDst t;
-        t.rec = reinterpret_cast<const uint8_t*>(d_payload) + (size_t)k * MI355_FEATURE_RECORD_BYTES;
-        t.kp = f.kp.as<mi355_keypoint>(); t.d8 = f.d8.as<uint8_t>(); t.xy = f.xy.as<float2>(); t.s8 = f.s8.as<int8_t>(); t.n8 = f.n8.as<int>();
-        t.n = f.n; t.npad = f.npad;
-        tab.push_back(t);
-    }
-    if (tab.empty()) return MI355_OK;
-    DevBuf& dtab = ctx->buf("install_tab");
-    MI_HIP(dtab.reserve(sizeof(InstallDst) * tab.size()));
-    MI_HIP(hipMemcpyAsync(dtab.p, tab.data(), sizeof(InstallDst) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(install_features_kernel, dim3(2048 / 32, (unsigned)tab.size()), dim3(256), 0, ctx->stream, dtab.as<InstallDst>());
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(ctx->stream));           // `tab` goes out of scope; the caller may reuse d_payload
-    return MI355_OK;
-}
-
-extern "C" int mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n) {
-    LOCKED_PROLOGUE
-    if (n < 0 || (n > 0 && (!hdr || !d_payload))) return MI355_ERR_ARG;
-    return install_features(ctx, hdr, d_payload, n, nullptr, 0);
-}
-
-// ---- chunk records (frames of any keypoint count: keep-all, <= ctx->keepall_max rows) ---------------------------------------------------------------
-// A frame travels as max(1, ceil(n / 2048)) records of the fixed layout, chunk c holding rows [row0, row0 + rows): a frame of <= 2048 keypoints
-// is ONE chunk, byte for byte the record above, so a transport that moves fixed records keeps one record size.
+// One record layout (feature_rows.h) under two headers.  A frame of any keypoint count (keep-all: <= ctx->keepall_max rows) travels as
+// max(1, ceil(n / 2048)) records, chunk c holding rows [row0, row0 + rows), each under a mi355_feature_chunk_header.  A frame of <= 2048
+// keypoints is ONE chunk {row0 0, rows n}; mi355_feature_header is that chunk's header cut to its first four fields, so the fixed entry points
+// are the chunk ones with a 2048-row ceiling per frame, and a transport that moves fixed records keeps one record size.
+static_assert(sizeof(mi355_feature_header) == 16, "feature header");
 static_assert(sizeof(mi355_feature_chunk_header) == 32, "feature chunk header");
-static_assert(MI355_FEATURE_CHUNK_ROWS * sizeof(mi355_keypoint) == REC_KP_BYTES && MI355_FEATURE_CHUNK_ROWS * 128 == REC_D8_BYTES, "chunk rows");
-static_assert((MI355_FEATURE_CHUNK_ROWS * sizeof(mi355_keypoint)) % 16 == 0, "a chunk's keypoints start 16-byte aligned");
 
 struct ChunkSrc { const uint8_t* kp; const uint8_t* d8; int row0, rows; };
 
-// pack_features_kernel with a row window: one workgroup column per chunk record (blockIdx.y), a lane per 16 bytes, zero fill beyond `rows`.
-// The grid's x extent covers a record in one pass (78 workgroups of 256 lanes), so every lane moves one 16-byte piece.
+// One workgroup column per record (blockIdx.y), a lane per 16 bytes: the frame's rows [row0, row0 + rows), zero fill beyond them.  The grid's
+// x extent is the caller's (PACK_GX below): 78 workgroups of 256 lanes cover a record in one pass, fewer walk it in strides.
 __global__ __launch_bounds__(256) void pack_feature_chunks_kernel(const ChunkSrc* src, uint8_t* payload) {
     const ChunkSrc s = src[blockIdx.y];
     uint4* dst = reinterpret_cast<uint4*>(payload + (size_t)blockIdx.y * MI355_FEATURE_RECORD_BYTES);
@@ -337,8 +211,10 @@ __global__ __launch_bounds__(256) void pack_feature_chunks_kernel(const ChunkSrc
     }
 }
 
-// install_features_kernel by chunk: one launch for every received chunk (blockIdx.y).  Record row r lands at image row row0 + r; the record
-// that holds an image's last chunk also writes the padding rows [n, npad) of s8 / n8 (lim = npad - row0 there, rows elsewhere).
+// One launch installs every received record (blockIdx.y): keypoints and descriptors move into the image's resident buffers and the matcher's
+// operands (xy, int8 rows, squared norms) are derived on the way -- the per-frame form (two copies + finish_features per frame) costs ~1500
+// API calls per step at C4.  Record row r lands at image row row0 + r; the record that holds an image's last chunk also writes the padding
+// rows [n, npad) of s8 / n8 (lim = npad - row0 there, rows elsewhere).
 struct ChunkDst { const uint8_t* rec; mi355_keypoint* kp; uint8_t* d8; float2* xy; int8_t* s8; int* n8; int row0, rows, lim, _pad; };
 
 __global__ __launch_bounds__(256) void install_feature_chunks_kernel(const ChunkDst* tab) {
@@ -346,20 +222,12 @@ __global__ __launch_bounds__(256) void install_feature_chunks_kernel(const Chunk
     const int r = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;      // 8 lanes per descriptor row, 16 bytes each
     if (r >= t.lim) return;
     const size_t row = (size_t)t.row0 + r;
-    uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);          // padding rows: zeros after the shift
+    uint4 v = feature_pad_piece();
     if (r < t.rows) {
         v = *reinterpret_cast<const uint4*>(t.rec + REC_D8_OFF + (size_t)r * 128 + part * 16);
         *reinterpret_cast<uint4*>(t.d8 + row * 128 + part * 16) = v;
     }
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) { const int u = (int)((w[q] >> (8 * b)) & 0xffu) - 128; s += u * u; }
-    *reinterpret_cast<uint4*>(t.s8 + row * 128 + part * 16) = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-    if (part == 0) t.n8[row] = s;
+    feature_row_piece(v, t.s8, t.n8, row, part);
     if (r < t.rows && part < 7) {
         const unsigned kw = reinterpret_cast<const unsigned*>(t.rec + (size_t)r * sizeof(mi355_keypoint))[part];
         reinterpret_cast<unsigned*>(t.kp + row)[part] = kw;
@@ -369,47 +237,74 @@ __global__ __launch_bounds__(256) void install_feature_chunks_kernel(const Chunk
 
 static int chunks_of(int n_kp) { return n_kp > 0 ? (n_kp + MI355_FEATURE_CHUNK_ROWS - 1) / MI355_FEATURE_CHUNK_ROWS : 1; }
 
-// caller holds the ctx lock and has resolved pending extractions
+// Image img_id's resident features for a pack, at most max_rows keypoints: 2048 for the fixed entry points (one record per frame),
+// ctx->keepall_max for the chunk ones.  nullptr, the ctx's error set under `who`, where they are missing or larger.  The caller holds the ctx
+// lock and has resolved pending extractions.
+static const Features* packable(mi355_ctx* ctx, const char* who, int img_id, int max_rows) {
+    auto it = ctx->feats.find(img_id);
+    if (it == ctx->feats.end()) { ctx->set_error(std::string(who) + ": no resident features for image " + std::to_string(img_id)); return nullptr; }
+    if (it->second.n >= 0 && it->second.n <= max_rows) return &it->second;
+    if (max_rows == MI355_FEATURE_CHUNK_ROWS) ctx->set_error(std::string(who) + ": more than 2048 keypoints");
+    else ctx->set_error(std::string(who) + ": image " + std::to_string(img_id) + " has more than keepall_max=" + std::to_string(max_rows) + " keypoints");
+    return nullptr;
+}
+
+// the records img_ids' features take
 static int count_chunks(mi355_ctx* ctx, const char* who, const int32_t* img_ids, int n, int* n_records) {
     long long total = 0;
     for (int k = 0; k < n; k++) {
-        auto it = ctx->feats.find(img_ids[k]);
-        if (it == ctx->feats.end()) { ctx->set_error(std::string(who) + ": no resident features for image " + std::to_string(img_ids[k])); return MI355_ERR_ARG; }
-        const int nk = it->second.n;
-        if (nk < 0 || nk > ctx->keepall_max) { ctx->set_error(std::string(who) + ": image " + std::to_string(img_ids[k]) + " has more than keepall_max=" + std::to_string(ctx->keepall_max) + " keypoints"); return MI355_ERR_ARG; }
-        total += chunks_of(nk);
+        const Features* f = packable(ctx, who, img_ids[k], ctx->keepall_max);
+        if (!f) return MI355_ERR_ARG;
+        total += chunks_of(f->n);
     }
     if (total > 0x7fffffffLL) { ctx->set_error(std::string(who) + ": too many records"); return MI355_ERR_ARG; }
     *n_records = (int)total;
     return MI355_OK;
 }
 
-// headers to the host array, the pack enqueued on the ctx stream; `src_buf`: the device table (reserved here, before anything is enqueued)
-static int pack_chunks(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_chunk_header* hdr, uint8_t* d_payload, int n_records) {
+static void put_header(mi355_feature_chunk_header* hdr, size_t q, const mi355_feature_chunk_header& h) { hdr[q] = h; }
+static void put_header(mi355_feature_header* hdr, size_t q, const mi355_feature_chunk_header& h) { hdr[q] = mi355_feature_header{h.img_id, h.n_kp, h.w, h.h}; }
+
+// workgroups per record of the pack launch (its grid-stride loop takes any): a record in one pass, and the fixed entry points' 16, which
+// packs a call's 63 whole records in 11.0 us against 11.8
+constexpr unsigned PACK_GX = (MI355_FEATURE_RECORD_BYTES / 16 + 255) / 256, PACK_GX_FIXED = 16;
+
+// The one pack: img_ids' features, none above max_rows keypoints, as n_records records (the fixed form: a record per frame; the chunk form:
+// what count_chunks said).  Headers of either form to the host array hdr, the pack enqueued on the ctx stream, gx workgroups per record,
+// and waited for.
+template <class Header>
+static int pack_chunks(mi355_ctx* ctx, const char* who, int max_rows, const int32_t* img_ids, int n, Header* hdr, uint8_t* d_payload, int n_records, unsigned gx) {
     if (n_records == 0) return MI355_OK;
     std::vector<ChunkSrc> src;
     src.reserve(n_records);
     for (int k = 0; k < n; k++) {
-        const Features& f = ctx->feats.find(img_ids[k])->second;          // count_chunks found every id
-        const int nc = chunks_of(f.n);
+        const Features* f = packable(ctx, who, img_ids[k], max_rows);
+        if (!f) return MI355_ERR_ARG;
+        const int nc = chunks_of(f->n);
         for (int c = 0; c < nc; c++) {
-            mi355_feature_chunk_header& h = hdr[src.size()];
-            const int row0 = c * MI355_FEATURE_CHUNK_ROWS, rows = f.n - row0 < MI355_FEATURE_CHUNK_ROWS ? f.n - row0 : MI355_FEATURE_CHUNK_ROWS;
-            h.img_id = img_ids[k]; h.n_kp = f.n; h.w = f.w; h.h = f.h; h.chunk = c; h.n_chunks = nc; h.row0 = row0; h.rows = rows > 0 ? rows : 0;
-            src.push_back(ChunkSrc{f.kp.as<uint8_t>(), f.d8.as<uint8_t>(), row0, h.rows});
+            const int row0 = c * MI355_FEATURE_CHUNK_ROWS, rows = f->n - row0 < MI355_FEATURE_CHUNK_ROWS ? f->n - row0 : MI355_FEATURE_CHUNK_ROWS;
+            put_header(hdr, src.size(), mi355_feature_chunk_header{img_ids[k], f->n, f->w, f->h, c, nc, row0, rows > 0 ? rows : 0});
+            src.push_back(ChunkSrc{f->kp.as<uint8_t>(), f->d8.as<uint8_t>(), row0, rows > 0 ? rows : 0});
         }
     }
-    DevBuf& dsrc = ctx->buf("pack_chunk_src");
+    DevBuf& dsrc = ctx->buf("pack_src");
     MI_HIP(dsrc.reserve(sizeof(ChunkSrc) * src.size()));
     MI_HIP(hipMemcpyAsync(dsrc.p, src.data(), sizeof(ChunkSrc) * src.size(), hipMemcpyHostToDevice, ctx->stream));
-    constexpr unsigned GX = (MI355_FEATURE_RECORD_BYTES / 16 + 255) / 256;
     {
         ProfScope ps(ctx, "feature_pack", 2.0 * (double)MI355_FEATURE_RECORD_BYTES * (double)src.size());
-        hipLaunchKernelGGL(pack_feature_chunks_kernel, dim3(GX, (unsigned)src.size()), dim3(256), 0, ctx->stream, dsrc.as<ChunkSrc>(), d_payload);
+        hipLaunchKernelGGL(pack_feature_chunks_kernel, dim3(gx, (unsigned)src.size()), dim3(256), 0, ctx->stream, dsrc.as<ChunkSrc>(), d_payload);
     }
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(ctx->stream));           // `src` goes out of scope
     return MI355_OK;
+}
+
+extern "C" int mi355_pack_features_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_header* hdr, void* d_payload) {
+    LOCKED_PROLOGUE
+    if (n < 0 || (n > 0 && (!img_ids || !hdr || !d_payload))) return MI355_ERR_ARG;
+    if (n == 0) return MI355_OK;
+    { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
+    return pack_chunks(ctx, "pack_features", MI355_FEATURE_CHUNK_ROWS, img_ids, n, hdr, reinterpret_cast<uint8_t*>(d_payload), n, PACK_GX_FIXED);
 }
 
 extern "C" int mi355_feature_chunk_count(mi355_ctx* ctx, const int32_t* img_ids, int n, int* n_records) {
@@ -430,27 +325,29 @@ extern "C" int mi355_pack_feature_chunks_dev(mi355_ctx* ctx, const int32_t* img_
     { int rc = count_chunks(ctx, "pack_feature_chunks", img_ids, n, &nr); if (rc != MI355_OK) return rc; }
     if (nr > max_records) { ctx->set_error("pack_feature_chunks: " + std::to_string(nr) + " records do not fit in max_records = " + std::to_string(max_records)); return MI355_ERR_ARG; }
     if (nr > 0 && (!hdr || !d_payload)) return MI355_ERR_ARG;
-    { int rc = pack_chunks(ctx, img_ids, n, hdr, reinterpret_cast<uint8_t*>(d_payload), nr); if (rc != MI355_OK) return rc; }
+    { int rc = pack_chunks(ctx, "pack_feature_chunks", ctx->keepall_max, img_ids, n, hdr, reinterpret_cast<uint8_t*>(d_payload), nr, PACK_GX); if (rc != MI355_OK) return rc; }
     *n_records = nr;
     return MI355_OK;
 }
 
-// Checks the whole table, then installs it (one launch).  Records with img_id < 0 and the images in skip_ids are left out.  Nothing of the
-// ctx's features changes before every image of the table has passed (missing / duplicate chunks, disagreeing headers, rows that do not tile).
-static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n, const int32_t* skip_ids, int n_skip) {
+// Checks the whole table, then installs it (one launch).  Records with img_id < 0 and the images in skip_ids are left out; max_rows is the
+// ceiling of a frame's n_kp.  Nothing of the ctx's features changes before every image of the table has passed (missing / duplicate chunks,
+// disagreeing headers, rows that do not tile).  The caller has resolved the pending extractions the table lands on.
+static int install_chunks(mi355_ctx* ctx, const char* who, int max_rows, const mi355_feature_chunk_header* hdr, const void* d_payload, int n,
+                          const int32_t* skip_ids, int n_skip) {
     std::map<int, std::vector<int>> by_img;              // image -> its records, in chunk order after the sort
     for (int k = 0; k < n; k++) {
         const mi355_feature_chunk_header& h = hdr[k];
-        if (h.img_id < 0) continue;
+        if (h.img_id < 0) continue;                      // padding record of a rank with fewer records
         bool skip = false;
         for (int q = 0; q < n_skip; q++) if (skip_ids[q] == h.img_id) { skip = true; break; }
         if (!skip) by_img[h.img_id].push_back(k);
     }
-    auto bad = [&](int img, const std::string& why) { ctx->set_error("install_feature_chunks: image " + std::to_string(img) + ": " + why); return MI355_ERR_ARG; };
+    auto bad = [&](int img, const std::string& why) { ctx->set_error(std::string(who) + ": image " + std::to_string(img) + ": " + why); return MI355_ERR_ARG; };
     for (auto& kv : by_img) {
         std::vector<int>& ks = kv.second;
         const mi355_feature_chunk_header& h0 = hdr[ks[0]];
-        if (h0.n_kp < 0 || h0.n_kp > ctx->keepall_max) return bad(kv.first, "n_kp outside [0, " + std::to_string(ctx->keepall_max) + "] (keepall_max)");
+        if (h0.n_kp < 0 || h0.n_kp > max_rows) return bad(kv.first, "n_kp outside [0, " + std::to_string(max_rows) + "]" + (max_rows == MI355_FEATURE_CHUNK_ROWS ? "" : " (keepall_max)"));
         if (h0.w <= 0 || h0.h <= 0) return bad(kv.first, "bad image size");
         if (h0.n_chunks < 1 || h0.n_chunks != (int)ks.size()) return bad(kv.first, "n_chunks = " + std::to_string(h0.n_chunks) + " but " + std::to_string(ks.size()) + " records");
         for (int k : ks) {
@@ -470,7 +367,8 @@ static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr,
         if (next != h0.n_kp) return bad(kv.first, "rows do not tile [0, n_kp)");
     }
     if (by_img.empty()) return MI355_OK;
-    // the table is good: resident buffers (grow only: sized for 2048 rows at least, like install_features), then one launch
+    // the table is good: resident buffers (grow only, sized for 2048 rows at least: no allocation in steady state when the counts change
+    // from step to step), then one launch
     std::vector<ChunkDst> tab;
     tab.reserve(n);
     int max_lim = 0;
@@ -497,7 +395,7 @@ static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr,
             tab.push_back(t);
         }
     }
-    DevBuf& dtab = ctx->buf("install_chunk_tab");
+    DevBuf& dtab = ctx->buf("install_tab");
     MI_HIP(dtab.reserve(sizeof(ChunkDst) * tab.size()));
     MI_HIP(hipMemcpyAsync(dtab.p, tab.data(), sizeof(ChunkDst) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
     {
@@ -509,11 +407,31 @@ static int install_chunks(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr,
     return MI355_OK;
 }
 
+// Fixed headers enter as one-chunk headers {chunk 0, n_chunks 1, row0 0, rows n_kp} under the 2048-row ceiling: an image named twice has
+// more records than n_chunks.  Pending extractions are waited for only where the table lands on one.
+static int install_fixed(mi355_ctx* ctx, const char* who, const mi355_feature_header* hdr, const void* d_payload, int n, const int32_t* skip_ids, int n_skip) {
+    std::vector<mi355_feature_chunk_header> ch(n);
+    bool pending = false;
+    for (int k = 0; k < n; k++) {
+        ch[k] = mi355_feature_chunk_header{hdr[k].img_id, hdr[k].n_kp, hdr[k].w, hdr[k].h, 0, 1, 0, hdr[k].n_kp};
+        auto it = ctx->feats.find(hdr[k].img_id);
+        pending = pending || (hdr[k].img_id >= 0 && it != ctx->feats.end() && it->second.pending);
+    }
+    if (pending) { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
+    return install_chunks(ctx, who, MI355_FEATURE_CHUNK_ROWS, ch.data(), d_payload, n, skip_ids, n_skip);
+}
+
+extern "C" int mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n) {
+    LOCKED_PROLOGUE
+    if (n < 0 || (n > 0 && (!hdr || !d_payload))) return MI355_ERR_ARG;
+    return install_fixed(ctx, "install_features", hdr, d_payload, n, nullptr, 0);
+}
+
 extern "C" int mi355_install_feature_chunks_dev(mi355_ctx* ctx, const mi355_feature_chunk_header* hdr, const void* d_payload, int n_records) {
     LOCKED_PROLOGUE
     if (n_records < 0 || (n_records > 0 && (!hdr || !d_payload))) return MI355_ERR_ARG;
     { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }     // an extraction in flight must not land on installed rows
-    return install_chunks(ctx, hdr, d_payload, n_records, nullptr, 0);
+    return install_chunks(ctx, "install_feature_chunks", ctx->keepall_max, hdr, d_payload, n_records, nullptr, 0);
 }
 
 // ---- communicator ------------------------------------------------------------------------------------------------------------
@@ -595,23 +513,7 @@ extern "C" int mi355_allgather_features(mi355_ctx* ctx, const int32_t* img_ids, 
     auto local = [&]() -> int {
         if (n_local < 0 || n_max_per_rank < n_local || (n_local > 0 && !img_ids)) { ctx->set_error("allgather_features: bad arguments"); return MI355_ERR_ARG; }
         { int rc = mi_resolve_features(ctx); if (rc != MI355_OK) return rc; }
-        if (n_local == 0) return MI355_OK;
-        std::vector<PackSrc> src(n_local);
-        for (int k = 0; k < n_local; k++) {
-            auto it = ctx->feats.find(img_ids[k]);
-            if (it == ctx->feats.end()) { ctx->set_error("allgather_features: no resident features for image " + std::to_string(img_ids[k])); return MI355_ERR_ARG; }
-            const Features& f = it->second;
-            if (f.n > 2048) { ctx->set_error("allgather_features: more than 2048 keypoints"); return MI355_ERR_ARG; }       // as mi355_pack_features_dev
-            my_hdr[k].img_id = img_ids[k]; my_hdr[k].n_kp = f.n; my_hdr[k].w = f.w; my_hdr[k].h = f.h;
-            src[k] = PackSrc{f.kp.as<uint8_t>(), f.d8.as<uint8_t>(), f.n};
-        }
-        DevBuf& dsrc = ctx->buf("pack_src");
-        MI_HIP(dsrc.reserve(sizeof(PackSrc) * n_local));
-        MI_HIP(hipMemcpyAsync(dsrc.p, src.data(), sizeof(PackSrc) * n_local, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(pack_features_kernel, dim3(16, n_local), dim3(256), 0, ctx->stream, dsrc.as<PackSrc>(), my_pay);
-        MI_HIP(hipGetLastError());
-        MI_HIP(hipStreamSynchronize(ctx->stream));       // `src` goes out of scope
-        return MI355_OK;
+        return pack_chunks(ctx, "allgather_features", MI355_FEATURE_CHUNK_ROWS, img_ids, n_local, my_hdr, my_pay, n_local, PACK_GX_FIXED);      // as mi355_pack_features_dev
     };
     const int rc_local = local();
     std::string err_local;
@@ -628,7 +530,7 @@ extern "C" int mi355_allgather_features(mi355_ctx* ctx, const int32_t* img_ids, 
     if (rc_local != MI355_OK) { ctx->set_error(err_local); return rc_local; }
     for (int r = 0; r < world; r++)
         if (hdr[nm * r].img_id == -2) { ctx->set_error("allgather_features: rank " + std::to_string(r) + " failed before the exchange"); return MI355_ERR_FAILED; }
-    return install_features(ctx, hdr.data(), dpay.p, (int)(nm * world), img_ids, n_local);      // own frames are resident already
+    return install_fixed(ctx, "allgather_features", hdr.data(), dpay.p, (int)(nm * world), img_ids, n_local);      // own frames are resident already
 }
 
 // The chunk-record form: no n_max, the counts travel first.  Two small all-gathers of {records, status} carry every rank-local outcome -- the
@@ -676,7 +578,7 @@ extern "C" int mi355_allgather_feature_chunks(mi355_ctx* ctx, const int32_t* img
         MI_HIP(dhdr.reserve(sizeof(mi355_feature_chunk_header) * R * world));
         MI_HIP(dpay.reserve((size_t)MI355_FEATURE_RECORD_BYTES * R * world));
         for (size_t k = 0; k < R; k++) { my_hdr[k] = mi355_feature_chunk_header{-1, 0, 0, 0, 0, 0, 0, 0}; }
-        { const int rc = pack_chunks(ctx, img_ids, n_local, my_hdr, dpay.as<uint8_t>() + (size_t)MI355_FEATURE_RECORD_BYTES * R * rank, n_rec); if (rc != MI355_OK) return rc; }
+        { const int rc = pack_chunks(ctx, "allgather_feature_chunks", ctx->keepall_max, img_ids, n_local, my_hdr, dpay.as<uint8_t>() + (size_t)MI355_FEATURE_RECORD_BYTES * R * rank, n_rec, PACK_GX); if (rc != MI355_OK) return rc; }
         MI_HIP(hipMemcpyAsync(dhdr.as<mi355_feature_chunk_header>() + R * rank, my_hdr, sizeof(mi355_feature_chunk_header) * R, hipMemcpyHostToDevice, ctx->stream));
         return MI355_OK;
     };
@@ -691,7 +593,7 @@ extern "C" int mi355_allgather_feature_chunks(mi355_ctx* ctx, const int32_t* img
     MI_HIP(hipStreamSynchronize(ctx->stream));
     // 6. install: padding records skipped, own frames too unless asked for (every rank checks the same table: a bad one fails everywhere)
     const bool own = (flags & MI355_FEATURES_INSTALL_OWN) != 0;
-    return install_chunks(ctx, hdr.data(), dpay.p, (int)(R * world), own ? nullptr : img_ids, own ? 0 : n_local);
+    return install_chunks(ctx, "allgather_feature_chunks", ctx->keepall_max, hdr.data(), dpay.p, (int)(R * world), own ? nullptr : img_ids, own ? 0 : n_local);
 }
 
 extern "C" int mi355_allgather_results(mi355_ctx* ctx, const mi355_pair_result* d_local, int n_local, int flags, int root,

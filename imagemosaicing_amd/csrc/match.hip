@@ -21,6 +21,7 @@
 // in the loop) and the two half-waves are merged once at the end.  A wave owns 64 queries (two B operands): every A fragment and
 // every row constant read from LDS feeds two MFMAs.
 #include "common.h"
+#include "feature_rows.h"
 #include <algorithm>
 
 namespace {
@@ -358,26 +359,13 @@ __global__ void finalize_kernel(const PairDesc* pairs, const int* nsel, int n_pa
 // ---- features ------------------------------------------------------------------------------------------------
 // 8 lanes per descriptor row (16 bytes each), 32 rows per workgroup: a workgroup per row was 2048 workgroups of 128 threads per image,
 // dispatch-bound (7 us per image; 3.5 ms for the 500 images a rank installs after the feature exchange)
-__global__ __launch_bounds__(256) void finish_features_kernel(const mi355_keypoint* kp, const uint8_t* d8, int n, const int* d_n, int npad,
-                                                              float2* xy, int8_t* s8, int* n8) {
+__global__ __launch_bounds__(256) void finish_features_kernel(const mi355_keypoint* kp, const uint8_t* d8, int n, int npad, float2* xy, int8_t* s8, int* n8) {
     const int row = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;
     if (row >= npad) return;
-    if (d_n) n = *d_n;                                       // count still on the device (asynchronous SIFT)
-    uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);     // padding rows: zeros after the shift
+    uint4 v = feature_pad_piece();
     if (row < n) v = *reinterpret_cast<const uint4*>(d8 + (size_t)row * 128 + part * 16);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) { const int t = (int)((w[q] >> (8 * b)) & 0xffu) - 128; s += t * t; }
-    // the matcher's operand: the descriptor moved to int8 (u - 128 = u ^ 0x80 as a byte)
-    *reinterpret_cast<uint4*>(s8 + (size_t)row * 128 + part * 16) = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-    if (part == 0) {
-        n8[row] = s;
-        if (row < n) xy[row] = make_float2(kp[row].x, kp[row].y);
-    }
+    feature_row_piece(v, s8, n8, row, part);
+    if (part == 0 && row < n) xy[row] = make_float2(kp[row].x, kp[row].y);
 }
 
 // the same for all frames of a SIFT batch in one launch (blockIdx.y = frame): 32 launches of 5 us at the tail of every batch were 160 us
@@ -390,22 +378,11 @@ __global__ __launch_bounds__(256) void finish_features_batch_kernel(FinishBatch 
     const int k = blockIdx.y;
     const int row = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;
     if (row >= npad) return;
-    const int n = d_n[(size_t)k * n_stride];
-    const uint8_t* d8 = fb.d8[k];
-    uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
-    if (row < n) v = *reinterpret_cast<const uint4*>(d8 + (size_t)row * 128 + part * 16);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) { const int t = (int)((w[q] >> (8 * b)) & 0xffu) - 128; s += t * t; }
-    *reinterpret_cast<uint4*>(fb.s8[k] + (size_t)row * 128 + part * 16) = make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-    s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-    if (part == 0) {
-        fb.n8[k][row] = s;
-        if (row < n) fb.xy[k][row] = make_float2(fb.kp[k][row].x, fb.kp[k][row].y);
-    }
+    const int n = d_n[(size_t)k * n_stride];             // the count is still on the device (asynchronous SIFT)
+    uint4 v = feature_pad_piece();
+    if (row < n) v = *reinterpret_cast<const uint4*>(fb.d8[k] + (size_t)row * 128 + part * 16);
+    feature_row_piece(v, fb.s8[k], fb.n8[k], row, part);
+    if (part == 0 && row < n) fb.xy[k][row] = make_float2(fb.kp[k][row].x, fb.kp[k][row].y);
 }
 
 __global__ void desc_f32_to_u8_kernel(const float* f, uint8_t* d8, size_t count) {
@@ -539,16 +516,14 @@ void split_large_pairs(const std::vector<PairDesc>& pd, std::vector<BigPairDev>&
 
 }  // namespace
 
-int mi_finish_features(mi355_ctx* ctx, Features& f, const int* d_n, hipStream_t st) {
-    if (!st) st = ctx->stream;
-    const int nmax = d_n ? KSTRIDE : f.n;
-    f.npad = row_pad(nmax);
-    MI_HIP(f.xy.reserve(sizeof(float2) * (size_t)(nmax > 0 ? nmax : 1)));
+int mi_finish_features(mi355_ctx* ctx, Features& f) {
+    f.npad = row_pad(f.n);
+    MI_HIP(f.xy.reserve(sizeof(float2) * (size_t)(f.n > 0 ? f.n : 1)));
     MI_HIP(f.s8.reserve((size_t)128 * (size_t)f.npad));
     MI_HIP(f.n8.reserve(sizeof(int) * (size_t)f.npad));
-    ProfScope ps(ctx, "features", (double)f.npad * 128 * 2, st);
-    hipLaunchKernelGGL(finish_features_kernel, dim3((f.npad + 31) / 32), dim3(256), 0, st,
-                       f.kp.as<mi355_keypoint>(), f.d8.as<uint8_t>(), f.n, d_n, f.npad, f.xy.as<float2>(), f.s8.as<int8_t>(), f.n8.as<int>());
+    ProfScope ps(ctx, "features", (double)f.npad * 128 * 2);
+    hipLaunchKernelGGL(finish_features_kernel, dim3((f.npad + 31) / 32), dim3(256), 0, ctx->stream,
+                       f.kp.as<mi355_keypoint>(), f.d8.as<uint8_t>(), f.n, f.npad, f.xy.as<float2>(), f.s8.as<int8_t>(), f.n8.as<int>());
     MI_HIP(hipGetLastError());
     return MI355_OK;
 }

@@ -578,7 +578,10 @@ int  mi355_screen_pairs(mi355_ctx* ctx, const int32_t* img_ids, int n, const mi3
 typedef struct { int32_t img_id /* < 0: padding record */, n_kp, w, h; } mi355_feature_header;
 /* Transport-agnostic halves: pack resident features into records at d_payload (device, n x MI355_FEATURE_RECORD_BYTES; headers to
  * the HOST array hdr) / install records as resident features (as if extracted here).  Used by callers that bring their own
- * transport (MPI, the gloo CPU tests); mi355_allgather_features does both around one RCCL all-gather. */
+ * transport (MPI, the gloo CPU tests); mi355_allgather_features does both around one RCCL all-gather.  A record is the one-chunk
+ * case of the chunk records below ({chunk 0, n_chunks 1, row0 0, rows n_kp}; this header is the chunk header's first four fields), and
+ * the install checks the whole table like theirs: a bad header (n_kp outside [0, 2048], w or h <= 0) or an image named twice returns
+ * MI355_ERR_ARG and leaves the ctx's features as they were. */
 int  mi355_pack_features_dev(mi355_ctx* ctx, const int32_t* img_ids, int n, mi355_feature_header* hdr, void* d_payload);
 int  mi355_install_features_dev(mi355_ctx* ctx, const mi355_feature_header* hdr, const void* d_payload, int n);
 

@@ -5,7 +5,9 @@ which carries frames of any keypoint count -- keep-all frames (nfeatures <= 0) h
     (mi355_bf_match, mi355_match_pairs, both the <= 2048 path and the large-pair path) gives the same bytes on both contexts;
   * the record layout: chunk c holds rows [2048 c, 2048 c + rows), zeros elsewhere; a frame of <= 2048 keypoints is one chunk, byte for byte
     mi355_pack_features_dev's record;
-  * malformed tables raise and change nothing;
+  * malformed tables raise and change nothing, the fixed form's included (a bad header, an image named twice);
+  * one layout, two headers: records packed by the fixed form install through the chunk form and the other way round, at frame sizes around
+    the 256-row padding and the 2048-row record; a smaller frame installed over a larger one leaves no stale padding rows;
   * RCCL, a communicator of one rank: the collective over keep-all frames, re-installing the rank's own frames, leaves features and pair
     records as they were; an unknown id fails and the communicator still works.
 """
@@ -218,3 +220,123 @@ def test_rccl_collective_world1_keepall(src):
     assert np.array_equal(rec0.view(np.uint8), rec2.view(np.uint8))
     ex.close()
     ctx.close()
+
+
+# ---- one layout, two headers: the fixed record is the chunk {row0 0, rows n_kp} --------------------------------------------------------------
+EDGE = [0, 1, 255, 256, 257, 2047, 2048]          # image id k has EDGE[k] keypoints: around the 256-row padding and the 2048-row record
+EDGE_PAIRS = [(6, 5), (5, 6), (4, 6), (6, 4), (3, 4), (2, 3), (1, 6), (6, 1), (4, 2)]
+
+
+@pytest.fixture(scope="module")
+def edge():
+    """a ctx with the synthetic frames 0..6 of EDGE keypoints; their fixed and chunk packs (headers, payload on the device)"""
+    import torch
+    import imagemosaicing_amd as im
+    a = im.Context(0)
+    for k, n in enumerate(EDGE):
+        kp, d = synth_features(n, k)
+        a.SetFeatures(k, kp, d, W, H)
+    ids = list(range(len(EDGE)))
+    fixed = torch.empty((len(ids), im.FEATURE_RECORD_BYTES), dtype=torch.uint8, device="cuda")
+    chunks = torch.empty((len(ids), im.FEATURE_RECORD_BYTES), dtype=torch.uint8, device="cuda")
+    fh = a.PackFeaturesDev(ids, fixed.data_ptr())
+    ch = a.PackFeatureChunksDev(ids, chunks.data_ptr(), len(ids))
+    assert len(ch) == len(ids) and torch.equal(fixed, chunks)
+    yield a, ids, fh, fixed, ch, chunks
+    a.close()
+
+
+def as_chunk_headers(fh):
+    import imagemosaicing_amd as im
+    ch = np.zeros(len(fh), im.FEATURE_CHUNK_HEADER)
+    for f in ("img_id", "n_kp", "w", "h"):
+        ch[f] = fh[f]
+    ch["n_chunks"] = 1
+    ch["rows"] = fh["n_kp"]
+    return ch
+
+
+def as_fixed_headers(ch):
+    import imagemosaicing_amd as im
+    fh = np.zeros(len(ch), im.FEATURE_HEADER)
+    for f in ("img_id", "n_kp", "w", "h"):
+        fh[f] = ch[f]
+    return fh
+
+
+def same_matches(a, b, pairs):
+    for i, j in pairs:
+        for x, y in zip(a.BFMatch(i, j, True, 2048), b.BFMatch(i, j, True, 2048)):
+            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (i, j)
+    ra, rb = a.MatchPairs(pairs, 2.5, 3), b.MatchPairs(pairs, 2.5, 3)
+    assert np.array_equal(ra.view(np.uint8), rb.view(np.uint8)), "pair records differ"
+    return ra
+
+
+@pytest.mark.parametrize("form", ["fixed_pack_chunk_install", "chunk_pack_fixed_install"])
+def test_cross_form_install(edge, form):
+    import imagemosaicing_amd as im
+    src, ids, fh, fixed, ch, chunks = edge
+    assert [int(n) for n in fh["n_kp"]] == EDGE and np.array_equal(as_chunk_headers(fh), ch) and np.array_equal(as_fixed_headers(ch), fh)
+    dst = im.Context(0)
+    if form == "fixed_pack_chunk_install":
+        dst.InstallFeatureChunksDev(as_chunk_headers(fh), fixed.data_ptr())
+    else:
+        dst.InstallFeaturesDev(as_fixed_headers(ch), chunks.data_ptr())
+    same_features(src, dst, ids)
+    rec = same_matches(src, dst, EDGE_PAIRS)
+    assert int(rec[0]["accepted"]) == 1               # 2048 against 2047 rows of one pool
+    dst.close()
+
+
+def test_shrinking_reinstall_rewrites_the_padding_rows(edge):
+    """257 keypoints, then 1 under the same id: the rows [1, 256) the matcher reads as padding must not keep the first frame's descriptors"""
+    import imagemosaicing_amd as im
+    src, ids, fh, fixed, ch, chunks = edge
+    dst, fresh = im.Context(0), im.Context(0)
+    h = fh[[4, 6]].copy()
+    h["img_id"] = [7, 8]
+    pay, pay1 = fixed[[4, 6]].contiguous(), fixed[[1]].contiguous()
+    dst.InstallFeaturesDev(h, pay.data_ptr())
+    h1 = fh[[1]].copy()
+    h1["img_id"] = 7
+    dst.InstallFeaturesDev(h1, pay1.data_ptr())
+    for k, q in ((7, 1), (8, 6)):
+        kp, d = src.GetFeatures(q)
+        fresh.SetFeatures(k, kp, d, W, H)
+    same_features(fresh, dst, [7, 8])
+    same_matches(fresh, dst, [(7, 8), (8, 7)])
+    dst.close(); fresh.close()
+
+
+def test_fixed_table_is_checked_before_anything_changes(edge):
+    import imagemosaicing_amd as im
+    src, ids, fh, fixed, ch, chunks = edge
+    dst = im.Context(0)
+    for k, q in ((10, 2), (11, 4)):                   # what dst holds before: frames 2 and 4 as images 10 and 11
+        kp, d = src.GetFeatures(q)
+        dst.SetFeatures(k, kp, d, W, H)
+    before = [dst.GetFeatures(k) for k in (10, 11)]
+    pay = fixed[[1, 3, 5]].contiguous()
+    good = fh[[1, 3, 5]].copy()
+    good["img_id"] = [10, 11, 12]
+
+    def broken(field, value):
+        h = good.copy()
+        h[field][2] = value
+        return h
+
+    for name, h in (("n_kp = 2049", broken("n_kp", 2049)), ("w = 0", broken("w", 0)), ("an image named twice", broken("img_id", 10))):
+        with pytest.raises(im.Mi355Error):
+            dst.InstallFeaturesDev(h, pay.data_ptr())
+        for k, (kp, d) in zip((10, 11), before):
+            kp1, d1 = dst.GetFeatures(k)
+            assert len(kp1) == len(kp) and np.array_equal(kp1.view(np.uint8), kp.view(np.uint8)) and np.array_equal(d1, d), (name, k)
+        with pytest.raises(im.Mi355Error):
+            dst.GetFeatures(12)                       # not created either
+    dst.InstallFeaturesDev(good, pay.data_ptr())      # the good table still installs
+    for k, q in ((10, 1), (11, 3), (12, 5)):
+        ka, da = src.GetFeatures(q)
+        kb, db = dst.GetFeatures(k)
+        assert np.array_equal(ka.view(np.uint8), kb.view(np.uint8)) and np.array_equal(da, db), k
+    dst.close()

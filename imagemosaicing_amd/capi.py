@@ -62,6 +62,18 @@ class MedianParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("depth", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class SeamCutParams(C.Structure):
+    _fields_ = [("ramp", C.c_int32), ("level", C.c_int32), ("depth", C.c_int32), ("data_weight", C.c_int32), ("diff_weight", C.c_int32),
+                ("seam_penalty", C.c_int32), ("miss_cost", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SeamReport(C.Structure):
+    _fields_ = [("energy_before", C.c_int64), ("energy_after", C.c_int64), ("changed", C.c_int32), ("fallback", C.c_int32)]
+
+
+SEAM_CELL = np.dtype([("frame", "<u2", 8), ("omega", "u1", 8), ("gray", "u1", 8)])     # mi355_seam_cell, 32 bytes
+
+
 class Camera(C.Structure):
     """mi355_camera: a Brown-Conrady camera in pixels, OpenCV's coefficient order and signs"""
     _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
@@ -922,6 +934,87 @@ class Context:
         self._chk(self.L.mi355_mosaic_seamline_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
         return need
 
+    # ---- optimised seamlines (mi355_seam_*, mi355_mosaic_seamcut*, csrc/seamcut.hip) ------------------------------------------
+    def _dev_frames(self, d_imgs, w, h, ws, h9s):
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        n = len(w)
+        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
+        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
+        return n, ptrs, w, h, ws, np.ascontiguousarray(h9s, np.float32)
+
+    def SeamCandidatesDev(self, d_imgs, w, h, ws, h9s, d_cand, gw, gh, params=None, **kw):
+        """mi355_seam_candidates_dev: the cell records (SEAM_CELL, 32 bytes each) of the gh x gw grid into device memory d_cand"""
+        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
+        p = params if params is not None else seamcut_params(**kw)
+        self._chk(self.L.mi355_seam_candidates_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cand or 0) or None),
+                                                   int(gw), int(gh)))
+
+    def SeamLabelsDev(self, d_cand, gw, gh, d_cells, params=None, **kw):
+        """mi355_seam_labels_dev: device records in, the uint16 [gh, gw] cell map into device memory d_cells; returns the report dict"""
+        p = params if params is not None else seamcut_params(**kw)
+        r = SeamReport()
+        self._chk(self.L.mi355_seam_labels_dev(self._h, C.c_void_p(int(d_cand or 0) or None), int(gw), int(gh), C.byref(p),
+                                               C.c_void_p(int(d_cells or 0) or None), C.byref(r)))
+        return _report(r)
+
+    def SeamCellsDev(self, d_imgs, w, h, ws, h9s, d_cells, gw, gh, params=None, **kw):
+        """mi355_seam_cells_dev: candidates and labels in one call; returns the report dict"""
+        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
+        p = params if params is not None else seamcut_params(**kw)
+        r = SeamReport()
+        self._chk(self.L.mi355_seam_cells_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None),
+                                              int(gw), int(gh), C.byref(r)))
+        return _report(r)
+
+    def MosaicSeamCutDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_cells=0, d_owner=0, d_count=0, params=None, **kw):
+        """mi355_mosaic_seamcut_dev: the seamline render following the device cell map d_cells (0: candidates and labels are made first, all
+        three stages in one call); outputs, stripes and withheld frames as MosaicSeamlineDev; complete on return"""
+        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
+        p = params if params is not None else seamcut_params(**kw)
+        self._chk(self.L.mi355_mosaic_seamcut_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None),
+                                                  C.c_void_p(int(d_canvas or 0) or None), int(cw), int(ch), int(cws),
+                                                  C.c_void_p(int(d_owner or 0) or None), C.c_void_p(int(d_count or 0) or None),
+                                                  int(row0), int(rows if rows >= 0 else ch)))
+
+    def MosaicSeamCut(self, imgs, h9s, params=None, want_owner=False, **kw):
+        """mi355_mosaic_seamcut: host images in, all three stages, outputs as MosaicSeamline"""
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamcut_params(**kw)
+        canvas, owner = C.c_void_p(), C.c_void_p()
+        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_mosaic_seamcut(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
+                                              C.byref(cws), C.byref(owner) if want_owner else None))
+        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
+        self.L.mi355_free(canvas)
+        if not want_owner:
+            return buf, cw.value, ch.value, cws.value
+        own = _copy_out(owner, 2 * ch.value * cw.value, np.uint16).reshape(ch.value, cw.value)
+        self.L.mi355_free(owner)
+        return buf, cw.value, ch.value, cws.value, own
+
+    def MosaicSeamCutInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
+        """mi355_mosaic_seamcut_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamcut_params(**kw)
+        cw, ch, _, _ = mosaic_layout(w, h, h9s)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_seamcut_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
+                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
+    def SeamCutCover(self, w, h, h9s, d_cells, row0=0, rows=-1, params=None, **kw):
+        """mi355_mosaic_seamcut_cover: need[k] = 1 exactly for the frames that own a pixel of canvas rows [row0, row0 + rows) under d_cells"""
+        n = len(w)
+        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else seamcut_params(**kw)
+        need = np.zeros(n, np.uint8)
+        self._chk(self.L.mi355_mosaic_seamcut_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None), int(row0), int(rows),
+                                                    _p(need)))
+        return need
+
     # ---- median render (mi355_mosaic_median*, csrc/median.hip) -------------------------------------------------------------
     def MosaicMedian(self, imgs, h9s, params=None, want_spread=False, **kw):
         """mi355_mosaic_median: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_spread (canvas, cw, ch, cws, spread [ch, cw]
@@ -1369,6 +1462,42 @@ def median_params(ramp=None, depth=None):
         if v is not None:
             setattr(p, name, int(v))
     return p
+
+
+def seamcut_params(ramp=None, level=None, depth=None, data_weight=None, diff_weight=None, seam_penalty=None, miss_cost=None):
+    """mi355_seamcut_params: the library's defaults (mi355_default_seamcut_params: ramp 0, level 3, depth 4, costs 1, 2, 2, 32) with the given
+    fields replaced"""
+    p = SeamCutParams()
+    load_library().mi355_default_seamcut_params(C.byref(p))
+    for name, v in (("ramp", ramp), ("level", level), ("depth", depth), ("data_weight", data_weight), ("diff_weight", diff_weight),
+                    ("seam_penalty", seam_penalty), ("miss_cost", miss_cost)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def seam_grid(w, h, h9s, level):
+    """(gw, gh): the cell grid of the survey's canvas at `level`"""
+    cw, ch, _, _ = mosaic_layout(w, h, h9s)
+    s = 1 << int(level)
+    return (cw + s - 1) // s, (ch + s - 1) // s
+
+
+def _report(r):
+    return dict(energy_before=int(r.energy_before), energy_after=int(r.energy_after), changed=int(r.changed), fallback=int(r.fallback))
+
+
+def seam_labels_host(cand, params=None, **kw):
+    """mi355_seam_labels_host: cell records [gh, gw] of SEAM_CELL in, (cells [gh, gw] uint16, report dict) out; no GPU"""
+    cand = np.ascontiguousarray(cand, SEAM_CELL)
+    gh, gw = cand.shape
+    p = params if params is not None else seamcut_params(**kw)
+    cells = np.zeros((gh, gw), np.uint16)
+    r = SeamReport()
+    rc = load_library().mi355_seam_labels_host(_p(cand), int(gw), int(gh), C.byref(p), _p(cells), C.byref(r))
+    if rc != 0:
+        raise Mi355Error(rc, "seam_labels_host: bad arguments")
+    return cells, _report(r)
 
 
 def undistort_params(out_fx=None, out_fy=None, out_cx=None, out_cy=None, fill=None):

@@ -196,6 +196,9 @@ int mi_mosaic_seamline_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* 
 int mi_mosaic_median_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                          const mi355_median_params* params, uint8_t* d_canvas, int cw, int ch, int cws, uint8_t* d_spread, uint16_t* d_count,
                          int row0, int rows, uint8_t* cover_only);      // median.hip
+int mi_mosaic_seamcut_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                          const mi355_seamcut_params* params, const uint16_t* d_cells, uint8_t* d_canvas, int cw, int ch, int cws, uint16_t* d_owner,
+                          uint16_t* d_count, int row0, int rows, uint8_t* cover_only);      // seamcut.hip; d_cells NULL: candidates and labels first
 int mi_mosaic_overview_dev(mi355_ctx*, const uint8_t* d_rows, int cw, int ch, int cws, const uint16_t* d_valid_rows, int nodata, int levels,
                            uint8_t* const* d_levels, uint16_t* const* d_covers, int row0, int rows, int only_level = 0);      // overview.hip; only_level = l: d_levels / d_covers entries other than l - 1 may be NULL (the preview)
 int mi_sift_flush(mi355_ctx*);                               // enqueues every partly filled batch (no wait)

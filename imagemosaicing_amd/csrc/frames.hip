@@ -319,6 +319,19 @@ extern "C" int mi355_mosaic_median_into(mi355_ctx* ctx, const uint8_t* const* im
     });
 }
 
+extern "C" int mi355_mosaic_seamcut_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                          const int* ws, int n, const float* h9s, const mi355_seamcut_params* params, uint8_t* dst, int dst_pitch,
+                                          int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || (!imgs && !img_ids)) { ctx->set_error("mosaic_seamcut_into: bad arguments"); return MI355_ERR_ARG; }
+    int lw, lh, lws;
+    const int rc = render_layout(ctx, "mosaic_seamcut_into", w, h, n, h9s, &lw, &lh, &lws);
+    if (rc != MI355_OK) return rc;
+    return render_into(ctx, "mosaic_seamcut_into", imgs, img_ids, w, h, ws, n, h9s, nullptr, dst, dst_pitch, cw, ch, lw, lh, lws, [&](const uint8_t* const* d, uint8_t* dc) {
+        return mi_mosaic_seamcut_dev(ctx, d, w, h, ws, n, h9s, params, nullptr, dc, lw, lh, lws, nullptr, nullptr, 0, lh, nullptr);
+    });
+}
+
 extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
                                          const int* ws, int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch,
                                          int cw, int ch) {

@@ -313,6 +313,72 @@ int  mi355_mosaic_median(mi355_ctx* ctx, const uint8_t* const* imgs, const int* 
 int  mi355_mosaic_median_cover(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const mi355_median_params* params,
                                int row0, int rows, uint8_t* need);
 
+/* ---- optimised seamlines: a cost-aware owner map on a grid of canvas cells, and the render that follows it (csrc/seamcut.hip) ----------
+ * The seamline render cuts every overlap down its geometric middle, whatever is there.  Here the seam is moved, cell by cell, to where the two
+ * frames agree: three stages, integers throughout, restated in numpy by tests/seamcut_ref.py.  The reference has no such mode.
+ * Grid: cells of s x s canvas pixels, s = 1 << level, gw = ceil(cw / s) by gh = ceil(ch / s) over the canvas of mi355_mosaic_layout; the probe
+ *   of cell (cx, cy) is canvas pixel (min(cx s + s / 2, cw - 1), min(cy s + s / 2, ch - 1)).
+ * 1. Candidates (mi355_seam_candidates_dev).  Which frames give the probe a sample, and their weight omega, are the seamline render's own
+ *   statement (frame skipping, params.ramp, the 2^20 side limit, n <= 65535 included).  The cell's candidates are the m = min(|C|, depth)
+ *   contributing frames that are largest in the seamline order (omega, k): slot 0 is the seamline owner of the probe, slots m .. 7 are empty
+ *   (all fields 0).  A slot holds frame + 1, omega, and the gray signature: (sum + num / 2) / num over the num >= 1 pixels of the cell, clipped
+ *   to the canvas, at which that frame gives a sample, of the gray (1868 B + 9617 G + 4899 R + 8192) >> 14 of the sample bytes.  A cell mean, not
+ *   the probe's one sample: one bilinear sample carries the texture's sub-pixel disagreement, and every seam would look expensive.
+ * 2. Labels (mi355_seam_labels_dev; mi355_seam_labels_host gives the same bits without a GPU).  32-bit integers:
+ *     D(p, a)  = data_weight (omega_0(p) - omega_a(p))                                     slot a of cell p
+ *     V        = 0 where 4-neighbour cells p, q carry the same frame, else seam_penalty + diff_weight (d(p) + d(q)), with
+ *     d(x)     = |g_k(x) - g_l(x)| where the two frames k, l are both candidates of cell x, else miss_cost
+ *     L_r(p, a) = D(p, a) + min_b [L_r(p - r, b) + V] - min_b L_r(p - r, b)                for each of the four axis directions r,
+ *                 = D(p, a) at the start of a path and behind a cell without candidates
+ *     S(p, a)  = sum_r L_r(p, a); the label of p is the argmin over its filled slots of (S, a): the lower slot -- the deeper frame -- wins a tie.
+ *   L_r <= 16 * 254 + 255 + 16 * 510 = 12479, S < 2^16.  The energy of a labelling is sum_p D + sum V over the 4-neighbour pairs whose cells both
+ *   have a candidate (64-bit).  energy_before is that of the all-slot-0 labelling, which is the seamline render's; energy_after that of the
+ *   argmin labelling.  If energy_after > energy_before the all-slot-0 labelling is returned and `fallback` set: by its own measure the result
+ *   is never worse than the seamline render.  `changed` counts the cells of the RETURNED labelling whose label is not slot 0.
+ *   Cell map: uint16_t [gh][gw]: frame + 1 where the returned label is not slot 0, and 0 elsewhere -- a cell without candidates, and a cell that
+ *   keeps its slot 0: there the render keeps the seamline rule pixel by pixel, so that a labelling which moves nothing IS the seamline render
+ *   (a cell that named its probe's owner would pull the whole cell to that frame and turn every untouched seam into a staircase).
+ * 3. Render (mi355_mosaic_seamcut_dev): the seamline render with one more input.  For pixel (x, y), f = cells[y >> level][x >> level] - 1: if
+ *   f >= 0 and frame f gives the pixel a sample the owner is f, else the seamline owner; out = s_owner; d_owner, d_count, stripes (row0, rows),
+ *   row padding as the seamline render.  d_cells == NULL: stages 1 and 2 run first, over the whole canvas, into a map the ctx keeps -- on every
+ *   call, and stage 1 needs every frame it does not skip, so no pointer may be withheld in this form: render stripes, and withhold frames
+ *   by mi355_mosaic_seamcut_cover, with a map made once by mi355_seam_cells_dev.
+ * Consequences: an all-zero cell map, depth = 1, and diff_weight = seam_penalty = 0 each give the seamline render's bytes, owner and count;
+ *   energy_after <= energy_before or the fallback is set; the count map does not depend on the cell map.
+ * Cost: stage 1 samples what a depth-`depth` median render samples (each candidate over its cell) in one launch of one wave per cell; stage 2
+ *   is four launches of one wave per scanline, a sequential chain of 8 x 8 slot pairs per step, plus three per-cell passes over 32 + 16 + 3
+ *   bytes a cell; stage 3 is the seamline render plus one map load per lane and row.
+ * Pointers: stage 1 reads every frame the renders do not skip: d_imgs[k] == NULL for one of them is MI355_ERR_ARG naming it.  Stage 3 follows
+ *   the seamline render: a frame that owns no pixel of the rows under the rule above may be NULL; NULL for one that does is MI355_ERR_ARG before
+ *   anything is written.  mi355_mosaic_seamcut_cover: need[k] = 1 exactly for the frames that own a pixel of the rows under that rule.
+ * Errors: every field of the parameters is range-checked -- ramp >= 0, level 2..5, depth 1..8, data_weight and diff_weight 0..16, seam_penalty
+ *   and miss_cost 0..255 -- MI355_ERR_ARG outside; gw, gh must be the layout's at params.level; otherwise as the seamline twins.
+ * The cost defaults are data_weight 1, diff_weight 2, seam_penalty 2, miss_cost 32.  diff_weight was raised from the first value 1 after the
+ *   quality measurement: on small frames, where omega falls by 8 a pixel, no rectangle placed astride the seam was given to one owner at 1, 57
+ *   of the 355 searched two- and three-frame placements were at 2 and 85 at 4; a larger seam_penalty changed nothing (scratch/seamcut_quality.py,
+ *   profiles/seamcut_quality.json).  A rectangle placed symmetrically on the seam stays cut at any of them: DESIGN 5 says why. */
+#define MI355_SEAMCUT_MAX_DEPTH 8
+typedef struct { int32_t ramp, level, depth, data_weight, diff_weight, seam_penalty, miss_cost, reserved; } mi355_seamcut_params;
+typedef struct { uint16_t frame[MI355_SEAMCUT_MAX_DEPTH]; uint8_t omega[MI355_SEAMCUT_MAX_DEPTH]; uint8_t gray[MI355_SEAMCUT_MAX_DEPTH]; } mi355_seam_cell;   /* 32 bytes */
+typedef struct { int64_t energy_before, energy_after; int32_t changed, fallback; } mi355_seam_report;
+void mi355_default_seamcut_params(mi355_seamcut_params* p);          /* ramp 0, level 3, depth 4, data_weight 1, diff_weight 2, seam_penalty 2, miss_cost 32 */
+int  mi355_seam_candidates_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                               const mi355_seamcut_params* params, mi355_seam_cell* d_cand /* DEVICE, gh x gw */, int gw, int gh);
+int  mi355_seam_labels_dev(mi355_ctx* ctx, const mi355_seam_cell* d_cand, int gw, int gh, const mi355_seamcut_params* params,
+                           uint16_t* d_cells /* DEVICE, gh x gw */, mi355_seam_report* report /* HOST, may be NULL */);
+int  mi355_seam_labels_host(const mi355_seam_cell* cand, int gw, int gh, const mi355_seamcut_params* params, uint16_t* cells, mi355_seam_report* report);
+/* stages 1 and 2, the records in a buffer of the ctx */
+int  mi355_seam_cells_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                          const mi355_seamcut_params* params, uint16_t* d_cells, int gw, int gh, mi355_seam_report* report);
+int  mi355_mosaic_seamcut_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                              const mi355_seamcut_params* params, const uint16_t* d_cells, uint8_t* d_canvas, int cw, int ch, int cws,
+                              uint16_t* d_owner, uint16_t* d_count, int row0, int rows);
+/* host images in, all three stages; *canvas and, when owner != NULL, *owner (ch x cw) are allocated by the library -> mi355_free */
+int  mi355_mosaic_seamcut(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                          const mi355_seamcut_params* params, uint8_t** canvas, int* cw, int* ch, int* cws, uint16_t** owner);
+int  mi355_mosaic_seamcut_cover(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const mi355_seamcut_params* params,
+                                const uint16_t* d_cells /* DEVICE */, int row0, int rows, uint8_t* need);
+
 /* LaplacianPyramidBlending warp stage (MosaicImage.cpp:2233-2460) + FindMasksByDistMap (:1761-1881):
  * per kept image a tight chip (3ch u8; the reference then converts to CV_16S), its validity mask and, with
  * find_masks!=0, the exclusive distance-map ownership masks.  h9s must carry the resScale multiplication of
@@ -396,6 +462,9 @@ int  mi355_mosaic_seamline_into(mi355_ctx* ctx, const uint8_t* const* imgs, cons
 /* mi355_mosaic_median's canvas with mi355_mosaic_seamline_into's sources, destination and download */
 int  mi355_mosaic_median_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                               int n, const float* h9s, const mi355_median_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
+/* mi355_mosaic_seamcut's canvas (all three stages) with mi355_mosaic_seamline_into's sources, destination and download */
+int  mi355_mosaic_seamcut_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                               int n, const float* h9s, const mi355_seamcut_params* params, uint8_t* dst, int dst_pitch, int cw, int ch);
 int  mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
                                int n, const float* h9s, const uint8_t* keep, int band, uint8_t* dst, int dst_pitch, int cw, int ch);
 

@@ -1015,6 +1015,91 @@ class Context:
                                                     _p(need)))
         return need
 
+    # ---- multiband blend along optimised seams (mi355_blend_seam_*, mi355_*_seam*, csrc/blend_seam.hip) ------------------------
+    def BlendSeamCellsDev(self, d_imgs, w, h, ws, h9s, d_cells, gw, gh, keep=None, d_cand=0, params=None, **kw):
+        """mi355_blend_seam_cells_dev: candidates (in the blend's geometry) and labels; the uint16 [gh, gw] cell map into device memory
+        d_cells, the records into d_cand when given; returns the report dict"""
+        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
+        p = params if params is not None else seamcut_params(**kw)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        r = SeamReport()
+        self._chk(self.L.mi355_blend_seam_cells_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), C.byref(p),
+                                                    C.c_void_p(int(d_cells or 0) or None), int(gw), int(gh), C.byref(r), C.c_void_p(int(d_cand or 0) or None)))
+        return _report(r)
+
+    def ChipsAndMasksSeam(self, imgs, h9s, keep=None, cells=None, params=None, **kw):
+        """mi355_chips_and_masks_seam: ChipsAndMasks(find_masks=True) whose ownership follows the host cell map `cells` ([gh, gw] uint16;
+        None: candidates and labels are made first).  The same dictionary; feeds MultiBandBlend."""
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        p = params if params is not None else seamcut_params(**kw)
+        if cells is None:
+            gw, gh = blend_seam_grid(w, h, h9s, p.level, keep_a)
+        else:
+            cells = np.ascontiguousarray(cells, np.uint16)
+            gh, gw = cells.shape
+        nch = C.c_int(0)
+        chips = C.c_void_p()
+        cimgs = C.POINTER(C.c_void_p)()
+        masks = C.POINTER(C.c_void_p)()
+        cw, ch = C.c_int(), C.c_int()
+        self._chk(self.L.mi355_chips_and_masks_seam(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), C.byref(p), _p(cells), int(gw), int(gh),
+                                                    C.byref(nch), C.byref(chips), C.byref(cimgs), C.byref(masks), C.byref(cw), C.byref(ch)))
+        nv = nch.value
+        info = _copy_out(chips, nv * CHIPINFO.itemsize, CHIPINFO)
+        out_c, out_m = [], []
+        for v in range(nv):
+            cwv, chv = int(info[v]["w"]), int(info[v]["h"])
+            cws_, mws = (cwv * 3 + 3) & ~3, (cwv + 3) & ~3
+            out_c.append(_copy_out(cimgs[v], chv * cws_, np.uint8).reshape(chv, cws_))
+            out_m.append(_copy_out(masks[v], chv * mws, np.uint8).reshape(chv, mws))
+            self.L.mi355_free(C.c_void_p(cimgs[v]))
+            self.L.mi355_free(C.c_void_p(masks[v]))
+        self.L.mi355_free(chips)
+        self.L.mi355_free(C.cast(cimgs, C.c_void_p))
+        self.L.mi355_free(C.cast(masks, C.c_void_p))
+        return dict(cw=cw.value, ch=ch.value, chips=info, chip_imgs=out_c, masks=out_m)
+
+    def MosaicBlendedSeamDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, keep=None, band=5, d_cells=0, gw=None, gh=None, params=None, **kw):
+        """mi355_mosaic_blended_seam_dev: device frames in, the blended canvas into device memory d_canvas; the ownership follows the device
+        cell map d_cells (0: it is made first).  Enqueued on the ctx's stream and waited for."""
+        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
+        p = params if params is not None else seamcut_params(**kw)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        if gw is None or gh is None:
+            gw, gh = blend_seam_grid(w, h, h9s, p.level, keep_a)
+        self._chk(self.L.mi355_mosaic_blended_seam_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(band), C.byref(p),
+                                                       C.c_void_p(int(d_cells or 0) or None), int(gw), int(gh), C.c_void_p(int(d_canvas or 0) or None),
+                                                       int(cw), int(ch), int(cws)))
+        self.synchronize()
+
+    def MosaicBlendedSeam(self, imgs, h9s, keep=None, band=5, params=None, **kw):
+        """mi355_mosaic_blended_seam: host images in, all three stages and the blend; outputs as MosaicBlended"""
+        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        p = params if params is not None else seamcut_params(**kw)
+        out = C.c_void_p()
+        ow, oh, ows = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.mi355_mosaic_blended_seam(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(band), C.byref(p), C.byref(out),
+                                                   C.byref(ow), C.byref(oh), C.byref(ows)))
+        buf = _copy_out(out, ows.value * oh.value, np.uint8).reshape(oh.value, ows.value)
+        self.L.mi355_free(out)
+        return buf, ow.value, oh.value, ows.value
+
+    def MosaicBlendedSeamInto(self, imgs, img_ids, h9s, keep=None, band=5, out=None, pitch=None, geom=None, params=None, **kw):
+        """mi355_mosaic_blended_seam_into, sources and destination as MosaicBlendedInto.  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        p = params if params is not None else seamcut_params(**kw)
+        cw, ch, _ = blend_layout(w, h, h9s, keep_a)
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(self.L.mi355_mosaic_blended_seam_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), _p(keep_a), int(band), C.byref(p),
+                                                        C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
+        return out, cw, ch
+
     # ---- median render (mi355_mosaic_median*, csrc/median.hip) -------------------------------------------------------------
     def MosaicMedian(self, imgs, h9s, params=None, want_spread=False, **kw):
         """mi355_mosaic_median: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_spread (canvas, cw, ch, cws, spread [ch, cw]
@@ -1479,6 +1564,13 @@ def seamcut_params(ramp=None, level=None, depth=None, data_weight=None, diff_wei
 def seam_grid(w, h, h9s, level):
     """(gw, gh): the cell grid of the survey's canvas at `level`"""
     cw, ch, _, _ = mosaic_layout(w, h, h9s)
+    s = 1 << int(level)
+    return (cw + s - 1) // s, (ch + s - 1) // s
+
+
+def blend_seam_grid(w, h, h9s, level, keep=None):
+    """(gw, gh): the cell grid of the blend's canvas (blend_layout) at `level`"""
+    cw, ch, _ = blend_layout(w, h, h9s, keep)
     s = 1 << int(level)
     return (cw + s - 1) // s, (ch + s - 1) // s
 

@@ -655,7 +655,7 @@ int blend_core(mi355_ctx* ctx, chips::ChipSet* set, const uint8_t* const* chips,
     MI_HIP(gwgt.reserve(batches.max_px * sizeof(float) + 16));
     MI_HIP(dpar.reserve((size_t)(nc > 0 ? nc : 1) * sizeof(ChipP)));
     if (!set) { MI_HIP(ctx->buf("blend_chip").reserve(batches.max_cb + 16)); MI_HIP(ctx->buf("blend_mask").reserve(batches.max_mb + 16)); }
-    if (set) {
+    if (set && !set->pixels_made) {
         // the chips hold no pixels yet: each chip's are made inside the part of the chip its active windows read (chip_pixel_window); here
         // the windows of all chips go to the device, the launches follow batch by batch
         std::vector<int> wins((size_t)4 * (nc > 0 ? nc : 1));
@@ -678,7 +678,7 @@ int blend_core(mi355_ctx* ctx, chips::ChipSet* set, const uint8_t* const* chips,
     MI_HIP(hipMemsetAsync(dwgt.p, 0, p.loff[nb + 1] * sizeof(float), st));
     for (const bp::Batch& bt : batches.v) {
         if (!set) { const int rc = b.stage_batch(bt); if (rc != MI355_OK) return rc; }
-        if (set) { const int rc = mi_chip_pixels_launch(ctx, *set, bt.b0, bt.b1 - bt.b0); if (rc != MI355_OK) return rc; }      // the batch's chip pixels, one launch
+        if (set && !set->pixels_made) { const int rc = mi_chip_pixels_launch(ctx, *set, bt.b0, bt.b1 - bt.b0); if (rc != MI355_OK) return rc; }      // the batch's chip pixels, one launch (the seam forms made whole chips)
         if (nb == 0) b.accumulate_flat(bt);
         else {
             // the chips' parameters of this batch (the slot of the previous batch may still be read: one slot per batch, sized once)
@@ -735,4 +735,26 @@ int mi_mosaic_blended_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const in
     rc = blend_core(ctx, &set, nullptr, nullptr, nullptr, 0, p, BlendOut{p.copy_out ? full.as<uint8_t>() : d_canvas, cws, nullptr, nullptr, nullptr, nullptr});
     if (rc == MI355_OK && p.copy_out && hipMemcpyAsync(d_canvas, full.as<uint8_t>() + (size_t)row0 * cws, (size_t)rows * cws, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = MI355_ERR_DEVICE;
     return rc;
+}
+
+// The one-call blend along optimised seams (blend_seam.hip: definition, kernels, entry checks): the chip stage in its seam form -- whole chips,
+// the cell map unless one is given, the ownership that follows it -- and the blender as it is, on the owned boxes.  Whole canvas only.
+int mi_mosaic_blended_seam_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                               const uint8_t* keep, int band, const mi355_seamcut_params* params, const uint16_t* d_cells, int gw, int gh,
+                               uint8_t* d_canvas, int cw, int ch, int cws) {
+    if (!d_canvas || cws < 3 * cw || (cws & 3)) { ctx->set_error("mosaic_blended_seam_dev: canvas geometry does not match mi355_blend_layout"); return MI355_ERR_ARG; }
+    chips::Request req{chips::Request::SEAM_DEVICE};
+    req.seam.params = params; req.seam.gw = gw; req.seam.gh = gh;
+    req.seam.make_cells = d_cells == nullptr;
+    req.seam.d_cells = const_cast<uint16_t*>(d_cells);           // (read only unless make_cells)
+    if (!d_cells) {
+        DevBuf& dcells = ctx->buf("blend_seam_cells");
+        MI_HIP(dcells.reserve(sizeof(uint16_t) * (size_t)gw * gh));
+        req.seam.d_cells = dcells.as<uint16_t>();
+    }
+    chips::ChipSet set;
+    const int rc = mi_chips_and_masks_dev(ctx, d_imgs, w, h, ws, n, h9s, keep, req, set);
+    if (rc != MI355_OK) return rc;
+    if (set.W != cw || set.H != ch) { ctx->set_error("mosaic_blended_seam_dev: canvas geometry does not match mi355_blend_layout"); return MI355_ERR_ARG; }
+    return blend_core(ctx, &set, nullptr, nullptr, nullptr, 0, bp::make_plan(cw, ch, band), BlendOut{d_canvas, cws, nullptr, nullptr, nullptr, nullptr});
 }

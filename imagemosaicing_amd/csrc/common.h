@@ -199,6 +199,13 @@ int mi_mosaic_median_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w,
 int mi_mosaic_seamcut_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                           const mi355_seamcut_params* params, const uint16_t* d_cells, uint8_t* d_canvas, int cw, int ch, int cws, uint16_t* d_owner,
                           uint16_t* d_count, int row0, int rows, uint8_t* cover_only);      // seamcut.hip; d_cells NULL: candidates and labels first
+int mi_seam_labels_dev(mi355_ctx*, const mi355_seam_cell* d_cand, int gw, int gh, const mi355_seamcut_params* params, uint16_t* d_cells,
+                       mi355_seam_report* report);      // seamcut.hip: stage 2 on any records; complete on return
+int mi_seamcut_params_check(mi355_ctx*, const char* who, const mi355_seamcut_params* params);      // seamcut.hip: every field against its range
+// blend.hip: the one-call blend along optimised seams (blend_seam.hip has the entry checks).  d_cells NULL: stages 1 and 2 first
+int mi_mosaic_blended_seam_dev(mi355_ctx*, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                               const uint8_t* keep, int band, const mi355_seamcut_params* params, const uint16_t* d_cells, int gw, int gh,
+                               uint8_t* d_canvas, int cw, int ch, int cws);
 int mi_mosaic_overview_dev(mi355_ctx*, const uint8_t* d_rows, int cw, int ch, int cws, const uint16_t* d_valid_rows, int nodata, int levels,
                            uint8_t* const* d_levels, uint16_t* const* d_covers, int row0, int rows, int only_level = 0);      // overview.hip; only_level = l: d_levels / d_covers entries other than l - 1 may be NULL (the preview)
 int mi_sift_flush(mi355_ctx*);                               // enqueues every partly filled batch (no wait)

@@ -345,6 +345,44 @@ extern "C" int mi355_mosaic_blended_into(mi355_ctx* ctx, const uint8_t* const* i
                        [&](const uint8_t* const* d, uint8_t* dc) { return mi_mosaic_blended_dev(ctx, d, w, h, ws, n, h9s, keep, band, dc, lw, lh, lws); });
 }
 
+// The blend along optimised seams (blend_seam.hip) with mi355_mosaic_blended_into's sources and download: all three stages in the call.
+int mi_blend_seam_host_entry(mi355_ctx*, const char* who, const int* w, const int* h, int n, const float* h9s, const uint8_t* keep,
+                             const mi355_seamcut_params* params, int* cw, int* ch, int* gw, int* gh);      // blend_seam.hip
+extern "C" int mi355_mosaic_blended_seam_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h,
+                                              const int* ws, int n, const float* h9s, const uint8_t* keep, int band, const mi355_seamcut_params* params,
+                                              uint8_t* dst, int dst_pitch, int cw, int ch) {
+    LOCKED_PROLOGUE
+    if (!w || !h || !ws || !h9s || n <= 0 || (!imgs && !img_ids)) { ctx->set_error("mosaic_blended_seam_into: bad arguments"); return MI355_ERR_ARG; }
+    mi355_seamcut_params dp;
+    if (!params) { mi355_default_seamcut_params(&dp); params = &dp; }
+    int lw = 0, lh = 0, gw = 0, gh = 0;
+    const int rc = mi_blend_seam_host_entry(ctx, "mosaic_blended_seam_into", w, h, n, h9s, keep, params, &lw, &lh, &gw, &gh);
+    if (rc != MI355_OK) return rc;
+    const int lws = (lw * 3 + 3) & ~3;
+    return render_into(ctx, "mosaic_blended_seam_into", imgs, img_ids, w, h, ws, n, h9s, keep, dst, dst_pitch, cw, ch, lw, lh, lws, [&](const uint8_t* const* d, uint8_t* dc) {
+        return mi_mosaic_blended_seam_dev(ctx, d, w, h, ws, n, h9s, keep, band, params, nullptr, gw, gh, dc, lw, lh, lws);
+    });
+}
+
+// ... into a malloc'd canvas of the layout's own pitch
+extern "C" int mi355_mosaic_blended_seam(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                         const uint8_t* keep, int band, const mi355_seamcut_params* params, uint8_t** out, int* out_w, int* out_h, int* out_ws) {
+    if (!ctx) return MI355_ERR_ARG;
+    if (!out || !w || !h || !h9s || n <= 0) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->set_error("mosaic_blended_seam: bad arguments"); return MI355_ERR_ARG; }
+    int lw = 0, lh = 0;
+    if (mi_blend_layout(w, h, n, h9s, keep, &lw, &lh) != MI355_OK || lw <= 0 || lh <= 0) { std::lock_guard<std::mutex> lk(ctx->mu); ctx->set_error("mosaic_blended_seam: empty canvas"); return MI355_ERR_FAILED; }
+    const int lws = (lw * 3 + 3) & ~3;
+    uint8_t* host = (uint8_t*)calloc((size_t)lws, (size_t)lh);       // the row padding stays zero
+    if (!host) return MI355_ERR_NOMEM;
+    const int rc = mi355_mosaic_blended_seam_into(ctx, imgs, nullptr, w, h, ws, n, h9s, keep, band, params, host, lws, lw, lh);      // (takes the lock)
+    if (rc != MI355_OK) { free(host); return rc; }
+    *out = host;
+    if (out_w) *out_w = lw;
+    if (out_h) *out_h = lh;
+    if (out_ws) *out_ws = lws;
+    return MI355_OK;
+}
+
 // ---- striped preview ------------------------------------------------------------------------------------------------------
 // Level `level` of a render's canvas without that canvas: the survey is rendered stripe by stripe into ONE stripe buffer, each stripe is
 // reduced by the overview kernel (overview.hip) into the level's buffer, and only that level comes back.  The render launchers address the

@@ -353,6 +353,14 @@ bool sc_grid_ok(int gw, int gh, std::string& err) {
     if (!params) { mi355_default_seamcut_params(&dp_); params = &dp_; }                       \
     { std::string e_; if (!sc_params_ok(params, e_)) { ctx->set_error(std::string(who) + ": " + e_); return MI355_ERR_ARG; } }
 
+// the range check for the callers outside this file (blend_seam.hip)
+int mi_seamcut_params_check(mi355_ctx* ctx, const char* who, const mi355_seamcut_params* params) {
+    std::string e;
+    if (sc_params_ok(params, e)) return MI355_OK;
+    ctx->set_error(std::string(who) + ": " + e);
+    return MI355_ERR_ARG;
+}
+
 extern "C" void mi355_default_seamcut_params(mi355_seamcut_params* p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));

@@ -20,6 +20,7 @@
 #include "hmath.h"
 #include "mosaic_frame.h"
 #include "chips.h"
+#include "chip_own.h"
 
 namespace {
 
@@ -482,27 +483,13 @@ int mi_warp_image(mi355_ctx* ctx, const uint8_t* src, int w, int h, int ws, int 
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-struct ChipDev { int x0, y0, w, h, mws; size_t map_off; };
-
 // ImageMath.cpp:88-103 LineOf2Points1
 void line_of_2_points(float& a, float& b, float& c, float x1, float y1, float x2, float y2) {
     if (fabs((double)(x1 - x2)) < 0.000001) { a = 1.0f; b = 0.0f; c = -x1; }
     else { a = (y1 - y2) / (x1 - x2); b = -1.0f; c = y1 - a * x1; }
 }
 
-struct LineSet { float A[4], B[4], C[4], inv[4]; };
-
-// distance of chip pixel (c, r) to the nearest of the 4 quad edges (MosaicImage.cpp:1790-1826); ONE expression for both kernels below:
-// the ownership kernel recomputes what the maximum kernel saw, so the values must be the same bits
-__device__ __forceinline__ float quad_min_dist(const LineSet& L, int c, int r) {
-    float minDist = (float)(1 << 29);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float d = fabsf(L.A[i] * (float)c + L.B[i] * (float)r + L.C[i]) * L.inv[i];
-        if (d < minDist) minDist = d;
-    }
-    return minDist;
-}
+// (ChipDev, LineSet, quad_min_dist, OwnEntry and the block constants: chip_own.h, shared with blend_seam.hip)
 
 // per chip: the chip-wide maximum of that distance over the valid pixels (float bits, all >= 0).  The distances themselves are NOT
 // stored (round 2 kept a float map per chip pixel: 4 of the 8 bytes per chip pixel, 101 GB for the 2000 chips of C5)
@@ -540,12 +527,6 @@ __global__ __launch_bounds__(256) void distmax_kernel(const ChipDev* chips, uint
 // validity is read from the masks (255 = sample exists), the distance is recomputed and divided by the chip's maximum (:1828), then
 // every covering chip's mask byte is rewritten: 255 for the owner, 0 for the others.  A mask byte belongs to exactly one canvas
 // pixel, so the thread of that pixel is the only one that touches it.
-constexpr int OWN_BLK = 256;
-constexpr int OWN_ROWS = 4;
-// The chips of the block (uniform over the workgroup: 64 x 4 threads inside one block) are staged in LDS, 32 at a time: with the
-// descriptors read per thread and per chip from global memory every candidate was a chain of four dependent loads (list -> chip ->
-// mask pointer -> mask byte) and the kernel ran at 0.2 TB/s of its own byte traffic.
-struct OwnEntry { int x0, y0, w, h, mws, k; float maxv; int pad; uint8_t* mask; LineSet L; };
 __global__ __launch_bounds__(256) void owner_kernel(const ChipDev* chips, const LineSet* lines, const unsigned* maxbits, const int* list_off, const int* list,
                                                     int bx_n, int rectW, int rectH, uint8_t* const* masks, int row_beg) {
     constexpr int NE = 32;
@@ -804,13 +785,40 @@ struct ChipStage {
         return MI355_OK;
     }
 
+    // the seam forms: the pixels of WHOLE chips, from the arguments the validity pass left on the device -- stage 1 of the blend along
+    // optimised seams reads every candidate's bytes around the seams, before anybody knows what a chip will own
+    int whole_pixels_launch() {
+        const int na = (int)av.size();
+        if (na <= 0) return MI355_OK;
+        ProfScope ps(ctx, "warp", (double)chip_total);
+        for (int v0 = 0; v0 < na; v0 += 65535)
+            hipLaunchKernelGGL((warp_chips_kernel<2>), dim3(((mw + 3) / 4 + 63) / 64, (mh + 3) / 4, na - v0 < 65535 ? na - v0 : 65535), dim3(64, 4), 0, ctx->stream,
+                               ctx->buf("chip_warp_args").as<WarpArgs>() + v0);
+        set.pixels_made = true;
+        return MI355_OK;
+    }
+
+    // the seam forms without a chip: an empty cell map, nothing else
+    int no_chips_cells() {
+        const chips::SeamRequest& sq = req.seam;
+        if (!sq.make_cells) return MI355_OK;
+        const size_t cells = (size_t)sq.gw * sq.gh;
+        MI_HIP(hipMemsetAsync(sq.d_cells, 0, sizeof(uint16_t) * cells, ctx->stream));
+        if (sq.d_cand) MI_HIP(hipMemsetAsync(sq.d_cand, 0, sizeof(mi355_seam_cell) * cells, ctx->stream));
+        if (sq.report) memset(sq.report, 0, sizeof(*sq.report));
+        MI_HIP(hipStreamSynchronize(ctx->stream));
+        return MI355_OK;
+    }
+
     // FindMasksByDistMap for the chips that reach the stripe: per chip its maximum distance, per canvas pixel its owner, and (the one-call
-    // form) per chip the box of what it owns
+    // form) per chip the box of what it owns.  The seam forms: between the maxima and the owners stage 1 and the labels make the cell map
+    // (unless it came with the request), and the owners follow it (blend_seam.hip).
     int ownership() {
         const int na = (int)av.size(), newW = set.W, newH = set.H;
         const bool boxes = req.one_call();
         const mi355_chip_info* ci = set.info.data();
         uint8_t* dmasks = ctx->buf("chip_masks").as<uint8_t>();
+        const uint8_t* dchips = ctx->buf("chip_imgs").as<uint8_t>();
         DevBuf& dmeta = ctx->buf("chip_meta");
         // chip lists per 256 x 256 canvas block (host: the chips' rectangles are known), ascending chip index inside a block; entries are
         // positions in `av`.  One walk over a chip's blocks serves the count and the fill.
@@ -842,7 +850,7 @@ struct ChipStage {
         auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
         const size_t o_cd = 0, o_mp = up16(o_cd + sizeof(ChipDev) * na), o_mx = up16(o_mp + sizeof(uint8_t*) * na), o_ln = up16(o_mx + sizeof(unsigned) * na),
                      o_lo = up16(o_ln + sizeof(LineSet) * na), o_ls = up16(o_lo + sizeof(int) * loff.size()), o_bb = up16(o_ls + sizeof(int) * lst.size()),
-                     meta_bytes = o_bb + sizeof(int) * 4 * na;
+                     o_cp = up16(o_bb + sizeof(int) * 4 * na), o_im = up16(o_cp + sizeof(uint8_t*) * na), meta_bytes = o_im + sizeof(int) * na;
         MI_HIP(dmeta.reserve(meta_bytes + 64));
         uint8_t* mb = dmeta.as<uint8_t>();
         ChipDev* d_cd = reinterpret_cast<ChipDev*>(mb + o_cd);
@@ -852,7 +860,8 @@ struct ChipStage {
         int* d_loff = reinterpret_cast<int*>(mb + o_lo);
         int* d_list = reinterpret_cast<int*>(mb + o_ls);
         // one host image of the whole meta area, one copy (six small copies from pageable memory cost ~0.35 ms each on the stream): chip
-        // descriptors, mask pointers, the maxima (zero), the edge lines, the block lists, the owned boxes' start values
+        // descriptors, mask pointers, the maxima (zero), the edge lines, the block lists, the owned boxes' start values, and for the seam forms
+        // the chips' pixel pointers and image indices
         std::vector<uint8_t> blob(meta_bytes, 0);
         memcpy(blob.data() + o_cd, cda.data(), sizeof(ChipDev) * na);
         for (int q = 0; q < na; q++) { uint8_t* mp = dmasks + set.mask_off[av[q]]; memcpy(blob.data() + o_mp + sizeof(uint8_t*) * q, &mp, sizeof(mp)); }
@@ -861,6 +870,11 @@ struct ChipStage {
         memcpy(blob.data() + o_ls, lst.data(), sizeof(int) * lst.size());
         memset(blob.data() + o_bb, 0x7f, sizeof(int) * 2 * na);
         memset(blob.data() + o_bb + sizeof(int) * 2 * na, 0xff, sizeof(int) * 2 * na);
+        for (int q = 0; q < na; q++) {
+            const uint8_t* cp = dchips + set.chip_off[av[q]];
+            memcpy(blob.data() + o_cp + sizeof(uint8_t*) * q, &cp, sizeof(cp));
+            memcpy(blob.data() + o_im + sizeof(int) * q, &ci[av[q]].img, sizeof(int));
+        }
         MI_HIP(hipMemcpyAsync(mb, blob.data(), meta_bytes, hipMemcpyHostToDevice, ctx->stream));
         int* d_bbmin = boxes ? reinterpret_cast<int*>(mb + o_bb) : nullptr;      // [2 na] minima, then [2 na] maxima
         int* d_bbmax = boxes ? d_bbmin + 2 * na : nullptr;
@@ -872,7 +886,25 @@ struct ChipStage {
                                    d_cd + v0, d_mptr + v0, d_lines + v0, d_max + v0);
         }
         dim3 grid((newW + 63) / 64, (row_end - row_beg + 4 * OWN_ROWS - 1) / (4 * OWN_ROWS));
-        {
+        if (req.seams()) {
+            const chips::SeamRequest& sq = req.seam;
+            const chips::OwnTables tab{d_cd, d_mptr, reinterpret_cast<const uint8_t* const*>(mb + o_cp), reinterpret_cast<const int*>(mb + o_im), d_max, d_lines,
+                                       d_loff, d_list, bx_n, newW, newH};
+            if (sq.make_cells) {
+                mi355_seam_cell* d_cand = sq.d_cand;
+                if (!d_cand) {
+                    DevBuf& dc = ctx->buf("blend_seam_candidates");
+                    MI_HIP(dc.reserve(sizeof(mi355_seam_cell) * (size_t)sq.gw * sq.gh));
+                    d_cand = dc.as<mi355_seam_cell>();
+                }
+                int rc = mi_blend_seam_candidates_launch(ctx, tab, sq.params, d_cand, sq.gw, sq.gh);
+                if (rc == MI355_OK) rc = mi_seam_labels_dev(ctx, d_cand, sq.gw, sq.gh, sq.params, sq.d_cells, sq.report);      // (waits for the stream)
+                if (rc != MI355_OK) return rc;
+            }
+            if (sq.stop_after_cells) { MI_HIP(hipStreamSynchronize(ctx->stream)); return MI355_OK; }
+            const int rc = mi_owner_cells_launch(ctx, tab, sq.d_cells, sq.gw, sq.params->level);
+            if (rc != MI355_OK) return rc;
+        } else {
             ProfScope ps(ctx, "owner", (double)newW * (row_end - row_beg));
             hipLaunchKernelGGL(owner_kernel, grid, block, 0, ctx->stream, d_cd, d_lines, d_max, d_loff, d_list, bx_n, newW, row_end, d_mptr, row_beg);
         }
@@ -907,6 +939,7 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
     canvas_layout(w, h, n, h9s, keep, s.lay);
     const int newH = s.lay.H;
     s.striped = req.row_lo > 0 || req.row_hi < newH - 1;
+    if (req.seams() && (!req.seam.params || !req.seam.d_cells || !req.find_masks || req.cover_only)) { ctx->set_error("chips: incomplete seam request"); return MI355_ERR_ARG; }
     if (s.striped && req.form != chips::Request::BLEND_DEVICE) { ctx->set_error("chips: a row window needs the one-call blend's form"); return MI355_ERR_ARG; }
     s.row_beg = (req.row_lo < 0 ? 0 : req.row_lo) & ~(4 * OWN_ROWS - 1);
     s.row_end = req.row_hi >= newH - 1 ? newH : ((req.row_hi + 4 * OWN_ROWS) & ~(4 * OWN_ROWS - 1));
@@ -921,7 +954,8 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
     MI_HIP(ctx->buf("chip_masks").reserve(s.mask_total + 16));
     // deferred pixels (the one-call blend): every mask byte of a chip's columns is written by the validity pass, the pixels later and only
     // inside the chip's active window (mi_chip_pixels_prepare / _launch); row padding is never read there, so nothing is cleared
-    if (!req.one_call()) {
+    // (the public two-stage seam form hands whole chips and masks to the host, row padding included: cleared as the public form's)
+    if (!req.one_call() || req.form == chips::Request::SEAM_HOST) {
         MI_HIP(hipMemsetAsync(ctx->buf("chip_imgs").p, 0, s.chip_total, ctx->stream));
         MI_HIP(hipMemsetAsync(ctx->buf("chip_masks").p, 0, s.mask_total, ctx->stream));
     }
@@ -930,7 +964,9 @@ int mi_chips_and_masks_dev(mi355_ctx* ctx, const uint8_t* const* imgs, const int
         rc = s.validity_launch();
         set.owned.assign((size_t)4 * set.n(), 0);            // per chip an empty box, until ownership() finds what it owns
         for (int v = 0; v < set.n(); v++) { set.owned[4 * v + 2] = -1; set.owned[4 * v + 3] = -1; }
+        if (rc == MI355_OK && req.seams()) rc = s.whole_pixels_launch();
     }
+    if (rc == MI355_OK && req.seams() && s.av.empty()) rc = s.no_chips_cells();
     // validity masks are final here unless the distance-map ownership is requested
     if (rc == MI355_OK && req.find_masks && !s.av.empty()) rc = s.ownership();
     if (rc != MI355_OK) return rc;
@@ -985,9 +1021,15 @@ int mi_blend_layout(const int* w, const int* h, int n, const float* h9s, const u
 int mi_chips_and_masks(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n,
                        const float* h9s, const uint8_t* keep, int find_masks, int* n_chips, mi355_chip_info** chips_out,
                        uint8_t*** chip_imgs, uint8_t*** masks_out, int* cw_out, int* ch_out) {
+    return mi_chips_and_masks_host(ctx, imgs, w, h, ws, n, h9s, keep, chips::Request{chips::Request::PUBLIC, find_masks}, n_chips, chips_out, chip_imgs, masks_out, cw_out, ch_out);
+}
+
+// ... of any form of the stage whose chips hold their pixels on return (PUBLIC, SEAM_HOST)
+int mi_chips_and_masks_host(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s, const uint8_t* keep,
+                            const chips::Request& req, int* n_chips, mi355_chip_info** chips_out, uint8_t*** chip_imgs, uint8_t*** masks_out, int* cw_out, int* ch_out) {
     if (!chip_imgs || !masks_out || !n_chips || !chips_out) return MI355_ERR_ARG;
     chips::ChipSet set;
-    int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, chips::Request{chips::Request::PUBLIC, find_masks}, set);
+    int rc = mi_chips_and_masks_dev(ctx, imgs, w, h, ws, n, h9s, keep, req, set);
     if (rc != MI355_OK) return rc;                     // nothing was handed out
     if (cw_out) *cw_out = set.W;
     if (ch_out) *ch_out = set.H;

@@ -429,6 +429,58 @@ int  mi355_mosaic_blended_rows_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs,
 /* canvas size of LaplacianPyramidBlending for these transforms (MosaicImage.cpp:2233-2292; host geometry, no ctx) */
 int  mi355_blend_layout(const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, int* cw, int* ch, int* cws);
 
+/* ---- multiband blend along optimised seams (csrc/blend_seam.hip) -----------------------------------------------------------------------
+ * The multiband blend cuts every overlap where FindMasksByDistMap puts the seam: along the geometric middle, whatever lies there.  Here the
+ * seam finder of the optimised seamlines runs in front of the blender: a cell map moves the seam, cell by cell, to where the chips agree, the
+ * ownership masks follow the map, and the blender takes those masks as it takes any.  The cell map of mi355_seam_cells_dev cannot be reused: it
+ * lives on mi355_mosaic_layout's canvas under the seamline's sample rule and feather weights, while the blend's canvas always contains the
+ * origin, its chips carry sub-pixel shifts and its seam is the normalised-distance arg-max.  Integers everywhere except where the ownership's
+ * own float expression is reused; restated in numpy by tests/blend_seam_ref.py.  The reference has no such mode.
+ * Grid: the canvas is mi355_blend_layout's (cw x ch) for the same w, h, n, h9s, keep; s = 1 << level, gw = ceil(cw / s), gh = ceil(ch / s); the
+ *   probe of cell (cx, cy) is pixel (min(cx s + s / 2, cw - 1), min(cy s + s / 2, ch - 1)), as above.  Parameters: mi355_seamcut_params with the
+ *   same ranges and defaults; ramp has no meaning here and must be 0 (MI355_ERR_ARG otherwise).  n <= 65535.
+ * 1. Candidates.  For a chip v that covers canvas pixel p with validity byte 255, d_v(p) is the value FindMasksByDistMap compares there: the
+ *   distance to the nearest of the chip's four edge lines divided by the chip's maximum of it (over the whole chip), the same float bits.  Chip v
+ *   is a candidate of a cell iff it has a valid sample at the probe and d_v > 0 there (false for NaN and for 0).  Candidates are ordered by
+ *   (d_v descending as float, chip position ascending): slot 0 is exactly the probe's FindMasksByDistMap owner (strictly largest, first wins).
+ *   The cell keeps the first m = min(|C|, depth); slots m .. 7 are all-zero.  A slot holds frame = the chip's image index + 1
+ *   (mi355_chip_info.img + 1); omega = 1 + (int) min(d_v * 254.0f, 254.0f), one float32 multiply, then truncation -- monotone in d, so
+ *   omega_0 >= omega_a and the label stage's data term stays >= 0; gray = (sum + num / 2) / num over the num >= 1 pixels of the cell, clipped
+ *   to the canvas, where that chip's validity byte is 255, of (1868 B + 9617 G + 4899 R + 8192) >> 14 of the chip's own bytes.  The records
+ *   are mi355_seam_cell, gh x gw.
+ * 2. Labels: mi355_seam_labels_dev, unchanged.  The cell map holds frame + 1 where the label left slot 0, and 0 elsewhere.
+ * 3. Ownership under a map.  For canvas pixel (x, y), f = cells[y >> level][x >> level] - 1.  If f >= 0 and some kept chip has img == f and
+ *   validity byte 255 at the pixel, that chip owns the pixel (validity is enough, d > 0 is not required); otherwise the owner is the
+ *   FindMasksByDistMap owner.  A map value that names a dropped frame, a skipped frame, a frame that does not cover the pixel, or an id above n
+ *   is not an error: the pixel keeps that rule.  Masks come out as mi355_chips_and_masks': 255 for the owner, 0 for every other covering chip.
+ * Consequences: an all-zero map, depth = 1, and diff_weight = seam_penalty = 0 each give the bytes of mi355_chips_and_masks(find_masks = 1) and
+ *   of mi355_mosaic_blended; energy_after <= energy_before or `fallback` is set.
+ * Cost: the chip stage makes the pixels of whole chips (stage 1 reads every candidate's bytes around the seams), where mi355_mosaic_blended
+ *   makes them inside the owned windows only; stage 1 reads chip bytes and takes no bilinear sample; stage 3 is the ownership plus one map
+ *   load per thread.  Whole canvas only: there is no stripe form.  Three-channel frames.
+ * Errors: every parameter field is range-checked; gw, gh must be the grid of mi355_blend_layout's canvas at params.level; a NULL frame that is
+ *   kept and not skipped is MI355_ERR_ARG naming it; the ctx goes on working after every refusal.
+ * mi355_blend_seam_cells_dev: stages 1 and 2 from DEVICE frames; the records go to d_cand too when it is given; complete on return.
+ * mi355_chips_and_masks_seam: the public two-stage form, host frames; cells = NULL: stages 1 and 2 first.  Outputs as mi355_chips_and_masks,
+ *   the masks after stage 3; they feed mi355_multiband_blend.
+ * mi355_mosaic_blended_seam_dev: device frames in, device canvas out, as mi355_mosaic_blended_dev; d_cells = NULL: the map is made first.
+ * mi355_mosaic_blended_seam / _into: all three stages with the sources and the download of mi355_mosaic_blended_into (declared here, described
+ *   with the kept frames below); *out is library-allocated (mi355_free), rows padded to 4 bytes. */
+int  mi355_blend_seam_cells_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                const uint8_t* keep, const mi355_seamcut_params* params, uint16_t* d_cells /* DEVICE, gh x gw */, int gw, int gh,
+                                mi355_seam_report* report /* HOST, may be NULL */, mi355_seam_cell* d_cand /* DEVICE, may be NULL */);
+int  mi355_chips_and_masks_seam(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                const uint8_t* keep, const mi355_seamcut_params* params, const uint16_t* cells /* HOST gh x gw, NULL = stages 1 and 2 first */,
+                                int gw, int gh, int* n_chips, mi355_chip_info** chips, uint8_t*** chip_imgs, uint8_t*** masks, int* canvas_w, int* canvas_h);
+int  mi355_mosaic_blended_seam_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                                   const uint8_t* keep, int band, const mi355_seamcut_params* params, const uint16_t* d_cells /* DEVICE, NULL = make it */,
+                                   int gw, int gh, uint8_t* d_canvas, int cw, int ch, int cws);
+int  mi355_mosaic_blended_seam(mi355_ctx* ctx, const uint8_t* const* imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                               const uint8_t* keep, int band, const mi355_seamcut_params* params, uint8_t** out, int* out_w, int* out_h, int* out_ws);
+int  mi355_mosaic_blended_seam_into(mi355_ctx* ctx, const uint8_t* const* imgs, const int32_t* img_ids, const int* w, const int* h, const int* ws,
+                                    int n, const float* h9s, const uint8_t* keep, int band, const mi355_seamcut_params* params, uint8_t* dst,
+                                    int dst_pitch, int cw, int ch);
+
 /* ---- frames kept in HBM after extraction, renders into caller memory ----------------------------------------------------
  * The reference's driver extracts features from pImgPoses[i].pImg and later renders the same images with the same indices
  * (MosaicWithoutPos.cpp:4430-4679) without changing a pixel in between.  With mi355_set_option(ctx, "keep_frames", 1) every host-frame

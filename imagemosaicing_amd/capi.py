@@ -50,6 +50,10 @@ class BlockGainParams(C.Structure):
                 ("grid_y", C.c_int32), ("smooth", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SharpParams(C.Structure):
+    _fields_ = [("prior", C.c_float), ("blur_ratio", C.c_float), ("step", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FeatherParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -107,6 +111,11 @@ assert GAIN_PAIR_STATS.itemsize == 64
 # mi355_block_gain_stats: the statistics of one (cell_a, cell_b) of listed pair `pair` (an index into the pair list)
 BLOCK_GAIN_STATS = np.dtype([("pair", "<i4"), ("cell_a", "<i4"), ("cell_b", "<i4"), ("reserved", "<i4"), ("n", "<i8"), ("sum_a", "<i8", (3,)),
                              ("sum_b", "<i8", (3,))])
+# mi355_sharp_pair_stats / mi355_sharp_frame_stats: Laplacian energy and centre gray of one listed pair / one frame ("frame sharpness")
+SHARP_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("e_a", "<i8"), ("e_b", "<i8"), ("s_a", "<i8"), ("s_b", "<i8")])
+SHARP_FRAME_STATS = np.dtype([("n", "<i8"), ("e", "<i8"), ("s", "<i8")])
+SHARP_KEPT, SHARP_DROPPED, SHARP_CUT_VERTEX, SHARP_NO_PAIR = 0, 1, 2, 3
+assert SHARP_PAIR_STATS.itemsize == 48 and SHARP_FRAME_STATS.itemsize == 24 and C.sizeof(SharpParams) == 16
 PAIR_NORMAL_BLOCK = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("_pad", "<i4"), ("cost", "<f8"), ("g", "<f8", (16,)), ("N", "<f8", (136,))])
 
 
@@ -806,6 +815,31 @@ class Context:
         g = np.zeros((n, 3), np.float32)
         self._chk(self.L.mi355_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
         return g
+
+    # ---- frame sharpness (mi355_sharp_*, csrc/sharp.hip) ---------------------------------------------------------------------
+    def SharpStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, frames=True):
+        """Laplacian statistics of the listed pairs (positions in the frame list) on the lattice of `step`: (SHARP_PAIR_STATS [n_pairs],
+        SHARP_FRAME_STATS [n], or None with frames=False: then no per-frame tiles are launched)"""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        st = np.zeros(npairs, SHARP_PAIR_STATS)
+        fs = np.zeros(n, SHARP_FRAME_STATS) if frames else None
+        self._chk(self.L.mi355_sharp_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), _p(st),
+                                               _p(fs) if frames else None))
+        return st, fs
+
+    def SharpnessDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
+        """statistics, solve, flag and select on the device frames (which are only read): (sharp [n] float32, status [n] uint8, h9s_kept
+        [n, 9] float32 -- h9s with m8 = 0 for the dropped frames, status 1).  params: SharpParams (sharp_params()) or keyword fields of it."""
+        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        ab, npairs = self._pairs_ab(pairs)
+        h9s = np.ascontiguousarray(h9s, np.float32)
+        p = params if params is not None else sharp_params(**kw)
+        sharp = np.zeros(n, np.float32)
+        status = np.zeros(n, np.uint8)
+        self._chk(self.L.mi355_sharpness_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(sharp), _p(status)))
+        return sharp, status, drop_sharp_frames(h9s, status)
 
     # ---- block gain compensation (mi355_block_gain_*, csrc/gain.hip) -------------------------------------------------------
     def BlockGainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, grid_x=8, grid_y=6):
@@ -1520,6 +1554,19 @@ def block_gain_params(sigma_n=None, sigma_g=None, channels=None, step=None, grid
     return p
 
 
+def sharp_params(prior=None, blur_ratio=None, step=None):
+    """mi355_sharp_params: the library's defaults (mi355_default_sharp_params: 0.01, 0.58, 8) with the given fields replaced"""
+    p = SharpParams()
+    load_library().mi355_default_sharp_params(C.byref(p))
+    if prior is not None:
+        p.prior = float(prior)
+    if blur_ratio is not None:
+        p.blur_ratio = float(blur_ratio)
+    if step is not None:
+        p.step = int(step)
+    return p
+
+
 def feather_params(ramp=None):
     """mi355_feather_params: the library's defaults (mi355_default_feather_params: ramp 0 = a full tent per frame) with the given fields replaced"""
     p = FeatherParams()
@@ -1837,6 +1884,40 @@ def solve_gains(pair_stats, frame_cover, params=None, **kw):
     if rc < 0:
         raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
     return g
+
+
+def solve_sharpness(pair_stats, n, params=None, **kw):
+    """mi355_solve_sharpness (host only): (sharp [n] float32, rel [n] float64) from SHARP_PAIR_STATS records"""
+    L = load_library()
+    st = np.ascontiguousarray(pair_stats, SHARP_PAIR_STATS)
+    n = int(n)
+    p = params if params is not None else sharp_params(**kw)
+    sharp, rel = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float64)
+    rc = L.mi355_solve_sharpness(_p(st), len(st), n, C.byref(p), _p(sharp), _p(rel))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return sharp[:max(n, 0)], rel[:max(n, 0)]
+
+
+def select_sharp_frames(pair_stats, n, params=None, **kw):
+    """mi355_select_sharp_frames (host only): (status [n] uint8 -- 0 kept, 1 blurred and dropped, 2 blurred but kept (a cut vertex), 3 no
+    usable pair --, sharp [n] float32) from SHARP_PAIR_STATS records"""
+    L = load_library()
+    st = np.ascontiguousarray(pair_stats, SHARP_PAIR_STATS)
+    n = int(n)
+    p = params if params is not None else sharp_params(**kw)
+    status, sharp = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
+    rc = L.mi355_select_sharp_frames(_p(st), len(st), n, C.byref(p), _p(status), _p(sharp))
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return status[:max(n, 0)], sharp[:max(n, 0)]
+
+
+def drop_sharp_frames(h9s, status):
+    """h9s [n, 9] float32 with m8 = 0 (the renders' skip convention) for the frames a sharpness selection dropped (status 1)"""
+    out = np.array(h9s, np.float32).reshape(-1, 9).copy()
+    out[np.asarray(status) == SHARP_DROPPED, 8] = 0
+    return out
 
 
 def solve_block_gains(records, pairs, cell_cover, params=None, **kw):

@@ -4,11 +4,28 @@
 #include "../../include/mi355_mosaic.h"
 #include <functional>
 #include <string>
+#include <utility>
+#include <vector>
 
 namespace mi_gain {
 
 constexpr int MAX_FRAMES = 65535;
 constexpr int MAX_GRID = 16;                  // block gains: cells per axis
+
+// A symmetric positive definite system on a graph, A = diag(diag) + off[q] at (u_q, v_q) and (v_q, u_q) for the edges in list order, solved as
+// the gain solves need it: reverse Cuthill-McKee order, envelope Cholesky, one step of iterative refinement; single-threaded double in a
+// fixed order, so the same bits on every call.  build once per graph, solve per right-hand side and set of values.
+struct EnvelopeGraph {
+    int m = 0;
+    double work = 0.0;                          // multiply-adds of one factorisation
+    std::vector<std::pair<int, int>> edges;
+    std::vector<int> order, pos, fst;
+    std::vector<size_t> rp;
+    std::vector<double> E, r, d, xp;
+    void build(int m, const std::vector<std::pair<int, int>>& edges);
+    // x (m values, unknown order) or, where a pivot is not positive, the unknown it belongs to; -1: solved
+    int solve(const std::vector<double>& diag, const std::vector<double>& off, const std::vector<double>& rhs, std::vector<double>& x);
+};
 
 bool check_frames_n(int n, std::string& err);
 bool check_pairs(const std::function<void(int, int&, int&)>& pair_at, int n_pairs, int n, std::string& err);   // pair_at(p, a, b) gives pair p

@@ -3,7 +3,8 @@
 // and their launchers and takes what it needs from here through gain.h.
 //
 //   mi355_solve_gains        single-threaded double: the normal equations over the frames that have one, reverse Cuthill-McKee order, an
-//                            envelope Cholesky factor and one step of iterative refinement.  Fixed order throughout: the same bits every call.
+//                            envelope Cholesky factor and one step of iterative refinement (EnvelopeGraph, which sharp_solve.cpp uses as
+//                            well).  Fixed order throughout: the same bits every call.
 //   mi355_solve_block_gains  the same solve (solve_nodes) over the nodes (frame, cell), iterating where the envelope would be too costly
 //                            (solve_pcg), then the smoothing of each frame's map.
 #include "gain.h"
@@ -14,6 +15,91 @@
 #include <unordered_map>
 #include <vector>
 
+
+namespace mi_gain {
+
+// reverse Cuthill-McKee: per component, start at the unvisited node of least degree (lowest index on ties), neighbours by (degree, index);
+// then the envelope: row i (permuted) holds columns fst[i] .. i
+void EnvelopeGraph::build(int m_, const std::vector<std::pair<int, int>>& edges_) {
+    m = m_; edges = edges_;
+    std::vector<std::vector<int>> adj((size_t)m);
+    for (const auto& e : edges) { adj[e.first].push_back(e.second); adj[e.second].push_back(e.first); }
+    for (auto& l : adj) std::sort(l.begin(), l.end());
+    order.clear(); order.reserve(m);
+    std::vector<char> seen((size_t)m, 0);
+    std::vector<int> by_deg(m);
+    for (int i = 0; i < m; i++) by_deg[i] = i;
+    std::stable_sort(by_deg.begin(), by_deg.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
+    for (int s : by_deg) {
+        if (seen[s]) continue;
+        size_t head = order.size();
+        order.push_back(s); seen[s] = 1;
+        std::vector<int> nb;
+        while (head < order.size()) {
+            const int u = order[head++];
+            nb.clear();
+            for (int v : adj[u]) if (!seen[v]) { nb.push_back(v); seen[v] = 1; }
+            std::stable_sort(nb.begin(), nb.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
+            order.insert(order.end(), nb.begin(), nb.end());
+        }
+    }
+    std::reverse(order.begin(), order.end());
+    pos.assign((size_t)m, 0);
+    for (int i = 0; i < m; i++) pos[order[i]] = i;
+    fst.assign((size_t)m, 0);
+    for (int i = 0; i < m; i++) { int f = i; for (int v : adj[order[i]]) f = std::min(f, pos[v]); fst[i] = f; }
+    rp.assign((size_t)m + 1, 0);
+    for (int i = 0; i < m; i++) rp[i + 1] = rp[i] + (size_t)(i - fst[i] + 1);
+    work = 0.0;
+    for (int i = 0; i < m; i++) work += (double)(i - fst[i]) * (double)(i - fst[i]);
+    E.clear();
+}
+
+int EnvelopeGraph::solve(const std::vector<double>& diag, const std::vector<double>& off, const std::vector<double>& rhs, std::vector<double>& x) {
+    E.assign(rp[m], 0.0);
+    r.resize((size_t)m); d.resize((size_t)m);
+    auto at = [&](int i, int j) -> double& { return E[rp[i] + (size_t)(j - fst[i])]; };   // j in [fst[i], i]
+    for (int i = 0; i < m; i++) at(pos[i], pos[i]) = diag[i];
+    for (size_t q = 0; q < edges.size(); q++) {
+        const int u = pos[edges[q].first], v = pos[edges[q].second];
+        if (u > v) at(u, v) += off[q]; else at(v, u) += off[q];
+    }
+    // envelope Cholesky, row by row
+    for (int i = 0; i < m; i++) {
+        for (int j = fst[i]; j < i; j++) {
+            double s = at(i, j);
+            for (int k = std::max(fst[i], fst[j]); k < j; k++) s -= at(i, k) * at(j, k);
+            at(i, j) = s / at(j, j);
+        }
+        double s = at(i, i);
+        for (int k = fst[i]; k < i; k++) s -= at(i, k) * at(i, k);
+        if (!(s > 0.0)) return order[i];
+        at(i, i) = std::sqrt(s);
+    }
+    auto lsolve = [&](std::vector<double>& b) {              // b := (L L^T)^-1 b, permuted positions
+        for (int i = 0; i < m; i++) { double s = b[i]; for (int k = fst[i]; k < i; k++) s -= at(i, k) * b[k]; b[i] = s / at(i, i); }
+        for (int i = m - 1; i >= 0; i--) { b[i] /= at(i, i); const double bi = b[i]; for (int k = fst[i]; k < i; k++) b[k] -= at(i, k) * bi; }
+    };
+    xp.resize((size_t)m);
+    for (int i = 0; i < m; i++) xp[pos[i]] = rhs[i];
+    lsolve(xp);
+    // one step of iterative refinement on the unfactored system: r = rhs - A x
+    for (int i = 0; i < m; i++) r[pos[i]] = rhs[i] - diag[i] * xp[pos[i]];
+    for (size_t q = 0; q < edges.size(); q++) {
+        const int u = pos[edges[q].first], v = pos[edges[q].second];
+        r[u] -= off[q] * xp[v]; r[v] -= off[q] * xp[u];
+    }
+    d = r;
+    lsolve(d);
+    for (int i = 0; i < m; i++) xp[i] += d[i];
+    x.resize((size_t)m);
+    for (int i = 0; i < m; i++) x[i] = xp[pos[i]];
+    return -1;
+}
+
+}  // namespace mi_gain
+
+using mi_gain::EnvelopeGraph;
 
 namespace {
 
@@ -77,7 +163,7 @@ int solve_pcg(const mi355_gain_pair_stats* ps, const std::vector<int>& live, con
 
 // The normal equations of the header over n unknowns ("frames" for mi355_solve_gains, the nodes (frame, cell) for the block gains): ps[p].a / .b
 // are unknowns, cover[k] is N_k.  x3: n x 3 doubles, 1 for an unknown without an equation (channels == 1: the one value in all three).
-// The factorisation is the envelope Cholesky below.  may_iterate (block gains only): where its envelope would cost more than ENVELOPE_WORK_MAX
+// The factorisation is EnvelopeGraph's envelope Cholesky.  may_iterate (block gains only): where its envelope would cost more than ENVELOPE_WORK_MAX
 // multiply-adds per channel, a Jacobi-preconditioned conjugate gradient in the same fixed order takes its place; it stops on a bound of the
 // error that it can prove (see there) and fails rather than return less.  unit names an unknown in the messages.
 int solve_nodes(const mi355_gain_pair_stats* ps, int n_pairs, const int64_t* cover, int n, float sigma_n, float sigma_g, int channels, const char* unit,
@@ -93,42 +179,14 @@ int solve_nodes(const mi355_gain_pair_stats* ps, int n_pairs, const int64_t* cov
     const int m = (int)node.size();
     std::fill(x3, x3 + 3 * (size_t)n, 1.0);
     if (m == 0) return MI355_OK;
-    std::vector<std::vector<int>> adj((size_t)m);
-    for (int p : live) { const int u = idx[ps[p].a], v = idx[ps[p].b]; adj[u].push_back(v); adj[v].push_back(u); }
-    for (auto& l : adj) std::sort(l.begin(), l.end());
-    // reverse Cuthill-McKee: per component, start at the unvisited node of least degree (lowest index on ties), neighbours by (degree, index)
-    std::vector<int> order; order.reserve(m);
-    std::vector<char> seen((size_t)m, 0);
-    std::vector<int> by_deg(m);
-    for (int i = 0; i < m; i++) by_deg[i] = i;
-    std::stable_sort(by_deg.begin(), by_deg.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
-    for (int s : by_deg) {
-        if (seen[s]) continue;
-        size_t head = order.size();
-        order.push_back(s); seen[s] = 1;
-        std::vector<int> nb;
-        while (head < order.size()) {
-            const int u = order[head++];
-            nb.clear();
-            for (int v : adj[u]) if (!seen[v]) { nb.push_back(v); seen[v] = 1; }
-            std::stable_sort(nb.begin(), nb.end(), [&](int x, int y) { return adj[x].size() < adj[y].size(); });
-            order.insert(order.end(), nb.begin(), nb.end());
-        }
-    }
-    std::reverse(order.begin(), order.end());
-    std::vector<int> pos((size_t)m);
-    for (int i = 0; i < m; i++) pos[order[i]] = i;
-    // envelope: row i (permuted) holds columns fst[i] .. i
-    std::vector<int> fst((size_t)m);
-    for (int i = 0; i < m; i++) { int f = i; for (int v : adj[order[i]]) f = std::min(f, pos[v]); fst[i] = f; }
-    std::vector<size_t> rp((size_t)m + 1, 0);
-    for (int i = 0; i < m; i++) rp[i + 1] = rp[i] + (size_t)(i - fst[i] + 1);
-    double work = 0.0;
-    for (int i = 0; i < m; i++) work += (double)(i - fst[i]) * (double)(i - fst[i]);
-    const bool iterate = may_iterate && work > ENVELOPE_WORK_MAX;
-    std::vector<double> E(iterate ? 0 : rp[m]), diag((size_t)m), rhs((size_t)m), x((size_t)m), r((size_t)m), d((size_t)m);
+    std::vector<std::pair<int, int>> edges;
+    edges.reserve(live.size());
+    for (int p : live) edges.emplace_back(idx[ps[p].a], idx[ps[p].b]);
+    EnvelopeGraph eg;
+    eg.build(m, edges);
+    const bool iterate = may_iterate && eg.work > ENVELOPE_WORK_MAX;
+    std::vector<double> diag((size_t)m), rhs((size_t)m), x((size_t)m);
     std::vector<double> off((size_t)live.size());
-    auto at = [&](int i, int j) -> double& { return E[rp[i] + (size_t)(j - fst[i])]; };   // j in [fst[i], i]
     const int nch = channels;
     for (int c = 0; c < nch; c++) {
         // the normal equations in pair-list order
@@ -148,49 +206,13 @@ int solve_nodes(const mi355_gain_pair_stats* ps, int n_pairs, const int64_t* cov
         if (iterate) {
             const int rc = solve_pcg(ps, live, idx, node, cover, diag, off, rhs, beta, x, err);
             if (rc != MI355_OK) return rc;
-            for (int i = 0; i < m; i++) {
-                if (nch == 3) x3[3 * (size_t)node[i] + c] = x[i];
-                else x3[3 * (size_t)node[i]] = x3[3 * (size_t)node[i] + 1] = x3[3 * (size_t)node[i] + 2] = x[i];
-            }
-            continue;
+        } else {
+            const int bad = eg.solve(diag, off, rhs, x);
+            if (bad >= 0) { err = std::string("the normal equations are not positive definite at ") + unit + " " + std::to_string(node[bad]); return MI355_ERR_FAILED; }
         }
-        std::fill(E.begin(), E.end(), 0.0);
-        for (int i = 0; i < m; i++) at(pos[i], pos[i]) = diag[i];
-        for (size_t q = 0; q < live.size(); q++) {
-            const int u = pos[idx[ps[live[q]].a]], v = pos[idx[ps[live[q]].b]];
-            if (u > v) at(u, v) += off[q]; else at(v, u) += off[q];
-        }
-        // envelope Cholesky, row by row
         for (int i = 0; i < m; i++) {
-            for (int j = fst[i]; j < i; j++) {
-                double s = at(i, j);
-                for (int k = std::max(fst[i], fst[j]); k < j; k++) s -= at(i, k) * at(j, k);
-                at(i, j) = s / at(j, j);
-            }
-            double s = at(i, i);
-            for (int k = fst[i]; k < i; k++) s -= at(i, k) * at(i, k);
-            if (!(s > 0.0)) { err = std::string("the normal equations are not positive definite at ") + unit + " " + std::to_string(node[order[i]]); return MI355_ERR_FAILED; }
-            at(i, i) = std::sqrt(s);
-        }
-        auto lsolve = [&](std::vector<double>& b) {              // b := (L L^T)^-1 b, permuted positions
-            for (int i = 0; i < m; i++) { double s = b[i]; for (int k = fst[i]; k < i; k++) s -= at(i, k) * b[k]; b[i] = s / at(i, i); }
-            for (int i = m - 1; i >= 0; i--) { b[i] /= at(i, i); const double bi = b[i]; for (int k = fst[i]; k < i; k++) b[k] -= at(i, k) * bi; }
-        };
-        for (int i = 0; i < m; i++) x[pos[i]] = rhs[i];
-        lsolve(x);
-        // one step of iterative refinement on the unfactored system: r = rhs - A x
-        for (int i = 0; i < m; i++) r[pos[i]] = rhs[i] - diag[i] * x[pos[i]];
-        for (size_t q = 0; q < live.size(); q++) {
-            const int u = pos[idx[ps[live[q]].a]], v = pos[idx[ps[live[q]].b]];
-            r[u] -= off[q] * x[v]; r[v] -= off[q] * x[u];
-        }
-        d = r;
-        lsolve(d);
-        for (int i = 0; i < m; i++) x[i] += d[i];
-        for (int i = 0; i < m; i++) {
-            const double g = x[pos[i]];
-            if (nch == 3) x3[3 * (size_t)node[i] + c] = g;
-            else x3[3 * (size_t)node[i]] = x3[3 * (size_t)node[i] + 1] = x3[3 * (size_t)node[i] + 2] = g;
+            if (nch == 3) x3[3 * (size_t)node[i] + c] = x[i];
+            else x3[3 * (size_t)node[i]] = x3[3 * (size_t)node[i] + 1] = x3[3 * (size_t)node[i] + 2] = x[i];
         }
     }
     return MI355_OK;

@@ -1104,6 +1104,89 @@ int  mi355_apply_block_gains_dev(mi355_ctx* ctx, const uint8_t* const* d_src, ui
 int  mi355_block_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                                      const int32_t* pairs_ab, int n_pairs, const mi355_block_gain_params* p, float* gains_out);
 
+/* ---- frame sharpness (opt-in; csrc/sharp.hip, csrc/sharp_solve.cpp, csrc/sharp.h) ---------------------------------------------------------
+ * One relative sharpness per frame from the frames' overlaps, and a selection that flags blurred frames (motion blur, missed focus) and
+ * drops those the survey can lose without falling apart.  A focus measure of one frame alone measures the ground as much as the lens; here
+ * two frames are compared over the SAME ground, on the canvas lattice, through the render's own map and sample.  Its place is the gain
+ * stage's, between alignment and render; no render changes.
+ *
+ * Frames, taking part, canvas, lattice (1 <= step <= 64, default 8), cover and sample: exactly as in "exposure gain compensation" above.
+ * Gray of a sample (B, G, R bytes): g = (1868 B + 9617 G + 4899 R + 8192) >> 14.
+ * Laplacian: frame k has a Laplacian at lattice point (x, y) when 1 <= x <= cw-2, 1 <= y <= ch-2 and k has a sample at all five canvas pixels
+ *   (x, y), (x-1, y), (x+1, y), (x, y-1), (x, y+1); then L = 4 g(x, y) - g(x-1, y) - g(x+1, y) - g(x, y-1) - g(x, y+1), an integer in
+ *   [-1020, 1020].  Each of the five source coordinates is the render's map of that integer canvas pixel (nothing is stepped incrementally),
+ *   so the five samples are the bytes the refined render would give those pixels from frame k.
+ * Statistics (integers: exact, independent of execution order):
+ *   per listed pair (a, b): n = the lattice points where both frames have a Laplacian, e_a / e_b = the sum of L^2 of frame a / b over those
+ *   points, s_a / s_b = the sum of g(x, y) (the centre sample) of frame a / b over them;
+ *   per frame k (optional): n, e, s likewise over all lattice points where k has a Laplacian -- an absolute figure for frames without
+ *   partners, for diagnostics only (it measures the ground as much as the lens).
+ * Solve (host only, double, single-threaded, fixed order: the same bits from call to call for the same record list; relisting the pairs in
+ *   another order changes the order of the sums and may change last bits, never more than the bound below):
+ *   a listed pair is usable when n > 0 and e_a, e_b, s_a, s_b are all > 0.  For a usable pair
+ *     d = 0.5 (ln e_a - ln e_b) - (ln s_a - ln s_b),
+ *   the log ratio of Laplacian amplitude, normalised by mean brightness so that an exposure difference is not read as sharpness.  The
+ *   unknowns l_k minimise  sum over usable pairs of n (l_a - l_b - d)^2  +  prior * sum_k W_k l_k^2,  W_k = the sum of n over the usable
+ *   pairs that hold k.  prior (default 0.01) fixes the gauge: a lone blurred frame among sharp partners comes out at d / (1 + prior), and
+ *   long-wavelength drift along a strip is damped.  l is within 1e-9 absolute of the exact minimiser (the factorisation of
+ *   mi355_solve_gains).  sharp[k] = (float)exp(l_k); a frame in no usable pair gets exactly 1.0f.
+ * Flag and select (host only): the partners of k are the frames it shares a usable pair with; m_k = the lower median of l over k's
+ *   partners; rel_k = l_k - m_k (0 for a frame without partners); k is blurred when rel_k < ln(blur_ratio).  The blurred frames are
+ *   visited by ascending rel (ties: lower index first); k is dropped only if the still-kept frames of its connected component stay
+ *   connected without it, in the usable-pair graph restricted to kept frames.  status[k]: 0 kept and not blurred, 1 blurred and dropped,
+ *   2 blurred but kept because removing it would split the survey, 3 no usable pair.  The caller drops a frame by setting h9s[9k+8] = 0, the
+ *   skip convention of every render.
+ *   Connectivity is all this rule guarantees.  Coverage is NOT checked: a dropped frame may leave a hole where no other frame covers the
+ *   ground.  A caller who needs to know compares the count map of mi355_mosaic_seamline_dev (or the need flags of
+ *   mi355_mosaic_seamline_cover) before and after.
+ * blur_ratio default 0.58: measured on synthetic strips (profiles/sharp_quality.json), the geometric mean of the lowest exp(rel) of an
+ *   unblurred frame and the exp(rel) of a frame blurred by a Gaussian of sigma 1.5 px.
+ * Errors (MI355_ERR_ARG, the message names the index or value): the statistics refuse what mi355_gain_stats_dev refuses (a == b, a
+ *   position outside [0, n), an unordered pair listed twice, step outside [1, 64], n > 65535, a taking-part frame with a NULL pointer or
+ *   w < 2, h < 2, ws < 3 w); the solve and the selection refuse prior <= 0 or not finite, blur_ratio outside (0, 1], and a record with a
+ *   negative n, e_a, e_b, s_a or s_b (and the pair-list errors above, on the records' a and b). */
+typedef struct {
+    int32_t a, b;               /* positions in the frame list */
+    int64_t n;                  /* lattice points where both frames have a Laplacian */
+    int64_t e_a, e_b;           /* sum of L^2 of frame a / frame b over those points */
+    int64_t s_a, s_b;           /* sum of the centre gray of frame a / frame b over those points */
+} mi355_sharp_pair_stats;       /* 48 B */
+typedef struct {
+    int64_t n, e, s;            /* lattice points where the frame has a Laplacian, sum of L^2, sum of centre gray */
+} mi355_sharp_frame_stats;      /* 24 B */
+typedef struct {
+    float prior;                /* regulariser, > 0 */
+    float blur_ratio;           /* a frame is blurred below this sharpness relative to its partners' lower median, in (0, 1] */
+    int32_t step;               /* lattice step in canvas pixels, 1..64 */
+    int32_t reserved;
+} mi355_sharp_params;
+#ifdef __cplusplus
+static_assert(sizeof(mi355_sharp_pair_stats) == 48, "mi355_sharp_pair_stats is 48 bytes");
+static_assert(sizeof(mi355_sharp_frame_stats) == 24 && sizeof(mi355_sharp_params) == 16, "mi355_sharp_frame_stats is 24 bytes, mi355_sharp_params 16");
+#else
+_Static_assert(sizeof(mi355_sharp_pair_stats) == 48, "mi355_sharp_pair_stats is 48 bytes");
+_Static_assert(sizeof(mi355_sharp_frame_stats) == 24 && sizeof(mi355_sharp_params) == 16, "mi355_sharp_frame_stats is 24 bytes, mi355_sharp_params 16");
+#endif
+#define MI355_SHARP_KEPT       0
+#define MI355_SHARP_DROPPED    1
+#define MI355_SHARP_CUT_VERTEX 2
+#define MI355_SHARP_NO_PAIR    3
+/* prior = 0.01, blur_ratio = 0.58, step = 8 */
+void mi355_default_sharp_params(mi355_sharp_params* p);
+/* the statistics (one launch over all pair tiles and, where frame_stats is given, all cover tiles; complete on return): pair_stats (HOST,
+ * n_pairs records, a / b filled in) and frame_stats (HOST, n records; may be NULL, and then no cover tiles are launched). */
+int  mi355_sharp_stats_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                           const int32_t* pairs_ab, int n_pairs, int step, mi355_sharp_pair_stats* pair_stats, mi355_sharp_frame_stats* frame_stats);
+/* sharp (n floats) and rel (n doubles; may be NULL) from the records (host only, no ctx, no device); p NULL: defaults (p->step is
+ * not used here; blur_ratio is checked though only the selection uses it).  Errors: mi355_last_error(NULL). */
+int  mi355_solve_sharpness(const mi355_sharp_pair_stats* pair_stats, int n_pairs, int n, const mi355_sharp_params* p, float* sharp, double* rel);
+/* status (n bytes) and sharp (n floats; may be NULL) from the records: the solve above, then flag and select (host only). */
+int  mi355_select_sharp_frames(const mi355_sharp_pair_stats* pair_stats, int n_pairs, int n, const mi355_sharp_params* p, uint8_t* status, float* sharp);
+/* statistics at p->step (no per-frame records), solve, flag and select; sharp (HOST, n floats; may be NULL), status (HOST, n bytes).  The
+ * frames are only read.  p NULL: defaults. */
+int  mi355_sharpness_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
+                         const int32_t* pairs_ab, int n_pairs, const mi355_sharp_params* p, float* sharp, uint8_t* status);
+
 /* ---- lens undistortion (opt-in; csrc/undistort.hip, csrc/lens.h) ---------------------------------------------------------------------
  * Every stage of this library relates two frames of flat ground by a homography, which holds for a pinhole camera only.  This pass
  * resamples BGR u8 frames of a camera with Brown-Conrady distortion (OpenCV's model, coefficient order and signs: k1, k2, p1, p2, k3) to an

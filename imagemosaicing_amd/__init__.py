@@ -16,6 +16,8 @@ from .capi import (  # noqa: F401
     BlockGainParams, BLOCK_GAIN_STATS, block_gain_params, solve_block_gains,
     SharpParams, SHARP_PAIR_STATS, SHARP_FRAME_STATS, SHARP_KEPT, SHARP_DROPPED, SHARP_CUT_VERTEX, SHARP_NO_PAIR, sharp_params, solve_sharpness,
     select_sharp_frames, drop_sharp_frames,
+    CoverParams, COVER_FRAME_STATS, COVER_BINS, COVER_NOT_CANDIDATE, COVER_DROPPED, COVER_KEPT_COVERAGE, COVER_CUT_VERTEX, COVER_NOT_EXAMINED,
+    cover_params, cover_select,
     FeatherParams, feather_params, SeamlineParams, seamline_params, MedianParams, median_params, SeamCutParams, SeamReport, SEAM_CELL, seamcut_params, seam_grid, blend_seam_grid, seam_labels_host,
     Camera, UndistortParams, undistort_params, undistort_fit, undistort_map,
     PAIR_NORMAL_BLOCK, ProjectiveParams, ProjectiveReport, projective_params, pair_normal_blocks_host, global_projective_refine, global_projective_refine_results,

@@ -54,6 +54,10 @@ class SharpParams(C.Structure):
     _fields_ = [("prior", C.c_float), ("blur_ratio", C.c_float), ("step", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CoverParams(C.Structure):
+    _fields_ = [("step", C.c_int32), ("min_depth", C.c_int32), ("max_loss", C.c_int64)]
+
+
 class FeatherParams(C.Structure):
     _fields_ = [("ramp", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -116,6 +120,12 @@ SHARP_PAIR_STATS = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<i8"), ("e_a", "
 SHARP_FRAME_STATS = np.dtype([("n", "<i8"), ("e", "<i8"), ("s", "<i8")])
 SHARP_KEPT, SHARP_DROPPED, SHARP_CUT_VERTEX, SHARP_NO_PAIR = 0, 1, 2, 3
 assert SHARP_PAIR_STATS.itemsize == 48 and SHARP_FRAME_STATS.itemsize == 24 and C.sizeof(SharpParams) == 16
+# mi355_cover_frame_stats: the lattice points a frame covers by their depth ("cover depth"); the selection's status codes
+COVER_FRAME_STATS = np.dtype([("at_depth", "<i8", (8,))])
+COVER_BINS = 9
+COVER_NOT_CANDIDATE, COVER_DROPPED, COVER_KEPT_COVERAGE, COVER_CUT_VERTEX, COVER_NOT_EXAMINED = 0, 1, 2, 3, 4
+COVER_STATS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)      # mi355_cover_stats_fn(user, keep, frame_stats)
+assert COVER_FRAME_STATS.itemsize == 64 and C.sizeof(CoverParams) == 16
 PAIR_NORMAL_BLOCK = np.dtype([("i", "<i4"), ("j", "<i4"), ("n_in", "<i4"), ("_pad", "<i4"), ("cost", "<f8"), ("g", "<f8", (16,)), ("N", "<f8", (136,))])
 
 
@@ -841,6 +851,33 @@ class Context:
         self._chk(self.L.mi355_sharpness_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(sharp), _p(status)))
         return sharp, status, drop_sharp_frames(h9s, status)
 
+    # ---- cover depth (mi355_cover_*, csrc/cover.hip) ----------------------------------------------------------------------------
+    def CoverStatsDev(self, w, h, h9s, keep=None, step=8):
+        """how deep the kept frames cover the canvas lattice of `step` (geometry only, no images): (COVER_FRAME_STATS [n], hist int64
+        [COVER_BINS]).  keep: n bytes, None = every frame."""
+        w, h, h9s, n, keep = _cover_args(w, h, h9s, keep)
+        fs = np.zeros(n, COVER_FRAME_STATS)
+        hist = np.zeros(COVER_BINS, np.int64)
+        self._chk(self.L.mi355_cover_stats_dev(self._h, _p(w), _p(h), n, _p(h9s), _p(keep), int(step), _p(fs), _p(hist)))
+        return fs, hist
+
+    def CoverSelectDev(self, w, h, h9s, order=None, pairs=None, keep=None, params=None, final=False, **kw):
+        """coverage-checked frame dropping with the kernel as the statistics of every round: (status [n] uint8 -- 0 not a candidate, 1
+        dropped, 2 kept for coverage, 3 kept as a cut vertex, 4 not examined --, keep_out [n] uint8, rounds, lost) and, with final=True, the
+        (COVER_FRAME_STATS [n], hist) under keep_out.  order: candidate positions by priority, None = every kept frame by ascending crit;
+        pairs: the graph that must stay connected, None = no connectivity check; params: CoverParams (cover_params()) or keyword fields."""
+        w, h, h9s, n, keep = _cover_args(w, h, h9s, keep)
+        order, n_order, ab, npairs = _cover_lists(order, pairs)
+        p = params if params is not None else cover_params(**kw)
+        status, keep_out = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        rounds, lost = C.c_int32(0), C.c_int64(0)
+        fs = np.zeros(n, COVER_FRAME_STATS) if final else None
+        hist = np.zeros(COVER_BINS, np.int64) if final else None
+        self._chk(self.L.mi355_cover_select_dev(self._h, _p(w), _p(h), n, _p(h9s), _p(keep), _p(order), n_order, _p(ab), npairs, C.byref(p),
+                                                _p(status), _p(keep_out), C.byref(rounds), C.byref(lost), _p(fs), _p(hist)))
+        out = (status, keep_out, int(rounds.value), int(lost.value))
+        return out + (fs, hist) if final else out
+
     # ---- block gain compensation (mi355_block_gain_*, csrc/gain.hip) -------------------------------------------------------
     def BlockGainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, grid_x=8, grid_y=6):
         """per-cell overlap statistics of the listed pairs: (BLOCK_GAIN_STATS records sorted by (pair, cell_a, cell_b), cell cover int64
@@ -1565,6 +1602,66 @@ def sharp_params(prior=None, blur_ratio=None, step=None):
     if step is not None:
         p.step = int(step)
     return p
+
+
+def cover_params(step=None, min_depth=None, max_loss=None):
+    """mi355_cover_params: the library's defaults (mi355_default_cover_params: 8, 1, 0) with the given fields replaced"""
+    p = CoverParams()
+    load_library().mi355_default_cover_params(C.byref(p))
+    for name, v in (("step", step), ("min_depth", min_depth), ("max_loss", max_loss)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def _cover_args(w, h, h9s, keep):
+    w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
+    h9s = np.ascontiguousarray(h9s, np.float32)
+    n = len(w)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, np.uint8)
+        if len(keep) != n:
+            raise ValueError("keep holds %d bytes for %d frames" % (len(keep), n))
+    return w, h, h9s, n, keep
+
+
+def _cover_lists(order, pairs):
+    if order is not None:
+        order = np.ascontiguousarray(np.asarray(order, np.int32).reshape(-1))
+    ab = np.ascontiguousarray(np.asarray(pairs if pairs is not None else [], np.int32).reshape(-1, 2))
+    return order, (len(order) if order is not None else 0), ab, len(ab)
+
+
+def cover_select(w, h, h9s, stats_fn, order=None, pairs=None, keep=None, params=None, **kw):
+    """mi355_cover_select (host only, no device): the selection of "cover depth" with the statistics of every round supplied by
+    stats_fn(keep [n] uint8) -> COVER_FRAME_STATS [n] (or an [n, 8] integer array).  Returns (status [n] uint8, keep_out [n] uint8, rounds,
+    lost).  An exception raised by stats_fn ends the selection and is raised again."""
+    L = load_library()
+    w, h, h9s, n, keep = _cover_args(w, h, h9s, keep)
+    order, n_order, ab, npairs = _cover_lists(order, pairs)
+    p = params if params is not None else cover_params(**kw)
+    raised = []
+
+    def call(_user, keep_ptr, fs_ptr):
+        try:
+            kp = np.ctypeslib.as_array(C.cast(keep_ptr, C.POINTER(C.c_uint8)), (n,)).copy()
+            fs = np.asarray(stats_fn(kp))
+            fs = np.ascontiguousarray(fs["at_depth"] if fs.dtype.names else fs, np.int64).reshape(n, 8)
+            C.memmove(fs_ptr, fs.ctypes.data, 64 * n)
+            return 0
+        except BaseException as e:                                   # nothing may unwind through the C frames
+            raised.append(e)
+            return -2                                                # MI355_ERR_FAILED
+    cb = COVER_STATS_FN(call)
+    status, keep_out = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+    rounds, lost = C.c_int32(0), C.c_int64(0)
+    rc = L.mi355_cover_select(_p(w), _p(h), n, _p(h9s), _p(keep), _p(order), n_order, _p(ab), npairs, C.byref(p), cb, None,
+                              _p(status), _p(keep_out), C.byref(rounds), C.byref(lost))
+    if raised:
+        raise raised[0]
+    if rc < 0:
+        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return status[:n], keep_out[:n], int(rounds.value), int(lost.value)
 
 
 def feather_params(ramp=None):

@@ -10,6 +10,7 @@
 #include "sharp.h"
 #include "gain.h"
 #include "host_error.h"
+#include "kept_graph.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -125,32 +126,15 @@ int select_sharp_frames(const mi355_sharp_pair_stats* ps, int n_pairs, int n, co
         if (!part[k].empty() && rel[k] < limit) blurred.push_back(k);
     }
     std::stable_sort(blurred.begin(), blurred.end(), [&](int x, int y) { return rel[x] < rel[y]; });     // ascending rel, lower index first on ties
-    // the components of the usable-pair graph and how many kept frames each still holds
-    std::vector<int> comp((size_t)n, -1), kept_in;
-    std::vector<int> queue;
-    for (int s = 0; s < n; s++) {
-        if (comp[s] >= 0 || part[s].empty()) continue;
-        const int c = (int)kept_in.size();
-        queue.assign(1, s); comp[s] = c;
-        for (size_t head = 0; head < queue.size(); head++)
-            for (int q : part[queue[head]]) if (comp[q] < 0) { comp[q] = c; queue.push_back(q); }
-        kept_in.push_back((int)queue.size());
-    }
-    std::vector<char> gone((size_t)n, 0);
-    std::vector<int> seen((size_t)n, -1);
+    // the components of the usable-pair graph and how many kept frames each still holds (kept_graph.h)
+    mi_graph::KeptGraph g;
+    g.build(part);
     for (size_t i = 0; i < blurred.size(); i++) {
         const int k = blurred[i];
-        // the kept frames of k's component without k: connected when a walk from one of k's kept partners reaches them all
-        int start = -1;
-        for (int q : part[k]) if (!gone[q]) { start = q; break; }
-        int reached = 0;
-        if (start >= 0) {
-            queue.assign(1, start); seen[start] = (int)i; reached = 1;
-            for (size_t head = 0; head < queue.size(); head++)
-                for (int q : part[queue[head]])
-                    if (q != k && !gone[q] && seen[q] != (int)i) { seen[q] = (int)i; queue.push_back(q); reached++; }
-        }
-        if (start >= 0 && reached == kept_in[comp[k]] - 1) { status[k] = MI355_SHARP_DROPPED; gone[k] = 1; kept_in[comp[k]]--; }
+        // the kept frames of k's component without k: connected when a walk from one of k's kept partners reaches them all.  The last kept
+        // frame of a component (no kept partner) is never dropped.
+        const int reached = g.reach_without(k);
+        if (reached > 0 && reached == g.others_kept(k)) { status[k] = MI355_SHARP_DROPPED; g.drop(k); }
         else status[k] = MI355_SHARP_CUT_VERTEX;
     }
     if (sharp)

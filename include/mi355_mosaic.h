@@ -1138,7 +1138,8 @@ int  mi355_block_gain_compensate_dev(mi355_ctx* ctx, uint8_t* const* d_imgs, con
  *   skip convention of every render.
  *   Connectivity is all this rule guarantees.  Coverage is NOT checked: a dropped frame may leave a hole where no other frame covers the
  *   ground.  A caller who needs to know compares the count map of mi355_mosaic_seamline_dev (or the need flags of
- *   mi355_mosaic_seamline_cover) before and after.
+ *   mi355_mosaic_seamline_cover) before and after.  "cover depth" below makes that check per candidate: mi355_cover_select_dev with the
+ *   blurred frames as its order drops only those whose ground stays covered.
  * blur_ratio default 0.58: measured on synthetic strips (profiles/sharp_quality.json), the geometric mean of the lowest exp(rel) of an
  *   unblurred frame and the exp(rel) of a frame blurred by a Gaussian of sigma 1.5 px.
  * Errors (MI355_ERR_ARG, the message names the index or value): the statistics refuse what mi355_gain_stats_dev refuses (a == b, a
@@ -1186,6 +1187,91 @@ int  mi355_select_sharp_frames(const mi355_sharp_pair_stats* pair_stats, int n_p
  * frames are only read.  p NULL: defaults. */
 int  mi355_sharpness_dev(mi355_ctx* ctx, const uint8_t* const* d_imgs, const int* w, const int* h, const int* ws, int n, const float* h9s,
                          const int32_t* pairs_ab, int n_pairs, const mi355_sharp_params* p, float* sharp, uint8_t* status);
+
+/* ---- cover depth (opt-in; csrc/cover.hip, csrc/cover_select.cpp, csrc/cover.h) -------------------------------------------------------------
+ * How many kept frames cover each point of the canvas lattice, which frames hold the thinly covered points, and a selection that drops
+ * frames only where the ground stays covered: the coverage check the sharpness selection above does not make, and the way to thin a survey
+ * flown at a high overlap.  Geometry only: the stage takes w, h, n, h9s and NO image pointers, and loads no pixel.
+ *
+ * Frames, taking part, canvas, lattice (1 <= step <= 64, default 8) and cover: exactly as in "exposure gain compensation" above.  Frame k
+ *   covers lattice point (x, y) when the pixel lies in k's clipped canvas box and the render's map of that integer pixel ((float)x - dGx,
+ *   (float)y - dGy through the inverse; nothing is stepped incrementally) falls inside [0, w-1) x [0, h-1).
+ * keep (n bytes; NULL: every frame is kept): the KEPT frames are those that take part and have keep[k] != 0.
+ * The canvas layout is mi355_mosaic_layout's for h9s AS PASSED; it does not depend on keep.  This is why dropping is expressed by keep and
+ *   not by h9s[9k+8] = 0: zeroing m8 may shift or shrink the layout, and with it the lattice, between two calls that are meant to be
+ *   compared.  Only once the selection is final does the caller set h9s[9k+8] = 0 for the dropped frames.
+ * Depth of a lattice point: d = the number of kept frames that cover it.
+ * Statistics (integers: exact, independent of tile shape, walk order and launch geometry):
+ *   hist[j], j = 0 .. MI355_COVER_BINS-1 (9 bins): the lattice points of the whole cw x ch canvas with d == j; the last bin takes d >= 8.
+ *     The bins sum to the number of lattice points, ((cw-1)/step + 1) * ((ch-1)/step + 1).
+ *   per frame k one mi355_cover_frame_stats: at_depth[j] = the lattice points k covers whose depth is j+1; the last entry takes d >= 8.  A
+ *     frame that is not kept gets zeros.
+ *   With every taking-part frame kept, sum_j at_depth[k][j] equals mi355_gain_stats_dev's frame_cover[k] at the same step; for 1 <= d <= 7,
+ *     sum_k at_depth[k][d-1] == d * hist[d].
+ *   crit_k(min_depth) = sum over j < min_depth of at_depth[k][j]: the lattice points that fall below min_depth when k alone is removed, plus
+ *     the points k covers that already lie below it.
+ * Selection (the rule is the definition).  order: n_order distinct frame positions, the candidates in priority order; NULL: every kept frame,
+ *   by ascending crit_k of the first round, ties to the lower index.  pairs_ab / n_pairs (optional): the graph whose connectivity must
+ *   survive, restricted to the frames kept on entry; the check is the sharpness selection's: the still-kept frames of k's component stay
+ *   connected without k (a frame with no still-kept partner is alone in its component and splits nothing).  Without a pair list there is no
+ *   connectivity check.
+ *   A candidate that does not take part, or is not kept on entry, gets status 4 and is never examined; a frame that is not a candidate gets
+ *   status 0.  kept = the kept frames; every other candidate starts WAITING.  Repeat while a candidate waits:
+ *     1. take the statistics under the current kept (one ROUND);
+ *     2. blocked = the empty list of boxes; walk the waiting candidates in order;
+ *     3. for a candidate k take its clipped canvas box (begX..endX, begY..endY, ends included).  If the box meets a box in blocked, k keeps
+ *        waiting and its box joins blocked;
+ *     4. otherwise k is settled: if crit_k(min_depth) > max_loss, status 2 (kept for coverage); else if removing it would split its
+ *        component, status 3 (kept as a cut vertex); else kept[k] = 0, status 1 (dropped), and its box joins blocked.
+ *   A settled candidate is never examined again (a cut vertex that a later drop would free stays status 3).  Each round settles the first
+ *   waiting candidate at least, so there are at most n_order rounds.  Outputs: status[n], keep_out[n] (1 for a frame still kept, 0
+ *   otherwise), rounds, lost = the sum of crit_k over the dropped frames at the time of their drop, and optionally the final frame_stats /
+ *   hist under keep_out (one more launch, made only when asked for).
+ *   Without a pair list the result equals the sequential greedy that recomputes the statistics after every single drop: a frame's
+ *   statistics depend only on frames whose boxes meet its own, and no candidate is settled before an earlier candidate whose box it meets.
+ *   With a pair list, connectivity is evaluated on the kept set of the moment; the result may differ from the sequential greedy in that
+ *   respect only (within a round, by the drops already made in it, which the sequential order may make later or earlier).
+ * Errors (MI355_ERR_ARG, the message names the index or value): step outside [1, 64], min_depth outside [1, 8], max_loss < 0, n > 65535, an
+ *   order entry outside [0, n) or listed twice, a taking-part frame with w < 2 or h < 2, and the pair-list errors of mi355_gain_stats_dev
+ *   (a == b, a position outside [0, n), an unordered pair listed twice). */
+#define MI355_COVER_BINS 9
+typedef struct {
+    int64_t at_depth[8];        /* lattice points the frame covers whose depth is j+1; [7]: depth >= 8 */
+} mi355_cover_frame_stats;      /* 64 B */
+typedef struct {
+    int32_t step;               /* lattice step in canvas pixels, 1..64 */
+    int32_t min_depth;          /* the depth the ground must keep, 1..8 */
+    int64_t max_loss;           /* lattice points a single drop may take below min_depth, >= 0 */
+} mi355_cover_params;           /* 16 B */
+#ifdef __cplusplus
+static_assert(sizeof(mi355_cover_frame_stats) == 64 && sizeof(mi355_cover_params) == 16, "mi355_cover_frame_stats is 64 bytes, mi355_cover_params 16");
+#else
+_Static_assert(sizeof(mi355_cover_frame_stats) == 64 && sizeof(mi355_cover_params) == 16, "mi355_cover_frame_stats is 64 bytes, mi355_cover_params 16");
+#endif
+#define MI355_COVER_NOT_CANDIDATE 0
+#define MI355_COVER_DROPPED       1
+#define MI355_COVER_KEPT_COVERAGE 2
+#define MI355_COVER_CUT_VERTEX    3
+#define MI355_COVER_NOT_EXAMINED  4
+/* step = 8, min_depth = 1, max_loss = 0 */
+void mi355_default_cover_params(mi355_cover_params* p);
+/* the statistics under keep (one launch; complete on return): frame_stats (HOST, n records; may be NULL) and hist (HOST, MI355_COVER_BINS
+ * values; may be NULL). */
+int  mi355_cover_stats_dev(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, int step,
+                           mi355_cover_frame_stats* frame_stats, int64_t* hist);
+/* what the selection asks of its caller once per round: fill frame_stats (n records) with the statistics under keep (n bytes, never NULL);
+ * a return other than MI355_OK ends the selection with that code */
+typedef int (*mi355_cover_stats_fn)(void* user, const uint8_t* keep, mi355_cover_frame_stats* frame_stats);
+/* the selection with the statistics supplied by the caller (host only, no ctx, no device; errors: mi355_last_error(NULL)).  status and
+ * keep_out hold n bytes; rounds and lost may be NULL; p NULL: defaults (p->step is checked, the statistics are the caller's). */
+int  mi355_cover_select(const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, const int32_t* order, int n_order,
+                        const int32_t* pairs_ab, int n_pairs, const mi355_cover_params* p, mi355_cover_stats_fn stats_fn, void* user,
+                        uint8_t* status, uint8_t* keep_out, int32_t* rounds, int64_t* lost);
+/* that loop with cover_depth_kernel at p->step as stats_fn; frame_stats (n records) / hist (MI355_COVER_BINS values) may be NULL, and where
+ * either is given the statistics under keep_out are taken once more at the end. */
+int  mi355_cover_select_dev(mi355_ctx* ctx, const int* w, const int* h, int n, const float* h9s, const uint8_t* keep, const int32_t* order,
+                            int n_order, const int32_t* pairs_ab, int n_pairs, const mi355_cover_params* p, uint8_t* status, uint8_t* keep_out,
+                            int32_t* rounds, int64_t* lost, mi355_cover_frame_stats* frame_stats, int64_t* hist);
 
 /* ---- lens undistortion (opt-in; csrc/undistort.hip, csrc/lens.h) ---------------------------------------------------------------------
  * Every stage of this library relates two frames of flat ground by a homography, which holds for a pinhole camera only.  This pass

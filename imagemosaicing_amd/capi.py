@@ -309,6 +309,8 @@ class Context:
 
     def set_option(self, name, value):
         self._chk(self.L.mi355_set_option(self._h, name.encode(), int(value)))
+        if name == "nfeatures":
+            self.params.nfeatures = int(value)
 
     def profile_enable(self, on=True):
         self._chk(self.L.mi355_profile_enable(self._h, int(bool(on))))

@@ -407,6 +407,20 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
         ctx->keepall_max = value;
         return MI355_OK;
     }
+    if (std::string(name) == "nfeatures") {
+        if (value > 2048) { ctx->set_error("set_option: nfeatures must be in [1, 2048], or <= 0 for keep-all"); return MI355_ERR_ARG; }
+        int rc = mi_resolve_features(ctx);
+        if (rc != MI355_OK) return rc;
+        ctx->p.nfeatures = value;
+        return MI355_OK;
+    }
+    if (std::string(name) == "select_margin") {
+        if (value < 0 || value > 65536) { ctx->set_error("set_option: select_margin must be in [0, 65536]"); return MI355_ERR_ARG; }
+        int rc = mi_resolve_features(ctx);
+        if (rc != MI355_OK) return rc;
+        ctx->select_margin = value;
+        return MI355_OK;
+    }
     if (std::string(name) == "big_subpairs_max") { ctx->big_sub_max = value < 1 ? 1 : value; return MI355_OK; }
     {
         struct { const char* n; int* p; } knobs[] = {{"ransac_split", &ctx->ransac_split}, {"strict_frames", &ctx->strict_frames}};

@@ -162,7 +162,8 @@ struct mi355_ctx {
     SurfState* surf = nullptr;                         // SURF variant of the path (surf.hip)
     int keepall_max = MI355_SIFT_KEEPALL_MAX;          // option "keepall_max": keypoints per keep-all frame (multiple of 2048 in [32768, 262144]); every check of a frame's or pair's keypoint count uses it
     int big_sub_max = 65536;                           // option "big_subpairs_max" (debug): sub-pairs of <= 2048 x 2048 per large-pair run of the matcher (bounds the nn workspaces: 12 B x 2048 each)
-    int last_counts[8] = {0};                          // SIFT counters of the last frame: candidates, refined, keypoints, selected, overflow
+    int select_margin = 256;                           // option "select_margin": top-k SIFT's first orientation pass takes the strongest nfeatures + margin refined points
+    int last_counts[8] = {0};                          // SIFT counters of the last frame: candidates, refined, keypoints, selected, overflow, second orientation pass ran
 
     void set_error(const std::string& s) { err = s; }
     DevBuf& buf(const std::string& name) { return ws[name]; }

@@ -19,8 +19,10 @@
 //   extrema_stream / extrema_kernel   DoG never materialised in HBM: the 6 Gaussian levels are read once, 26-neighbour
 //                         test on the 5 DoG planes (extrema_stream: row extremes in registers, the raw rows in a wave-private
 //                         LDS ring; extrema_kernel: LDS tiles), candidates leave with their 3x3x3 neighbourhood
-//   refine                one lane per candidate: quadratic fit, contrast / edge tests, duplicate claim bitmap, response histogram
-//   select_unclaim        response threshold above which nfeatures + 256 refined points lie; takes the claim bits back
+//   refine                one lane per candidate: quadratic fit, contrast / edge tests; every accepted point is stored, also those of
+//                         several start points that converged to one location
+//   select_unique         response threshold above which nfeatures + margin refined points lie; lists the points above it, each
+//                         location once (a hash of the few thousand locations in LDS)
 //   orient                one wave per refined point above the threshold: 36-bin histogram in order-free fixed point,
 //                         smoothing + peaks via lane shuffles
 //   topk                  one workgroup per frame: radix select of the nfeatures-th response, bitonic sort of the
@@ -273,13 +275,13 @@ struct OctaveDev { lvl_t* lv[N_LEVELS]; int w, h; };
 constexpr int ECAP = 128;
 constexpr int REG_STRIDE = 32;              // one counter of the NREG candidate regions per 128-byte line
 // batched launches: frame f = blockIdx.y (z for refine) works on its own copy of every buffer, a fixed stride apart
-struct BatchStride { size_t pyr, claimed, cand, refined, kps, cube, sel, mins; };   // elements of the respective type (sel: selected keypoints per frame; mins: keep-all's start-key table)
+struct BatchStride { size_t pyr, cand, refined, kps, cube, sel, mins; };   // elements of the respective type (sel: selected keypoints per frame; mins: keep-all's start-key table)
 struct FrameOuts { mi355_keypoint* kp[SIFT_BATCH_MAX]; uint8_t* d8[SIFT_BATCH_MAX]; };
 
 // ---------- K3b: sub-pixel refinement ---------------------------------------------------------------------------
 struct Refined { int o, layer, r, c; float xi, xr, xc, contr, scl; unsigned start; };      // start: keep-all: (layer, row, column) of the extremum the fit started from, packed 2 + 14 + 14 bits
 
-struct PyrDev { OctaveDev oc[MAX_OCT]; unsigned* claimed[MAX_OCT]; unsigned* mins[MAX_OCT]; int n_oct; };      // mins: keep-all only (one word per claim bit)
+struct PyrDev { OctaveDev oc[MAX_OCT]; unsigned* mins[MAX_OCT]; int n_oct; };      // mins: keep-all only (one word per layer of every pixel)
 
 // DoG[lvl] = G[lvl + 1] - G[lvl]: 16-bit integers (cv::subtract into CV_16S; the samples are 0 .. 12240, nothing saturates), exact as float
 __device__ __forceinline__ float dogv(const OctaveDev& oc, size_t foff, int lvl, int r, int c) {
@@ -802,10 +804,11 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
     }
 }
 
+constexpr unsigned KEY_BINS = 65536;         // top-k: the frame's histogram of the refined records' 16-bit response keys (select_unique_kernel)
 __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned long long* cand_all, const unsigned* cand_counts, unsigned cand_cap, unsigned* cand_total,
                                                      float contrast_thr, float edge_thr, float sigma,
                                                      Refined* out, unsigned* out_count, unsigned out_cap, unsigned* out_resp, BatchStride bs,
-                                                     const float* cube_all, unsigned cube_cap) {
+                                                     const float* cube_all, unsigned cube_cap, unsigned* khist /* top-k: KEY_BINS words per frame; keep-all: null */) {
     const size_t fr = blockIdx.z, foff = fr * bs.pyr;             // frame of the batch
     cube_all += fr * bs.cube;
     cand_all += fr * bs.cand; cand_counts += fr * CCNT_STRIDE; cand_total += fr * CNT_STRIDE;
@@ -889,13 +892,9 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
             if (!alive || it >= MAX_INTERP) continue;
             if (!fit_accept(dv, L, R, C, f, contrast_thr, edge_thr, contr)) continue;
         }
-        // duplicates: several start points may converge to one location -> first claim wins (all claims carry identical values)
-        const size_t bit = ((size_t)R * oc.w + C) * 4 + (size_t)L;
-        const unsigned mask = 1u << (bit & 31);
-        if (!P.mins[o]) {
-            const unsigned old = atomicOr(&P.claimed[o][fr * bs.claimed + (bit >> 5)], mask);
-            if (old & mask) continue;
-        }
+        // duplicates: several start points may converge to one location, and each of them is stored (the records carry identical values
+        // but for `start`: the same fit on the same 27 integers).  Top-k mode drops them where the list is short -- unique_compact_lds(), among
+        // the few thousand points that are oriented at all; keep-all keeps the record of the smallest start key (below)
         // one atomic per wave, not per point: ~67 000 points of a 12 MP frame on ONE counter serialise in the L2 (0.65 ms per batch measured)
         const unsigned long long act = __ballot(1);
         const int leader = __builtin_ctzll(act), lane_id = (int)(threadIdx.x & 63);
@@ -909,25 +908,24 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
             rr.start = start;
             out[slot] = rr;
             out_resp[slot] = __float_as_uint(fabsf(contr));
+            if (khist) {
+                // the selection's histogram: one count per stored record.  The responses share their exponent byte, so the counts fall on a few
+                // hundred words per frame: equal keys inside the wave are merged with ballots first, as topk_kernel does with its digits
+                const unsigned key = (__float_as_uint(fabsf(contr)) >> 15) & 0xffffu;
+                unsigned long long peers = __ballot(1);
+#pragma unroll
+                for (int b = 0; b < 16; b++) {
+                    const unsigned long long bm = __ballot((key >> b) & 1u);
+                    peers &= ((key >> b) & 1u) ? bm : ~bm;
+                }
+                if ((peers & ((1ull << lane_id) - 1ull)) == 0ull) atomicAdd(&khist[fr * KEY_BINS + key], (unsigned)__popcll(peers));
+            }
             // keep-all (nfeatures <= 0): OpenCV's list is in generation order and of several start points that converge to one location the
             // FIRST in that order keeps it -- every start point is stored, the location remembers its smallest start key, keepall_live_kernel
             // keeps the record that holds it.  The key is entered only once the record has its slot: keepall_reset_kernel walks the STORED
             // records, so "entry below all ones <=> a stored record points at it" holds also for a frame that overflows the list
-            if (P.mins[o]) atomicMin(&P.mins[o][fr * bs.mins + bit], start);
-        } else if (!P.mins[o]) atomicAnd(&P.claimed[o][fr * bs.claimed + (bit >> 5)], ~mask);      // list full (the frame fails): keep "bit set <=> record stored"
-    }
-}
-
-// The claim bitmaps (4 bits per pixel of every octave: 32 MB per 12 MP frame) are zero between batches: instead of clearing
-// them wholesale per batch, the bits this batch set -- exactly one per stored refined record -- are taken back.
-__device__ __forceinline__ void unclaim_body(const PyrDev& P, const Refined* ref, const unsigned* ref_count, unsigned ref_cap, const BatchStride& bs, size_t fr, unsigned first, unsigned step) {
-    ref += fr * bs.refined; ref_count += fr * CNT_STRIDE;
-    unsigned n = *ref_count;
-    if (n > ref_cap) n = ref_cap;
-    for (unsigned i = first; i < n; i += step) {
-        const Refined rr = ref[i];
-        const size_t bit = ((size_t)rr.r * P.oc[rr.o].w + rr.c) * 4 + (size_t)rr.layer;
-        atomicAnd(&P.claimed[rr.o][fr * bs.claimed + (bit >> 5)], ~(1u << (bit & 31)));
+            if (P.mins[o]) atomicMin(&P.mins[o][fr * bs.mins + ((size_t)R * oc.w + C) * 4 + (size_t)L], start);
+        }
     }
 }
 
@@ -978,69 +976,55 @@ struct KpRec {
     unsigned start;                     // keep-all: the refined point's start key
 };
 
-// Only the nfeatures strongest keypoints survive, and the response is known before the orientation: a 65536-bin
-// histogram of the response bits (filled by refine_kernel) gives a threshold T such that at least `want` refined
-// points have response >= T.  Pass 0 orients those; if that turns out to yield fewer than nfeatures keypoints
-// (points without any histogram peak), top-k raises a flag and pass 1 orients the rest -- same final result as
-// orienting everything, ~40x less work in the common case.
-// The selection is one workgroup per frame walking ~67 000 responses three times (latency, not bandwidth: 32 workgroups on the whole
-// chip), taking the claim bits back is 2 M scattered atomics per batch (bandwidth): as two launches they cost their sum (112 + 88 us per
-// batch of 32), in ONE grid -- workgroup 0 of a frame selects, the others unclaim -- the longer of the two.
-constexpr int UNCLAIM_WGS = 32;                       // workgroups per frame beside the selecting one
-__global__ __launch_bounds__(1024) void select_unclaim_kernel(PyrDev P, const Refined* ref, BatchStride bs,
-                                                              const unsigned* resp /* |response| bits of the refined points */, const unsigned* ref_count, unsigned ref_cap,
-                                                              unsigned want, unsigned* ctrl /* [0]=T bits [1]=fallback flag [2]=points >= T */, size_t resp_stride,
-                                                              unsigned* list /* indices of the points >= T, what orientation pass 0 walks */) {
-    if (blockIdx.x > 0) { unclaim_body(P, ref, ref_count, ref_cap, bs, blockIdx.y, (blockIdx.x - 1) * 1024 + threadIdx.x, (gridDim.x - 1) * 1024); return; }
-    // two-pass radix select over the 16-bit key (8 exponent + 8 mantissa bits) of the responses;
-    // T = lower edge of the first key (from the top) at which the count of points with key >= it reaches `want`
-    resp += (size_t)blockIdx.y * resp_stride; ref_count += (size_t)blockIdx.y * CNT_STRIDE; ctrl += (size_t)blockIdx.y * CNT_STRIDE;
-    list += (size_t)blockIdx.y * resp_stride;
-    __shared__ unsigned s_h[16][256];               // a private histogram per wave: LDS conflicts stay inside one wave
-    __shared__ unsigned s_sel[2], s_cnt;
-    const int tid = threadIdx.x, wv = tid >> 6;
-    unsigned n = *ref_count;
-    if (n > ref_cap) n = ref_cap;
-    if (n <= want) {                                  // everything is oriented
-        if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; ctrl[2] = n; }
-        for (unsigned i = tid; i < n; i += 1024) list[i] = i;
-        return;
+// ---- one record per location ---------------------------------------------------------------------------------------
+// refine_kernel stores a record for every start point that was accepted, and start points that converged to one (octave, layer, row,
+// column) left identical records.  Each location is oriented once: the workgroup that lists the points of an orientation pass enters
+// their locations into an open-addressing hash table and lists a point only if its location was not there yet.  Which of several
+// identical records stays is immaterial (the total order is established by top-k).  The table: UNIQ_LDS slots of the workgroup's LDS
+// for up to UNIQ_LDS / 2 points (pass 0 of a usual frame: nfeatures + margin and the ties at the threshold); beyond that, and for
+// pass 1, the frame's candidate list, which is dead once refine_kernel has run -- cleared by the workgroup that uses it, as far as it
+// uses it (twice the points, rounded up to a power of two), so the common path clears nothing in memory.
+constexpr unsigned UNIQ_LDS = 8192;
+constexpr unsigned long long UNIQ_EMPTY = ~0ull;      // no location's key: the octave field of loc_key() is below MAX_OCT
+__device__ __forceinline__ unsigned long long loc_key(int o, int layer, int r, int c) {      // make_layout(): r, c < 2^20
+    return ((unsigned long long)(unsigned)o << 48) | ((unsigned long long)(unsigned)layer << 44) | ((unsigned long long)(unsigned)r << 22) | (unsigned long long)(unsigned)c;
+}
+// true: the key entered the table with this call.  At most mask + 1 probes; a full table is reported as the frame's overflow
+__device__ __forceinline__ bool uniq_insert(unsigned long long* tab, unsigned mask, unsigned long long key, int* overflow) {
+    unsigned h = (unsigned)((key * 0x9e3779b97f4a7c15ull) >> 32) & mask;
+    for (unsigned probe = 0; probe <= mask; probe++) {
+        const unsigned long long old = atomicCAS(&tab[h], UNIQ_EMPTY, key);
+        if (old == UNIQ_EMPTY) return true;
+        if (old == key) return false;
+        h = (h + 1u) & mask;
     }
+    *overflow = 1;
+    return false;
+}
+// a compaction step of whole waves: the lanes with `take` append `value` to dst[0 .. cap) behind *counter (a word of LDS); returns the slot
+__device__ __forceinline__ unsigned wave_append(bool take, unsigned value, unsigned* dst, unsigned cap, unsigned* counter) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long bm = __builtin_amdgcn_ballot_w64(take);
+    if (!bm) return 0xffffffffu;
+    const int first = __builtin_ctzll(bm);
+    unsigned base = 0;
+    if (lane == first) base = atomicAdd(counter, (unsigned)__builtin_popcountll(bm));      // (LDS: a returning global atomic per wave and trip was a round trip each)
+    base = __shfl(base, first) + (unsigned)__builtin_popcountll(bm & ((1ull << lane) - 1ull));
+    if (take && base < cap) dst[base] = value;
+    return take ? base : 0xffffffffu;
+}
+// One workgroup of 1024, the table in memory: list <- the indices i < n with lo <= resp[i] < hi, one per location; returns how many.
+// m: an upper bound of the points in that range; g_tab: g_cap slots, a power of two >= 1024.  The location is tested inside the walk (a
+// dependent load of the record in every trip that lists a point): for the rare lists that LDS does not hold, and for pass 1.
+__device__ __forceinline__ unsigned unique_compact_mem(const Refined* ref, const unsigned* resp, unsigned n, unsigned lo, unsigned hi, unsigned m,
+                                                       unsigned long long* g_tab, unsigned g_cap, unsigned* list, unsigned* s_cnt, int* overflow) {
+    const int tid = threadIdx.x;
+    unsigned size = 1024;
+    while (size < 2u * m && size < g_cap) size <<= 1;
+    for (unsigned i = tid; i < size; i += 1024) g_tab[i] = UNIQ_EMPTY;
+    if (tid == 0) *s_cnt = 0;
+    __syncthreads();
     const unsigned nr = (n + 1023u) & ~1023u;
-    unsigned above = 0, hi_sel = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int i = tid; i < 16 * 256; i += 1024) (&s_h[0][0])[i] = 0;
-        __syncthreads();
-        for (unsigned i0 = tid; i0 < nr; i0 += 8 * 1024) {
-            unsigned vv[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) { const unsigned i = i0 + 1024u * u; vv[u] = i < n ? resp[i] : 0u; }      // 8 loads in flight (one at a time: 65 round trips per pass)
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (i0 + 1024u * u >= n) continue;
-                const unsigned key = (vv[u] >> 15) & 0xffffu;
-                if (pass == 0) atomicAdd(&s_h[wv][key >> 8], 1u);
-                else if ((key >> 8) == hi_sel) atomicAdd(&s_h[wv][key & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (tid < 256) { unsigned t = 0; for (int w = 0; w < 16; w++) t += s_h[w][tid]; s_h[0][tid] = t; }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned cum = above; int b = 255;
-            for (; b >= 0; b--) { if (cum + s_h[0][b] >= want) break; cum += s_h[0][b]; }
-            if (b < 0) b = 0;
-            s_sel[0] = (unsigned)b; s_sel[1] = cum;
-        }
-        __syncthreads();
-        if (pass == 0) { hi_sel = s_sel[0]; above = s_sel[1]; }
-        else if (tid == 0) { ctrl[0] = ((hi_sel << 8) | s_sel[0]) << 15; ctrl[1] = 0; s_cnt = 0; }
-        __syncthreads();
-    }
-    // the points at or above the threshold, compacted (order free: the total order is established by top-k), so that the
-    // orientation pass hands exactly one point to each wave instead of letting 4096 waves look for ~2300 among ~94 000
-    const unsigned T = ((hi_sel << 8) | s_sel[0]) << 15;
-    const int lane = tid & 63;
     for (unsigned i0 = tid; i0 < nr; i0 += 8 * 1024) {
         unsigned vv[8];
 #pragma unroll
@@ -1048,19 +1032,110 @@ __global__ __launch_bounds__(1024) void select_unclaim_kernel(PyrDev P, const Re
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const unsigned i = i0 + 1024u * u;
-            const bool take = i < n && vv[u] >= T;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(take);
-            if (m) {
-                const int first = __builtin_ctzll(m);
-                unsigned base = 0;
-                if (lane == first) base = atomicAdd(&s_cnt, (unsigned)__builtin_popcountll(m));      // (LDS: a returning global atomic per wave and trip was a round trip each)
-                base = __shfl(base, first);
-                if (take) list[base + (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = i;
-            }
+            bool take = i < n && vv[u] >= lo && vv[u] < hi;
+            if (take) { const Refined& rr = ref[i]; take = uniq_insert(g_tab, size - 1u, loc_key(rr.o, rr.layer, rr.r, rr.c), overflow); }
+            wave_append(take, i, list, n, s_cnt);
         }
     }
     __syncthreads();
-    if (tid == 0) ctrl[2] = s_cnt;
+    return *s_cnt;
+}
+// The same with the table in LDS (s_tab: UNIQ_LDS slots), for at most UNIQ_LDS / 2 points with response >= lo.  The walk only compacts
+// their indices into s_idx (UNIQ_LDS / 2 words); the records are read from that short list -- a dependent load in ceil(m / 1024) = 3
+// trips, where testing inside the walk puts one into most of a wave's ~78 (one lane in 35 is listed).
+__device__ __forceinline__ unsigned unique_compact_lds(const Refined* ref, const unsigned* resp, unsigned n, unsigned lo,
+                                                       unsigned long long* s_tab, unsigned* s_idx, unsigned* list, unsigned* s_cnt /* two words of LDS */, int* overflow) {
+    const int tid = threadIdx.x;
+    for (unsigned i = tid; i < UNIQ_LDS; i += 1024) s_tab[i] = UNIQ_EMPTY;
+    if (tid == 0) { s_cnt[0] = 0; s_cnt[1] = 0; }
+    __syncthreads();
+    const unsigned nr = (n + 1023u) & ~1023u;
+    for (unsigned i0 = tid; i0 < nr; i0 += 8 * 1024) {
+        unsigned vv[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) { const unsigned i = i0 + 1024u * u; vv[u] = i < n ? resp[i] : 0u; }      // 8 loads in flight (one at a time: a round trip per trip)
+#pragma unroll
+        for (int u = 0; u < 8; u++) { const unsigned i = i0 + 1024u * u; wave_append(i < n && vv[u] >= lo, i, s_idx, UNIQ_LDS / 2, &s_cnt[1]); }
+    }
+    __syncthreads();
+    const unsigned ma = s_cnt[1] < UNIQ_LDS / 2 ? s_cnt[1] : UNIQ_LDS / 2;
+    for (unsigned j0 = 0; j0 < ma; j0 += 1024) {
+        const unsigned j = j0 + tid;
+        bool take = j < ma;
+        unsigned i = 0;
+        if (take) { i = s_idx[j]; const Refined& rr = ref[i]; take = uniq_insert(s_tab, UNIQ_LDS - 1u, loc_key(rr.o, rr.layer, rr.r, rr.c), overflow); }
+        wave_append(take, i, list, n, &s_cnt[0]);
+    }
+    __syncthreads();
+    return s_cnt[0];
+}
+
+// Only the nfeatures strongest keypoints survive, and the response is known before the orientation: a threshold T such that at
+// least `want` = nfeatures + margin refined records have response >= T.  Pass 0 orients those, each location once; if that turns out
+// to yield fewer than nfeatures keypoints (points without any histogram peak, several records of one location among the `want`),
+// top-k raises a flag and pass 1 orients the rest -- same final result as orienting everything, ~35x less work in the common case.
+// T comes from the frame's histogram of the 16-bit keys (resp_bits >> 15) & 0xffff -- the exponent byte and the top eight mantissa
+// bits -- which refine_kernel filled: T = lower edge of the first key, from the top, at which the count of records with a key at or
+// above it reaches `want` (what two 8-bit radix passes over the responses give: tests/test_sift_select_ref.py).  One workgroup per
+// frame reads the 65 536 words once, 64 consecutive keys per thread, puts them back to zero for the work area's next batch, and then
+// walks the ~80 000 responses ONCE to list the points at or above T (latency, not bandwidth: 32 workgroups on the whole chip).
+__global__ __launch_bounds__(1024) void select_unique_kernel(const Refined* ref, BatchStride bs,
+                                                             const unsigned* resp /* |response| bits of the refined points */, const unsigned* ref_count, unsigned ref_cap,
+                                                             unsigned want, unsigned* ctrl /* [0]=T bits [1]=fallback flag [2]=listed points >= T [3]=listed points < T (pass 1) */, size_t resp_stride,
+                                                             unsigned* list /* indices of the points >= T, one per location: what orientation pass 0 walks */,
+                                                             unsigned* khist /* KEY_BINS words per frame */, unsigned long long* g_tab, unsigned g_cap, int* overflow) {
+    ref += (size_t)blockIdx.y * bs.refined; g_tab += (size_t)blockIdx.y * bs.cand; overflow += (size_t)blockIdx.y * CNT_STRIDE; khist += (size_t)blockIdx.y * KEY_BINS;
+    resp += (size_t)blockIdx.y * resp_stride; ref_count += (size_t)blockIdx.y * CNT_STRIDE; ctrl += (size_t)blockIdx.y * CNT_STRIDE;
+    list += (size_t)blockIdx.y * resp_stride;
+    __shared__ unsigned s_idx[UNIQ_LDS / 2], s_wtot[16], s_sel[2], s_cnt[2];
+    __shared__ unsigned long long s_tab[UNIQ_LDS];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    unsigned n = *ref_count;
+    if (n > ref_cap) n = ref_cap;
+    // thread t holds the keys 64 t .. 64 t + 63 (16 loads of 16 bytes in flight), and leaves zeros behind
+    unsigned hv[64];
+    {
+        uint4* hp = reinterpret_cast<uint4*>(khist) + (size_t)tid * 16;
+#pragma unroll
+        for (int q = 0; q < 16; q++) { const uint4 v = hp[q]; hv[4 * q] = v.x; hv[4 * q + 1] = v.y; hv[4 * q + 2] = v.z; hv[4 * q + 3] = v.w; }
+#pragma unroll
+        for (int q = 0; q < 16; q++) hp[q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (n <= want) {                                  // everything is oriented, each location once
+        if (n <= UNIQ_LDS / 2) unique_compact_lds(ref, resp, n, 0u, s_tab, s_idx, list, s_cnt, overflow);
+        else unique_compact_mem(ref, resp, n, 0u, 0xffffffffu, n, g_tab, g_cap, list, s_cnt, overflow);
+        if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; ctrl[2] = s_cnt[0]; }
+        return;
+    }
+    // records with a key at or above the lowest of this thread's: its own, those of the higher lanes of its wave, those of the higher waves
+    unsigned own = 0;
+#pragma unroll
+    for (int b = 0; b < 64; b++) own += hv[b];
+    unsigned suf = own;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const unsigned v = __shfl_down(suf, off); if (lane + off < 64) suf += v; }
+    if (lane == 0) s_wtot[wv] = suf;
+    if (tid == 0) { s_sel[0] = 0; s_sel[1] = n; }
+    __syncthreads();
+    for (int w = wv + 1; w < 16; w++) suf += s_wtot[w];
+    // n > want records are in the histogram (one per stored record), so exactly one thread's keys take the count past `want`
+    if (suf >= want && suf - own < want) {
+        unsigned cum = suf - own, key = 0, m = 0;
+        bool found = false;
+#pragma unroll
+        for (int b = 63; b >= 0; b--) {
+            if (!found && cum + hv[b] >= want) { found = true; key = (unsigned)tid * 64u + (unsigned)b; m = cum + hv[b]; }
+            cum += hv[b];
+        }
+        s_sel[0] = key << 15; s_sel[1] = m;
+    }
+    __syncthreads();
+    // the points at or above the threshold, compacted (order free: the total order is established by top-k), so that the
+    // orientation pass hands exactly one point to each wave instead of letting 4096 waves look for ~2300 among ~80 000
+    const unsigned T = s_sel[0], m = s_sel[1] < n ? s_sel[1] : n;      // m: how many records lie at or above T
+    if (2u * m <= UNIQ_LDS) unique_compact_lds(ref, resp, n, T, s_tab, s_idx, list, s_cnt, overflow);
+    else unique_compact_mem(ref, resp, n, T, 0xffffffffu, m, g_tab, g_cap, list, s_cnt, overflow);
+    if (tid == 0) { ctrl[0] = T; ctrl[1] = 0; ctrl[2] = s_cnt[0]; }
 }
 
 // ---------- gradient of a level sample (K4 orientations, K5 descriptors) ----------------------------------------------------------
@@ -1104,17 +1179,16 @@ __global__ __launch_bounds__(256) void orient_kernel(PyrDev P, const Refined* re
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned n = *ref_count;
     if (n > ref_cap) n = ref_cap;
-    if (pass == 0) n = ctrl[2] < n ? ctrl[2] : n;               // pass 0 walks the compacted list of points >= T
+    // either pass walks a compacted list with one point per location: pass 0 the points >= T (select_unique_kernel), pass 1 those below
+    // (listed by the top-k workgroup that asked for the pass); keep-all: the live records (keepall_live_kernel)
+    { const unsigned nl = ctrl[pass == 0 ? 2 : 3]; n = nl < n ? nl : n; }
     if (tid == 0) s_on = 0;
     __syncthreads();
     for (unsigned base = blockIdx.x * 4; base < n; base += gridDim.x * 4) {        // uniform trip count per workgroup
         unsigned k = base + wv;
-        bool take = false;
-        if (k < n) {
-            if (pass == 0) { k = list[k]; take = true; }
-            else take = __float_as_uint(fabsf(ref[k].contr)) < Tbits;
-        }
+        const bool take = k < n;
         if (take) {
+            k = list[k];
             const Refined rr = ref[k];
             const OctaveDev& oc = P.oc[__builtin_amdgcn_readfirstlane(rr.o)];                     // one keypoint per wave: scalar level, width and height
             const lvl_t* img = oc.lv[__builtin_amdgcn_readfirstlane(rr.layer)] + foff;
@@ -1216,8 +1290,11 @@ __device__ __forceinline__ unsigned long long tie_key(const KpRec& k) {
 }
 
 __global__ __launch_bounds__(1024) void topk_kernel(const KpRec* kps, const unsigned* resp, const unsigned* kp_count, unsigned kp_cap, int nfeatures,
-                                                    FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, unsigned* ctrl, int pass, BatchStride bs) {
+                                                    FrameOuts outs, SelRec* out_sel, int* out_n, int* overflow, unsigned* ctrl, int pass, BatchStride bs,
+                                                    const Refined* ref, const unsigned* ref_resp, const unsigned* ref_count, unsigned ref_cap,      // pass 0: what a fallback pass lists from
+                                                    unsigned* list, unsigned long long* g_tab, unsigned g_cap, int* fell_back) {
     const size_t fr = blockIdx.x;                                 // one workgroup per frame of the batch
+    ref += fr * bs.refined; ref_resp += fr * bs.refined; ref_count += fr * CNT_STRIDE; list += fr * bs.refined; g_tab += fr * bs.cand; fell_back += fr * CNT_STRIDE;
     kps += fr * bs.kps; resp += fr * bs.kps; kp_count += fr * CNT_STRIDE; out_sel += fr * bs.sel; out_n += fr * CNT_STRIDE; overflow += fr * CNT_STRIDE; ctrl += fr * CNT_STRIDE;
     mi355_keypoint* out_kp = outs.kp[0];
 #pragma unroll
@@ -1335,11 +1412,22 @@ __global__ __launch_bounds__(1024) void topk_kernel(const KpRec* kps, const unsi
         SelRec sr; sr.ptx = k.ptx; sr.pty = k.pty; sr.scl = k.scl; sr.angle = k.angle; sr.o = k.o; sr.layer = k.layer;
         out_sel[i] = sr;
     }
+    // pass 0 oriented only the refined points with response >= T: fewer than nfeatures keypoints came out while
+    // weaker refined points exist -> orient those too (pass 1) and select again
+    const unsigned Tbits = ctrl[0];
+    const bool fall = pass == 0 && Tbits != 0 && keep < K;        // uniform over the workgroup
     if (tid == 0) {
         *out_n = (int)keep;
-        // pass 0 oriented only the refined points with response >= T: fewer than nfeatures keypoints came out while
-        // weaker refined points exist -> orient those too (pass 1) and select again
-        if (pass == 0 && ctrl[0] != 0 && keep < K) ctrl[1] = 1;
+        if (fall) { ctrl[1] = 1; *fell_back = 1; }
+    }
+    if (fall) {
+        // rare, and may be slow: the points below T, each location once (records of one location share their response, so all of them lie
+        // on one side of T), through a table in the frame's dead candidate list that this workgroup clears for itself
+        unsigned nr = *ref_count;
+        if (nr > ref_cap) nr = ref_cap;
+        __syncthreads();                                          // s_misc[2] (M) has been read by everyone
+        const unsigned cnt = unique_compact_mem(ref, ref_resp, nr, 0u, Tbits, nr, g_tab, g_cap, list, &s_misc[2], overflow);
+        if (tid == 0) ctrl[3] = cnt;
     }
 }
 
@@ -1635,8 +1723,8 @@ BlurFn blur_kernel(const Launch& L) {
 // the device buffers of a batch work area: every per-frame buffer nb times, a stride of the layout apart
 struct SiftBufs {
     DevBuf pyr;                              // all Gaussian levels
-    DevBuf claimed;                          // duplicate claim bitmaps
     DevBuf cand, refined, kps, kresp, sel, counters, rhist, ccnt;
+    DevBuf khist;                            // top-k: per frame, the histogram of the refined records' response keys; all zero between batches
     DevBuf olist;                            // per frame: indices of the refined points at or above the response threshold
     DevBuf mins;                             // keep-all (nfeatures <= 0): smallest start key per refined location, all ones between batches
     DevBuf ksort;                            // keep-all: per frame, its keys sorted tile by tile (keepall_sort_tiles_kernel)
@@ -1644,19 +1732,20 @@ struct SiftBufs {
     hipError_t reserve(const Layout& l, int nb, hipStream_t st) {
         const Strides& bs = l.bs;
         const struct { DevBuf* b; size_t bytes; } want[] = {
-            {&pyr, bs.pyr * sizeof(lvl_t)}, {&claimed, bs.claimed * sizeof(unsigned)}, {&cand, bs.cand * sizeof(unsigned long long)},
+            {&pyr, bs.pyr * sizeof(lvl_t)}, {&cand, bs.cand * sizeof(unsigned long long)},
             {&refined, bs.refined * sizeof(Refined)}, {&kps, bs.kps * sizeof(KpRec)}, {&kresp, bs.kps * sizeof(unsigned)}, {&sel, bs.sel * sizeof(SelRec)},
             {&mins, bs.mins * sizeof(unsigned)}, {&ksort, l.ksort_stride * sizeof(unsigned long long)}, {&counters, CNT_STRIDE * sizeof(unsigned)},
-            {&rhist, bs.refined * sizeof(unsigned)}, {&olist, bs.refined * sizeof(unsigned)}, {&ccnt, CCNT_STRIDE * sizeof(unsigned)}, {&cube, bs.cube * sizeof(float)}};
+            {&rhist, bs.refined * sizeof(unsigned)}, {&khist, l.keepall ? 0 : KEY_BINS * sizeof(unsigned)}, {&olist, bs.refined * sizeof(unsigned)}, {&ccnt, CCNT_STRIDE * sizeof(unsigned)}, {&cube, bs.cube * sizeof(float)}};
         for (const auto& w : want) {
-            if (!w.bytes) { w.b->release(); continue; }      // mins, ksort without keep-all
+            if (!w.bytes) { w.b->release(); continue; }      // mins, ksort without keep-all; khist with it
             if (const hipError_t e = w.b->reserve((size_t)nb * w.bytes); e != hipSuccess) return e;
         }
-        // the claim bits are kept zero between batches (select_unclaim_kernel takes them back), the start keys all ones (keepall_reset_kernel)
-        if (const hipError_t e = hipMemsetAsync(claimed.p, 0, (size_t)nb * bs.claimed * sizeof(unsigned), st); e != hipSuccess) return e;
-        return l.keepall ? hipMemsetAsync(mins.p, 0xff, (size_t)nb * bs.mins * sizeof(unsigned), st) : hipSuccess;
+        // keep-all's start keys are kept all ones between batches (keepall_reset_kernel).  The layout still numbers a claim bitmap per octave
+        // (Strides::claimed): nothing backs it, duplicates leave in unique_compact_lds() / _mem()
+        // top-k's key histograms are kept zero likewise: select_unique_kernel puts back what refine_kernel counted
+        return l.keepall ? hipMemsetAsync(mins.p, 0xff, (size_t)nb * bs.mins * sizeof(unsigned), st) : hipMemsetAsync(khist.p, 0, (size_t)nb * KEY_BINS * sizeof(unsigned), st);
     }
-    void release() { for (DevBuf* b : {&pyr, &claimed, &cand, &refined, &kps, &kresp, &sel, &counters, &rhist, &ccnt, &olist, &mins, &ksort, &cube}) b->release(); }
+    void release() { for (DevBuf* b : {&pyr, &khist, &cand, &refined, &kps, &kresp, &sel, &counters, &rhist, &ccnt, &olist, &mins, &ksort, &cube}) b->release(); }
 };
 
 }  // namespace
@@ -1783,18 +1872,17 @@ static int sift_prepare(mi355_ctx* ctx, SiftWork* s, const Layout& lay, int nb) 
     if (s->lay.same_key(lay) && s->nb == nb) return MI355_OK;
     MI_HIP(hipStreamSynchronize(s->stream));
     MI_HIP(s->b.reserve(lay, nb, s->stream));
-    // with the layout's offsets and strides (multiples of 64 elements) every level, bitmap and frame copy then starts on a 128-byte boundary
-    if ((((uintptr_t)s->b.pyr.p) | ((uintptr_t)s->b.claimed.p)) & 127) { ctx->set_error("sift: work area is not 128-byte aligned"); return MI355_ERR_FAILED; }
+    // with the layout's offsets and strides (multiples of 64 elements) every level and frame copy then starts on a 128-byte boundary
+    if (((uintptr_t)s->b.pyr.p) & 127) { ctx->set_error("sift: work area is not 128-byte aligned"); return MI355_ERR_FAILED; }
     memset(&s->P, 0, sizeof(s->P));
     for (int o = 0; o < lay.n_oct; o++) {
         const Octave& oc = lay.oc[o];
         s->P.oc[o].w = oc.w; s->P.oc[o].h = oc.h;
         for (int i = 0; i < N_LEVELS; i++) s->P.oc[o].lv[i] = s->b.pyr.as<lvl_t>() + oc.lv[i];
-        s->P.claimed[o] = s->b.claimed.as<unsigned>() + oc.claimed;
         s->P.mins[o] = lay.keepall ? s->b.mins.as<unsigned>() + oc.mins : nullptr;
     }
     s->P.n_oct = lay.n_oct;
-    s->bs = BatchStride{lay.bs.pyr, lay.bs.claimed, lay.bs.cand, lay.bs.refined, lay.bs.kps, lay.bs.cube, lay.bs.sel, lay.bs.mins};
+    s->bs = BatchStride{lay.bs.pyr, lay.bs.cand, lay.bs.refined, lay.bs.kps, lay.bs.cube, lay.bs.sel, lay.bs.mins};
     s->lay = lay; s->nb = nb;
     return MI355_OK;
 }
@@ -1860,7 +1948,7 @@ struct BatchRun {
     std::vector<SiftWork::Pend> pend;        // the batch's n frames
     std::vector<Features*> fs;
     int n;
-    unsigned* cnt;                           // per frame: [0] candidates [1] refined [2] keypoints [3] n_sel [4] overflow [8,9] ctrl
+    unsigned* cnt;                           // per frame: [0] candidates [1] refined [2] keypoints [3] n_sel [4] overflow [5] pass 1 ran [8..11] ctrl
     FrameOuts outs;
     int enqueue_pyramid();
     void enqueue_keypoints();
@@ -1921,20 +2009,26 @@ void BatchRun::enqueue_keypoints() {
     const Layout& lay = s->lay;
     const BatchStride bs = s->bs;
     const unsigned kmax = (unsigned)lay.kmax;
+    // top-k: the hash table of unique_compact_mem() where LDS does not hold it -- the frame's candidate list, dead after refine_kernel; the largest
+    // power of two of slots in it (make_layout: >= 4 px0 + 65536 candidates for at most px0 / 8 + 65536 refined points, so twice the points fit)
+    unsigned uniq_cap = 1024;
+    while ((size_t)uniq_cap * 2 <= bs.cand && uniq_cap < (1u << 31)) uniq_cap <<= 1;
     {
         ProfScope ps(ctx, "refine", 0.0, st);
         hipLaunchKernelGGL(refine_kernel, dim3(REFINE_GX, NREG, n), dim3(256), 0, st, s->P, d.cand.as<unsigned long long>(), d.ccnt.as<unsigned>(), lay.cand_cap, cnt + 0,
-                           ctx->p.contrast_threshold, ctx->p.edge_threshold, 1.6f, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, d.rhist.as<unsigned>(), bs, d.cube.as<float>(), lay.cube_cap);
+                           ctx->p.contrast_threshold, ctx->p.edge_threshold, 1.6f, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, d.rhist.as<unsigned>(), bs, d.cube.as<float>(), lay.cube_cap,
+                           lay.keepall ? nullptr : d.khist.as<unsigned>());
     }
     {
-        // keep-all: every refined point that holds its location's smallest start key is oriented; top-k: those above the response threshold of nfeatures + 256
+        // keep-all: every refined point that holds its location's smallest start key is oriented; top-k: one point per location above the response threshold of nfeatures + margin
         ProfScope ps(ctx, "kp_select", 0.0, st);
         if (lay.keepall) {
             hipLaunchKernelGGL(keepall_live_kernel, dim3(256, n), dim3(256), 0, st, s->P, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, cnt + 8, d.olist.as<unsigned>(), bs);
             hipLaunchKernelGGL(keepall_reset_kernel, dim3(256, n), dim3(256), 0, st, s->P, d.refined.as<Refined>(), cnt + 1, lay.ref_cap, bs);
         } else {
-            hipLaunchKernelGGL(select_unclaim_kernel, dim3(1 + UNCLAIM_WGS, n), dim3(1024), 0, st, s->P, d.refined.as<Refined>(), bs, d.rhist.as<unsigned>(), cnt + 1, lay.ref_cap,
-                               (unsigned)ctx->p.nfeatures + 256u, cnt + 8, bs.refined, d.olist.as<unsigned>());
+            hipLaunchKernelGGL(select_unique_kernel, dim3(1, n), dim3(1024), 0, st, d.refined.as<Refined>(), bs, d.rhist.as<unsigned>(), cnt + 1, lay.ref_cap,
+                               (unsigned)ctx->p.nfeatures + (unsigned)ctx->select_margin, cnt + 8, bs.refined, d.olist.as<unsigned>(), d.khist.as<unsigned>(), d.cand.as<unsigned long long>(), uniq_cap,
+                               reinterpret_cast<int*>(cnt + 4));
         }
     }
     // top-k: pass 1 (everything below the response threshold) exits at once unless top-k asked for it; keep-all: one pass, the keypoints leave in generation order
@@ -1952,7 +2046,9 @@ void BatchRun::enqueue_keypoints() {
                                d.ksort.as<const unsigned long long>(), lay.ksort_stride, outs, d.sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), bs);
         } else {
             hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), 0, st, d.kps.as<KpRec>(), d.kresp.as<unsigned>(), cnt + 2, lay.kp_cap, ctx->p.nfeatures,
-                               outs, d.sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), cnt + 8, pass, bs);
+                               outs, d.sel.as<SelRec>(), reinterpret_cast<int*>(cnt + 3), reinterpret_cast<int*>(cnt + 4), cnt + 8, pass, bs,
+                               d.refined.as<Refined>(), d.rhist.as<unsigned>(), cnt + 1, lay.ref_cap, d.olist.as<unsigned>(), d.cand.as<unsigned long long>(), uniq_cap,
+                               reinterpret_cast<int*>(cnt + 5));
         }
     }
     ProfScope ps(ctx, "describe", 0.0, st);

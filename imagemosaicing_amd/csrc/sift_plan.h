@@ -50,7 +50,7 @@ const PyramidTaps& pyramid_taps();
 // One frame's work area.  Offsets and strides in elements of the respective buffer; every pyramid level starts on a 128-byte boundary
 // (offsets and bs.pyr are multiples of 64 samples: what the streamed kernels' 8-byte loads and the frame stride ask for holds by layout).
 struct Strides { size_t pyr, claimed, cand, refined, kps, cube, sel, mins; };      // sel: selected keypoints per frame; mins: keep-all's start-key table
-struct Octave { int w, h; size_t lv[N_LEVELS], claimed, mins; };      // claimed: duplicate claim bitmap (4 bits per pixel); mins: keep-all, one word per claim bit
+struct Octave { int w, h; size_t lv[N_LEVELS], claimed, mins; };      // claimed: duplicate claim bitmap (4 bits per pixel; numbered, but sift.hip backs it with no memory: duplicates leave in its selection); mins: keep-all, one word per claim bit
 struct Layout {
     int w = 0, h = 0; bool keepall = false; int kmax = 0;      // the key: frame size, keep-all and its ceiling (option "keepall_max")
     int n_oct = 0;

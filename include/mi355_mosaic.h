@@ -124,7 +124,11 @@ int  mi355_synchronize(mi355_ctx* ctx);
  * error), returns MI355_ERR_ARG and leaves the ceiling as it was.  Every rank of a multi-GPU run sets the same value: a rank whose ceiling
  * is below a frame it receives fails its install (MI355_ERR_ARG, its features unchanged) while the other ranks return normally;
  * "big_subpairs_max" (debug, default 65536): sub-pairs of <= 2048 x 2048 per run of the matcher's large-pair path (the same
- * results at any value >= 1). */
+ * results at any value >= 1); "select_margin" (0 .. 65536, default 256): top-k SIFT orients the strongest nfeatures + margin refined
+ * points first and the rest only if fewer than nfeatures keypoints came of them -- the same keypoints at any value, a small margin makes
+ * that second pass likely (mi355_last_sift_counters: out8[5] = 1 where it ran); resolves pending extractions first;
+ * "nfeatures" (<= 2048; <= 0: keep-all): mi355_params.nfeatures for the extractions that follow, frames already extracted keep their
+ * features; resolves pending extractions first. */
 int  mi355_set_option(mi355_ctx* ctx, const char* name, int value);
 void mi355_free(void* p);                               /* frees host buffers returned by this library */
 

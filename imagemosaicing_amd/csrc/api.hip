@@ -451,6 +451,7 @@ extern "C" int mi355_set_option(mi355_ctx* ctx, const char* name, int value) {
     if (std::string(name).rfind("profile_every:", 0) == 0) { ctx->prof[std::string(name).substr(14)].every = value < 1 ? 1 : value; return MI355_OK; }
     if (std::string(name) == "xstream_min_w") { ctx->xstream_min_w = value < 256 ? 256 : value; return MI355_OK; }
     if (std::string(name) == "xstream_min_frames") { ctx->xstream_min_frames = value < 1 ? 1 : value; return MI355_OK; }
+    if (std::string(name) == "narrow_routes") { ctx->narrow_routes = value ? 1 : 0; return MI355_OK; }
     ctx->set_error(std::string("set_option: unknown option ") + name);
     return MI355_ERR_ARG;
 }

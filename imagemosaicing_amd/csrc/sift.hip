@@ -9,7 +9,7 @@
 //
 // Host side (end of this file): frames collect into batches (SiftWork); sift_plan.{h,cpp} decides a batch's layout and its pyramid and
 // extrema launches, sift_run_batch enqueues them, and every launch covers all frames of the batch.  Kernels:
-//   blur16_stream<R,BGR,DS,W>  separable Gaussian of one level (>= 512 columns): a wave walks down a strip of 256 columns, rows arrive
+//   blur16_stream<R,BGR,DS,W>  separable Gaussian of one level (>= 384 columns; sift_plan's blur_streams()): a wave walks down a strip of 256 columns, rows arrive
 //                         once from HBM (8 bytes per lane: four 16-bit samples), the row-filtered rows of the last 2R+1 steps live in
 //                         registers (the column pass needs its taps centre first, then symmetric pairs: a gather, not a scatter),
 //                         no workgroup barrier; BGR = true forms gray x 48 of the caller's frame on the fly (base level, no gray
@@ -1959,6 +1959,7 @@ struct BatchRun {
 int BatchRun::enqueue_pyramid() {
     const PyramidTaps& taps = pyramid_taps();
     Routes routes = {ctx->blur_stream, ctx->xstream_min_w, ctx->xstream_min_frames, true};
+    routes.narrow = ctx->narrow_routes;
     for (const SiftWork::Pend& p : pend) routes.base_frames_aligned = routes.base_frames_aligned && ((uintptr_t)p.d_bgr & 3) == 0 && (p.ws & 3) == 0 && p.ws >= 3 * s->lay.w;
     for (const Launch& L : pyramid_launches(s->lay, n, routes)) {
         const OctaveDev& oc = s->P.oc[L.octave];

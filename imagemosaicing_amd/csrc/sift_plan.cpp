@@ -76,12 +76,12 @@ int batch_frames(int w, int h, bool keepall, int requested, int slots, size_t to
     return keepall ? std::min(nb, 8) : nb;
 }
 
-// Does this level go through blur16_stream?  Rows of whole 8-byte groups, last strip wider than the largest radius, enough columns and
-// rows to fill the chip, a radius the kernel is instantiated for; the decimated copy needs R = 8 and an even height (the even rows of
+// Does this level go through blur16_stream?  Rows of whole 8-byte groups, last strip wider than the largest radius, enough columns (512;
+// narrow: STREAM_NARROW_MIN_W, see sift_plan.h) and rows to fill the chip, a radius the kernel is instantiated for; the decimated copy needs R = 8 and an even height (the even rows of
 // every segment are then the even rows of the image).
 static bool blur_streams(const Routes& r, const Octave& oc, bool base, int R, bool ds) {
     const bool has_r = base ? R == 6 : (R == 5 || R == 6 || R == 8 || R == 10 || R == 13);
-    return r.blur_stream && has_r && (oc.w & 3) == 0 && ((oc.w & 255) == 0 || (oc.w & 255) > MAX_R) && oc.w >= 512 && oc.h >= 64 &&
+    return r.blur_stream && has_r && (oc.w & 3) == 0 && ((oc.w & 255) == 0 || (oc.w & 255) > MAX_R) && oc.w >= (r.narrow ? STREAM_NARROW_MIN_W : 512) && oc.h >= 64 &&
            (!base || r.base_frames_aligned) && (!ds || (R == 8 && (oc.h & 1) == 0));
 }
 
@@ -105,7 +105,13 @@ static Launch blur_launch(const Routes& r, const Octave& oc, int n, int o, int l
     L.waves = L.radius <= STREAM_W4_MAX_R ? 4 : 3;
     L.nstrip = (oc.w + 255) / 256;
     const int units = L.nstrip * n, nseg = (WAVE_SLOTS * L.waves + units - 1) / units;
-    L.L = (std::max((oc.h + nseg - 1) / nseg, STREAM_MIN_L) + 1) & ~1;
+    const int rows = (oc.h + nseg - 1) / nseg;
+    L.L = (std::max(rows, STREAM_MIN_L) + 1) & ~1;
+    if (r.narrow && rows < STREAM_MIN_L) {
+        // STREAM_MIN_L leaves SIMDs with one wave or none: shorter segments, STREAM_NARROW_WAVES waves on every SIMD
+        const int nseg2 = (WAVE_SLOTS * STREAM_NARROW_WAVES + units - 1) / units;
+        L.L = std::min((std::max((oc.h + nseg2 - 1) / nseg2, STREAM_NARROW_MIN_L) + 1) & ~1, L.L);
+    }
     return m.streamed(BLUR_STREAM);
 }
 

@@ -36,7 +36,14 @@ constexpr int KA_TILE = 4096;               // keep-all: keys per sorted tile (k
 constexpr size_t CNT_STRIDE = 64, CCNT_STRIDE = (size_t)64 * 32, SEL_STRIDE = 2048;
 constexpr int WAVE_SLOTS = 1024;            // SIMDs of the chip: a streamed launch is sized to whole rounds of WAVE_SLOTS x waves per SIMD
 constexpr int STREAM_MIN_L = 64;            // blur16_stream: fewest rows per segment (2R halo rows are read again per segment)
-constexpr int STREAM_W4_MAX_R = 8;          // blur16_stream: 4 waves per SIMD up to this radius (the register ring of the row results, 4 x (2R + 2), fits 128 registers), 3 above (168)
+// Routes::narrow (option "narrow_routes"): blur16_stream from STREAM_NARROW_MIN_W columns on (two strips, the second at least half full:
+// three quarters of the lanes carry pixels; a single partial strip would also ask reflect101 for columns past 2 w - 2 in its right halo
+// lanes below 137 columns, and launches that narrow do not fill the chip); and where STREAM_MIN_L leaves a launch short of its `waves`
+// per SIMD, segments sized for STREAM_NARROW_WAVES waves on every SIMD, no shorter than STREAM_NARROW_MIN_L rows and no longer than
+// STREAM_MIN_L: a lone wave issues at half the SIMD's rate, so two waves of L + 2R + 1 steps finish before one of 64 + 2R + 1
+// (profiles/narrow_octaves_kernel_stats.txt has the sweep over L)
+constexpr int STREAM_NARROW_MIN_W = 384, STREAM_NARROW_WAVES = 2, STREAM_NARROW_MIN_L = 16;
+constexpr int STREAM_W4_MAX_R = 8;         // blur16_stream: 4 waves per SIMD up to this radius (the register ring of the row results, 4 x (2R + 2), fits 128 registers), 3 above (168)
 constexpr int REFINE_GX = 2;                // refine_kernel: workgroups per candidate region (32 x 64 regions x frames of mostly empty workgroups cost more to dispatch than the fits)
 
 // cv::getGaussianKernel(ksize, sigma, CV_32F) into k[0 .. 2r]; returns the radius r
@@ -67,8 +74,9 @@ Layout make_layout(int w, int h, bool keepall, int kmax, std::string& err);     
 int batch_frames(int w, int h, bool keepall, int requested, int slots, size_t total_mem);
 
 // The pyramid and extrema launches of a batch of n frames, in stream order.  blur_stream / xstream_min_w / xstream_min_frames: the
-// options of those names; base_frames_aligned: every caller frame's pointer and pitch a multiple of 4 and its pitch >= 3 w.
-struct Routes { int blur_stream, xstream_min_w, xstream_min_frames; bool base_frames_aligned; };
+// options of those names; base_frames_aligned: every caller frame's pointer and pitch a multiple of 4 and its pitch >= 3 w; narrow: the
+// option "narrow_routes" (0: the launches as they were before it existed).
+struct Routes { int blur_stream, xstream_min_w, xstream_min_frames; bool base_frames_aligned; int narrow = 0; };
 enum Kind { BLUR_STREAM, BLUR_TILE, DOWNSAMPLE, EXTREMA_STREAM, EXTREMA_TILE };
 struct Launch {
     Kind kind; int octave, level;      // level: the one written (DOWNSAMPLE: 0 of `octave`; extrema: -1)

@@ -104,12 +104,14 @@ int  mi355_synchronize(mi355_ctx* ctx);
  * level and every keypoint stage of all frames of the batch in one launch each; batches of very large frames are shortened
  * so that the work areas stay under 60 % of the device memory, keep-all batches (nfeatures <= 0) hold at most 8;
  * "sift_slots" = batch work areas that may be in flight at once, each on its own stream (1..4, default 3; a work area
- * holds the pyramids and candidate lists of one batch); "blur_stream" = 1 (default) runs pyramid levels of at least 512
- * columns and 64 rows whose width is a multiple of 4 (with a last 256-column strip that is full or wider than 16) through the barrier-free streaming Gaussian and lets big octaves
+ * holds the pyramids and candidate lists of one batch); "blur_stream" = 1 (default) runs pyramid levels of at least 384
+ * columns (512 with "narrow_routes" = 0) and 64 rows whose width is a multiple of 4 (with a last 256-column strip that is full or wider than 16) through the barrier-free streaming Gaussian and lets big octaves
  * take the streamed extrema kernel, 0 forces the tiled kernels everywhere (same bits either way);
- * "xstream_min_w" (>= 256, default 1500) / "xstream_min_frames" (>= 1, default 4): octaves at least that wide and 3/4 as
+ * "xstream_min_w" (>= 256, default 1000) / "xstream_min_frames" (>= 1, default 4): octaves at least that wide and 3/4 as
  * high, in batches of at least that many frames, take the streamed extrema kernel instead of the tiled one (same candidates
- * either way); "serial_heavy" = 1 (measurement only, default 0): the pyramid + extrema phase of a batch waits for the previous
+ * either way); "narrow_routes" = 1 (default): the streaming Gaussian also takes levels of 384 to 508 columns, and a launch of
+ * it that 64-row segments would leave with fewer waves than the chip has slots for runs in shorter segments (16 to 64 rows,
+ * about two waves per SIMD), 0: the routes as they were before the option (same bits either way); "serial_heavy" = 1 (measurement only, default 0): the pyramid + extrema phase of a batch waits for the previous
  * batch's, so that the chip-filling kernels of different batches never overlap and their event-bracketed durations are
  * exclusive (the whole job loses ~10 %); "sift_cascade" and "keepall_order" are accepted and ignored (the kernels they chose
  * between are gone); "profile_every:<class>" = n (measurement only, default 1): with

@@ -3,9 +3,11 @@
 // table with its upload and candidate lists, the "which table entries were used" pass (all warp.hip), and the host forms' staging and
 // download (frames.hip).  Device side: the 2 x 2 texel loads, "frame f gives canvas pixel (x, y) this sample" (also gain.hip), and the
 // lane / tile prologue and 12-byte row store of feather_tile_kernel, seamline_tile_kernel and median_tile_kernel.  mosaic_tile_kernel spells the same
-// map / bounds / hm::bilin / store steps inline, unchanged, so that its code object stays what it was (one more VGPR than its 72 would cost
-// it a wave per SIMD); tests/test_gpu_gain.py pins the helpers against the render (per-frame samples and cover equal the oracle's refined
-// canvas).
+// map / bounds / hm::bilin / store steps inline, so that its registers stay what they are: 63 VGPRs, 8 waves per SIMD, one register below the
+// 64 at which it loses a wave (72 and 7 waves while load_quad3 took its bytes out of a 64-bit integer).  Issuing the loads of a row's four
+// pixels together before the arithmetic was tried on top: 96 to 104 VGPRs, or 120 bytes of scratch at a forced 64, and a slower kernel
+// (CHANGELOG.md).  tests/test_gpu_gain.py pins the helpers against the render (per-frame samples and cover equal the oracle's refined
+// canvas); tests/test_gpu_sample_paths.py pins the two load forms and the byte positions in every kernel that samples.
 #pragma once
 #include "common.h"
 #include "hmath.h"
@@ -66,35 +68,47 @@ int mi_render_host_end(mi355_ctx* ctx, int lw, int lh, int lws, uint8_t** canvas
 
 namespace {
 
-template <int CH>
-__device__ __forceinline__ void load_pair(const uint8_t* s, float& a, float& b, float& c, float& a1, float& b1, float& c1);
+// Texel addresses come out of a table in memory (FrameDev::src), so to the compiler they are generic pointers: flat loads.  Frames are
+// device allocations; through the global address space the same loads are global_load_* (the idiom of match.hip, guided.hip, blend.hip).
+#define GLOBAL_PTR(T, p) ((const __attribute__((address_space(1))) T*)(p))
 
-// 6 bytes (two BGR pixels) with one dword + one ushort load; the device handles unaligned addresses.
+template <int CH>
+__device__ __forceinline__ void load_pair(const uint8_t* s, uint32_t& lo, uint32_t& hi);
+
+// 6 bytes (two BGR pixels) as the words {bytes 0..3, bytes 4..5}: one dword + one ushort load; the device handles unaligned addresses.
 template <>
-__device__ __forceinline__ void load_pair<3>(const uint8_t* s, float& b0, float& g0, float& r0, float& b1, float& g1, float& r1) {
-    uint32_t lo; uint16_t hi;
-    __builtin_memcpy(&lo, s, 4);
-    __builtin_memcpy(&hi, s + 4, 2);
+__device__ __forceinline__ void load_pair<3>(const uint8_t* s, uint32_t& lo, uint32_t& hi) {
+    uint16_t h;
+    __builtin_memcpy(&lo, GLOBAL_PTR(void, s), 4);
+    __builtin_memcpy(&h, GLOBAL_PTR(void, s + 4), 2);
+    hi = h;
+}
+
+// the same two words out of ONE 8-byte load: the 8 bytes stay one object and are split by value into their 32-bit halves.  (Copied into two
+// addressable words, the compiler split some of the loads into two dword loads; the load count is one of the canvas kernel's two bounds.)
+__device__ __forceinline__ void load_wide3(const uint8_t* s, uint32_t& lo, uint32_t& hi) {
+    uint64_t q;
+    __builtin_memcpy(&q, GLOBAL_PTR(void, s), 8);
+    lo = (uint32_t)q; hi = (uint32_t)(q >> 32);
+}
+
+// the six bytes of two BGR pixels in {lo, hi} as floats: each one v_cvt_f32_ubyteN of a 32-bit register.  (Taken with shifts of the uint64_t
+// itself, every byte was the generic u64 -> f32 conversion, six instructions: 73 of the 183 vector instructions of a sampled pixel.)  One
+// spelling after the wide / narrow choice, so that neither form's knowledge of the upper bits of hi turns a byte into a shift and a u32 convert.
+__device__ __forceinline__ void bytes6(uint32_t lo, uint32_t hi, float& b0, float& g0, float& r0, float& b1, float& g1, float& r1) {
     b0 = (float)(lo & 0xff); g0 = (float)((lo >> 8) & 0xff); r0 = (float)((lo >> 16) & 0xff);
-    b1 = (float)(lo >> 24);  g1 = (float)(hi & 0xff);        r1 = (float)(hi >> 8);
+    b1 = (float)(lo >> 24);  g1 = (float)(hi & 0xff);        r1 = (float)((hi >> 8) & 0xff);
 }
 
 // the two BGR pixel pairs of a 2 x 2 neighbourhood (rows s and s + ws): one 8-byte load per row where 8 bytes from s still lie inside the row's
 // pitch (6 are used), else the 4 + 2 byte form -- half the load instructions of a sample (the canvas kernel is bound by their number)
 __device__ __forceinline__ void load_quad3(const uint8_t* s, int ws, bool wide, float& b00, float& g00, float& r00, float& b01, float& g01, float& r01,
                                            float& b10, float& g10, float& r10, float& b11, float& g11, float& r11) {
-    if (wide) {
-        uint64_t q0, q1;
-        __builtin_memcpy(&q0, s, 8);
-        __builtin_memcpy(&q1, s + ws, 8);
-        b00 = (float)(q0 & 0xff); g00 = (float)((q0 >> 8) & 0xff); r00 = (float)((q0 >> 16) & 0xff);
-        b01 = (float)((q0 >> 24) & 0xff); g01 = (float)((q0 >> 32) & 0xff); r01 = (float)((q0 >> 40) & 0xff);
-        b10 = (float)(q1 & 0xff); g10 = (float)((q1 >> 8) & 0xff); r10 = (float)((q1 >> 16) & 0xff);
-        b11 = (float)((q1 >> 24) & 0xff); g11 = (float)((q1 >> 32) & 0xff); r11 = (float)((q1 >> 40) & 0xff);
-    } else {
-        load_pair<3>(s, b00, g00, r00, b01, g01, r01);
-        load_pair<3>(s + ws, b10, g10, r10, b11, g11, r11);
-    }
+    uint32_t lo0, hi0, lo1, hi1;
+    if (wide) { load_wide3(s, lo0, hi0); load_wide3(s + ws, lo1, hi1); }
+    else { load_pair<3>(s, lo0, hi0); load_pair<3>(s + ws, lo1, hi1); }
+    bytes6(lo0, hi0, b00, g00, r00, b01, g01, r01);
+    bytes6(lo1, hi1, b10, g10, r10, b11, g11, r11);
 }
 
 // canvas pixel (xD, yD) -> source coordinate of frame f (xf = xD - dGx, yf = yD - dGy)

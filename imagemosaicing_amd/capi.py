@@ -247,8 +247,79 @@ def default_params():
     return p
 
 
+# ---- marshalling: one implementation of each job the wrappers below share ------------------------------------------------
+def _params(cls, default_fn_name, fields):
+    """cls as the library's default_fn_name fills it, then the given fields (None: not given) assigned, each coerced by its declared ctypes
+    type.  A name that is not a field is a TypeError."""
+    p = cls()
+    getattr(load_library(), default_fn_name)(C.byref(p))
+    kinds = dict(cls._fields_)
+    for name, v in fields.items():
+        if name not in kinds:
+            raise TypeError("%s has no field %r" % (cls.__name__, name))
+        if v is not None:
+            setattr(p, name, float(v) if kinds[name] in (C.c_float, C.c_double) else int(v))
+    return p
+
+
+def _resolve(params, maker, kw):
+    """the params object a wrapper was given, or maker's from the keyword fields"""
+    return params if params is not None else maker(**kw)
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _ref(x):
+    """a structure by reference; None stays None (the library's NULL)"""
+    return C.byref(x) if x is not None else None
+
+
+def _arr(a, dtype):
+    """a as a contiguous array of dtype; None stays None (the library's NULL)"""
+    return None if a is None else np.ascontiguousarray(a, dtype)
+
+
+def _dptr(x):
+    """a device address (0 / None: NULL) as the pointer argument of a call"""
+    return C.c_void_p(int(x or 0) or None)
+
+
+def _dptrs(xs, at_least=0):
+    """device addresses (0 / None: NULL) as an array of pointers; None: no array"""
+    if xs is None:
+        return None
+    return (C.c_void_p * max(len(xs), at_least))(*[int(x or 0) or None for x in xs])
+
+
+def _dev_frames(d_imgs, w, h, ws, h9s=None):
+    """n, pointers, w, h, ws, h9s of a list of device frames as every call takes them.  d_imgs None: no pointers (a call that reads no
+    pixels), ws None: no pitches, h9s None: the call takes no transforms."""
+    w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
+    n = len(w)
+    return n, _dptrs(d_imgs, n), w, h, _arr(ws, np.int32), _arr(h9s, np.float32)
+
+
+def _host_frames(imgs):
+    """n, the images as contiguous uint8 arrays, their pointers, w, h, ws.  The pointer array holds addresses only: the caller keeps the
+    returned images referenced until its call has returned."""
+    imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+    ptrs = (C.c_void_p * len(imgs))(*[i.ctypes.data for i in imgs])
+    w = np.array([i.shape[1] for i in imgs], np.int32)
+    h = np.array([i.shape[0] for i in imgs], np.int32)
+    ws = np.array([i.strides[0] for i in imgs], np.int32)
+    return len(imgs), imgs, ptrs, w, h, ws
+
+
+def _geom(w, h, h9s):
+    """n, w, h, h9s of a survey given by its frames' sizes and transforms alone"""
+    return len(w), np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32), np.ascontiguousarray(h9s, np.float32)
+
+
+def _h9rows(h9s):
+    """the transforms as float32 rows of 9, whichever shape they come in"""
+    return np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
 
 
 def _img_geom(img):
@@ -258,18 +329,41 @@ def _img_geom(img):
     return img, w, h, img.strides[0], ch
 
 
-def _copy_out(ptr, nbytes, dtype):
-    """Copies nbytes from a library-owned host buffer into a fresh numpy array of dtype."""
-    if nbytes == 0:
-        return np.zeros(0, dtype)
-    raw = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(nbytes,)).copy()
-    return raw.view(dtype)
+def _owned(L, ptr, count, dtype, copy=True, free=True, want=True):
+    """count items of dtype from a library-owned host buffer: a private copy, or (copy=False) a view valid as long as the library says.
+    free: the buffer goes back through mi355_free afterwards; want=False: it only goes back, nothing is copied."""
+    out = None
+    if want:
+        if not ptr or count == 0:
+            out = np.zeros(0, dtype)
+        else:
+            raw = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,))
+            out = (raw.copy() if copy else raw).view(dtype)
+    if free:
+        L.mi355_free(ptr)
+    return out
 
 
-def _view_out(ptr, nbytes, dtype, copy):
-    """A library-owned host buffer as a numpy array of dtype: a private copy, or (copy=False) a view valid as long as the library says."""
-    raw = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(nbytes,))
-    return (raw.copy() if copy else raw).view(dtype)
+def _host_chk(rc, what=None, positive=True):
+    """the error path of the wrappers that take no ctx: raises Mi355Error with the fixed text `what`, or (None) the library's last error.
+    positive: rc > 0 is a failure too."""
+    if rc < 0 or (positive and rc != 0):
+        raise Mi355Error(rc, what if what is not None else (load_library().mi355_last_error(None) or b"").decode())
+    return rc
+
+
+def _load(fn_name, what, dtype, *args):
+    """the load_* shape: fn(args..., &array, &count) hands back a malloc'd array of dtype, which is copied and freed"""
+    L = load_library()
+    ptr, n = C.c_void_p(), C.c_int(0)
+    _host_chk(getattr(L, fn_name)(*args, C.byref(ptr), C.byref(n)), what)
+    return _owned(L, ptr, n.value, dtype)
+
+
+def _write(fn_name, what, path, a, *dims):
+    """the write_* shape: fn(path, array, its dims...)"""
+    L = load_library()
+    _host_chk(getattr(L, fn_name)(path.encode(), _p(a), *dims), what)
 
 
 class Context:
@@ -278,10 +372,8 @@ class Context:
     def __init__(self, device=0, params=None):
         self.L = load_library()
         self._h = C.c_void_p()
-        rc = self.L.mi355_create(C.byref(self._h), C.byref(params) if params is not None else None, int(device))
-        if rc != 0:
-            raise Mi355Error(rc, (self.L.mi355_last_error(None) or b"").decode())
-        self.params = params if params is not None else default_params()
+        _host_chk(self.L.mi355_create(C.byref(self._h), _ref(params), int(device)))
+        self.params = _resolve(params, default_params, {})
         self.device = int(device)
 
     def close(self):
@@ -299,6 +391,68 @@ class Context:
         if rc < 0:
             raise Mi355Error(rc, (self.L.mi355_last_error(self._h) or b"").decode())
         return rc
+
+    # ---- the forms every render comes in.  `lead` holds the family's own arguments, which stand between the transforms and the outputs ----
+    def _render_host(self, fn, imgs, h9s, lead=(), want_pixels=True, extra=None):
+        """host images in, the library's canvas out: fn(ctx, frames, n, h9s, *lead, &canvas, &cw, &ch, &cws[, &map]).  extra: None where fn has no
+        map output, else (wanted, dtype) of the [ch, cw] map behind the canvas.  Returns (canvas rows x cws or None, cw, ch, cws[, map])."""
+        n, imgs, ptrs, w, h, ws = _host_frames(imgs)
+        h9s = _arr(h9s, np.float32)
+        canvas, more = C.c_void_p(), C.c_void_p()
+        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
+        tail = () if extra is None else (C.byref(more) if extra[0] else None,)
+        self._chk(fn(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), *lead, C.byref(canvas), C.byref(cw), C.byref(ch), C.byref(cws), *tail))
+        buf = _owned(self.L, canvas, ch.value * cws.value, np.uint8, want=want_pixels)
+        out = (buf.reshape(ch.value, cws.value) if want_pixels else None, cw.value, ch.value, cws.value)
+        if extra is None or not extra[0]:
+            return out
+        return out + (_owned(self.L, more, ch.value * cw.value, extra[1]).reshape(ch.value, cw.value),)
+
+    def _render_dev(self, fn, d_imgs, w, h, ws, h9s, lead, d_canvas, cw, ch, cws, maps=(), stripe=None):
+        """device frames into a device canvas: fn(ctx, frames, n, h9s, *lead, canvas, cw, ch, cws, *maps[, row0, rows]).  maps: the device
+        addresses of the render's per-pixel maps; stripe: (row0, rows), rows < 0 = the whole canvas, None where fn takes no stripe."""
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
+        rows = () if stripe is None else (int(stripe[0]), int(stripe[1] if stripe[1] >= 0 else ch))
+        self._chk(fn(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), *lead, _dptr(d_canvas), int(cw), int(ch), int(cws),
+                     *[_dptr(m) for m in maps], *rows))
+
+    def _render_into(self, fn, imgs, img_ids, h9s, lead, layout, out, pitch, geom):
+        """kept frames and / or host images into caller memory: fn(ctx, sources, n, h9s, *lead, out, pitch, cw, ch), the canvas's (cw, ch)
+        being the first two of layout(w, h, h9s).  Returns (out, cw, ch)."""
+        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
+        h9s = _arr(h9s, np.float32)
+        cw, ch = layout(w, h, h9s)[:2]
+        out, pitch = self._out_array(out, pitch, cw, ch)
+        self._chk(fn(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), *lead, C.c_void_p(out.ctypes.data), int(pitch),
+                     int(cw), int(ch)))
+        return out, cw, ch
+
+    def _render_cover(self, fn, w, h, h9s, lead, row0, rows, first=()):
+        """which frames a stripe of a render reads, from the geometry alone: fn(ctx, *first, w, h, n, h9s, *lead, row0, rows, need)"""
+        n, w, h, h9s = _geom(w, h, h9s)
+        need = np.zeros(n, np.uint8)
+        self._chk(fn(self._h, *first, _p(w), _p(h), n, _p(h9s), *lead, int(row0), int(rows), _p(need)))
+        return need
+
+    def _chips(self, fn, *args):
+        """fn(ctx, *args, &n, &chips, &imgs, &masks, &cw, &ch): the library-owned chips of a warp stage as ChipsAndMasks' dictionary"""
+        nch = C.c_int(0)
+        chips = C.c_void_p()
+        cimgs = C.POINTER(C.c_void_p)()
+        masks = C.POINTER(C.c_void_p)()
+        cw, ch = C.c_int(), C.c_int()
+        self._chk(fn(self._h, *args, C.byref(nch), C.byref(chips), C.byref(cimgs), C.byref(masks), C.byref(cw), C.byref(ch)))
+        nv = nch.value
+        info = _owned(self.L, chips, nv, CHIPINFO)
+        out_c, out_m = [], []
+        for v in range(nv):
+            cwv, chv = int(info[v]["w"]), int(info[v]["h"])
+            cws_, mws = (cwv * 3 + 3) & ~3, (cwv + 3) & ~3
+            out_c.append(_owned(self.L, C.c_void_p(cimgs[v]), chv * cws_, np.uint8).reshape(chv, cws_))
+            out_m.append(_owned(self.L, C.c_void_p(masks[v]), chv * mws, np.uint8).reshape(chv, mws))
+        self.L.mi355_free(C.cast(cimgs, C.c_void_p))
+        self.L.mi355_free(C.cast(masks, C.c_void_p))
+        return dict(cw=cw.value, ch=ch.value, chips=info, chip_imgs=out_c, masks=out_m)
 
     # ---- plumbing ----------------------------------------------------------------------------
     def set_stream(self, hip_stream):
@@ -455,31 +609,16 @@ class Context:
         dst = C.c_void_p()
         dw, dh, dws = C.c_int(), C.c_int(), C.c_int()
         self._chk(self.L.mi355_warp_image(self._h, _p(img), w, h, ws, ch, _p(h9), C.byref(dst), C.byref(dw), C.byref(dh), C.byref(dws)))
-        buf = _copy_out(dst, dh.value * dws.value, np.uint8).reshape(dh.value, dws.value)
-        self.L.mi355_free(dst)
+        buf = _owned(self.L, dst, dh.value * dws.value, np.uint8).reshape(dh.value, dws.value)
         return buf, dw.value, dh.value, dws.value
 
     def MosaicImagesRefined(self, imgs, h9s, want_pixels=True):
         """CMosaicByPose::MosaicImagesRefined (float), MosaicWithoutPos.cpp:2194-2352.  want_pixels=False: the canvas the library returns is
         released without the numpy copy (bench.py times the C call, not this binding)."""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        canvas = C.c_void_p()
-        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_refined(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(canvas), C.byref(cw), C.byref(ch), C.byref(cws)))
-        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value) if want_pixels else None
-        self.L.mi355_free(canvas)
-        return buf, cw.value, ch.value, cws.value
+        return self._render_host(self.L.mi355_mosaic_refined, imgs, h9s, want_pixels=want_pixels)
 
     def MosaicImagesRefinedDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1):
-        n = len(d_imgs)
-        ptrs = (C.c_void_p * n)(*[int(p) for p in d_imgs])
-        w = np.ascontiguousarray(w, np.int32)
-        h = np.ascontiguousarray(h, np.int32)
-        ws = np.ascontiguousarray(ws, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        self._chk(self.L.mi355_mosaic_refined_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.c_void_p(int(d_canvas)),
-                                                  int(cw), int(ch), int(cws), int(row0), int(rows if rows >= 0 else ch)))
+        self._render_dev(self.L.mi355_mosaic_refined_dev, d_imgs, w, h, ws, h9s, (), d_canvas, cw, ch, cws, stripe=(row0, rows))
 
     # ---- SURF variant (GetMatchedPairsOneToAllSurf, MosaicWithoutPos.cpp:5300-5533) ---------------------
     def SurfExtract(self, img_id, bgr, hessian=50.0, max_kp=4096):
@@ -574,9 +713,7 @@ class Context:
         ptr, n = C.c_void_p(), C.c_int(0)
         flags = (1 if accepted_only else 0) | (0 if wait else 2)
         self._chk(self.L.mi355_allgather_results(self._h, C.c_void_p(int(d_local)), int(n_local), flags, int(root), C.byref(ptr), C.byref(n)))
-        if not ptr.value or n.value == 0:
-            return np.zeros(0, PAIR_RESULT)
-        return _view_out(ptr, n.value * PAIR_RESULT.itemsize, PAIR_RESULT, copy)
+        return _owned(self.L, ptr, n.value, PAIR_RESULT, copy=copy, free=False)
 
     def PairMomentsDev(self, d_results, n, d_out):
         """one PAIR_MOMENTS record per pair record, device to device (ctx stream)"""
@@ -595,7 +732,7 @@ class Context:
         a = _projective_args(w, h, start, fixed, label)
         out, rep = np.zeros(len(a[2]), IMAGE_TRANSFORM), ProjectiveReport()
         self._chk(self.L.mi355_global_projective_refine_dev(self._h, C.c_void_p(int(d_results) or None), int(n_pairs), len(a[2]), _p(a[0]), _p(a[1]), _p(a[3]), _p(a[4]), _p(a[2]),
-                                                            C.byref(params) if params is not None else None, _p(out), C.byref(rep)))
+                                                            _ref(params), _p(out), C.byref(rep)))
         return out, rep.as_dict()
 
     # ---- lens self-calibration (mi355_pair_calib_blocks_dev, mi355_calibrate_lens_dev; csrc/calib.hip) --------------------------
@@ -604,15 +741,15 @@ class Context:
         one row per record, host), device to device (ctx stream)"""
         h8 = None if h8 is None else np.ascontiguousarray(h8, np.float64).reshape(-1, 8)
         assert h8 is None or len(h8) >= int(n)
-        self._chk(self.L.mi355_pair_calib_blocks_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), _p(h8), C.byref(cam) if cam is not None else None,
-                                                     int(min_ties), C.c_void_p(int(d_out or 0) or None)))
+        self._chk(self.L.mi355_pair_calib_blocks_dev(self._h, _dptr(d_results), int(n), _p(h8), _ref(cam),
+                                                     int(min_ties), _dptr(d_out)))
 
     def CalibrateLensDev(self, d_results, n_pairs, start, params=None, **kw):
         """mi355_calibrate_lens_dev: the Brown-Conrady coefficients of the camera `start` (Camera; its intrinsics are held fixed) from device
         pair records of the original frames; returns (Camera, report dict)"""
-        p = params if params is not None else calib_params(**kw)
+        p = _resolve(params, calib_params, kw)
         out, rep = Camera(), CalibReport()
-        self._chk(self.L.mi355_calibrate_lens_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), C.byref(start) if start is not None else None, C.byref(p),
+        self._chk(self.L.mi355_calibrate_lens_dev(self._h, _dptr(d_results), int(n_pairs), _ref(start), C.byref(p),
                                                   C.byref(out), C.byref(rep)))
         return out, rep.as_dict()
 
@@ -622,11 +759,11 @@ class Context:
         correlation peak of the patch around its partner in image j.  d_imgs: device frames (0 / None: not held), w, h, ws their geometry;
         d_status (uint8 [n, 400]), d_ncc2 (float32 [n, 400]), d_report (TIE_REPORT [n]): device buffers, 0 = not wanted.  params: TieParams
         (tie_params()) or its keyword fields (radius, search, drop_mask, min_ncc).  Enqueued on the ctx stream."""
-        n_img, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
-        p = params if params is not None else tie_params(**kw)
-        self._chk(self.L.mi355_refine_ties_dev(self._h, C.c_void_p(int(d_in or 0) or None), int(n), ptrs, _p(w), _p(h), _p(ws), n_img, C.byref(p),
-                                               C.c_void_p(int(d_out or 0) or None), C.c_void_p(int(d_status or 0) or None),
-                                               C.c_void_p(int(d_ncc2 or 0) or None), C.c_void_p(int(d_report or 0) or None)))
+        n_img, ptrs, w, h, ws, _ = _dev_frames(d_imgs, w, h, ws)
+        p = _resolve(params, tie_params, kw)
+        self._chk(self.L.mi355_refine_ties_dev(self._h, _dptr(d_in), int(n), ptrs, _p(w), _p(h), _p(ws), n_img, C.byref(p),
+                                               _dptr(d_out), _dptr(d_status),
+                                               _dptr(d_ncc2), _dptr(d_report)))
 
     def RefineTies(self, results, imgs, img_ids=None, geom=None, params=None, **kw):
         """mi355_refine_ties: host PAIR_RESULT records in; image k from the kept frame of img_ids[k] (>= 0) or from the host image imgs[k]
@@ -634,7 +771,7 @@ class Context:
         res = np.ascontiguousarray(results, PAIR_RESULT)
         n = len(res)
         ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        p = params if params is not None else tie_params(**kw)
+        p = _resolve(params, tie_params, kw)
         out = np.zeros(n, PAIR_RESULT)
         status, ncc2, report = np.zeros((n, 400), np.uint8), np.zeros((n, 400), np.float32), np.zeros(n, TIE_REPORT)
         self._chk(self.L.mi355_refine_ties(self._h, _p(res), n, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), C.byref(p), _p(out), _p(status), _p(ncc2),
@@ -646,33 +783,26 @@ class Context:
         library, see AllGatherResults for `copy`)"""
         ptr, n = C.c_void_p(), C.c_int(0)
         self._chk(self.L.mi355_allgather_moments(self._h, C.c_void_p(int(d_local)), int(n_local), C.byref(ptr), C.byref(n)))
-        if not ptr.value or n.value == 0:
-            return np.zeros(0, PAIR_MOMENTS)
-        return _view_out(ptr, n.value * PAIR_MOMENTS.itemsize, PAIR_MOMENTS, copy)
+        return _owned(self.L, ptr, n.value, PAIR_MOMENTS, copy=copy, free=False)
 
     def StripeCover(self, w, h, h9s, row0, rows, blended=False, keep=None, band=5, exact=False):
         """mi355_mosaic_stripe_cover: need[k] = 1 when rendering canvas rows [row0, row0 + rows) reads frame k.  exact (refined canvas only): the
         frames that give at least one pixel its sample (a device pass), instead of every frame whose box meets the rows"""
-        n = len(w)
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        need = np.zeros(n, np.uint8)
+        keep_a = _arr(keep, np.uint8)
         mode = 1 if blended else (2 if exact else 0)
-        self._chk(self.L.mi355_mosaic_stripe_cover(self._h, mode, _p(w), _p(h), n, _p(h9s), _p(keep_a), int(band), int(row0), int(rows), _p(need)))
-        return need
+        return self._render_cover(self.L.mi355_mosaic_stripe_cover, w, h, h9s, (_p(keep_a), int(band)), row0, rows, first=(mode,))
 
     def ExchangeFrames(self, d_frames, h, ws, need, owner=None, own_through_rccl=False):
         """mi355_exchange_frames.  d_frames: per frame this rank's device pointer (0 / None where it does not hold the frame); need: [G, n]
         uint8 table (the same on every rank), or [n]: this rank's own row (the rows are all-gathered inside the call).  Returns (pointers for
         the stripe calls -- 0 where the rank's stripe does not read the frame --, bytes received, bytes sent)."""
         n = len(d_frames)
-        ptrs = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in d_frames])
+        ptrs = _dptrs(d_frames, 1)
         h = np.ascontiguousarray(h, np.int32); ws = np.ascontiguousarray(ws, np.int32)
         need = np.ascontiguousarray(need, np.uint8)
         local = need.ndim == 1
         assert need.shape[-1] == n
-        own_a = None if owner is None else np.ascontiguousarray(owner, np.int32)
+        own_a = _arr(owner, np.int32)
         out = (C.c_void_p * max(n, 1))()
         br, bs = C.c_uint64(0), C.c_uint64(0)
         flags = (1 if own_through_rccl else 0) | (2 if local else 0)
@@ -686,35 +816,9 @@ class Context:
 
     def ChipsAndMasks(self, imgs, h9s, keep=None, find_masks=True):
         """LaplacianPyramidBlending warp stage + FindMasksByDistMap (MosaicImage.cpp:2233-2460, 1761-1881)."""
-        n = len(imgs)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        nch = C.c_int(0)
-        chips = C.c_void_p()
-        cimgs = C.POINTER(C.c_void_p)()
-        masks = C.POINTER(C.c_void_p)()
-        cw, ch = C.c_int(), C.c_int()
-        self._chk(self.L.mi355_chips_and_masks(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(bool(find_masks)),
-                                               C.byref(nch), C.byref(chips), C.byref(cimgs), C.byref(masks), C.byref(cw), C.byref(ch)))
-        nv = nch.value
-        info = _copy_out(chips, nv * CHIPINFO.itemsize, CHIPINFO)
-        out_c, out_m = [], []
-        for v in range(nv):
-            cwv, chv = int(info[v]["w"]), int(info[v]["h"])
-            cws_, mws = (cwv * 3 + 3) & ~3, (cwv + 3) & ~3
-            out_c.append(_copy_out(cimgs[v], chv * cws_, np.uint8).reshape(chv, cws_))
-            out_m.append(_copy_out(masks[v], chv * mws, np.uint8).reshape(chv, mws))
-            self.L.mi355_free(C.c_void_p(cimgs[v]))
-            self.L.mi355_free(C.c_void_p(masks[v]))
-        self.L.mi355_free(chips)
-        self.L.mi355_free(C.cast(cimgs, C.c_void_p))
-        self.L.mi355_free(C.cast(masks, C.c_void_p))
-        return dict(cw=cw.value, ch=ch.value, chips=info, chip_imgs=out_c, masks=out_m)
+        n, imgs, ptrs, w, h, ws = _host_frames(imgs)
+        h9s, keep_a = _arr(h9s, np.float32), _arr(keep, np.uint8)
+        return self._chips(self.L.mi355_chips_and_masks, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(bool(find_masks)))
 
     def MultiBandBlend(self, chips, chip_imgs, masks, cw, ch, band=5):
         """detail::MultiBandBlender(false, band) over the chips of ChipsAndMasks (MosaicImage.cpp:2296-2299, 2451-2486)."""
@@ -727,27 +831,13 @@ class Context:
         out = C.c_void_p()
         ow, oh, ows = C.c_int(), C.c_int(), C.c_int()
         self._chk(self.L.mi355_multiband_blend(self._h, cp, mp, _p(info), n, int(cw), int(ch), int(band), C.byref(out), C.byref(ow), C.byref(oh), C.byref(ows)))
-        buf = _copy_out(out, ows.value * oh.value, np.uint8).reshape(oh.value, ows.value)
-        self.L.mi355_free(out)
+        buf = _owned(self.L, out, ows.value * oh.value, np.uint8).reshape(oh.value, ows.value)
         return buf, ow.value, oh.value, ows.value
 
     def MosaicBlended(self, imgs, h9s, keep=None, band=5):
         """LaplacianPyramidBlending in one call (MosaicImage.cpp:2205-2510): chips, masks and blend stay on the device."""
-        n = len(imgs)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        out = C.c_void_p()
-        ow, oh, ows = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_blended(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(band), C.byref(out), C.byref(ow), C.byref(oh), C.byref(ows)))
-        buf = _copy_out(out, ows.value * oh.value, np.uint8).reshape(oh.value, ows.value)
-        self.L.mi355_free(out)
-        return buf, ow.value, oh.value, ows.value
-
+        keep_a = _arr(keep, np.uint8)
+        return self._render_host(self.L.mi355_mosaic_blended, imgs, h9s, (_p(keep_a), int(band)))
 
     def MosaicBlendedDev(self, d_ptrs, w, h, ws, h9s, keep=None, band=5, row0=0, rows=-1):
         """LaplacianPyramidBlending with the survey resident in HBM: device frames in, device canvas out (a torch uint8 tensor
@@ -756,11 +846,8 @@ class Context:
         wrapper synchronises torch's stream before the call (a recycled block may still be in use by pending torch work) and the ctx's
         stream after it: the tensor it returns is complete and safe to use on any stream."""
         import torch
-        n = len(d_ptrs)
-        ptrs = (C.c_void_p * n)(*[int(p) for p in d_ptrs])
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32); ws = np.ascontiguousarray(ws, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_ptrs, w, h, ws, h9s)
+        keep_a = _arr(keep, np.uint8)
         cw, ch, cws = blend_layout(w, h, h9s, keep_a)
         if rows >= 0:
             # one stripe of the canvas (a rank's share): the tensor holds the rows row0 .. row0 + rows - 1; cw, ch, cws stay the whole canvas's
@@ -779,22 +866,6 @@ class Context:
 
     # ---- exposure gain compensation (mi355_gain_*, csrc/gain.hip) ----------------------------------------------------------
     @staticmethod
-    def _frame_args(d_imgs, w, h, ws):
-        n = len(d_imgs)
-        ptrs = (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
-        return n, ptrs, np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32), np.ascontiguousarray(ws, np.int32)
-
-    @staticmethod
-    def _host_args(imgs):
-        """n, the images as contiguous uint8 arrays (alive over the call), their pointers, w, h, ws"""
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        ptrs = (C.c_void_p * len(imgs))(*[i.ctypes.data for i in imgs])
-        w = np.array([i.shape[1] for i in imgs], np.int32)
-        h = np.array([i.shape[0] for i in imgs], np.int32)
-        ws = np.array([i.strides[0] for i in imgs], np.int32)
-        return len(imgs), imgs, ptrs, w, h, ws
-
-    @staticmethod
     def _pairs_ab(pairs):
         ab = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
         return ab, len(ab)
@@ -802,9 +873,8 @@ class Context:
     def GainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8):
         """overlap statistics of the listed pairs (positions in the frame list) on the lattice of `step`: (GAIN_PAIR_STATS [n_pairs],
         frame cover N_k int64 [n])"""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
         st = np.zeros(npairs, GAIN_PAIR_STATS)
         cover = np.zeros(n, np.int64)
         self._chk(self.L.mi355_gain_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), _p(st), _p(cover)))
@@ -812,18 +882,17 @@ class Context:
 
     def ApplyGainsDev(self, d_src, d_dst, w, h, ws, gains):
         """d_dst[k] = LUT_k(d_src[k]) (d_dst[k] may be d_src[k]); gains [n, 3] float32.  Complete on return."""
-        n, sp, w, h, ws = self._frame_args(d_src, w, h, ws)
-        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        n, sp, w, h, ws, _ = _dev_frames(d_src, w, h, ws)
+        dp = _dptrs(d_dst, n)
         g = np.ascontiguousarray(gains, np.float32).reshape(n, 3)
         self._chk(self.L.mi355_apply_gains_dev(self._h, sp, dp, _p(w), _p(h), _p(ws), n, _p(g)))
 
     def GainCompensateDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
         """statistics, solve and in-place apply on the device frames; returns the gains [n, 3] float32.  params: GainParams (gain_params())
         or keyword fields of it."""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else gain_params(**kw)
+        p = _resolve(params, gain_params, kw)
         g = np.zeros((n, 3), np.float32)
         self._chk(self.L.mi355_gain_compensate_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(g)))
         return g
@@ -832,9 +901,8 @@ class Context:
     def SharpStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, frames=True):
         """Laplacian statistics of the listed pairs (positions in the frame list) on the lattice of `step`: (SHARP_PAIR_STATS [n_pairs],
         SHARP_FRAME_STATS [n], or None with frames=False: then no per-frame tiles are launched)"""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
         st = np.zeros(npairs, SHARP_PAIR_STATS)
         fs = np.zeros(n, SHARP_FRAME_STATS) if frames else None
         self._chk(self.L.mi355_sharp_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), _p(st),
@@ -844,10 +912,9 @@ class Context:
     def SharpnessDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
         """statistics, solve, flag and select on the device frames (which are only read): (sharp [n] float32, status [n] uint8, h9s_kept
         [n, 9] float32 -- h9s with m8 = 0 for the dropped frames, status 1).  params: SharpParams (sharp_params()) or keyword fields of it."""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else sharp_params(**kw)
+        p = _resolve(params, sharp_params, kw)
         sharp = np.zeros(n, np.float32)
         status = np.zeros(n, np.uint8)
         self._chk(self.L.mi355_sharpness_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, C.byref(p), _p(sharp), _p(status)))
@@ -870,7 +937,7 @@ class Context:
         pairs: the graph that must stay connected, None = no connectivity check; params: CoverParams (cover_params()) or keyword fields."""
         w, h, h9s, n, keep = _cover_args(w, h, h9s, keep)
         order, n_order, ab, npairs = _cover_lists(order, pairs)
-        p = params if params is not None else cover_params(**kw)
+        p = _resolve(params, cover_params, kw)
         status, keep_out = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
         rounds, lost = C.c_int32(0), C.c_int64(0)
         fs = np.zeros(n, COVER_FRAME_STATS) if final else None
@@ -884,24 +951,19 @@ class Context:
     def BlockGainStatsDev(self, d_imgs, w, h, ws, h9s, pairs, step=8, grid_x=8, grid_y=6):
         """per-cell overlap statistics of the listed pairs: (BLOCK_GAIN_STATS records sorted by (pair, cell_a, cell_b), cell cover int64
         [n, grid_y * grid_x])"""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
         cover = np.zeros((n, max(int(grid_x) * int(grid_y), 0)), np.int64)
         recs, nrec = C.c_void_p(), C.c_int64(0)
         self._chk(self.L.mi355_block_gain_stats_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(ab), npairs, int(step), int(grid_x), int(grid_y),
                                                     C.byref(recs), C.byref(nrec), _p(cover)))
-        st = np.zeros(nrec.value, BLOCK_GAIN_STATS)
-        if nrec.value:
-            C.memmove(st.ctypes.data, recs, st.nbytes)
-        self.L.mi355_free(recs)
-        return st, cover
+        return _owned(self.L, recs, nrec.value, BLOCK_GAIN_STATS), cover
 
     def ApplyBlockGainsDev(self, d_src, d_dst, w, h, ws, gains):
         """d_dst[k] = d_src[k] times its interpolated gain map (d_dst[k] may be d_src[k]); gains [n, grid_y, grid_x, 3] float32.  Complete
         on return."""
-        n, sp, w, h, ws = self._frame_args(d_src, w, h, ws)
-        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        n, sp, w, h, ws, _ = _dev_frames(d_src, w, h, ws)
+        dp = _dptrs(d_dst, n)
         g = np.ascontiguousarray(gains, np.float32)
         if g.ndim != 4 or g.shape[0] != n or g.shape[3] != 3:
             raise ValueError("gains must be [n, grid_y, grid_x, 3]")
@@ -910,10 +972,9 @@ class Context:
     def BlockGainCompensateDev(self, d_imgs, w, h, ws, h9s, pairs, params=None, **kw):
         """statistics, solve, smoothing and in-place apply on the device frames; returns the gain maps [n, grid_y, grid_x, 3] float32.
         params: BlockGainParams (block_gain_params()) or keyword fields of it."""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
         ab, npairs = self._pairs_ab(pairs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else block_gain_params(**kw)
+        p = _resolve(params, block_gain_params, kw)
         g = np.zeros((n, max(p.grid_y, 0), max(p.grid_x, 0), 3), np.float32)
         if g.size > (1 << 28):
             g = np.zeros((n, 1, 1, 3), np.float32)                # a grid the library refuses
@@ -924,321 +985,177 @@ class Context:
     def MosaicFeathered(self, imgs, h9s, params=None, want_pixels=True, **kw):
         """mi355_mosaic_feathered: host images in, (canvas rows x cws, cw, ch, cws) out.  params: FeatherParams (feather_params()) or its
         keyword fields (ramp)."""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else feather_params(**kw)
-        canvas = C.c_void_p()
-        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_feathered(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
-                                                C.byref(cws)))
-        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value) if want_pixels else None
-        self.L.mi355_free(canvas)
-        return buf, cw.value, ch.value, cws.value
+        p = _resolve(params, feather_params, kw)
+        return self._render_host(self.L.mi355_mosaic_feathered, imgs, h9s, (C.byref(p),), want_pixels=want_pixels)
 
     def MosaicFeatheredDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, params=None, **kw):
         """mi355_mosaic_feathered_dev: device frames (0 / None: withheld) into the device canvas, rows [row0, row0 + rows); complete on return"""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else feather_params(**kw)
-        self._chk(self.L.mi355_mosaic_feathered_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas)),
-                                                    int(cw), int(ch), int(cws), int(row0), int(rows if rows >= 0 else ch)))
+        p = _resolve(params, feather_params, kw)
+        self._render_dev(self.L.mi355_mosaic_feathered_dev, d_imgs, w, h, ws, h9s, (C.byref(p),), d_canvas, cw, ch, cws, stripe=(row0, rows))
 
     def MosaicFeatheredInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
         """mi355_mosaic_feathered_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else feather_params(**kw)
-        cw, ch, _, _ = mosaic_layout(w, h, h9s)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_feathered_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
-                                                     C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        p = _resolve(params, feather_params, kw)
+        return self._render_into(self.L.mi355_mosaic_feathered_into, imgs, img_ids, h9s, (C.byref(p),), mosaic_layout, out, pitch, geom)
 
     # ---- seamline render (mi355_mosaic_seamline*, csrc/seamline.hip) -------------------------------------------------------
     def MosaicSeamline(self, imgs, h9s, params=None, want_owner=False, **kw):
         """mi355_mosaic_seamline: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_owner (canvas, cw, ch, cws, owner [ch, cw]
         uint16: owning frame + 1, 0 where nothing covers).  params: SeamlineParams (seamline_params()) or its keyword fields (ramp)."""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamline_params(**kw)
-        canvas, owner = C.c_void_p(), C.c_void_p()
-        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_seamline(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
-                                               C.byref(cws), C.byref(owner) if want_owner else None))
-        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
-        self.L.mi355_free(canvas)
-        if not want_owner:
-            return buf, cw.value, ch.value, cws.value
-        own = _copy_out(owner, 2 * ch.value * cw.value, np.uint16).reshape(ch.value, cw.value)
-        self.L.mi355_free(owner)
-        return buf, cw.value, ch.value, cws.value, own
+        p = _resolve(params, seamline_params, kw)
+        return self._render_host(self.L.mi355_mosaic_seamline, imgs, h9s, (C.byref(p),), extra=(want_owner, np.uint16))
 
     def MosaicSeamlineDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_owner=0, d_count=0, params=None, **kw):
         """mi355_mosaic_seamline_dev: device frames (0 / None: withheld; d_imgs None when d_canvas is 0) into the device canvas and / or the
         uint16 [ch, cw] maps d_owner, d_count (0: not wanted), rows [row0, row0 + rows); complete on return"""
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        n = len(w)
-        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
-        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamline_params(**kw)
-        self._chk(self.L.mi355_mosaic_seamline_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas or 0) or None),
-                                                   int(cw), int(ch), int(cws), C.c_void_p(int(d_owner or 0) or None), C.c_void_p(int(d_count or 0) or None),
-                                                   int(row0), int(rows if rows >= 0 else ch)))
+        p = _resolve(params, seamline_params, kw)
+        self._render_dev(self.L.mi355_mosaic_seamline_dev, d_imgs, w, h, ws, h9s, (C.byref(p),), d_canvas, cw, ch, cws, maps=(d_owner, d_count),
+                         stripe=(row0, rows))
 
     def MosaicSeamlineInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
         """mi355_mosaic_seamline_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamline_params(**kw)
-        cw, ch, _, _ = mosaic_layout(w, h, h9s)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_seamline_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
-                                                    C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        p = _resolve(params, seamline_params, kw)
+        return self._render_into(self.L.mi355_mosaic_seamline_into, imgs, img_ids, h9s, (C.byref(p),), mosaic_layout, out, pitch, geom)
 
     def SeamlineCover(self, w, h, h9s, row0=0, rows=-1, params=None, **kw):
         """mi355_mosaic_seamline_cover: need[k] = 1 exactly for the frames that own at least one pixel of canvas rows [row0, row0 + rows)"""
-        n = len(w)
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamline_params(**kw)
-        need = np.zeros(n, np.uint8)
-        self._chk(self.L.mi355_mosaic_seamline_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
-        return need
+        p = _resolve(params, seamline_params, kw)
+        return self._render_cover(self.L.mi355_mosaic_seamline_cover, w, h, h9s, (C.byref(p),), row0, rows)
 
     # ---- optimised seamlines (mi355_seam_*, mi355_mosaic_seamcut*, csrc/seamcut.hip) ------------------------------------------
-    def _dev_frames(self, d_imgs, w, h, ws, h9s):
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        n = len(w)
-        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
-        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
-        return n, ptrs, w, h, ws, np.ascontiguousarray(h9s, np.float32)
-
     def SeamCandidatesDev(self, d_imgs, w, h, ws, h9s, d_cand, gw, gh, params=None, **kw):
         """mi355_seam_candidates_dev: the cell records (SEAM_CELL, 32 bytes each) of the gh x gw grid into device memory d_cand"""
-        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
-        p = params if params is not None else seamcut_params(**kw)
-        self._chk(self.L.mi355_seam_candidates_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cand or 0) or None),
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
+        p = _resolve(params, seamcut_params, kw)
+        self._chk(self.L.mi355_seam_candidates_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), _dptr(d_cand),
                                                    int(gw), int(gh)))
 
     def SeamLabelsDev(self, d_cand, gw, gh, d_cells, params=None, **kw):
         """mi355_seam_labels_dev: device records in, the uint16 [gh, gw] cell map into device memory d_cells; returns the report dict"""
-        p = params if params is not None else seamcut_params(**kw)
+        p = _resolve(params, seamcut_params, kw)
         r = SeamReport()
-        self._chk(self.L.mi355_seam_labels_dev(self._h, C.c_void_p(int(d_cand or 0) or None), int(gw), int(gh), C.byref(p),
-                                               C.c_void_p(int(d_cells or 0) or None), C.byref(r)))
+        self._chk(self.L.mi355_seam_labels_dev(self._h, _dptr(d_cand), int(gw), int(gh), C.byref(p),
+                                               _dptr(d_cells), C.byref(r)))
         return _report(r)
 
     def SeamCellsDev(self, d_imgs, w, h, ws, h9s, d_cells, gw, gh, params=None, **kw):
         """mi355_seam_cells_dev: candidates and labels in one call; returns the report dict"""
-        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
-        p = params if params is not None else seamcut_params(**kw)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
+        p = _resolve(params, seamcut_params, kw)
         r = SeamReport()
-        self._chk(self.L.mi355_seam_cells_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None),
+        self._chk(self.L.mi355_seam_cells_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), _dptr(d_cells),
                                               int(gw), int(gh), C.byref(r)))
         return _report(r)
 
     def MosaicSeamCutDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_cells=0, d_owner=0, d_count=0, params=None, **kw):
         """mi355_mosaic_seamcut_dev: the seamline render following the device cell map d_cells (0: candidates and labels are made first, all
         three stages in one call); outputs, stripes and withheld frames as MosaicSeamlineDev; complete on return"""
-        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
-        p = params if params is not None else seamcut_params(**kw)
-        self._chk(self.L.mi355_mosaic_seamcut_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None),
-                                                  C.c_void_p(int(d_canvas or 0) or None), int(cw), int(ch), int(cws),
-                                                  C.c_void_p(int(d_owner or 0) or None), C.c_void_p(int(d_count or 0) or None),
-                                                  int(row0), int(rows if rows >= 0 else ch)))
+        p = _resolve(params, seamcut_params, kw)
+        self._render_dev(self.L.mi355_mosaic_seamcut_dev, d_imgs, w, h, ws, h9s, (C.byref(p), _dptr(d_cells)), d_canvas, cw, ch, cws,
+                         maps=(d_owner, d_count), stripe=(row0, rows))
 
     def MosaicSeamCut(self, imgs, h9s, params=None, want_owner=False, **kw):
         """mi355_mosaic_seamcut: host images in, all three stages, outputs as MosaicSeamline"""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamcut_params(**kw)
-        canvas, owner = C.c_void_p(), C.c_void_p()
-        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_seamcut(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
-                                              C.byref(cws), C.byref(owner) if want_owner else None))
-        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
-        self.L.mi355_free(canvas)
-        if not want_owner:
-            return buf, cw.value, ch.value, cws.value
-        own = _copy_out(owner, 2 * ch.value * cw.value, np.uint16).reshape(ch.value, cw.value)
-        self.L.mi355_free(owner)
-        return buf, cw.value, ch.value, cws.value, own
+        p = _resolve(params, seamcut_params, kw)
+        return self._render_host(self.L.mi355_mosaic_seamcut, imgs, h9s, (C.byref(p),), extra=(want_owner, np.uint16))
 
     def MosaicSeamCutInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
         """mi355_mosaic_seamcut_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamcut_params(**kw)
-        cw, ch, _, _ = mosaic_layout(w, h, h9s)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_seamcut_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
-                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        p = _resolve(params, seamcut_params, kw)
+        return self._render_into(self.L.mi355_mosaic_seamcut_into, imgs, img_ids, h9s, (C.byref(p),), mosaic_layout, out, pitch, geom)
 
     def SeamCutCover(self, w, h, h9s, d_cells, row0=0, rows=-1, params=None, **kw):
         """mi355_mosaic_seamcut_cover: need[k] = 1 exactly for the frames that own a pixel of canvas rows [row0, row0 + rows) under d_cells"""
-        n = len(w)
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else seamcut_params(**kw)
-        need = np.zeros(n, np.uint8)
-        self._chk(self.L.mi355_mosaic_seamcut_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), C.c_void_p(int(d_cells or 0) or None), int(row0), int(rows),
-                                                    _p(need)))
-        return need
+        p = _resolve(params, seamcut_params, kw)
+        return self._render_cover(self.L.mi355_mosaic_seamcut_cover, w, h, h9s, (C.byref(p), _dptr(d_cells)), row0, rows)
 
     # ---- multiband blend along optimised seams (mi355_blend_seam_*, mi355_*_seam*, csrc/blend_seam.hip) ------------------------
     def BlendSeamCellsDev(self, d_imgs, w, h, ws, h9s, d_cells, gw, gh, keep=None, d_cand=0, params=None, **kw):
         """mi355_blend_seam_cells_dev: candidates (in the blend's geometry) and labels; the uint16 [gh, gw] cell map into device memory
         d_cells, the records into d_cand when given; returns the report dict"""
-        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
-        p = params if params is not None else seamcut_params(**kw)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        n, ptrs, w, h, ws, h9s = _dev_frames(d_imgs, w, h, ws, h9s)
+        p = _resolve(params, seamcut_params, kw)
+        keep_a = _arr(keep, np.uint8)
         r = SeamReport()
         self._chk(self.L.mi355_blend_seam_cells_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), C.byref(p),
-                                                    C.c_void_p(int(d_cells or 0) or None), int(gw), int(gh), C.byref(r), C.c_void_p(int(d_cand or 0) or None)))
+                                                    _dptr(d_cells), int(gw), int(gh), C.byref(r), _dptr(d_cand)))
         return _report(r)
 
     def ChipsAndMasksSeam(self, imgs, h9s, keep=None, cells=None, params=None, **kw):
         """mi355_chips_and_masks_seam: ChipsAndMasks(find_masks=True) whose ownership follows the host cell map `cells` ([gh, gw] uint16;
         None: candidates and labels are made first).  The same dictionary; feeds MultiBandBlend."""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        p = params if params is not None else seamcut_params(**kw)
+        n, imgs, ptrs, w, h, ws = _host_frames(imgs)
+        h9s, keep_a = _arr(h9s, np.float32), _arr(keep, np.uint8)
+        p = _resolve(params, seamcut_params, kw)
         if cells is None:
             gw, gh = blend_seam_grid(w, h, h9s, p.level, keep_a)
         else:
             cells = np.ascontiguousarray(cells, np.uint16)
             gh, gw = cells.shape
-        nch = C.c_int(0)
-        chips = C.c_void_p()
-        cimgs = C.POINTER(C.c_void_p)()
-        masks = C.POINTER(C.c_void_p)()
-        cw, ch = C.c_int(), C.c_int()
-        self._chk(self.L.mi355_chips_and_masks_seam(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), C.byref(p), _p(cells), int(gw), int(gh),
-                                                    C.byref(nch), C.byref(chips), C.byref(cimgs), C.byref(masks), C.byref(cw), C.byref(ch)))
-        nv = nch.value
-        info = _copy_out(chips, nv * CHIPINFO.itemsize, CHIPINFO)
-        out_c, out_m = [], []
-        for v in range(nv):
-            cwv, chv = int(info[v]["w"]), int(info[v]["h"])
-            cws_, mws = (cwv * 3 + 3) & ~3, (cwv + 3) & ~3
-            out_c.append(_copy_out(cimgs[v], chv * cws_, np.uint8).reshape(chv, cws_))
-            out_m.append(_copy_out(masks[v], chv * mws, np.uint8).reshape(chv, mws))
-            self.L.mi355_free(C.c_void_p(cimgs[v]))
-            self.L.mi355_free(C.c_void_p(masks[v]))
-        self.L.mi355_free(chips)
-        self.L.mi355_free(C.cast(cimgs, C.c_void_p))
-        self.L.mi355_free(C.cast(masks, C.c_void_p))
-        return dict(cw=cw.value, ch=ch.value, chips=info, chip_imgs=out_c, masks=out_m)
+        return self._chips(self.L.mi355_chips_and_masks_seam, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), C.byref(p), _p(cells),
+                           int(gw), int(gh))
 
     def MosaicBlendedSeamDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, keep=None, band=5, d_cells=0, gw=None, gh=None, params=None, **kw):
         """mi355_mosaic_blended_seam_dev: device frames in, the blended canvas into device memory d_canvas; the ownership follows the device
         cell map d_cells (0: it is made first).  Enqueued on the ctx's stream and waited for."""
-        n, ptrs, w, h, ws, h9s = self._dev_frames(d_imgs, w, h, ws, h9s)
-        p = params if params is not None else seamcut_params(**kw)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        p = _resolve(params, seamcut_params, kw)
+        keep_a = _arr(keep, np.uint8)
         if gw is None or gh is None:
             gw, gh = blend_seam_grid(w, h, h9s, p.level, keep_a)
-        self._chk(self.L.mi355_mosaic_blended_seam_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(band), C.byref(p),
-                                                       C.c_void_p(int(d_cells or 0) or None), int(gw), int(gh), C.c_void_p(int(d_canvas or 0) or None),
-                                                       int(cw), int(ch), int(cws)))
+        self._render_dev(self.L.mi355_mosaic_blended_seam_dev, d_imgs, w, h, ws, h9s,
+                         (_p(keep_a), int(band), C.byref(p), _dptr(d_cells), int(gw), int(gh)), d_canvas, cw, ch, cws)
         self.synchronize()
 
     def MosaicBlendedSeam(self, imgs, h9s, keep=None, band=5, params=None, **kw):
         """mi355_mosaic_blended_seam: host images in, all three stages and the blend; outputs as MosaicBlended"""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        p = params if params is not None else seamcut_params(**kw)
-        out = C.c_void_p()
-        ow, oh, ows = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_blended_seam(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), _p(keep_a), int(band), C.byref(p), C.byref(out),
-                                                   C.byref(ow), C.byref(oh), C.byref(ows)))
-        buf = _copy_out(out, ows.value * oh.value, np.uint8).reshape(oh.value, ows.value)
-        self.L.mi355_free(out)
-        return buf, ow.value, oh.value, ows.value
+        keep_a = _arr(keep, np.uint8)
+        p = _resolve(params, seamcut_params, kw)
+        return self._render_host(self.L.mi355_mosaic_blended_seam, imgs, h9s, (_p(keep_a), int(band), C.byref(p)))
 
     def MosaicBlendedSeamInto(self, imgs, img_ids, h9s, keep=None, band=5, out=None, pitch=None, geom=None, params=None, **kw):
         """mi355_mosaic_blended_seam_into, sources and destination as MosaicBlendedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        p = params if params is not None else seamcut_params(**kw)
-        cw, ch, _ = blend_layout(w, h, h9s, keep_a)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_blended_seam_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), _p(keep_a), int(band), C.byref(p),
-                                                        C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        keep_a = _arr(keep, np.uint8)
+        p = _resolve(params, seamcut_params, kw)
+        return self._render_into(self.L.mi355_mosaic_blended_seam_into, imgs, img_ids, h9s, (_p(keep_a), int(band), C.byref(p)),
+                                 lambda w, h, h9s: blend_layout(w, h, h9s, keep_a), out, pitch, geom)
 
     # ---- median render (mi355_mosaic_median*, csrc/median.hip) -------------------------------------------------------------
     def MosaicMedian(self, imgs, h9s, params=None, want_spread=False, **kw):
         """mi355_mosaic_median: host images in, (canvas rows x cws, cw, ch, cws) out -- with want_spread (canvas, cw, ch, cws, spread [ch, cw]
         uint8: the largest per-channel range of the selected samples).  params: MedianParams (median_params()) or its keyword fields (ramp,
         depth)."""
-        n, imgs, ptrs, w, h, ws = self._host_args(imgs)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else median_params(**kw)
-        canvas, spread = C.c_void_p(), C.c_void_p()
-        cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-        self._chk(self.L.mi355_mosaic_median(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.byref(canvas), C.byref(cw), C.byref(ch),
-                                             C.byref(cws), C.byref(spread) if want_spread else None))
-        buf = _copy_out(canvas, ch.value * cws.value, np.uint8).reshape(ch.value, cws.value)
-        self.L.mi355_free(canvas)
-        if not want_spread:
-            return buf, cw.value, ch.value, cws.value
-        spr = _copy_out(spread, ch.value * cw.value, np.uint8).reshape(ch.value, cw.value)
-        self.L.mi355_free(spread)
-        return buf, cw.value, ch.value, cws.value, spr
+        p = _resolve(params, median_params, kw)
+        return self._render_host(self.L.mi355_mosaic_median, imgs, h9s, (C.byref(p),), extra=(want_spread, np.uint8))
 
     def MosaicMedianDev(self, d_imgs, w, h, ws, h9s, d_canvas, cw, ch, cws, row0=0, rows=-1, d_spread=0, d_count=0, params=None, **kw):
         """mi355_mosaic_median_dev: device frames (0 / None: withheld; d_imgs None when d_canvas and d_spread are 0) into the device canvas and /
         or the maps d_spread (uint8 [ch, cw]) and d_count (uint16 [ch, cw]) (0: not wanted), rows [row0, row0 + rows); complete on return"""
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        n = len(w)
-        ptrs = None if d_imgs is None else (C.c_void_p * n)(*[int(p or 0) or None for p in d_imgs])
-        ws = None if ws is None else np.ascontiguousarray(ws, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else median_params(**kw)
-        self._chk(self.L.mi355_mosaic_median_dev(self._h, ptrs, _p(w), _p(h), _p(ws), n, _p(h9s), C.byref(p), C.c_void_p(int(d_canvas or 0) or None),
-                                                 int(cw), int(ch), int(cws), C.c_void_p(int(d_spread or 0) or None), C.c_void_p(int(d_count or 0) or None),
-                                                 int(row0), int(rows if rows >= 0 else ch)))
+        p = _resolve(params, median_params, kw)
+        self._render_dev(self.L.mi355_mosaic_median_dev, d_imgs, w, h, ws, h9s, (C.byref(p),), d_canvas, cw, ch, cws, maps=(d_spread, d_count),
+                         stripe=(row0, rows))
 
     def MosaicMedianInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None, params=None, **kw):
         """mi355_mosaic_median_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else median_params(**kw)
-        cw, ch, _, _ = mosaic_layout(w, h, h9s)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_median_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), C.byref(p),
-                                                  C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        p = _resolve(params, median_params, kw)
+        return self._render_into(self.L.mi355_mosaic_median_into, imgs, img_ids, h9s, (C.byref(p),), mosaic_layout, out, pitch, geom)
 
     def MedianCover(self, w, h, h9s, row0=0, rows=-1, params=None, **kw):
         """mi355_mosaic_median_cover: need[k] = 1 exactly for the frames that are among the selected of at least one pixel of canvas rows
         [row0, row0 + rows)"""
-        n = len(w)
-        w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else median_params(**kw)
-        need = np.zeros(n, np.uint8)
-        self._chk(self.L.mi355_mosaic_median_cover(self._h, _p(w), _p(h), n, _p(h9s), C.byref(p), int(row0), int(rows), _p(need)))
-        return need
+        p = _resolve(params, median_params, kw)
+        return self._render_cover(self.L.mi355_mosaic_median_cover, w, h, h9s, (C.byref(p),), row0, rows)
 
     # ---- lens undistortion (mi355_undistort_*, csrc/undistort.hip) ---------------------------------------------------------
     def UndistortFramesDev(self, d_src, d_dst, w, h, ws_src, ws_dst, cam, params=None, **kw):
         """mi355_undistort_frames_dev: device frames d_src resampled from the distorted camera `cam` (Camera) to the pinhole camera of params
         (UndistortParams / undistort_params() keyword fields) into d_dst (d_dst[k] == d_src[k] with equal pitches: in place).  Complete on
         return; returns n_outside, int64 [n]: the pixels of each frame without a sample."""
-        n, sp, w, h, ws_src = self._frame_args(d_src, w, h, ws_src)
+        n, sp, w, h, ws_src, _ = _dev_frames(d_src, w, h, ws_src)
         if len(d_dst) != n:
             raise ValueError("d_src and d_dst must list the same frames")
-        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        dp = _dptrs(d_dst, n)
         ws_dst = np.ascontiguousarray(ws_dst, np.int32)
-        p = params if params is not None else undistort_params(**kw)
+        p = _resolve(params, undistort_params, kw)
         out = np.zeros(n, np.int64)
         self._chk(self.L.mi355_undistort_frames_dev(self._h, sp, dp, _p(w), _p(h), _p(ws_src), _p(ws_dst), n, C.byref(cam), C.byref(p), _p(out)))
         return out
@@ -1252,7 +1169,7 @@ class Context:
         if out.dtype != np.uint8 or out.shape != img.shape or out.strides[1:] != (3, 1):
             raise ValueError("out must have img's shape and contiguous rows")
         h, w = img.shape[:2]
-        p = params if params is not None else undistort_params(**kw)
+        p = _resolve(params, undistort_params, kw)
         cnt = C.c_int64(0)
         self._chk(self.L.mi355_undistort_image(self._h, C.c_void_p(img.ctypes.data), w, h, int(img.strides[0]), C.c_void_p(out.ctypes.data),
                                                int(out.strides[0]), C.byref(cam), C.byref(p), C.byref(cnt)))
@@ -1264,21 +1181,21 @@ class Context:
         (local_warp_stats_len(n, grid_x, grid_y) int64 values, cleared by the call).  w, h, h9s: the frames' sizes and frame-to-canvas
         matrices.  params: LocalWarpParams (local_warp_params()) or its keyword fields.  Enqueued on the ctx stream."""
         w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
-        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+        h9s = _h9rows(h9s)
         if not (len(w) == len(h) == len(h9s)):
             raise ValueError("w, h and h9s must list the same frames")
-        p = params if params is not None else local_warp_params(**kw)
-        self._chk(self.L.mi355_tie_residual_stats_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), _p(w), _p(h), _p(h9s), len(w), C.byref(p),
-                                                      C.c_void_p(int(d_stats or 0) or None)))
+        p = _resolve(params, local_warp_params, kw)
+        self._chk(self.L.mi355_tie_residual_stats_dev(self._h, _dptr(d_results), int(n_pairs), _p(w), _p(h), _p(h9s), len(w), C.byref(p),
+                                                      _dptr(d_stats)))
 
     def ApplyLocalWarpsDev(self, d_src, d_dst, w, h, ws_src, ws_dst, grids):
         """mi355_apply_local_warps_dev: device frames d_src resampled by their displacement grids (float32 [n, grid_y + 1, grid_x + 1, 2],
         source pixels) into d_dst (d_dst[k] == d_src[k] with equal pitches: in place).  Complete on return; returns n_clamped, int64 [n]:
         the pixels of each frame whose sample position was clamped to the frame."""
-        n, sp, w, h, ws_src = self._frame_args(d_src, w, h, ws_src)
+        n, sp, w, h, ws_src, _ = _dev_frames(d_src, w, h, ws_src)
         if len(d_dst) != n:
             raise ValueError("d_src and d_dst must list the same frames")
-        dp = (C.c_void_p * n)(*[int(p or 0) or None for p in d_dst])
+        dp = _dptrs(d_dst, n)
         ws_dst = np.ascontiguousarray(ws_dst, np.int32)
         g = np.ascontiguousarray(grids, np.float32)
         if g.ndim != 4 or g.shape[0] != n or g.shape[3] != 2:
@@ -1291,22 +1208,22 @@ class Context:
     def LocalRegisterDev(self, d_results, n_pairs, d_imgs, w, h, ws, h9s, params=None, **kw):
         """mi355_local_register_dev: residual statistics of the device pair records, the per-frame solve and the apply in place on the
         device frames.  Returns (grids float32 [n, grid_y + 1, grid_x + 1, 2], report LOCAL_WARP_REPORT [n])."""
-        n, ptrs, w, h, ws = self._frame_args(d_imgs, w, h, ws)
-        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+        n, ptrs, w, h, ws, _ = _dev_frames(d_imgs, w, h, ws)
+        h9s = _h9rows(h9s)
         if len(h9s) != n:
             raise ValueError("h9s must list the same frames")
-        p = params if params is not None else local_warp_params(**kw)
+        p = _resolve(params, local_warp_params, kw)
         ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
         grids = np.zeros((n, p.grid_y + 1, p.grid_x + 1, 2) if ok else (n, 1, 1, 2), np.float32)
         rep = np.zeros(n, LOCAL_WARP_REPORT)
-        self._chk(self.L.mi355_local_register_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), ptrs, _p(w), _p(h), _p(ws), n, _p(h9s),
+        self._chk(self.L.mi355_local_register_dev(self._h, _dptr(d_results), int(n_pairs), ptrs, _p(w), _p(h), _p(ws), n, _p(h9s),
                                                   C.byref(p), _p(grids), _p(rep)))
         return grids, rep
 
     # ---- pair verification (mi355_pair_edges_dev, mi355_pair_cycles_dev, mi355_pair_residuals_dev, mi355_verify_pairs_dev; csrc/verify.hip) ------
     def PairEdgesDev(self, d_results, n, n_images, d_out):
         """mi355_pair_edges_dev: one PAIR_EDGE per device pair record, device to device (ctx stream)"""
-        self._chk(self.L.mi355_pair_edges_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), int(n_images), C.c_void_p(int(d_out or 0) or None)))
+        self._chk(self.L.mi355_pair_edges_dev(self._h, _dptr(d_results), int(n), int(n_images), _dptr(d_out)))
 
     def PairCyclesDev(self, edges, n_images, cycle_tol=6.0):
         """mi355_pair_cycles_dev: the triangle counts of host PAIR_EDGE records, formed on the device; returns PAIR_CYCLE [n]"""
@@ -1318,24 +1235,24 @@ class Context:
     def PairResidualsDev(self, d_results, n, h9s, label, d_out):
         """mi355_pair_residuals_dev: one PAIR_RESIDUAL per device pair record under the transforms h9s (float32 [n_images, 9], host) and the
         labels (int32 [n_images], host, or None), device to device (ctx stream)"""
-        h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
-        lb = None if label is None else np.ascontiguousarray(label, np.int32)
+        h9s = _h9rows(h9s)
+        lb = _arr(label, np.int32)
         assert lb is None or len(lb) == len(h9s)
-        self._chk(self.L.mi355_pair_residuals_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n), _p(h9s), _p(lb), len(h9s),
-                                                  C.c_void_p(int(d_out or 0) or None)))
+        self._chk(self.L.mi355_pair_residuals_dev(self._h, _dptr(d_results), int(n), _p(h9s), _p(lb), len(h9s),
+                                                  _dptr(d_out)))
 
     def VerifyPairsDev(self, d_results, n_pairs, n_images, d_out, fixed=None, params=None, **kw):
         """mi355_verify_pairs_dev: n_pairs device pair records d_results -> d_out (may be d_results) with every usable pair that is not kept
         demoted.  Returns (label int32 [n_images], transforms IMAGE_TRANSFORM [n_images], report VERIFY_REPORT [n_pairs], summary
         VERIFY_SUMMARY scalar).  params: VerifyParams (verify_params()) or its keyword fields."""
-        p = params if params is not None else verify_params(**kw)
-        ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
+        p = _resolve(params, verify_params, kw)
+        ff = _arr(fixed, np.int32)
         assert ff is None or len(ff) == int(n_images)
         m = max(int(n_images), 1)
         label, tr = np.zeros(m, np.int32), np.zeros(m, IMAGE_TRANSFORM)
         rep, summ = np.zeros(max(int(n_pairs), 0), VERIFY_REPORT), np.zeros(1, VERIFY_SUMMARY)
-        self._chk(self.L.mi355_verify_pairs_dev(self._h, C.c_void_p(int(d_results or 0) or None), int(n_pairs), int(n_images), _p(ff), C.byref(p),
-                                                C.c_void_p(int(d_out or 0) or None), _p(label), _p(tr), _p(rep), _p(summ)))
+        self._chk(self.L.mi355_verify_pairs_dev(self._h, _dptr(d_results), int(n_pairs), int(n_images), _p(ff), C.byref(p),
+                                                _dptr(d_out), _p(label), _p(tr), _p(rep), _p(summ)))
         return label, tr, rep, summ[0]
 
     # ---- guided matching (mi355_guided_select_dev, mi355_guided_match_dev, mi355_guided_match; csrc/guided.hip) ------
@@ -1344,21 +1261,21 @@ class Context:
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         guides = np.ascontiguousarray(guides, np.float32).reshape(-1, 9)
         assert len(pairs) == len(guides)
-        return pairs, guides, params if params is not None else default_guided_params(**kw)
+        return pairs, guides, _resolve(params, default_guided_params, kw)
 
     def GuidedSelectDev(self, pairs, guides, d_a, d_b, d_nsel, d_dist=0, params=None, **kw):
         """mi355_guided_select_dev: the guided selection of the pairs (int32 [n, 2], host) under the guides (float32 [n, 9], image j -> image i, host)
         into device lists d_a, d_b (n x 400 SFPOINT), d_nsel (n int32) and d_dist (n x 400 int32, or 0); one launch on the ctx stream.
         params: GuidedParams (default_guided_params()) or its keyword fields."""
         pairs, guides, p = self._guided_args(pairs, guides, params, kw)
-        self._chk(self.L.mi355_guided_select_dev(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), C.c_void_p(int(d_a or 0) or None),
-                                                 C.c_void_p(int(d_b or 0) or None), C.c_void_p(int(d_nsel or 0) or None), C.c_void_p(int(d_dist or 0) or None)))
+        self._chk(self.L.mi355_guided_select_dev(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), _dptr(d_a),
+                                                 _dptr(d_b), _dptr(d_nsel), _dptr(d_dist)))
 
     def GuidedMatchDev(self, pairs, guides, d_out, ransac_dist=2.5, seed=1, params=None, **kw):
         """mi355_guided_match_dev: guided selection plus the pair stage's tail, n PAIR_RESULT records at the device pointer d_out"""
         pairs, guides, p = self._guided_args(pairs, guides, params, kw)
         self._chk(self.L.mi355_guided_match_dev(self._h, _p(pairs), len(pairs), _p(guides), C.byref(p), C.c_float(ransac_dist), C.c_uint32(seed),
-                                                C.c_void_p(int(d_out or 0) or None)))
+                                                _dptr(d_out)))
 
     def GuidedMatch(self, pairs, guides, ransac_dist=2.5, seed=1, params=None, **kw):
         """mi355_guided_match: the same, returns PAIR_RESULT [n]"""
@@ -1371,15 +1288,8 @@ class Context:
     def MosaicOverviewDev(self, d_rows, cw, ch, cws, levels, d_levels, d_covers=None, d_valid_rows=0, nodata=NODATA_NONE, row0=0, rows=-1):
         """mi355_mosaic_overview_dev: d_rows / d_valid_rows are the device addresses of canvas row row0 / map row row0; d_levels[l - 1] the
         whole device buffer of level l (overview_layout), d_covers None or a list whose entries may be 0.  Enqueued on the ctx stream."""
-        def arr(v):
-            if v is None:
-                return None
-            a = (C.c_void_p * len(v))()
-            for k, x in enumerate(v):
-                a[k] = int(x or 0) or None
-            return a
-        self._chk(self.L.mi355_mosaic_overview_dev(self._h, C.c_void_p(int(d_rows or 0) or None), int(cw), int(ch), int(cws),
-                                                   C.c_void_p(int(d_valid_rows or 0) or None), int(nodata), int(levels), arr(d_levels), arr(d_covers),
+        self._chk(self.L.mi355_mosaic_overview_dev(self._h, _dptr(d_rows), int(cw), int(ch), int(cws),
+                                                   _dptr(d_valid_rows), int(nodata), int(levels), _dptrs(d_levels), _dptrs(d_covers),
                                                    int(row0), int(rows)))
 
     def MosaicOverview(self, canvas, cw, levels, valid=None, nodata=NODATA_NONE, want_covers=False):
@@ -1387,21 +1297,17 @@ class Context:
         [oh_l, ows_l] out -- with want_covers (levels, covers), covers[l - 1] a [oh_l, ow_l] uint16 array."""
         canvas = np.ascontiguousarray(canvas, np.uint8)
         ch, cws = canvas.shape
-        v = None if valid is None else np.ascontiguousarray(valid, np.uint16)
+        v = _arr(valid, np.uint16)
         lv, cv = C.POINTER(C.c_void_p)(), C.POINTER(C.c_void_p)()
         self._chk(self.L.mi355_mosaic_overview(self._h, _p(canvas), int(cw), int(ch), int(cws), _p(v), int(nodata), int(levels), C.byref(lv),
                                                C.byref(cv) if want_covers else None))
         geo = overview_layout(cw, ch, levels)
 
-        def take(arr, l, nbytes, dtype, shape):
-            a = _copy_out(C.c_void_p(arr[l]), nbytes, dtype).reshape(shape)
-            self.L.mi355_free(C.c_void_p(arr[l]))
-            return a
-        outs = [take(lv, l, geo[l][2] * geo[l][1], np.uint8, (geo[l][1], geo[l][2])) for l in range(levels)]
+        outs = [_owned(self.L, C.c_void_p(lv[l]), geo[l][2] * geo[l][1], np.uint8).reshape(geo[l][1], geo[l][2]) for l in range(levels)]
         self.L.mi355_free(lv)
         if not want_covers:
             return outs
-        covs = [take(cv, l, 2 * geo[l][0] * geo[l][1], np.uint16, (geo[l][1], geo[l][0])) for l in range(levels)]
+        covs = [_owned(self.L, C.c_void_p(cv[l]), geo[l][0] * geo[l][1], np.uint16).reshape(geo[l][1], geo[l][0]) for l in range(levels)]
         self.L.mi355_free(cv)
         return outs, covs
 
@@ -1410,8 +1316,8 @@ class Context:
         MosaicImagesRefinedInto.  Returns (out, ow, oh), with want_cover (out, ow, oh, cover [oh, ow] uint16).  dims: (ow, oh) to pass in place
         of the layout's (the library refuses any other)."""
         ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        p = params if params is not None else preview_params(**kw)
+        h9s = _arr(h9s, np.float32)
+        p = _resolve(params, preview_params, kw)
         cw, ch, _, _ = mosaic_layout(w, h, h9s)
         ow, oh, _ = overview_layout(cw, ch, p.level)[-1] if 1 <= p.level <= 7 else (cw, ch, 0)      # a bad level is the library's to refuse
         if dims is not None:
@@ -1469,47 +1375,29 @@ class Context:
     def MosaicImagesRefinedInto(self, imgs, img_ids, h9s, out=None, pitch=None, geom=None):
         """mi355_mosaic_refined_into: image k from the kept frame of img_ids[k] (>= 0) or the host image imgs[k]; the canvas is written into
         out (rows of `pitch` bytes, default out's row stride; out=None: a fresh (ch, cws) array).  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        cw, ch, _, _ = mosaic_layout(w, h, h9s)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_refined_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s),
-                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        return self._render_into(self.L.mi355_mosaic_refined_into, imgs, img_ids, h9s, (), mosaic_layout, out, pitch, geom)
 
     def MosaicBlendedInto(self, imgs, img_ids, h9s, keep=None, band=5, out=None, pitch=None, geom=None):
         """mi355_mosaic_blended_into, sources and destination as MosaicImagesRefinedInto.  Returns (out, cw, ch)."""
-        ptrs, ids, w, h, ws, _keep = self._into_args(imgs, img_ids, geom)
-        h9s = np.ascontiguousarray(h9s, np.float32)
-        keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-        cw, ch, _ = blend_layout(w, h, h9s, keep_a)
-        out, pitch = self._out_array(out, pitch, cw, ch)
-        self._chk(self.L.mi355_mosaic_blended_into(self._h, ptrs, _p(ids), _p(w), _p(h), _p(ws), len(ids), _p(h9s), _p(keep_a), int(band),
-                                                   C.c_void_p(out.ctypes.data), int(pitch), int(cw), int(ch)))
-        return out, cw, ch
+        keep_a = _arr(keep, np.uint8)
+        return self._render_into(self.L.mi355_mosaic_blended_into, imgs, img_ids, h9s, (_p(keep_a), int(band)),
+                                 lambda w, h, h9s: blend_layout(w, h, h9s, keep_a), out, pitch, geom)
 
 
 # ---- host-only helpers (no ctx) ---------------------------------------------------------------------------
 def comm_unique_id():
     """128-byte RCCL id for mi355_comm_init (rank 0 creates it, every rank receives it by any transport)"""
-    L = load_library()
     buf = (C.c_uint8 * 128)()
-    rc = L.mi355_comm_unique_id(buf)
-    if rc != 0:
-        raise Mi355Error(rc, "comm_unique_id: librccl not usable")
+    _host_chk(load_library().mi355_comm_unique_id(buf), "comm_unique_id: librccl not usable")
     return bytes(buf)
 
 
 def blend_layout(w, h, h9s, keep=None):
     """canvas size (cw, ch, cws) of LaplacianPyramidBlending for these transforms (MosaicImage.cpp:2233-2292)"""
-    L = load_library()
-    w = np.ascontiguousarray(w, np.int32); h = np.ascontiguousarray(h, np.int32)
-    h9s = np.ascontiguousarray(h9s, np.float32)
-    keep_a = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    n, w, h, h9s = _geom(w, h, h9s)
+    keep_a = _arr(keep, np.uint8)
     cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
-    rc = L.mi355_blend_layout(_p(w), _p(h), len(w), _p(h9s), _p(keep_a), C.byref(cw), C.byref(ch), C.byref(cws))
-    if rc != 0:
-        raise Mi355Error(rc, "blend_layout")
+    _host_chk(load_library().mi355_blend_layout(_p(w), _p(h), n, _p(h9s), _p(keep_a), C.byref(cw), C.byref(ch), C.byref(cws)), "blend_layout")
     return cw.value, ch.value, cws.value
 
 
@@ -1519,28 +1407,18 @@ def comm_available():
 
 
 def mosaic_layout(w, h, h9s):
-    L = load_library()
-    w = np.ascontiguousarray(w, np.int32)
-    h = np.ascontiguousarray(h, np.int32)
-    h9s = np.ascontiguousarray(h9s, np.float32)
+    n, w, h, h9s = _geom(w, h, h9s)
     cw, ch, cws = C.c_int(), C.c_int(), C.c_int()
     dG = np.zeros(2, np.float32)
-    rc = L.mi355_mosaic_layout(_p(w), _p(h), len(w), _p(h9s), C.byref(cw), C.byref(ch), C.byref(cws), _p(dG))
-    if rc != 0:
-        raise Mi355Error(rc, "mosaic_layout")
+    _host_chk(load_library().mi355_mosaic_layout(_p(w), _p(h), n, _p(h9s), C.byref(cw), C.byref(ch), C.byref(cws), _p(dG)), "mosaic_layout")
     return cw.value, ch.value, cws.value, dG
 
 
 def resample_by_overlap(w, h, h9s, overlapT=0.7):
     """ResampleByOverlap (MosaicImage.cpp:2069-2201): keep[k] = vecAbandonInd[k]"""
-    L = load_library()
-    w = np.ascontiguousarray(w, np.int32)
-    h = np.ascontiguousarray(h, np.int32)
-    h9s = np.ascontiguousarray(h9s, np.float32)
-    keep = np.zeros(len(w), np.uint8)
-    rc = L.mi355_resample_by_overlap(_p(w), _p(h), len(w), _p(h9s), C.c_float(overlapT), _p(keep))
-    if rc != 0:
-        raise Mi355Error(rc, "resample_by_overlap")
+    n, w, h, h9s = _geom(w, h, h9s)
+    keep = np.zeros(n, np.uint8)
+    _host_chk(load_library().mi355_resample_by_overlap(_p(w), _p(h), n, _p(h9s), C.c_float(overlapT), _p(keep)), "resample_by_overlap")
     return keep
 
 
@@ -1555,71 +1433,33 @@ def surf_pair_schedule(n_images):
 
 def screen_params(window=0, top_k=256, partners=None, min_score=None, ratio_pct=80):
     """mi355_screen_params: the library's defaults (mi355_default_screen_params) with the given fields replaced"""
-    p = ScreenParams()
-    load_library().mi355_default_screen_params(C.byref(p))
-    p.window, p.top_k, p.ratio_pct = int(window), int(top_k), int(ratio_pct)
-    if partners is not None:
-        p.partners = int(partners)
-    if min_score is not None:
-        p.min_score = int(min_score)
-    return p
+    return _params(ScreenParams, "mi355_default_screen_params",
+                   dict(window=window, top_k=top_k, partners=partners, min_score=min_score, ratio_pct=ratio_pct))
 
 
 def gain_params(sigma_n=None, sigma_g=None, channels=None, step=None):
     """mi355_gain_params: the library's defaults (mi355_default_gain_params: 10, 0.1, 3, 8) with the given fields replaced"""
-    p = GainParams()
-    load_library().mi355_default_gain_params(C.byref(p))
-    if sigma_n is not None:
-        p.sigma_n = float(sigma_n)
-    if sigma_g is not None:
-        p.sigma_g = float(sigma_g)
-    if channels is not None:
-        p.channels = int(channels)
-    if step is not None:
-        p.step = int(step)
-    return p
+    return _params(GainParams, "mi355_default_gain_params", dict(sigma_n=sigma_n, sigma_g=sigma_g, channels=channels, step=step))
 
 
 def block_gain_params(sigma_n=None, sigma_g=None, channels=None, step=None, grid_x=None, grid_y=None, smooth=None):
     """mi355_block_gain_params: the library's defaults (mi355_default_block_gain_params: 10, 0.1, 3, 8, 8 x 6, 2) with the given fields replaced"""
-    p = BlockGainParams()
-    load_library().mi355_default_block_gain_params(C.byref(p))
-    for name, v in (("sigma_n", sigma_n), ("sigma_g", sigma_g)):
-        if v is not None:
-            setattr(p, name, float(v))
-    for name, v in (("channels", channels), ("step", step), ("grid_x", grid_x), ("grid_y", grid_y), ("smooth", smooth)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(BlockGainParams, "mi355_default_block_gain_params",
+                   dict(sigma_n=sigma_n, sigma_g=sigma_g, channels=channels, step=step, grid_x=grid_x, grid_y=grid_y, smooth=smooth))
 
 
 def sharp_params(prior=None, blur_ratio=None, step=None):
     """mi355_sharp_params: the library's defaults (mi355_default_sharp_params: 0.01, 0.58, 8) with the given fields replaced"""
-    p = SharpParams()
-    load_library().mi355_default_sharp_params(C.byref(p))
-    if prior is not None:
-        p.prior = float(prior)
-    if blur_ratio is not None:
-        p.blur_ratio = float(blur_ratio)
-    if step is not None:
-        p.step = int(step)
-    return p
+    return _params(SharpParams, "mi355_default_sharp_params", dict(prior=prior, blur_ratio=blur_ratio, step=step))
 
 
 def cover_params(step=None, min_depth=None, max_loss=None):
     """mi355_cover_params: the library's defaults (mi355_default_cover_params: 8, 1, 0) with the given fields replaced"""
-    p = CoverParams()
-    load_library().mi355_default_cover_params(C.byref(p))
-    for name, v in (("step", step), ("min_depth", min_depth), ("max_loss", max_loss)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(CoverParams, "mi355_default_cover_params", dict(step=step, min_depth=min_depth, max_loss=max_loss))
 
 
 def _cover_args(w, h, h9s, keep):
-    w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
-    h9s = np.ascontiguousarray(h9s, np.float32)
-    n = len(w)
+    n, w, h, h9s = _geom(w, h, h9s)
     if keep is not None:
         keep = np.ascontiguousarray(keep, np.uint8)
         if len(keep) != n:
@@ -1641,7 +1481,7 @@ def cover_select(w, h, h9s, stats_fn, order=None, pairs=None, keep=None, params=
     L = load_library()
     w, h, h9s, n, keep = _cover_args(w, h, h9s, keep)
     order, n_order, ab, npairs = _cover_lists(order, pairs)
-    p = params if params is not None else cover_params(**kw)
+    p = _resolve(params, cover_params, kw)
     raised = []
 
     def call(_user, keep_ptr, fs_ptr):
@@ -1661,50 +1501,31 @@ def cover_select(w, h, h9s, stats_fn, order=None, pairs=None, keep=None, params=
                               _p(status), _p(keep_out), C.byref(rounds), C.byref(lost))
     if raised:
         raise raised[0]
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(rc, positive=False)
     return status[:n], keep_out[:n], int(rounds.value), int(lost.value)
 
 
 def feather_params(ramp=None):
     """mi355_feather_params: the library's defaults (mi355_default_feather_params: ramp 0 = a full tent per frame) with the given fields replaced"""
-    p = FeatherParams()
-    load_library().mi355_default_feather_params(C.byref(p))
-    if ramp is not None:
-        p.ramp = int(ramp)
-    return p
+    return _params(FeatherParams, "mi355_default_feather_params", dict(ramp=ramp))
 
 
 def seamline_params(ramp=None):
     """mi355_seamline_params: the library's defaults (mi355_default_seamline_params: ramp 0 = a full tent per frame) with the given fields replaced"""
-    p = SeamlineParams()
-    load_library().mi355_default_seamline_params(C.byref(p))
-    if ramp is not None:
-        p.ramp = int(ramp)
-    return p
+    return _params(SeamlineParams, "mi355_default_seamline_params", dict(ramp=ramp))
 
 
 def median_params(ramp=None, depth=None):
     """mi355_median_params: the library's defaults (mi355_default_median_params: ramp 0 = a full tent per frame, depth 0 = 5 frames) with the
     given fields replaced"""
-    p = MedianParams()
-    load_library().mi355_default_median_params(C.byref(p))
-    for name, v in (("ramp", ramp), ("depth", depth)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(MedianParams, "mi355_default_median_params", dict(ramp=ramp, depth=depth))
 
 
 def seamcut_params(ramp=None, level=None, depth=None, data_weight=None, diff_weight=None, seam_penalty=None, miss_cost=None):
     """mi355_seamcut_params: the library's defaults (mi355_default_seamcut_params: ramp 0, level 3, depth 4, costs 1, 2, 2, 32) with the given
     fields replaced"""
-    p = SeamCutParams()
-    load_library().mi355_default_seamcut_params(C.byref(p))
-    for name, v in (("ramp", ramp), ("level", level), ("depth", depth), ("data_weight", data_weight), ("diff_weight", diff_weight),
-                    ("seam_penalty", seam_penalty), ("miss_cost", miss_cost)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(SeamCutParams, "mi355_default_seamcut_params",
+                   dict(ramp=ramp, level=level, depth=depth, data_weight=data_weight, diff_weight=diff_weight, seam_penalty=seam_penalty, miss_cost=miss_cost))
 
 
 def seam_grid(w, h, h9s, level):
@@ -1729,82 +1550,39 @@ def seam_labels_host(cand, params=None, **kw):
     """mi355_seam_labels_host: cell records [gh, gw] of SEAM_CELL in, (cells [gh, gw] uint16, report dict) out; no GPU"""
     cand = np.ascontiguousarray(cand, SEAM_CELL)
     gh, gw = cand.shape
-    p = params if params is not None else seamcut_params(**kw)
+    p = _resolve(params, seamcut_params, kw)
     cells = np.zeros((gh, gw), np.uint16)
     r = SeamReport()
-    rc = load_library().mi355_seam_labels_host(_p(cand), int(gw), int(gh), C.byref(p), _p(cells), C.byref(r))
-    if rc != 0:
-        raise Mi355Error(rc, "seam_labels_host: bad arguments")
+    _host_chk(load_library().mi355_seam_labels_host(_p(cand), int(gw), int(gh), C.byref(p), _p(cells), C.byref(r)), "seam_labels_host: bad arguments")
     return cells, _report(r)
 
 
 def undistort_params(out_fx=None, out_fy=None, out_cx=None, out_cy=None, fill=None):
     """mi355_undistort_params: the library's defaults (mi355_default_undistort_params: the camera's own intrinsics, fill 0) with the given
     fields replaced"""
-    p = UndistortParams()
-    load_library().mi355_default_undistort_params(C.byref(p))
-    for name, v in (("out_fx", out_fx), ("out_fy", out_fy), ("out_cx", out_cx), ("out_cy", out_cy)):
-        if v is not None:
-            setattr(p, name, float(v))
-    if fill is not None:
-        p.fill = int(fill)
-    return p
+    return _params(UndistortParams, "mi355_default_undistort_params", dict(out_fx=out_fx, out_fy=out_fy, out_cx=out_cx, out_cy=out_cy, fill=fill))
 
 
 def tie_params(radius=None, search=None, drop_mask=None, min_ncc=None):
     """mi355_tie_params: the library's defaults (radius 7, search 3, drop_mask 0, min_ncc 0.7) with the given fields replaced"""
-    p = TieParams()
-    load_library().mi355_default_tie_params(C.byref(p))
-    for name, v in (("radius", radius), ("search", search), ("drop_mask", drop_mask)):
-        if v is not None:
-            setattr(p, name, int(v))
-    if min_ncc is not None:
-        p.min_ncc = float(min_ncc)
-    return p
+    return _params(TieParams, "mi355_default_tie_params", dict(radius=radius, search=search, drop_mask=drop_mask, min_ncc=min_ncc))
 
 
 def local_warp_params(grid_x=None, grid_y=None, min_ties=None, max_residual=None, max_shift=None, smooth=None, prior=None):
     """mi355_local_warp_params: the library's defaults (mi355_default_local_warp_params) with the given fields replaced"""
-    p = LocalWarpParams()
-    load_library().mi355_default_local_warp_params(C.byref(p))
-    for name, v in (("grid_x", grid_x), ("grid_y", grid_y), ("min_ties", min_ties)):
-        if v is not None:
-            setattr(p, name, int(v))
-    for name, v in (("max_residual", max_residual), ("max_shift", max_shift), ("smooth", smooth), ("prior", prior)):
-        if v is not None:
-            setattr(p, name, float(v))
-    return p
+    return _params(LocalWarpParams, "mi355_default_local_warp_params",
+                   dict(grid_x=grid_x, grid_y=grid_y, min_ties=min_ties, max_residual=max_residual, max_shift=max_shift, smooth=smooth, prior=prior))
 
 
 def verify_params(cycle_tol=None, gate_abs=None, gate_k=None, max_rounds=None, bridges=None):
     """mi355_verify_params: the library's defaults (6.0, 3.0, 4.0, 8, 1) with the given fields replaced"""
-    p = VerifyParams()
-    load_library().mi355_default_verify_params(C.byref(p))
-    for name, v in (("cycle_tol", cycle_tol), ("gate_abs", gate_abs), ("gate_k", gate_k)):
-        if v is not None:
-            setattr(p, name, float(v))
-    for name, v in (("max_rounds", max_rounds), ("bridges", bridges)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
-
-
-def _host_rc(L, rc):
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    return _params(VerifyParams, "mi355_default_verify_params",
+                   dict(cycle_tol=cycle_tol, gate_abs=gate_abs, gate_k=gate_k, max_rounds=max_rounds, bridges=bridges))
 
 
 def default_guided_params(radius=None, max_dist2=None, ratio=None, reserved=None):
     """mi355_guided_params: the library's defaults (radius 4, max_dist2 90000, ratio 0.8) with the given fields replaced"""
-    p = GuidedParams()
-    load_library().mi355_default_guided_params(C.byref(p))
-    for name, v in (("radius", radius), ("ratio", ratio)):
-        if v is not None:
-            setattr(p, name, float(v))
-    for name, v in (("max_dist2", max_dist2), ("reserved", reserved)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(GuidedParams, "mi355_default_guided_params", dict(radius=radius, max_dist2=max_dist2, ratio=ratio, reserved=reserved))
 
 
 def guided_candidates(w, h, transforms, have=None, min_points=0, max_pairs=None):
@@ -1812,14 +1590,13 @@ def guided_candidates(w, h, transforms, have=None, min_points=0, max_pairs=None)
     m[8] == 0: not placed) says overlap and `have` ([m, 2]) does not cover, with their guides (float32 [n, 9], image j -> image i).
     max_pairs=None sizes the buffers by a count-only call first; an explicit max_pairs below the count raises (the count is in the message)."""
     L = load_library()
+    if max_pairs is None:
+        max_pairs = guided_candidates_count(w, h, transforms, have, min_points)
     t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 9)
     hv = np.zeros((0, 2), np.int32) if have is None else np.ascontiguousarray(have, np.int32).reshape(-1, 2)
     n = C.c_int(0)
-    if max_pairs is None:
-        _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), None, None, 0, C.byref(n)))
-        max_pairs = n.value
     pairs, guides = np.zeros((max(int(max_pairs), 1), 2), np.int32), np.zeros((max(int(max_pairs), 1), 9), np.float32)
-    _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), _p(pairs), _p(guides), int(max_pairs), C.byref(n)))
+    _host_chk(L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), _p(pairs), _p(guides), int(max_pairs), C.byref(n)), positive=False)
     return pairs[:n.value].copy(), guides[:n.value].copy()
 
 
@@ -1829,7 +1606,7 @@ def guided_candidates_count(w, h, transforms, have=None, min_points=0):
     t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 9)
     hv = np.zeros((0, 2), np.int32) if have is None else np.ascontiguousarray(have, np.int32).reshape(-1, 2)
     n = C.c_int(0)
-    _host_rc(L, L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), None, None, 0, C.byref(n)))
+    _host_chk(L.mi355_guided_candidates(int(w), int(h), len(t), _p(t), _p(hv), len(hv), int(min_points), None, None, 0, C.byref(n)), positive=False)
     return n.value
 
 
@@ -1841,7 +1618,7 @@ def merge_pair_results(base, extra):
     e = np.ascontiguousarray(extra, PAIR_RESULT)
     out = np.zeros(max(len(b) + len(e), 1), PAIR_RESULT)
     n = C.c_int(0)
-    _host_rc(L, L.mi355_merge_pair_results(_p(b), len(b), _p(e), len(e), _p(out), C.byref(n)))
+    _host_chk(L.mi355_merge_pair_results(_p(b), len(b), _p(e), len(e), _p(out), C.byref(n)), positive=False)
     return out[:n.value].copy()
 
 
@@ -1850,7 +1627,7 @@ def pair_edges_host(results, n_images):
     L = load_library()
     r = np.ascontiguousarray(results, PAIR_RESULT)
     out = np.zeros(len(r), PAIR_EDGE)
-    _host_rc(L, L.mi355_pair_edges_host(_p(r), len(r), int(n_images), _p(out)))
+    _host_chk(L.mi355_pair_edges_host(_p(r), len(r), int(n_images), _p(out)), positive=False)
     return out
 
 
@@ -1859,7 +1636,7 @@ def pair_cycles_host(edges, n_images, cycle_tol=6.0):
     L = load_library()
     e = np.ascontiguousarray(edges, PAIR_EDGE)
     out = np.zeros(len(e), PAIR_CYCLE)
-    _host_rc(L, L.mi355_pair_cycles_host(_p(e), len(e), int(n_images), C.c_double(cycle_tol), _p(out)))
+    _host_chk(L.mi355_pair_cycles_host(_p(e), len(e), int(n_images), C.c_double(cycle_tol), _p(out)), positive=False)
     return out
 
 
@@ -1867,11 +1644,11 @@ def pair_residuals_host(results, h9s, label=None):
     """mi355_pair_residuals_host (host only): PAIR_RESIDUAL [n] of host PAIR_RESULT records under h9s (float32 [n_images, 9]) and label"""
     L = load_library()
     r = np.ascontiguousarray(results, PAIR_RESULT)
-    h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
-    lb = None if label is None else np.ascontiguousarray(label, np.int32)
+    h9s = _h9rows(h9s)
+    lb = _arr(label, np.int32)
     assert lb is None or len(lb) == len(h9s)
     out = np.zeros(len(r), PAIR_RESIDUAL)
-    _host_rc(L, L.mi355_pair_residuals_host(_p(r), len(r), _p(h9s), _p(lb), len(h9s), _p(out)))
+    _host_chk(L.mi355_pair_residuals_host(_p(r), len(r), _p(h9s), _p(lb), len(h9s), _p(out)), positive=False)
     return out
 
 
@@ -1880,13 +1657,13 @@ def verify_pairs_results(results, n_images, fixed=None, params=None, **kw):
     IMAGE_TRANSFORM [n_images], report VERIFY_REPORT [n], summary VERIFY_SUMMARY scalar)"""
     L = load_library()
     r = np.ascontiguousarray(results, PAIR_RESULT)
-    p = params if params is not None else verify_params(**kw)
-    ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
+    p = _resolve(params, verify_params, kw)
+    ff = _arr(fixed, np.int32)
     assert ff is None or len(ff) == int(n_images)
     m = max(int(n_images), 1)
     out, label, tr = np.zeros(len(r), PAIR_RESULT), np.zeros(m, np.int32), np.zeros(m, IMAGE_TRANSFORM)
     rep, summ = np.zeros(len(r), VERIFY_REPORT), np.zeros(1, VERIFY_SUMMARY)
-    _host_rc(L, L.mi355_verify_pairs_results(_p(r), len(r), int(n_images), _p(ff), C.byref(p), _p(out), _p(label), _p(tr), _p(rep), _p(summ)))
+    _host_chk(L.mi355_verify_pairs_results(_p(r), len(r), int(n_images), _p(ff), C.byref(p), _p(out), _p(label), _p(tr), _p(rep), _p(summ)), positive=False)
     return out, label, tr, rep, summ[0]
 
 
@@ -1900,31 +1677,27 @@ def tie_residual_stats_host(results, w, h, h9s, params=None, **kw):
     L = load_library()
     res = np.ascontiguousarray(results, PAIR_RESULT)
     w, h = np.ascontiguousarray(w, np.int32), np.ascontiguousarray(h, np.int32)
-    h9s = np.ascontiguousarray(h9s, np.float32).reshape(-1, 9)
+    h9s = _h9rows(h9s)
     if not (len(w) == len(h) == len(h9s)):
         raise ValueError("w, h and h9s must list the same frames")
-    p = params if params is not None else local_warp_params(**kw)
+    p = _resolve(params, local_warp_params, kw)
     ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
     st = np.zeros(local_warp_stats_len(len(w), p.grid_x, p.grid_y) if ok else 8, np.int64)
-    rc = L.mi355_tie_residual_stats_host(_p(res), len(res), _p(w), _p(h), _p(h9s), len(w), C.byref(p), _p(st))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_tie_residual_stats_host(_p(res), len(res), _p(w), _p(h), _p(h9s), len(w), C.byref(p), _p(st)), positive=False)
     return st
 
 
 def solve_local_warps(stats, n, params=None, **kw):
     """mi355_solve_local_warps (host only): (grids float32 [n, grid_y + 1, grid_x + 1, 2], report LOCAL_WARP_REPORT [n]) from the sums"""
     L = load_library()
-    p = params if params is not None else local_warp_params(**kw)
+    p = _resolve(params, local_warp_params, kw)
     ok = 1 <= p.grid_x <= 16 and 1 <= p.grid_y <= 16
     st = np.ascontiguousarray(stats, np.int64)
     if ok and st.size != local_warp_stats_len(n, p.grid_x, p.grid_y):
         raise ValueError("stats must hold local_warp_stats_len(n, grid_x, grid_y) values")
     grids = np.zeros((n, p.grid_y + 1, p.grid_x + 1, 2) if ok else (n, 1, 1, 2), np.float32)
     rep = np.zeros(n, LOCAL_WARP_REPORT)
-    rc = L.mi355_solve_local_warps(_p(st), int(n), C.byref(p), _p(grids), _p(rep))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_solve_local_warps(_p(st), int(n), C.byref(p), _p(grids), _p(rep)), positive=False)
     return grids, rep
 
 
@@ -1932,32 +1705,23 @@ def undistort_fit(cam, w, h):
     """mi355_undistort_fit (host only): the UndistortParams of the widest pinhole camera whose w x h border lies inside the source"""
     L = load_library()
     p = UndistortParams()
-    rc = L.mi355_undistort_fit(C.byref(cam) if cam is not None else None, int(w), int(h), C.byref(p))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_undistort_fit(_ref(cam), int(w), int(h), C.byref(p)), positive=False)
     return p
 
 
 def undistort_map(cam, w, h, params=None, **kw):
     """mi355_undistort_map (host only): (xs, ys), float32 [h, w] each: the source coordinate of every output pixel"""
     L = load_library()
-    p = params if params is not None else undistort_params(**kw)
+    p = _resolve(params, undistort_params, kw)
     ok = 0 < int(w) <= 1 << 20 and 0 < int(h) <= 1 << 20
     xs, ys = (np.zeros((int(h), int(w)) if ok else (1, 1), np.float32) for _ in range(2))
-    rc = L.mi355_undistort_map(C.byref(cam) if cam is not None else None, C.byref(p), int(w), int(h), _p(xs), _p(ys))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_undistort_map(_ref(cam), C.byref(p), int(w), int(h), _p(xs), _p(ys)), positive=False)
     return xs, ys
 
 
 def preview_params(render=None, ramp=None, level=None, nodata=None):
     """mi355_preview_params: the library's defaults (refined render, ramp 0, level 3, exact coverage) with the given fields replaced"""
-    p = PreviewParams()
-    load_library().mi355_default_preview_params(C.byref(p))
-    for name, v in (("render", render), ("ramp", ramp), ("level", level), ("nodata", nodata)):
-        if v is not None:
-            setattr(p, name, int(v))
-    return p
+    return _params(PreviewParams, "mi355_default_preview_params", dict(render=render, ramp=ramp, level=level, nodata=nodata))
 
 
 def overview_layout(cw, ch, levels):
@@ -1977,11 +1741,9 @@ def solve_gains(pair_stats, frame_cover, params=None, **kw):
     st = np.ascontiguousarray(pair_stats, GAIN_PAIR_STATS)
     cover = np.ascontiguousarray(frame_cover, np.int64)
     n = len(cover)
-    p = params if params is not None else gain_params(**kw)
+    p = _resolve(params, gain_params, kw)
     g = np.zeros((max(n, 0), 3), np.float32)
-    rc = L.mi355_solve_gains(_p(st), len(st), _p(cover), n, C.byref(p), _p(g))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_solve_gains(_p(st), len(st), _p(cover), n, C.byref(p), _p(g)), positive=False)
     return g
 
 
@@ -1990,11 +1752,9 @@ def solve_sharpness(pair_stats, n, params=None, **kw):
     L = load_library()
     st = np.ascontiguousarray(pair_stats, SHARP_PAIR_STATS)
     n = int(n)
-    p = params if params is not None else sharp_params(**kw)
+    p = _resolve(params, sharp_params, kw)
     sharp, rel = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float64)
-    rc = L.mi355_solve_sharpness(_p(st), len(st), n, C.byref(p), _p(sharp), _p(rel))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_solve_sharpness(_p(st), len(st), n, C.byref(p), _p(sharp), _p(rel)), positive=False)
     return sharp[:max(n, 0)], rel[:max(n, 0)]
 
 
@@ -2004,11 +1764,9 @@ def select_sharp_frames(pair_stats, n, params=None, **kw):
     L = load_library()
     st = np.ascontiguousarray(pair_stats, SHARP_PAIR_STATS)
     n = int(n)
-    p = params if params is not None else sharp_params(**kw)
+    p = _resolve(params, sharp_params, kw)
     status, sharp = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
-    rc = L.mi355_select_sharp_frames(_p(st), len(st), n, C.byref(p), _p(status), _p(sharp))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_select_sharp_frames(_p(st), len(st), n, C.byref(p), _p(status), _p(sharp)), positive=False)
     return status[:max(n, 0)], sharp[:max(n, 0)]
 
 
@@ -2027,15 +1785,13 @@ def solve_block_gains(records, pairs, cell_cover, params=None, **kw):
     ab = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
     cover = np.ascontiguousarray(cell_cover, np.int64)
     n = len(cover)
-    p = params if params is not None else block_gain_params(**kw)
+    p = _resolve(params, block_gain_params, kw)
     gx, gy = p.grid_x, p.grid_y
     ok = 1 <= gx <= 16 and 1 <= gy <= 16
     if ok and cover.size != n * gx * gy:
         raise ValueError("cell_cover must hold n x grid_y * grid_x values")
     g = np.zeros((n, gy, gx, 3) if ok else (n, 1, 1, 3), np.float32)
-    rc = L.mi355_solve_block_gains(_p(st), C.c_int64(len(st)), _p(ab), len(ab), _p(cover), n, C.byref(p), _p(g))
-    if rc < 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_solve_block_gains(_p(st), C.c_int64(len(st)), _p(ab), len(ab), _p(cover), n, C.byref(p), _p(g)), positive=False)
     return g
 
 
@@ -2044,72 +1800,41 @@ def pair_schedule(n_images, window, rank=0, world=1):
     n = C.c_int(0)
     L.mi355_pair_schedule(int(n_images), int(window), int(rank), int(world), None, 0, C.byref(n))
     out = np.zeros((max(n.value, 1), 2), np.int32)
-    rc = L.mi355_pair_schedule(int(n_images), int(window), int(rank), int(world), _p(out), n.value, C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, "pair_schedule")
+    _host_chk(L.mi355_pair_schedule(int(n_images), int(window), int(rank), int(world), _p(out), n.value, C.byref(n)), "pair_schedule")
     return out[:n.value]
 
 
 def write_match_pairs(path, v):
     v = np.ascontiguousarray(v, MATCHPAIR)
-    rc = load_library().mi355_write_match_pairs(path.encode(), _p(v), len(v))
-    if rc != 0:
-        raise Mi355Error(rc, "write_match_pairs")
+    _write("mi355_write_match_pairs", "write_match_pairs", path, v, len(v))
 
 
 def load_match_pairs(path):
-    L = load_library()
-    ptr, n = C.c_void_p(), C.c_int(0)
-    rc = L.mi355_load_match_pairs(path.encode(), C.byref(ptr), C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, "load_match_pairs")
-    out = _copy_out(ptr, n.value * 40, MATCHPAIR)
-    L.mi355_free(ptr)
-    return out
+    return _load("mi355_load_match_pairs", "load_match_pairs", MATCHPAIR, path.encode())
 
 
 def write_match_pairs_txt(path, v):
     v = np.ascontiguousarray(v, MATCHPAIR)
-    rc = load_library().mi355_write_match_pairs_txt(path.encode(), _p(v), len(v))
-    if rc != 0:
-        raise Mi355Error(rc, "write_match_pairs_txt")
+    _write("mi355_write_match_pairs_txt", "write_match_pairs_txt", path, v, len(v))
 
 
 def write_transforms(path, t):
     t = np.ascontiguousarray(t, IMAGE_TRANSFORM)
-    rc = load_library().mi355_write_transforms(path.encode(), _p(t), len(t))
-    if rc != 0:
-        raise Mi355Error(rc, "write_transforms")
+    _write("mi355_write_transforms", "write_transforms", path, t, len(t))
 
 
 def load_transforms(path, tran0=False):
     """ImportTransform's format (count + 9 floats each), or with tran0=True the rows OutTransform writes (tran0.txt)"""
-    L = load_library()
-    ptr, n = C.c_void_p(), C.c_int(0)
-    rc = (L.mi355_load_tran0 if tran0 else L.mi355_load_transforms)(path.encode(), C.byref(ptr), C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, "load_transforms")
-    out = _copy_out(ptr, n.value * IMAGE_TRANSFORM.itemsize, IMAGE_TRANSFORM)
-    L.mi355_free(ptr)
-    return out
+    return _load("mi355_load_tran0" if tran0 else "mi355_load_transforms", "load_transforms", IMAGE_TRANSFORM, path.encode())
 
 
 def write_keypoints(path, kp):
     kp = np.ascontiguousarray(kp, KEYPOINT)
-    rc = load_library().mi355_write_keypoints(path.encode(), _p(kp), len(kp))
-    if rc != 0:
-        raise Mi355Error(rc, "write_keypoints")
+    _write("mi355_write_keypoints", "write_keypoints", path, kp, len(kp))
 
 
 def load_keypoints(path):
-    L = load_library()
-    ptr, n = C.c_void_p(), C.c_int(0)
-    rc = L.mi355_load_keypoints(path.encode(), C.byref(ptr), C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, "load_keypoints")
-    out = _copy_out(ptr, n.value * 28, KEYPOINT)
-    L.mi355_free(ptr)
-    return out
+    return _load("mi355_load_keypoints", "load_keypoints", KEYPOINT, path.encode())
 
 
 def write_descriptors_xml(path, desc):
@@ -2117,42 +1842,27 @@ def write_descriptors_xml(path, desc):
     d = np.ascontiguousarray(desc, np.float32)
     if d.ndim != 2:
         raise ValueError("descriptors: a 2-D array")
-    rc = load_library().mi355_write_descriptors_xml(path.encode(), _p(d), int(d.shape[0]), int(d.shape[1]))
-    if rc != 0:
-        raise Mi355Error(rc, "write_descriptors_xml")
+    _write("mi355_write_descriptors_xml", "write_descriptors_xml", path, d, int(d.shape[0]), int(d.shape[1]))
 
 
 def load_descriptors_xml(path):
     L = load_library()
     ptr, r, c = C.c_void_p(), C.c_int(0), C.c_int(0)
-    rc = L.mi355_load_descriptors_xml(path.encode(), C.byref(ptr), C.byref(r), C.byref(c))
-    if rc != 0:
-        raise Mi355Error(rc, "load_descriptors_xml")
-    out = _copy_out(ptr, r.value * c.value * 4, np.float32).reshape(r.value, c.value)
-    L.mi355_free(ptr)
-    return out
+    _host_chk(L.mi355_load_descriptors_xml(path.encode(), C.byref(ptr), C.byref(r), C.byref(c)), "load_descriptors_xml")
+    return _owned(L, ptr, r.value * c.value, np.float32).reshape(r.value, c.value)
 
 
 def results_to_match_pairs(results, fixed_flags=None):
-    L = load_library()
     results = np.ascontiguousarray(results, PAIR_RESULT)
-    ff = None if fixed_flags is None else np.ascontiguousarray(fixed_flags, np.int32)
-    ptr, n = C.c_void_p(), C.c_int(0)
-    rc = L.mi355_results_to_match_pairs(_p(results), len(results), _p(ff), C.byref(ptr), C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, "results_to_match_pairs")
-    out = _copy_out(ptr, n.value * 40, MATCHPAIR)
-    L.mi355_free(ptr)
-    return out
+    ff = _arr(fixed_flags, np.int32)
+    return _load("mi355_results_to_match_pairs", "results_to_match_pairs", MATCHPAIR, _p(results), len(results), _p(ff))
 
 
 def global_affine_align(match_pairs, n_images, fixed=None):
     v = np.ascontiguousarray(match_pairs, MATCHPAIR)
-    ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
+    ff = _arr(fixed, np.int32)
     out = np.zeros(n_images, IMAGE_TRANSFORM)
-    rc = load_library().mi355_global_affine_align(_p(v), len(v), int(n_images), _p(ff), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, "global_affine_align")
+    _host_chk(load_library().mi355_global_affine_align(_p(v), len(v), int(n_images), _p(ff), _p(out)), "global_affine_align")
     return out
 
 
@@ -2160,21 +1870,17 @@ def select_connected_results(results, n_images):
     """Select_Connected_Matched_Images straight from PAIR_RESULT records (accepted pairs with inliers are the edges)"""
     r = np.ascontiguousarray(results, PAIR_RESULT)
     label = np.zeros(n_images, np.int32)
-    rc = load_library().mi355_select_connected_results(_p(r), len(r), int(n_images), _p(label))
-    if rc != 0:
-        raise Mi355Error(rc, "select_connected_results")
+    _host_chk(load_library().mi355_select_connected_results(_p(r), len(r), int(n_images), _p(label)), "select_connected_results")
     return label
 
 
 def global_affine_align_results(results, n_images, fixed=None, label=None):
     """global_affine_align straight from PAIR_RESULT records; label: use only the pairs whose two images are labelled"""
     r = np.ascontiguousarray(results, PAIR_RESULT)
-    ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
-    lb = None if label is None else np.ascontiguousarray(label, np.int32)
+    ff = _arr(fixed, np.int32)
+    lb = _arr(label, np.int32)
     out = np.zeros(n_images, IMAGE_TRANSFORM)
-    rc = load_library().mi355_global_affine_align_results(_p(r), len(r), int(n_images), _p(ff), _p(lb), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, "global_affine_align_results")
+    _host_chk(load_library().mi355_global_affine_align_results(_p(r), len(r), int(n_images), _p(ff), _p(lb), _p(out)), "global_affine_align_results")
     return out
 
 
@@ -2182,24 +1888,18 @@ def pair_moments_host(results):
     """the second moments of every record's inlier coordinates, summed on the host (what mi355_pair_moments_dev forms on the device)"""
     r = np.ascontiguousarray(results, PAIR_RESULT)
     out = np.zeros(len(r), PAIR_MOMENTS)
-    rc = load_library().mi355_pair_moments_host(_p(r), len(r), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, "pair_moments_host")
+    _host_chk(load_library().mi355_pair_moments_host(_p(r), len(r), _p(out)), "pair_moments_host")
     return out
 
 
 def projective_params(**kw):
     """mi355_default_projective_params, with fields overridden by keyword"""
-    p = ProjectiveParams()
-    load_library().mi355_default_projective_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(ProjectiveParams, "mi355_default_projective_params", kw)
 
 
 def _projective_args(w, h, start, fixed, label):
     st = np.ascontiguousarray(start, IMAGE_TRANSFORM)
-    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+    i32 = lambda a: _arr(a, np.int32)
     w, h, fixed, label = i32(w), i32(h), i32(fixed), i32(label)
     for a in (w, h, fixed, label):
         assert a is None or len(a) == len(st)
@@ -2215,9 +1915,7 @@ def pair_normal_blocks_host(results, h8, part):
     assert len(h8) == len(part)
     out = np.zeros(len(r), PAIR_NORMAL_BLOCK)
     L = load_library()
-    rc = L.mi355_pair_normal_blocks_host(_p(r), len(r), _p(h8), _p(part), len(part), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_pair_normal_blocks_host(_p(r), len(r), _p(h8), _p(part), len(part), _p(out)))
     return out
 
 
@@ -2225,9 +1923,7 @@ def _projective_host(fn, data, w, h, start, fixed, label, params):
     w, h, st, fixed, label = _projective_args(w, h, start, fixed, label)
     out, rep = np.zeros(len(st), IMAGE_TRANSFORM), ProjectiveReport()
     L = load_library()
-    rc = getattr(L, fn)(_p(data), len(data), len(st), _p(w), _p(h), _p(fixed), _p(label), _p(st), C.byref(params) if params is not None else None, _p(out), C.byref(rep))
-    if rc != 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(getattr(L, fn)(_p(data), len(data), len(st), _p(w), _p(h), _p(fixed), _p(label), _p(st), _ref(params), _p(out), C.byref(rep)))
     return out, rep.as_dict()
 
 
@@ -2245,11 +1941,7 @@ def global_projective_refine(match_pairs, w, h, start, fixed=None, label=None, p
 def calib_params(**kw):
     """mi355_default_calib_params (20 trials, mask k1 | k2, min_ties 16, lambda 1e-3, up and down 10, min_rel_decrease 1e-6), with fields
     overridden by keyword"""
-    p = CalibParams()
-    load_library().mi355_default_calib_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(CalibParams, "mi355_default_calib_params", kw)
 
 
 def pair_calib_blocks_host(results, h8, cam, min_ties=16):
@@ -2260,19 +1952,15 @@ def pair_calib_blocks_host(results, h8, cam, min_ties=16):
     assert len(h8) == len(r)
     out = np.zeros(len(r), PAIR_CALIB_BLOCK)
     L = load_library()
-    rc = L.mi355_pair_calib_blocks_host(_p(r), len(r), _p(h8), C.byref(cam) if cam is not None else None, int(min_ties), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(L.mi355_pair_calib_blocks_host(_p(r), len(r), _p(h8), _ref(cam), int(min_ties), _p(out)))
     return out
 
 
 def _calibrate_host(fn, data, start, params, kw):
-    p = params if params is not None else calib_params(**kw)
+    p = _resolve(params, calib_params, kw)
     out, rep = Camera(), CalibReport()
     L = load_library()
-    rc = getattr(L, fn)(_p(data), len(data), C.byref(start) if start is not None else None, C.byref(p), C.byref(out), C.byref(rep))
-    if rc != 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(getattr(L, fn)(_p(data), len(data), _ref(start), C.byref(p), C.byref(out), C.byref(rep)))
     return out, rep.as_dict()
 
 
@@ -2298,36 +1986,29 @@ def match_pairs_to_results(match_pairs):
     out = np.zeros(n.value, PAIR_RESULT)
     if rc == 0 and n.value:
         rc = L.mi355_match_pairs_to_results(_p(v), len(v), _p(out), n.value, C.byref(n))
-    if rc != 0:
-        raise Mi355Error(rc, (L.mi355_last_error(None) or b"").decode())
+    _host_chk(rc)
     return out
 
 
 def select_connected_moments(moments, n_images):
     m = np.ascontiguousarray(moments, PAIR_MOMENTS)
     label = np.zeros(n_images, np.int32)
-    rc = load_library().mi355_select_connected_moments(_p(m), len(m), int(n_images), _p(label))
-    if rc != 0:
-        raise Mi355Error(rc, "select_connected_moments")
+    _host_chk(load_library().mi355_select_connected_moments(_p(m), len(m), int(n_images), _p(label)), "select_connected_moments")
     return label
 
 
 def global_affine_align_moments(moments, n_images, fixed=None, label=None):
     """the global alignment from the pairs' second moments: the same bits as global_affine_align_results on the records they were formed from"""
     m = np.ascontiguousarray(moments, PAIR_MOMENTS)
-    ff = None if fixed is None else np.ascontiguousarray(fixed, np.int32)
-    lb = None if label is None else np.ascontiguousarray(label, np.int32)
+    ff = _arr(fixed, np.int32)
+    lb = _arr(label, np.int32)
     out = np.zeros(n_images, IMAGE_TRANSFORM)
-    rc = load_library().mi355_global_affine_align_moments(_p(m), len(m), int(n_images), _p(ff), _p(lb), _p(out))
-    if rc != 0:
-        raise Mi355Error(rc, "global_affine_align_moments")
+    _host_chk(load_library().mi355_global_affine_align_moments(_p(m), len(m), int(n_images), _p(ff), _p(lb), _p(out)), "global_affine_align_moments")
     return out
 
 
 def select_connected(match_pairs, n_images):
     v = np.ascontiguousarray(match_pairs, MATCHPAIR)
     label = np.zeros(n_images, np.int32)
-    rc = load_library().mi355_select_connected(_p(v), len(v), int(n_images), _p(label))
-    if rc != 0:
-        raise Mi355Error(rc, "select_connected")
+    _host_chk(load_library().mi355_select_connected(_p(v), len(v), int(n_images), _p(label)), "select_connected")
     return label

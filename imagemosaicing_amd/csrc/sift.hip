@@ -805,6 +805,13 @@ void extrema_stream(OctaveDev oc, int octave, unsigned long long* cand, unsigned
 }
 
 constexpr unsigned KEY_BINS = 65536;         // top-k: the frame's histogram of the refined records' 16-bit response keys (select_unique_kernel)
+#ifdef MI355_REFINE_STATS
+// measurement build (scratch/refine_movers.py): refine_kernel runs every trajectory out and counts what the candidates do, summed over
+// all frames since the last reset; the words are named in that script
+__device__ unsigned long long g_refine_stats[40];
+#define RSTATN(k, v) atomicAdd(&g_refine_stats[k], (unsigned long long)(v))
+#define RSTAT(k) RSTATN(k, 1)
+#endif
 __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned long long* cand_all, const unsigned* cand_counts, unsigned cand_cap, unsigned* cand_total,
                                                      float contrast_thr, float edge_thr, float sigma,
                                                      Refined* out, unsigned* out_count, unsigned out_cap, unsigned* out_resp, BatchStride bs,
@@ -823,6 +830,7 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
         for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
         if (threadIdx.x == 0) cand_total[0] = tot;
     }
+    unsigned n_circ = 0u;                        // this lane's circling candidates dropped before their steps ran out
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const unsigned long long pk = cand[i];
         const int o = (int)((pk >> 48) & 0xff);
@@ -861,23 +869,77 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
 #pragma unroll
                 for (int e = 0; e < 9; e++) cv[dl * 9 + e] = (float)(v[dl + 1][e] - v[dl][e]);
         };
+        // A fit step is a function of its location alone (fit_step reads the 27 DoG values around it, the same integers from the cube,
+        // gather() and dogv()), and a location the candidate was fitted at before was left with "move": converged, rejected and diverged
+        // all end the loop.  So a move that lands on such a location repeats from there for ever; the candidate can only run out of
+        // steps and be dropped -- it is dropped at once.  The new location is compared with the last two and with the first, packed like
+        // `start` (which is the first): one more register.  Of the at most four earlier locations that leaves out the second, at the last
+        // test only -- a 3-cycle entered after one step runs its steps out as before (rare: profiles/refine_movers_stats.txt), as do
+        // the candidates of levels too large for the packing.
+        const bool track = oc.w <= 16384 && oc.h <= 16384;
+        unsigned seen = 0xffffffffu;                                                  // the location before the last (all ones: layer 15, never a location)
+#ifdef MI355_REFINE_STATS
+        int circ_at = 0, wasted = 0;
+        unsigned h1 = 0xffffffffu, h2 = 0xffffffffu, h3 = 0xffffffffu;
+        bool moved = false;
+        RSTAT(4);
+#endif
+        // the move of a step that did not converge; false: the candidate is dead (out of bounds, or back on a location of its own)
+        auto move = [&]() -> bool {
+            const int dC = (int)rintf(f.xc), dR = (int)rintf(f.xr), dL = (int)rintf(f.xi);
+            const unsigned here = ((unsigned)L << 28) | ((unsigned)R << 14) | (unsigned)C;
+            C += dC; R += dR; L += dL;
+            if (L < 1 || L > N_LAYERS || C < IMG_BORDER || C >= oc.w - IMG_BORDER || R < IMG_BORDER || R >= oc.h - IMG_BORDER) return false;
+            const unsigned now = ((unsigned)L << 28) | ((unsigned)R << 14) | (unsigned)C;
+            const bool back = track && it + 1 < MAX_INTERP && (now == here || now == seen || now == start);      // (the last step's move ends the loop anyway)
+            seen = here;
+#ifdef MI355_REFINE_STATS
+            moved = true;
+            const bool back4 = track && it + 1 < MAX_INTERP && (now == here || now == h1 || now == h2 || now == h3);      // against all four
+            h3 = h2; h2 = h1; h1 = here;
+            if (back4 && !circ_at) { circ_at = it + 1; if (!back) RSTAT(32); }
+            return true;                                                              // the measurement build runs every trajectory out
+#else
+            if (back) n_circ++;
+            return !back;
+#endif
+        };
         if (from_cube || can_gather) {
             for (; it < MAX_INTERP; it++) {
                 if (it == 0 && from_cube) {
                     const float* cb = cube_all + (size_t)reg * 32 * cube_cap + i;       // [element][candidate]: coalesced across the lanes
 #pragma unroll
                     for (int e = 0; e < 27; e++) cv[e] = cb[(size_t)e * cube_cap];
-                } else if (can_gather) gather(L, R, C);
-                else break;                                                            // (a saved cube on an odd-width level: the later steps through dogv())
+                } else if (can_gather) {
+#ifdef MI355_REFINE_STATS
+                    RSTAT(it ? it - 1 : 31);
+                    if (it) {                                                          // the move that led here, from the location it left
+                        const int dL = L - (int)(seen >> 28), dR = R - (int)((seen >> 14) & 0x3fffu), dC = C - (int)(seen & 0x3fffu);
+                        const int big = dL < -1 || dL > 1 || dR < -1 || dR > 1 || dC < -1 || dC > 1;
+                        const int pat = big ? 4 : dC ? 3 : (dR && dL) ? 2 : dL ? 1 : dR ? 0 : 5;
+                        RSTAT((circ_at ? 23 : 17) + pat);
+                        if (circ_at) wasted++; else RSTATN(29, pat == 0 ? 4 : pat == 1 ? 6 : pat == 2 ? 8 : 12);
+                    }
+#endif
+                    gather(L, R, C);
+                } else break;                                                          // (a saved cube on an odd-width level: the later steps through dogv())
                 const int L0 = L, R0 = R, C0 = C;
                 auto dvc = [&](int l, int r, int c) { return cv[(l - L0 + 1) * 9 + (r - R0 + 1) * 3 + (c - C0 + 1)]; };
                 f = fit_step(dvc, L, R, C);
                 const int stt = fit_state(f);
+#ifdef MI355_REFINE_STATS
+                if (stt == 1) RSTAT(9);
+                if (stt == 0) { RSTAT(moved ? 7 : 6); if (circ_at) RSTAT(30); }
+#endif
                 if (stt == 1) { alive = false; break; }
                 if (stt == 0) { accepted = fit_accept(dvc, L, R, C, f, contrast_thr, edge_thr, contr); alive = accepted; break; }
-                C += (int)rintf(f.xc); R += (int)rintf(f.xr); L += (int)rintf(f.xi);
-                if (L < 1 || L > N_LAYERS || C < IMG_BORDER || C >= oc.w - IMG_BORDER || R < IMG_BORDER || R >= oc.h - IMG_BORDER) { alive = false; break; }
+                if (!move()) { alive = false; break; }
             }
+#ifdef MI355_REFINE_STATS
+            if (moved) RSTAT(5);
+            if (it < MAX_INTERP && !accepted && alive == false && fit_state(f) == 2) { RSTAT(8); if (circ_at) RSTAT(30); }
+            if (it >= MAX_INTERP) { RSTAT(10); RSTAT(circ_at ? 10 + circ_at : 15); RSTATN(16, wasted); }
+#endif
             if (!alive || (can_gather && !accepted)) continue;                       // dead, rejected, or still moving after MAX_INTERP steps
         }
         if (!accepted) {
@@ -886,8 +948,7 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
                 const int stt = fit_state(f);
                 if (stt == 0) break;
                 if (stt == 1) { alive = false; break; }
-                C += (int)rintf(f.xc); R += (int)rintf(f.xr); L += (int)rintf(f.xi);
-                if (L < 1 || L > N_LAYERS || C < IMG_BORDER || C >= oc.w - IMG_BORDER || R < IMG_BORDER || R >= oc.h - IMG_BORDER) { alive = false; break; }
+                if (!move()) { alive = false; break; }
             }
             if (!alive || it >= MAX_INTERP) continue;
             if (!fit_accept(dv, L, R, C, f, contrast_thr, edge_thr, contr)) continue;
@@ -927,6 +988,9 @@ __global__ __launch_bounds__(256) void refine_kernel(PyrDev P, const unsigned lo
             if (P.mins[o]) atomicMin(&P.mins[o][fr * bs.mins + ((size_t)R * oc.w + C) * 4 + (size_t)L], start);
         }
     }
+    // the frame's counter 6 (mi355_last_sift_counters): one atomic per wave that has something to add
+    for (int off = 32; off > 0; off >>= 1) n_circ += __shfl_xor(n_circ, off);
+    if ((threadIdx.x & 63) == 0 && n_circ) atomicAdd(&cand_total[6], n_circ);
 }
 
 // ---- keep-all (nfeatures <= 0, cv::SIFT's default of its own: every keypoint, in OpenCV's generation order) ------------------------------
@@ -1749,6 +1813,15 @@ struct SiftBufs {
 };
 
 }  // namespace
+
+#ifdef MI355_REFINE_STATS
+extern "C" int mi355_debug_refine_stats(unsigned long long* out40, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return MI355_ERR_FAILED;
+    if (out40 && hipMemcpyFromSymbol(out40, HIP_SYMBOL(g_refine_stats), sizeof(g_refine_stats)) != hipSuccess) return MI355_ERR_FAILED;
+    if (reset) { const unsigned long long z[40] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_refine_stats), z, sizeof(z)) != hipSuccess) return MI355_ERR_FAILED; }
+    return MI355_OK;
+}
+#endif
 
 // One batch work area: room for `nb` frames and one stream.  Frames handed to mi_sift_extract_dev() collect in `pend`; a full batch
 // (or a flush) is enqueued by sift_run_batch() on that ONE in-order stream -- no reliance on how the runtime maps streams to hardware
